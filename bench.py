@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — Mrays/s of the ray / octree / triangle hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5|C5_1spp|H100k] [--scale S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5|C5_1spp|H100k] [--scale S] [--dump-outputs DIR] [--full]
 
 One step = one frame of the workload: every pixel's CastRay tree (closest-hit, shadow and reflection
 queries).  Default workload is the configuration BASELINE.json quotes its target on and which fits one GPU:
-C5 = the 1M-triangle mesh at 1920x1080, depth 3, 16 sub-rays per pixel; C2 / C3 / C4 are reported as short side
-measurements in "other_configs" at N=1.  The `roofline` block carries three fractions of the dominant kernel
+C5 = the 1M-triangle mesh at 1920x1080, depth 3, 16 sub-rays per pixel.  A plain run sets up, warms up, times the K
+steps and prints the line; --dump-outputs DIR also writes the last timed frame as DIR/rgba.npy.  --full adds everything
+else: the serialised side pass, host-output and blocking timings, the CPU baseline with its parity check of the
+last timed frame, C2 / C3 / C4 / G1 as short side measurements in "other_configs" at N=1, and the per-run metrics
+file.  The `roofline` block carries three fractions of the dominant kernel
 (the traversal launches: k_packet / k_intersect) -- reference-algorithm bytes, measured HBM traffic and VALU issue (the latter two from the
 committed rocprofv3 PMC passes of THIS build, profiles/pmc_traversal.json, divided by launch durations measured live
 with HIP events) -- and names as `bound` whichever physical limit is closest.
@@ -150,8 +153,9 @@ def time_frames_sharded(tracer, outs, steps, warmup, rank, world, width, height,
             j = complete()
         if j >= 0 and j % M != M - 1:
             flush((j // M) % 2, j % M + 1)               # the last, partly filled group
-        finish(0)
-        finish(1)
+        last = (j // M) % 2 if j >= 0 else 1
+        finish(1 - last)                                 # the older group first: the last frame is de-tiled last
+        finish(last)
     for i in range(warmup):
         frame(i)
     drain()
@@ -211,7 +215,7 @@ def time_frames(tracer, outs, steps, warmup, rank, world, width, height, gathere
     return dt, acc[0], acc[1]
 
 
-def run_config(name, scale, steps, warmup, rank, local_rank, world, with_stats=True, n_gpus_in_library=1):
+def run_config(name, scale, steps, warmup, rank, local_rank, world, with_stats=True, n_gpus_in_library=1, serial_pass=True):
     spec = xrt.configs.config(name, scale)
     torch.cuda.synchronize()
     mem0 = torch.cuda.mem_get_info()[0]   # free bytes of the device before the scene exists (hipMemGetInfo: everything on the card counts)
@@ -260,6 +264,8 @@ def run_config(name, scale, steps, warmup, rank, local_rank, world, with_stats=T
     mem2 = torch.cuda.mem_get_info()[0]   # after two frames in flight: both frame contexts hold their work buffers
     # the pixels the timed loop's own render objects produced last (read back after the timed region): what main() compares with the oracle
     last_frame = outs[(steps - 1) % 2].cpu().numpy().view(np.uint32).copy() if (world == 1 and steps > 0) else None
+    # N > 1: rank 0's gathered, de-tiled copy of the last timed frame (what --dump-outputs writes)
+    gathered_frame = final.cpu().numpy().view(np.uint32).copy() if (final is not None and steps > 0) else None
     if world > 1 and rank == 0 and os.environ.get("XRT_BENCH_VERIFY"):   # rehearsals: the gathered, de-tiled frame is the unsharded one
         whole = torch.zeros(W * H, dtype=torch.int32, device="cuda")
         tracer.RenderDevice(whole.data_ptr())
@@ -270,8 +276,8 @@ def run_config(name, scale, steps, warmup, rank, local_rank, world, with_stats=T
     device_memory = {"scene_GB": round((mem0 - mem1) / 1e9, 3), "frame_work_buffers_GB": round((mem1b - mem2) / 1e9, 3),
                      "what": "hipMemGetInfo differences: scene arrays after the build; work buffers of BOTH frame contexts (two frames in flight) after the timed frames, output buffers excluded"}
     res = dict(ms_longest=ms_longest, tile_balance=balance, rays=rays, seconds=dt, ms_intersect=ms_int, launches=launches, stats=st0, build_s=build_s, width=W, height=H, last_frame=last_frame, device_memory=device_memory,
-               tris=sum(m[0].ntri for m in spec.meshes), instances=len(spec.objects), overlapped=False)
-    if world == 1 and dt / max(steps, 1) * 1e3 >= 0.04:
+               tris=sum(m[0].ntri for m in spec.meshes), instances=len(spec.objects), overlapped=False, gathered_frame=gathered_frame)
+    if serial_pass and world == 1 and dt / max(steps, 1) * 1e3 >= 0.04:
         # The frames of the timed region overlapped pairwise on the GPU (two streams), so a launch's duration includes time
         # it shared with the other frame's launches.  A short serialised pass (one explicit stream) gives the duration of a
         # launch that has the GPU to itself -- the figure a roofline of the kernel is about.
@@ -490,6 +496,29 @@ def roofline_block(config, alg_bytes_per_launch, ms_per_launch, launches_per_fra
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, frame, width, height):
+    """--dump-outputs: the frame of the last timed step -- the packed Color[] (R in the low byte, include/xrt.h) a caller of
+    xrt_render_device receives -- as DIR/rgba.npy, float32 channels R, G, B, A (0..255) of shape (height, width, 4).  A frame
+    above DUMP_LIMIT_BYTES is written as a fixed, seeded sample of its pixels: rgba.npy of shape (k, 4) and their row-major
+    indices as rgba_pixel_index.npy (float64)."""
+    if frame is None:
+        print("bench.py: --dump-outputs: no timed step, nothing written", file=sys.stderr)
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    packed = np.asarray(frame, dtype=np.uint32).reshape(-1)
+    rgba = np.stack([(packed >> np.uint32(s)) & np.uint32(255) for s in (0, 8, 16, 24)], axis=1).astype(np.float32)
+    room = DUMP_LIMIT_BYTES - 4096   # (the .npy headers)
+    if rgba.nbytes <= room:
+        np.save(os.path.join(out_dir, "rgba.npy"), rgba.reshape(height, width, 4))
+        return
+    idx = np.sort(np.random.default_rng(0).choice(packed.size, size=room // (rgba.itemsize * 4 + 8), replace=False))
+    np.save(os.path.join(out_dir, "rgba.npy"), rgba[idx])
+    np.save(os.path.join(out_dir, "rgba_pixel_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -497,9 +526,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="C5", choices=list(WORKLOADS))
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the image (debug only; invalid as a benchmark)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the side measurements of the other configs")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline")
-    ap.add_argument("--no-host", action="store_true", help="skip the host-output (PCIe-inclusive) timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks: serialised pass, host-output and blocking timings, CPU baseline "
+                         "and parity, other configs, metrics file (a plain run only times the K steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step as DIR/rgba.npy (float32 channels R, G, B, A of the packed Color[])")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the side measurements of the other configs")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-host", action="store_true", help="with --full: skip the host-output (PCIe-inclusive) timing")
     ap.add_argument("--in-library", action="store_true",
                     help="N > 1 from ONE process: xrt_render_opts.n_gpus = N (replicas, per-device host threads, grouped RCCL send/recv and "
                          "de-tile inside libxrt) -- the path the C# host's single RenderInternal call would use; run as plain `python bench.py "
@@ -527,7 +561,10 @@ def main():
         else:
             dist.init_process_group(backend)
 
-    res, spec = run_config(args.config, args.scale, args.steps, args.warmup, rank, local_rank, world, n_gpus_in_library=args.gpus if in_library else 1)
+    res, spec = run_config(args.config, args.scale, args.steps, args.warmup, rank, local_rank, world, n_gpus_in_library=args.gpus if in_library else 1,
+                           serial_pass=args.full)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res["last_frame"] if world == 1 else res["gathered_frame"], spec.width, spec.height)
     # max over ranks of the timed region; total rays over ranks
     t = torch.tensor([res["seconds"]], dtype=torch.float64, device="cuda")
     r = torch.tensor([float(res["rays"]), float(intersect_bytes(res["stats"])), res["ms_intersect"], float(res["launches"]), float(res["stats"]["rays_traversed"])],
@@ -584,7 +621,7 @@ def main():
         }
         line["roofline"]["traversed_value"] = line["Mrays_per_s_traversed"]   # Mrays/s of the queries that reach the traversal kernels (`value` counts the primary rays k_raygen answers too)
         solo = world == 1 and not in_library   # the side measurements below are single-GPU figures
-        if solo and not args.no_host and args.scale == 1.0:
+        if args.full and solo and not args.no_host and args.scale == 1.0:
             try:
                 _, tracer_h = xrt.configs.build_product(spec, device=local_rank)
                 # (a fresh scene: six warm-up frames size both frame contexts, create their streams and let the library see a frame time)
@@ -595,7 +632,7 @@ def main():
                 del tracer_h
             except Exception as e:   # a side measurement must not take the headline down
                 line["host_output"] = {"error": str(e)[:200]}
-        if solo and args.scale == 1.0:
+        if args.full and solo and args.scale == 1.0:
             try:   # what the C# host's blocking RenderInternal sees: one frame at a time (libxrt splits it over two streams)
                 _, tracer_b = xrt.configs.build_product(spec, device=local_rank)
                 outb = torch.zeros(spec.width * spec.height, dtype=torch.int32, device="cuda")
@@ -613,7 +650,7 @@ def main():
                 del tracer_b, outb
             except Exception as e:
                 line["ms_per_step_blocking"] = None
-        if solo and args.scale == 1.0:
+        if args.full and solo and args.scale == 1.0:
             try:   # THE seam, literally (RT:103-126): one blocking xrt_render per frame, ending in the host's Color[] (page-locked)
                 _, tracer_x = xrt.configs.build_product(spec, device=local_rank)
                 hostb = np.zeros(spec.width * spec.height, dtype=np.uint32)
@@ -636,12 +673,12 @@ def main():
             except Exception as e:
                 line["ms_per_step_blocking_host"] = None
                 line["blocking_host_error"] = str(e)[:200]
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             line["cpu_baseline"], oracle_rgba, oracle_rows = cpu_baseline(spec)
             if res.get("last_frame") is not None:
                 line.update(parity_block(res["last_frame"], oracle_rgba, oracle_rows, spec.width))
                 parity_failed = not line["parity_ok"]
-        if solo and not args.no_extra and args.scale == 1.0:
+        if args.full and solo and not args.no_extra and args.scale == 1.0:
             other = {}
             for name, k in (("C2", 200), ("C3", 30), ("C4", 12), ("G1", 60)):   # (frames of 0.1-0.3 ms: enough of them for the clocks to have ramped up)   # G1: the scene the reference's own Stopwatch would time (Game1.cs)
                 if name == args.config:
@@ -680,14 +717,15 @@ def main():
         if parity_failed:
             print("bench.py: the timed loop's frame differs from the oracle in %d pixels of rows %s: the measurement is void"
                   % (line["parity_mismatched_pixels"], line["parity_rows"]), file=sys.stderr)
-        try:   # per-run metrics file: the line plus the frame's accounting
-            mdir = os.environ.get("XRT_METRICS_DIR", os.path.join(ROOT, "gpurun_out"))
-            os.makedirs(mdir, exist_ok=True)
-            with open(os.path.join(mdir, "bench_metrics_%s_n%d.json" % (args.config, world)), "w") as f:
-                json.dump({"line": line, "frame_stats": {k: (int(v) if isinstance(v, (int, np.integer)) else v) for k, v in st.items()},
-                           "argv": sys.argv[1:], "kernel_build_id": build_id(), "time": time.strftime("%Y-%m-%dT%H:%M:%S")}, f, indent=1)
-        except Exception:
-            pass
+        if args.full:
+            try:   # per-run metrics file: the line plus the frame's accounting
+                mdir = os.environ.get("XRT_METRICS_DIR", os.path.join(ROOT, "bench_out"))
+                os.makedirs(mdir, exist_ok=True)
+                with open(os.path.join(mdir, "bench_metrics_%s_n%d.json" % (args.config, world)), "w") as f:
+                    json.dump({"line": line, "frame_stats": {k: (int(v) if isinstance(v, (int, np.integer)) else v) for k, v in st.items()},
+                               "argv": sys.argv[1:], "kernel_build_id": build_id(), "time": time.strftime("%Y-%m-%dT%H:%M:%S")}, f, indent=1)
+            except Exception:
+                pass
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -363,51 +363,90 @@ def test_tight_leaf_boxes_adversarial(xrt, orc, emul, kind):
         assert len(hits_equal(ho, weak.intersect(rays, mode=1, mesh=0))) > 0
 
 
-REF_CONTENT = "/root/reference/RayTraceProject/RayTraceProjectContent"
+def _fbx6100_crate_bytes(xrt):
+    """Crate_Fragile.FBX as binary FBX 6100 (32-bit record headers; arrays as runs of scalar properties, as 6.x files store them),
+    written from the crate's FBX data in fixtures.py: Z-up, 8 vertices, 6 quads, normals per polygon vertex, UVs by index."""
+    fx = xrt.fixtures
+    pvi = [i for q in fx.CRATE_QUADS for i in list(q[:-1]) + [~q[-1]]]
+    normals = [float(c) for nv in fx.CRATE_NORMALS for _ in range(4) for c in nv]
+    tree = [("FBXHeaderExtension", [], [("FBXVersion", [6100], [])]),
+            ("GlobalSettings", [], [("Properties60", [], [("Property", ["UpAxis", "int", "", 2], [])])]),
+            ("Objects", [], [("Model", ["Model::Crate_Fragile", "Mesh"], [
+                ("Properties60", [], [("Property", ["Lcl Translation", "Lcl Translation", "A+", 0.0, 8.6e-07, 0.0], [])]),
+                ("Vertices", [float(c) for p in fx.CRATE_VERTICES for c in p], []),
+                ("PolygonVertexIndex", pvi, []),
+                ("LayerElementNormal", [0], [("MappingInformationType", ["ByPolygonVertex"], []), ("ReferenceInformationType", ["Direct"], []),
+                                             ("Normals", normals, [])]),
+                ("LayerElementUV", [0], [("MappingInformationType", ["ByPolygonVertex"], []), ("ReferenceInformationType", ["IndexToDirect"], []),
+                                         ("UV", [float(c) for uv in fx.CRATE_UVS for c in uv], []), ("UVIndex", [0, 1, 2, 3] * 6, [])])])])]
+    return _fbx7_bytes(tree, 6100), pvi, normals
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CONTENT), reason="the reference tree is only mounted in the build container")
-def test_fbx_import_of_the_reference_assets(xrt):
-    """Asset ingestion (fbx.py): the binary FBX 6100 crate imports to exactly the hand-written crate
-    fixture, the ASCII FBX 6.1 sphere to the committed data fixture, and the other meshes of the content project parse."""
+def _globe(m=16, k=8):
+    """A closed latitude-longitude globe of radius 1 as an FBX polygon soup: quads, triangles at the poles, counter-clockwise seen from
+    outside (the exporters' winding), unit normals per vertex."""
+    verts = [(0.0, 0.0, 1.0)]
+    for i in range(1, k):
+        th = np.pi * i / k
+        verts += [(np.sin(th) * np.cos(2 * np.pi * j / m), np.sin(th) * np.sin(2 * np.pi * j / m), np.cos(th)) for j in range(m)]
+    verts.append((0.0, 0.0, -1.0))
+    ring = lambda i, j: 1 + (i - 1) * m + j % m
+    polys = [[0, ring(1, j), ring(1, j + 1)] for j in range(m)]
+    polys += [[ring(i, j), ring(i + 1, j), ring(i + 1, j + 1), ring(i, j + 1)] for i in range(1, k - 1) for j in range(m)]
+    polys += [[len(verts) - 1, ring(k - 1, j + 1), ring(k - 1, j)] for j in range(m)]
+    v = np.array(verts, dtype=np.float64)
+    for p in polys:   # counter-clockwise seen from outside
+        assert np.dot(np.cross(v[p[1]] - v[p[0]], v[p[2]] - v[p[0]]), v[p].mean(axis=0)) > 0
+    return v, polys
+
+
+def _ascii61(name, up_axis, translation, rotation, scaling, v, polys, normals):
+    """A minimal ASCII FBX 6.1 file (the layout Blender writes): one Model of type Mesh, ByVertice normals."""
+    num = lambda a: ",".join(np.format_float_positional(float(x), unique=True) for x in np.ravel(a))
+    pvi = [i for p in polys for i in p[:-1] + [~p[-1]]]
+    prop = lambda key, val: '\t\t\tProperty: "%s", "%s", "A+",%s\n' % (key, key, num(val))
+    return ('; FBX 6.1.0 project file\nFBXHeaderExtension:  {\n\tFBXVersion: 6100\n}\nObjects:  {\n\tModel: "Model::%s", "Mesh" {\n\t\tVersion: 232\n'
+            '\t\tProperties60:  {\n%s%s%s\t\t}\n\t\tVertices: %s\n\t\tPolygonVertexIndex: %s\n\t\tLayerElementNormal: 0 {\n'
+            '\t\t\tMappingInformationType: "ByVertice"\n\t\t\tReferenceInformationType: "Direct"\n\t\t\tNormals: %s\n\t\t}\n\t}\n}\n'
+            'GlobalSettings:  {\n\tProperties60:  {\n\t\tProperty: "UpAxis", "int", "",%d\n\t}\n}\n'
+            % (name, prop("Lcl Translation", translation), prop("Lcl Rotation", rotation), prop("Lcl Scaling", scaling),
+               num(v), ",".join(str(i) for i in pvi), num(normals), up_axis))
+
+
+def test_fbx_import_of_the_reference_assets(xrt, tmp_path):
+    """Asset ingestion (fbx.py), without the reference's files (they are not part of the repository): the crate's FBX
+    data (fixtures.py) written as binary FBX 6100 parses back exactly and imports to exactly the crate fixture; an ASCII FBX 6.1 file
+    of the shape the content project's Blender exports have (Y-up, node rotation -90 about X, ByVertice normals) parses back exactly,
+    imports with winding that agrees with its normals, and the ModelProcessor rotation of 180 degrees about Y mirrors x and z."""
     import importlib
     fbx = importlib.import_module("xna-ray-trace_amd.fbx")
-    cm, up = fbx.load_fbx(os.path.join(REF_CONTENT, "Crate_Fragile.FBX"))
-    assert up == 2 and cm[0].normal_mapping == "ByPolygonVertex"
-    got, ref = fbx.import_mesh(cm[0], up, scale=0.6, apply_node_transform=False), xrt.fixtures.crate(1)
-    for f in ("v", "n", "uv", "surface_normal", "bbox"):
-        assert np.array_equal(getattr(got, f), getattr(ref, f)), f
-    sm, up = fbx.load_fbx(os.path.join(REF_CONTENT, "Sphere.fbx"))
-    sph = fbx.import_mesh(sm[0], up, scale=2.0, diffuse_color=(255, 0, 0, 100))
-    z = np.load(os.path.join(ROOT, "tests", "golden", "sphere_mesh.npz"))
-    assert sph.ntri == 960 and np.array_equal(sph.v, z["v"]) and np.array_equal(sph.n, z["n"]) and np.array_equal(sph.color, z["color"])
-    assert ((sph.surface_normal * sph.n[:, 0, :]).sum(axis=1) > 0.9).all()      # winding agrees with the exported normals (K4)
-    for name, ntri in (("torus.fbx", 1152), ("cube.fbx", 12), ("ground.fbx", 2)):
-        ms, up = fbx.load_fbx(os.path.join(REF_CONTENT, name))
-        assert fbx.import_mesh(ms[0], up).ntri == ntri
-    # ModelProcessor rotation parameters (contentproj:112-122,186-195,197-206): prism2 and chesspiece equal their committed
-    # fixtures, a rotation of 180 degrees about Y mirrors x and z of the unrotated import, winding still agrees with the normals
-    zc = np.load(os.path.join(ROOT, "tests", "golden", "content_meshes.npz"))
-    for name, asset, kw in (("prism", "prism2.fbx", dict(rotation=(-90.0, 0.0, 0.0), diffuse_color=(255, 255, 255, 100))),
-                            ("chesspiece", "chesspiece.fbx", dict(scale=3.0, rotation=(-90.0, 0.0, 0.0)))):
-        ms, up = fbx.load_fbx(os.path.join(REF_CONTENT, asset))
-        got = fbx.import_mesh(ms[0], up, **kw)
-        assert np.array_equal(got.v, zc[name + "_v"]) and np.array_equal(got.n, zc[name + "_n"]) and np.array_equal(got.color, zc[name + "_color"])
-        assert ((got.surface_normal * got.n[:, 0, :]).sum(axis=1) > 0).mean() > 0.99
-    # binary FBX 7.1 (zlib-compressed arrays, Geometry -> Model connections): the last two of the content directory's 17 files
-    ms, up = fbx.load_fbx(os.path.join(REF_CONTENT, "dna_exported_from_max2011.FBX"))
-    assert len(ms) == 40 and all(len(m.polygons) == 1596 for m in ms[:3])
-    dna = fbx.import_mesh(ms[0], up)
-    assert dna.ntri == 1728 and ((dna.surface_normal * dna.n[:, 0, :]).sum(axis=1) > 0).all()
-    ms, up = fbx.load_fbx(os.path.join(REF_CONTENT, "Sony_3D_Logo_by_Peter_Iliev_fbx.FBX"))
-    assert len(ms) == 1 and fbx.import_mesh(ms[0], up).ntri == 3268
-    import glob
-    files = sorted(glob.glob(os.path.join(REF_CONTENT, "*.fbx")) + glob.glob(os.path.join(REF_CONTENT, "*.FBX")))
-    assert len(files) == 17 and all(len(fbx.load_fbx(f)[0]) >= 1 for f in files)
-    ms, up = fbx.load_fbx(os.path.join(REF_CONTENT, "wossy.fbx"))
-    plain, turned = fbx.import_mesh(ms[0], up, scale=32.0), fbx.import_mesh(ms[0], up, scale=32.0, rotation=(0.0, 180.0, 0.0))
-    assert turned.ntri == plain.ntri == 9420
-    assert np.allclose(turned.v[..., 0], -plain.v[..., 0], atol=2e-4) and np.allclose(turned.v[..., 2], -plain.v[..., 2], atol=2e-4)
+    fx = xrt.fixtures
+    data, pvi, normals = _fbx6100_crate_bytes(xrt)
+    f = tmp_path / "Crate_Fragile.FBX"
+    f.write_bytes(data)
+    cm, up = fbx.load_fbx(str(f))
+    assert up == 2 and len(cm) == 1 and cm[0].normal_mapping == "ByPolygonVertex" and cm[0].translation == (0.0, 8.6e-07, 0.0)
+    assert np.array_equal(cm[0].vertices, np.array(fx.CRATE_VERTICES, dtype=np.float64)) and cm[0].polygons == [list(q) for q in fx.CRATE_QUADS]
+    assert np.array_equal(cm[0].normals.ravel(), normals) and np.array_equal(cm[0].uvs, np.array(fx.CRATE_UVS)) and cm[0].uv_index == [0, 1, 2, 3] * 6
+    got, ref = fbx.import_mesh(cm[0], up, scale=fx.CRATE_SCALE, apply_node_transform=False), fx.crate(1)
+    for a in ("v", "n", "uv", "surface_normal", "bbox"):
+        assert np.array_equal(getattr(got, a), getattr(ref, a)), a
+    v, polys = _globe()
+    tr, rot, sc = (0.25, -0.5, 1.0), (-90.00000933453802, 0.0, 0.0), (1.0, 1.0, 1.0)
+    f = tmp_path / "globe.fbx"
+    f.write_text(_ascii61("globe", 1, tr, rot, sc, v, polys, v))
+    ms, up = fbx.load_fbx(str(f))
+    assert up == 1 and len(ms) == 1 and ms[0].normal_mapping == "ByVertice" and ms[0].polygons == polys
+    assert np.array_equal(ms[0].vertices, v) and np.array_equal(ms[0].normals, v)
+    assert (ms[0].translation, ms[0].rotation, ms[0].scaling) == (tr, rot, sc)
+    plain = fbx.import_mesh(ms[0], up, scale=2.0, diffuse_color=(255, 0, 0, 100))
+    turned = fbx.import_mesh(ms[0], up, scale=2.0, diffuse_color=(255, 0, 0, 100), rotation=(0.0, 180.0, 0.0))
+    ntri = sum(len(p) - 2 for p in polys)
+    assert plain.ntri == turned.ntri == ntri
+    assert np.array_equal(plain.color, np.tile(np.array([255, 0, 0, 100], dtype=np.float32) / np.float32(255.0), (ntri, 1)))
+    for m in (plain, turned):
+        assert ((m.surface_normal * m.n[:, 0, :]).sum(axis=1) > 0.9).all()      # winding agrees with the exported normals (K4)
+    assert np.allclose(turned.v[..., 0], -plain.v[..., 0], atol=1e-6) and np.allclose(turned.v[..., 2], -plain.v[..., 2], atol=1e-6)
     assert np.array_equal(turned.v[..., 1], plain.v[..., 1])
 
 

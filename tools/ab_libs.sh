@@ -5,7 +5,7 @@
 LIBS=${1:-libxrt.so}; CFGS=${2:-C3 C4 C5}; ROUNDS=${3:-2}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 for i in $(seq 1 $ROUNDS); do for c in $CFGS; do for l in $LIBS; do
-  XRT_LIB_VARIANT=$l timeout -k 10 120 python3 $R/bench.py --config $c --no-extra --no-cpu --no-host --steps 30 --warmup 5 2>/dev/null | python3 -c "
+  XRT_LIB_VARIANT=$l timeout -k 10 120 python3 $R/bench.py --full --config $c --no-extra --no-cpu --no-host --steps 30 --warmup 5 2>/dev/null | python3 -c "
 import sys, json
 for x in sys.stdin:
     if x.startswith('{'):

@@ -4,7 +4,7 @@
 
 <dir> holds one sub-directory per pass, named pmc_<pass>_<config> (tools/refresh_profiles.sh): separate passes for FETCH_SIZE,
 WRITE_SIZE (they do not fit one pass, MI355X_MICROARCH.md "rocprofv3 PMC slots") and the SQ set.  Per config the counters are
-averaged over ALL traversal dispatches (k_intersect, the per-lane kernel, and k_packet, the wave-packet kernel) of `bench.py --config <config>` (every frame has the same launches).  FETCH_SIZE /
+averaged over ALL traversal dispatches (k_intersect, the per-lane kernel, and k_packet, the wave-packet kernel) of `bench.py --full --config <config>` (every frame has the same launches).  FETCH_SIZE /
 WRITE_SIZE are in KB; on gfx950 FETCH_SIZE tallies 128-byte requests at 64 bytes, so bench.py doubles it (MI355X_MICROARCH.md, HBM).
 The file is stamped with the hash of the kernel sources: bench.py quotes it only for that build."""
 import argparse, collections, csv, glob, json, os, re, sys
@@ -69,7 +69,7 @@ def main():
                 for (g, k), v in gt.items():
                     groups[g][k + "_KB" if k in ("FETCH_SIZE", "WRITE_SIZE") else k] = v / gn[(g, k)]
     out = {"build_id": build_id(), "kernel": args.kernel,
-           "note": "per traversal launch (k_intersect and k_packet together), averaged over every launch of `bench.py --config <cfg> --no-extra --no-cpu --no-host` under rocprofv3 --pmc "
+           "note": "per traversal launch (k_intersect and k_packet together), averaged over every launch of `bench.py --full --config <cfg> --no-extra --no-cpu --no-host` under rocprofv3 --pmc "
                    "(separate passes: FETCH_SIZE | WRITE_SIZE | SQ_*); FETCH_SIZE/WRITE_SIZE in KB, FETCH_SIZE counts half of streamed read bytes on gfx950",
            "configs": configs}
     need = ("FETCH_SIZE_KB", "WRITE_SIZE_KB", "SQ_INSTS_VALU", "SQ_THREAD_CYCLES_VALU")

@@ -4,7 +4,7 @@ gfx950: FETCH_SIZE tallies 128-byte read requests at 64 bytes, so streamed reads
 import csv, glob, json, sys
 out = sys.argv[1]
 res = {"note": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, kernel k_intersect only), KB per launch averaged over all launches of "
-               "`bench.py --config <cfg> --no-extra --no-cpu --steps 10 --warmup 2`; gfx950 correction: FETCH_SIZE counts 1/2 of streamed read bytes "
+               "`bench.py --full --config <cfg> --no-extra --no-cpu --steps 10 --warmup 2`; gfx950 correction: FETCH_SIZE counts 1/2 of streamed read bytes "
                "(MI355X_MICROARCH.md HBM section) -> traffic = (2*FETCH_SIZE + WRITE_SIZE) * 1024 bytes per launch"}
 for cfg in ("C2", "C3", "C5_1spp"):
     vals = {}
