@@ -119,6 +119,11 @@ namespace RayTraceProject.Native
                                                                             IntPtr dGathered, long rankStride, IntPtr dRgbaOut, IntPtr stream);
         // the primary rays of RayTracer.Render (RayTracer.cs:410-421), row-major
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_generate_primary_rays(IntPtr scene, ref XrtCamera camera, [Out] XrtRay[] raysOut);
+        // RayTracer.CastRay (RT:506) on caller-given rays, one recursion each (additive within ABI 203); INTEGRATION.md shows the n = 1 forwarding
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern unsafe int xrt_cast_rays(IntPtr scene, [In] XrtRay[] rays, long n, int iteration, float currentRefIndex,
+                                                                      XrtLight[] lights, int nLights, ref XrtRenderOpts opts, uint* rgbaOut, float* rgbF32Out, IntPtr stats);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_cast_rays_device(IntPtr scene, IntPtr dRays, long n, int iteration, float currentRefIndex,
+                                                                      XrtLight[] lights, int nLights, ref XrtRenderOpts opts, IntPtr dRgbaOut, IntPtr dRgbF32Out, IntPtr stream, IntPtr stats);
         // can n_gpus > 1 load RCCL?  OK or E_RCCL (-6) with the loader's message; no device is touched
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_rccl_probe();
         // diagnostics of the split walks of long packets (results never depend on them): subtrees handed over, taken, packets split, packets written by a taker

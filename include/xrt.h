@@ -380,6 +380,36 @@ float xrt_progress(const xrt_scene *scene);
 /* Primary rays of RayTracer.Render (RT:410-421): two Viewport.Unproject per pixel, row-major. */
 int xrt_generate_primary_rays(xrt_scene *scene, const xrt_camera *camera, xrt_ray *rays_out /* W*H */);
 
+/* ---- seam 3: RayTracer.CastRay (RT:506-737) on caller-given rays, batched ----------------------------------------------
+ * Added within ABI 203: these two exports are additive; no existing struct, field or entry point changed.
+ * For every i: CastRay(ref rays[i], out color, iteration, origin, null, current_ref_index) -- one recursion per ray, with lights,
+ * shadow rays, reflections, refraction (a ray tree on Transparent materials) and the RGBA8 quantisation of every level.
+ * origin = (rays[i].ignore_mesh, rays[i].ignore_tri), or null when ignore_tri < 0 (the convention of xrt_scene_intersect); a
+ * non-negative ignore_tri that names no triangle of the scene is XRT_E_INVALID_ARG here (xrt_cast_rays_device cannot look at the
+ * rays: it treats such an origin as null).  ignoreObject is not taken: it is a Mesh compared with ISpatialBodies and never matches
+ * (OSM:343).  The ray is used as given: it is not normalised (CastRay does not normalise it).
+ * Depth: CastRay from `iteration` reflects while iteration < MaxReflections (RT:545), i.e. a frame's recursion of
+ * max(0, max_reflections - iteration) generations; above 64 that is XRT_E_INVALID_ARG, and with Transparent materials above 12
+ * XRT_E_UNSUPPORTED, as for frames.  An iteration at or above max_reflections casts no reflection.
+ * current_ref_index is the first generation's currentRefIndex (RT:658: equal to a material's RefractionIndex means "inside"); a
+ * frame passes 1.0f (RT:424).
+ * opts: max_reflections / address_mode / filtering / collect_stats as for a frame; use_multisampling must be XRT_MS_OFF, shard_count
+ * and n_gpus 0 or 1 (else XRT_E_INVALID_ARG).
+ * rgba_out[i] = the packed Color; rgb_f32_out[i*3 ..] (may be NULL) = the vector handed to `new Color(...)` (RT:705/726/732), as in
+ * xrt_render.  stats_out (may be NULL): pixels = n; rays_closest, rays_shadow, hits_closest and shaded_hits always; hits_shadow and
+ * the reference work counters with collect_stats (as for frames).  n == 0 does nothing and returns XRT_OK.  Blocking; XRT_E_BUSY under the rule of xrt_render (RT:62-63):
+ * while another call renders on the scene or a begin/end ticket is open. */
+int xrt_cast_rays(xrt_scene *scene, const xrt_ray *rays, int64_t n, int32_t iteration, float current_ref_index,
+                  const xrt_light *lights, int32_t n_lights, const xrt_render_opts *opts,
+                  uint32_t *rgba_out, float *rgb_f32_out, xrt_stats *stats_out /* nullable */);
+
+/* The same on HBM buffers (d_rays: n xrt_ray, d_rgba_out: n words, d_rgb_f32_out: NULL or 3n floats; each 16-byte aligned, else
+ * XRT_E_INVALID_ARG), enqueued on `stream` (a hipStream_t; NULL = the scene's stream) and synchronised before it returns, like
+ * xrt_render_device.  The rays must be ready on `stream`. */
+int xrt_cast_rays_device(xrt_scene *scene, const void *d_rays, int64_t n, int32_t iteration, float current_ref_index,
+                         const xrt_light *lights, int32_t n_lights, const xrt_render_opts *opts,
+                         void *d_rgba_out, void *d_rgb_f32_out, void *stream, xrt_stats *stats_out /* nullable */);
+
 #ifdef __cplusplus
 }
 #endif

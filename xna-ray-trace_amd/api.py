@@ -542,6 +542,44 @@ class RayTracer:
         begin.begin, begin.end = begin, end
         return begin
 
+    # ---- RayTracer.CastRay (RT:506-737) on caller-given rays: xrt_cast_rays ----
+    def CastRays(self, rays, iteration=0, currentRefIndex=1.0, want_float=False, device=False, stream=None):
+        """CastRay(ref rays[i], out color, iteration, origin_i, null, currentRefIndex) for every ray of a batch, origin_i = the ray's
+        (ignore_mesh, ignore_tri).  Host form: `rays` an xrt_ray array (RAY_DTYPE) -> uint32 colours (and float32 (n, 3) colour vectors
+        with want_float).  device=True: `rays` a contiguous CUDA tensor of n 32-byte records (e.g. (n, 8) float32) -> torch tensors on
+        its device (int32 holding the packed colours; float32 (n, 3)), enqueued on `stream` (a torch stream, default: the current one)."""
+        opts, lights = self._opts_abi(shard_count=0), self._lights_abi()
+        opts.n_gpus = 0
+        st, lib = abi.xrt_stats(), abi.lib()
+        if device:
+            import torch
+            if not rays.is_contiguous() or rays.numel() * rays.element_size() % 32:
+                raise ValueError("rays: a contiguous tensor of 32-byte xrt_ray records")
+            n = rays.numel() * rays.element_size() // 32
+            rgba = torch.empty(n, dtype=torch.int32, device=rays.device)
+            rgbf = torch.empty((n, 3), dtype=torch.float32, device=rays.device) if want_float else None
+            s = stream if stream is not None else torch.cuda.current_stream(rays.device)
+            abi.check(lib.xrt_cast_rays_device(self.CurrentScene.handle, C.c_void_p(rays.data_ptr()), n, int(iteration), float(currentRefIndex),
+                                               lights, len(self.Lights), C.byref(opts), C.c_void_p(rgba.data_ptr()),
+                                               C.c_void_p(rgbf.data_ptr()) if want_float else None, C.c_void_p(s.cuda_stream), C.byref(st)))
+        else:
+            rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+            n = rays.shape[0]
+            rgba = np.zeros(n, dtype=np.uint32)
+            rgbf = np.zeros((n, 3), dtype=np.float32) if want_float else None
+            abi.check(lib.xrt_cast_rays(self.CurrentScene.handle, rays.ctypes.data_as(C.POINTER(abi.xrt_ray)), n, int(iteration), float(currentRefIndex),
+                                        lights, len(self.Lights), C.byref(opts), rgba.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                        _fp(rgbf) if want_float else None, C.byref(st)))
+        self.last_stats = st.as_dict()
+        return (rgba, rgbf) if want_float else rgba
+
+    def CastRay(self, ray, iteration=0, origin=None, currentRefIndex=1.0, want_float=False):
+        """RT:506: one ray = (position, direction) -> the packed Color (and its float colour vector with want_float).  origin: the
+        triangle the ray leaves, (mesh, index in Mesh.Triangles[]) as GetRayIntersection's ignoreTriangle, or None."""
+        im, it = (-1, -1) if origin is None else (self.CurrentScene.mesh_id(origin[0]), int(origin[1]))
+        out = self.CastRays(rays_array([ray[0]], [ray[1]], im, it), iteration, currentRefIndex, want_float)
+        return (int(out[0][0]), out[1][0]) if want_float else int(out[0])
+
     def GeneratePrimaryRays(self):
         """The rays of RT:410-421 for the whole target."""
         cam = self._camera_abi()

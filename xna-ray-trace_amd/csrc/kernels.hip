@@ -664,13 +664,83 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_raygen(RayGenParams g, SceneVi
         __syncthreads();   // the cells are reused by the next group
     }
 }
+// Generation 0 from a caller's ray list (xrt_cast_rays: RayTracer.CastRay, RT:506, on every ray) instead of the camera: path p of the pass is
+// ray g.batch[pathBase + p], used as given (CastRay does not normalise it).  Everything else is k_raygen's: a ray that cannot reach the
+// scene octree's root box is answered here (OSM:318-320), the others are compacted into the live list with one atomic per block and
+// group, and the long ones are listed.  The origin triangle travels in the ray record -- a name that is no triangle of the scene is
+// null, as the reference's caller would have passed it (tests: ResolveIgnore) -- with the long-ray mark of a reflection (tri ^ HEAVY_BIT).
+// A ray-tree pass also gets the ray's curRef (ShadeArgs::rayRef at generation 0: the caller's currentRefIndex, RT:658).
+__global__ __launch_bounds__(APPEND_BLOCK) void k_ingest(RayGenParams g, SceneView S, xrt_ray *rays, f4 *lvlB0, int *index, int *count, int P,
+                                                         long long pathBase, HeavyArgs H, int liveCap) {
+    __shared__ int ldsLive[RG_ROUNDS * 16], ldsHeavy[RG_ROUNDS * 16];
+    const f4 rlo = S.snodes[0], rhi = S.snodes[1];
+    const int span = RG_ROUNDS * APPEND_BLOCK;
+    const int groups = (P + span - 1) / span;
+    const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
+    for (int grp = (int)blockIdx.x; grp < groups; grp += (int)gridDim.x) {
+        int liveAt[RG_ROUNDS], heavyAt[RG_ROUNDS];
+        f4 keepA[RG_ROUNDS], keepB[RG_ROUNDS];   // the live rays of this thread as they will be stored
+#pragma unroll
+        for (int r = 0; r < RG_ROUNDS; r++) {
+            const int p = grp * span + r * APPEND_BLOCK + (int)threadIdx.x;
+            bool live = false, heavy = false;
+            keepA[r] = f4{0, 0, 0, 0}; keepB[r] = f4{0, 0, 0, 0};
+            if (p < P) {
+                const f4 *src = g.batch + 2 * (size_t)(pathBase + p);
+                const f4 a = src[0], b = src[1];   // o.xyz d.x | d.yz ignore_mesh ignore_tri
+                const v3 o = mk(a.x, a.y, a.z), d = mk(a.w, b.x, b.y);
+                int im = f2i(b.z), it = f2i(b.w);
+                if (it < 0 || im < 0 || im >= S.nMeshes || it >= S.meshes[im].ntri) { im = -1; it = -1; }
+                RayPre w = make_ray(o, d);
+                float key;
+                live = slab(w, rlo.x, rlo.y, rlo.z, rhi.x, rhi.y, rhi.z, key);   // OSM:460 on the root
+                heavy = live && H.list && long_ray(S, H, p, o, d);
+                keepA[r] = a;
+                keepB[r] = f4{b.x, b.y, i2f(im), i2f(heavy ? (it ^ HEAVY_BIT) : it)};
+                if (!live) lvlB0[p] = f4{0, 0, 0, i2f(FLAG_MISS)};   // generation 0 ends here (RT:729-733)
+            }
+            const unsigned long long ml = __ballot(live), mh = __ballot(heavy);
+            liveAt[r] = live ? lanes_below(ml) : -1;
+            heavyAt[r] = heavy ? lanes_below(mh) : -1;
+            if (lane == 0) { ldsLive[r * 16 + wave] = (int)__popcll(ml); ldsHeavy[r * 16 + wave] = (int)__popcll(mh); }
+        }
+        __syncthreads();
+        if (wave < 2 && (wave == 0 || H.list)) {   // wave 0 reserves the block's range of the live list, wave 1 of the long-ray list
+            int *cells = wave == 0 ? ldsLive : ldsHeavy;
+            const int c = cells[lane];
+            const int incl = wave_scan_add(c);
+            const int total = __builtin_amdgcn_readlane(incl, 63);
+            int base = 0;
+            if (lane == 0 && total) base = atomicAdd(wave == 0 ? count : H.count, total);
+            base = __builtin_amdgcn_readfirstlane(base);
+            cells[lane] = base + incl - c;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < RG_ROUNDS; r++) {
+            const int p = grp * span + r * APPEND_BLOCK + (int)threadIdx.x;
+            if (liveAt[r] >= 0) {
+                const int slot = ldsLive[r * 16 + wave] + liveAt[r];
+                if (slot < liveCap) {
+                    index[slot] = p;
+                    f4 *dst = reinterpret_cast<f4 *>(rays + slot);
+                    dst[0] = keepA[r]; dst[1] = keepB[r];
+                    if (g.batchRef) g.batchRef[slot] = g.batchRefIndex;
+                    if (heavyAt[r] >= 0) H.list[ldsHeavy[r * 16 + wave] + heavyAt[r]] = slot;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
 void launch_raygen(const RayGenParams &g, const SceneView &S, xrt_ray *rays, f4 *lvlB0, int *index, int *count, int P, long long pathBase,
                    const HeavyArgs &H, hipStream_t st, hipEvent_t startEvent, int liveCap) {
     static_assert(RG_ROUNDS * 16 == 64, "one wave scans the block's cells");
     int blocks = (P + RG_ROUNDS * APPEND_BLOCK - 1) / (RG_ROUNDS * APPEND_BLOCK);
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
-    hipExtLaunchKernelGGL(k_raygen, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap);
+    if (g.batch) hipExtLaunchKernelGGL(k_ingest, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap);
+    else hipExtLaunchKernelGGL(k_raygen, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap);
 }
 
 // ---- shading ----------------------------------------------------------------------------------------------------------

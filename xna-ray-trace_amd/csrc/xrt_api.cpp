@@ -265,6 +265,9 @@ struct xrt_scene {
     // per-frame work buffers
     DevBuf<xrt_ray> apiRays;
     DevBuf<xrt_hit> apiHits;
+    DevBuf<xrt_ray> castRays;     // xrt_cast_rays: the host's rays and their colours
+    DevBuf<uint32_t> castRGBA;
+    DevBuf<float> castF32;
     DevBuf<unsigned> queues;
     DevBuf<uint32_t> outRGBA;
     DevBuf<float> outF32;
@@ -436,7 +439,7 @@ struct xrt_scene {
             blocks.release(); leafNB.release(); leafTB.release(); refT.release(); refN.release(); refG.release(); snodes.release(); shade.release();
             childDfs.release(); srefs.release(); scull.release(); runTB.release(); triTB.release(); runBase.release(); pblocks.release(); lrec.release(); objMesh.release(); meshes.release();
             objects.release(); materials.release(); texels.release();
-            apiRays.release(); apiHits.release();
+            apiRays.release(); apiHits.release(); castRays.release(); castRGBA.release(); castF32.release();
 
             queues.release(); outRGBA.release(); outF32.release(); counters.release(); costMap.release(); waveTimes.release();
         }
@@ -597,6 +600,7 @@ int make_raygen(const xrt_camera *cam, const xrt_render_opts *o, RayGenParams &g
     g.cullSkipsRecord = 0;
     g.pathsDev = nullptr; g.pathsMul = 1; g.pathsCap = 0;
     g.tileOfSlot = nullptr;
+    g.batch = nullptr; g.batchRef = nullptr; g.batchRefIndex = 1.0f;
     if (g.shardRank < 0 || g.shardRank >= g.shardCount) return fail(XRT_E_INVALID_ARG, "shard_rank out of range");
     if (rootBox) {
         // Screen rectangle of the scene's root box.  A ray through pixel (x, y) that reaches the box at a point P has P
@@ -639,14 +643,24 @@ int make_raygen(const xrt_camera *cam, const xrt_render_opts *o, RayGenParams &g
 int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats);
 int split_arena(xrt_scene *s, DevBuf<unsigned> &items, DevBuf<unsigned> &recs, PacketArgs &PA, hipStream_t st);
 
+// A caller's ray list as the ray source of a pass (xrt_cast_rays): n rays in HBM, 16-byte aligned, and generation 0's curRef.
+struct BatchSrc {
+    const xrt_ray *rays = nullptr;
+    long long n = 0;
+    float refIndex = 1.0f;
+};
+
 // Enqueues one frame on `st`.  On return the frame's kernels and its counter read-back are in flight (F.pending);
 // frame_finish waits for them.  Adaptive supersampling and ray-tree frames need host decisions between their passes and
 // are complete when this returns.
+// batch != null: the paths are the batch's rays instead of the camera's pixels (cam is not read): one sample each, path p = ray p, no tiles,
+// no screen rectangle, no level map; d_out[p] / d_outF32[3p..] receive ray p's colour.  Such a pass takes the careful way (!fast): its
+// counters are read back per chunk, a ray tree is checked for overflow and retried chunk by chunk.
 int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, const xrt_light *lights, int nLights, const xrt_render_opts *opts,
-                uint32_t *d_out, float *d_outF32, hipStream_t st, int part = 0, int nParts = 1, bool heapFastAllowed = true) {
+                uint32_t *d_out, float *d_outF32, hipStream_t st, int part = 0, int nParts = 1, bool heapFastAllowed = true, const BatchSrc *batch = nullptr) {
     const bool stats = true;   // the read-back is two small pinned copies; always taken
     xrt_scene::WorkBufs &W = F.w;
-    if (!cam || !opts || (!lights && nLights > 0) || nLights < 0) return fail(XRT_E_INVALID_ARG, "xrt_render: null argument");
+    if ((!cam && !batch) || !opts || (!lights && nLights > 0) || nLights < 0) return fail(XRT_E_INVALID_ARG, "xrt_render: null argument");
     if (opts->max_reflections < 0 || opts->max_reflections > 64) return fail(XRT_E_INVALID_ARG, "max_reflections out of range");
     if (opts->address_mode < XRT_ADDRESS_CLAMP || opts->address_mode > XRT_ADDRESS_MIRROR)
         return fail(XRT_E_INVALID_ARG, "Value does not fall within the expected range: addressMode (MAT:85)");
@@ -667,22 +681,33 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         const f4 lo = s->host->arrays.snodes[0], hi = s->host->arrays.snodes[1];
         rootBox[0] = lo.x; rootBox[1] = lo.y; rootBox[2] = lo.z; rootBox[3] = hi.x; rootBox[4] = hi.y; rootBox[5] = hi.z;
     }
-    int rc = make_raygen(cam, opts, g, (haveRoot && !s->noRectCull) ? rootBox : nullptr);
-    if (rc != XRT_OK) return rc;
-    if (adaptive) g.samples = 4;
-    g.cullSkipsRecord = heap ? 0 : 1;   // (k_compose_tree reads every root record)
+    int rc = XRT_OK;
+    if (batch) {   // a ray list: one row of n "pixels", every path has its record (nothing is culled by a screen rectangle)
+        if (adaptive || msMode != XRT_MS_OFF || opts->shard_count > 1 || nParts > 1 || batch->n <= 0 || batch->n > 0x7fffffff / 2)
+            return fail(XRT_E_INTERNAL, "a ray batch is a plain pass of 1 .. 2^30 rays");
+        std::memset(&g, 0, sizeof(g));
+        g.width = (int)batch->n; g.height = 1; g.tilesX = (g.width + XRT_TILE_W - 1) / XRT_TILE_W; g.tilesY = 1;
+        g.shardCount = 1; g.samples = 1; g.quadLevel = -1; g.quadSize = 1.0f; g.pathsMul = 1;
+        g.cullX1 = g.width - 1;
+        g.batch = reinterpret_cast<const f4 *>(batch->rays); g.batchRefIndex = batch->refIndex;
+    } else {
+        rc = make_raygen(cam, opts, g, (haveRoot && !s->noRectCull) ? rootBox : nullptr);
+        if (rc != XRT_OK) return rc;
+        if (adaptive) g.samples = 4;
+        g.cullSkipsRecord = heap ? 0 : 1;   // (k_compose_tree reads every root record)
+    }
     const int R = opts->max_reflections;
     const int nL = nLights;
     const long long totalTiles = (long long)g.tilesX * g.tilesY;
     // an installed tile table for this frame geometry replaces the round-robin layout (xrt.h xrt_scene_set_tile_table)
-    const bool tabled = !s->tileTable.empty() && s->tableW == g.width && s->tableH == g.height && s->tableCount == g.shardCount;
+    const bool tabled = !batch && !s->tileTable.empty() && s->tableW == g.width && s->tableH == g.height && s->tableCount == g.shardCount;
     const int *const tableRow = tabled ? s->tileTable.data() + (size_t)g.shardRank * s->tableTpr : nullptr;
     g.tileOfSlot = tabled ? s->tileTableDev.p + (size_t)g.shardRank * s->tableTpr : nullptr;
     const long long myTiles = tabled ? s->tableTpr : shard_tiles_per_rank(totalTiles, g.shardCount, g.tilesX);   // tiles_per_rank (slots, some may be past the end)
     auto tile_of_slot = [&](long long sl) -> long long { return tabled ? (long long)tableRow[sl] : shard_tile(sl, g.shardRank, g.shardCount, g.tilesX); };
     const long long totalPixels = myTiles * 512;
     if (adaptive && totalPixels * 4 > 0x7fffffffLL) return fail(XRT_E_UNSUPPORTED, "frame too large for adaptive supersampling");
-    const long long framePaths = totalPixels * g.samples;   // the whole frame (this shard)
+    const long long framePaths = batch ? batch->n : totalPixels * g.samples;   // the whole frame (this shard)
     // part `part` of `nParts`: a contiguous range of the frame's paths (whole tiles), rendered by its own frame context
     const long long partStride = nParts > 1 ? ((framePaths / nParts + 8191) / 8192) * 8192 : framePaths;
     const long long partStart = (long long)part * partStride;
@@ -720,7 +745,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     // of the scene's root box, so a plain or 16-sub-ray frame of one chunk needs room for the rectangle's paths, not for every path
     // (C5: 52 % of the image); later generations have fewer rays than the one before.  (Adaptive frames: the deeper quadrant levels are
     // lists of up to a quadrant per pixel; ray trees: sized below.)
-    if (!heap && !adaptive && firstPaths <= chunkPaths) {
+    if (!heap && !adaptive && !batch && firstPaths <= chunkPaths) {
         const long long rectPaths = (long long)std::max(0, g.cullX1 - g.cullX0 + 1) * (long long)std::max(0, g.cullY1 - g.cullY0 + 1) * g.samples + 64;
         if (rectPaths < (long long)rayCap) { rayCap = (size_t)rectPaths; F.liveCap = rayCap; }
     }
@@ -753,7 +778,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     if ((unsigned long long)rayCap * (unsigned long long)(nL > 0 ? nL : 1) > (1ull << 30)) return fail(XRT_E_UNSUPPORTED, "frame too large: %zu rays x %d lights per generation", rayCap, nL);
     const size_t shadowCap = rayCap;   // hits of one generation (each emits nL shadow rays)
     const bool wantF32 = d_outF32 != nullptr && !adaptive && g.samples == 1;
-    const bool fuseResolve = !adaptive && !heap && g.samples == 1;   // k_compose writes the framebuffer itself
+    const bool fuseResolve = !adaptive && !heap && !batch && g.samples == 1;   // k_compose writes the framebuffer itself
     // buffers
     if ((rc = W.rays0.ensure(rayCap)) || (rc = W.rays1.ensure(rayCap)) || (rc = W.hits.ensure(rayCap)) || (rc = W.path0.ensure(rayCap)) ||
         (rc = W.path1.ensure(rayCap)) || (rc = W.hitFlags0.ensure(rayCap)) ||
@@ -771,7 +796,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
                  (rc = W.slotNode0.ensure(rayCap)) || (rc = W.slotNode1.ensure(rayCap)) ||
                  (rc = W.lvlAlpha.ensure((size_t)P * nodes))))
         return rc;
-    if (wantF32 && (rc = W.sampleF32.ensure((size_t)P * 3))) return rc;
+    if (wantF32 && !batch && (rc = W.sampleF32.ensure((size_t)P * 3))) return rc;   // (a batch's compose writes the caller's arrays)
     const int cntStride = 4 * (R + 2);          // per chunk: cnt[R+2], scnt[R+2], the long-ray list lengths [R+2], the shadow rays really emitted [R+2] (ShadeArgs::ae)
     constexpr int QW = 1 + 2 * PACKET_QUEUE_WORDS;   // per launch step k: the lane kernel's queue word and the heads of each packet launch (closest, shadow)
     const int qStride = QW * (R + 2);
@@ -787,10 +812,12 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     // pixel and level -- and a level that does not fit sets the same kind of word.
     const bool adaptiveFast = adaptive && !heap && heapFastAllowed && s->adaptiveFastOk && nParts == 1 && !opts->collect_stats && totalPixels * 4 <= chunkPaths &&
                               (quality + 2) * (R + 2) * 2 + 2 <= MAX_STAMP_ROWS;
-    const bool fast = (adaptive ? adaptiveFast : (!heap || heapFast)) && firstPaths <= chunkPaths && !opts->collect_stats;
+    const bool fast = (adaptive ? adaptiveFast : (!heap || heapFast)) && firstPaths <= chunkPaths && !opts->collect_stats && !batch;
     // Answered at emission (kernels.h ShadeArgs::ae): plain one-chunk frames of one-body scenes whose mesh CAN face away from a ray as a whole (its normal
     // box does not hold the origin).  Not with the counting pass -- it counts the reference's work for every query from the ray lists --, not for ray trees.
-    bool ae = fast && !heap && !adaptive && nParts == 1 && s->sceneMode == MODE_SINGLE && s->view.nodeCull != 0 && !s->noAnswerAtEmission;
+    // (a batch of one chunk too: what part A answers depends on the hits alone, not on where generation 0 came from)
+    bool ae = (fast || (batch && firstPaths <= chunkPaths && !opts->collect_stats)) && !heap && !adaptive && nParts == 1 && s->sceneMode == MODE_SINGLE &&
+              s->view.nodeCull != 0 && !s->noAnswerAtEmission;
     if (ae) {
         const MeshRec &m0 = s->host->arrays.meshes[0];
         ae = m0.nbMin[3] == 0.0f && (m0.nbMin[0] > 0.0f || m0.nbMax[0] < 0.0f || m0.nbMin[1] > 0.0f || m0.nbMax[1] < 0.0f || m0.nbMin[2] > 0.0f || m0.nbMax[2] < 0.0f);
@@ -857,7 +884,11 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     // is big enough for a launch to be more than its floor: G2 at 720p 1.12 -> 0.97 ms, the reference's default scene at 512x512 0.31 ->
     // 0.40 with packets, so not there; packets in every generation of a ray tree are 1.5-3 x slower (profiles/r03/packet_masks_ray_trees.txt))
     const int pkHeap = s->packetMaskHeap >= 0 ? s->packetMaskHeap : ((s->sceneMode == MODE_SCENE && (long long)g.width * g.height * g.samples >= 600000LL) ? 7 : 0);
-    const int pkMask = !s->packetOk ? 0 : (heap ? pkHeap : (s->packetMask >= 0 ? s->packetMask : pkAuto));
+    int pkMask = !s->packetOk ? 0 : (heap ? pkHeap : (s->packetMask >= 0 ? s->packetMask : pkAuto));
+    // A batch's generation 0 is in the caller's order, which nothing says is coherent: 64 consecutive rays need not be a patch of the same
+    // surface, and a packet of scattered rays walks the union of their paths.  It goes to the per-lane kernel unless XRT_PACKET / XRT_PACKET_HEAP
+    // name the packet kernel for it (bit 0; both kernels give the same answers).  Its later generations follow the hits as a frame's do.
+    if (batch && (heap ? s->packetMaskHeap : s->packetMask) < 0) pkMask &= ~1;
     const bool laneClosest = (pkMask & 5) != 5;   // some closest-hit generation is traced ray by ray: the long-ray feedback has a reader
     const bool wantFeedback = fast && !heap && !adaptive && s->deepMeshes && !s->noFeedback && laneClosest;   // (the paths of a deeper quadrant level are a list: no stable key)
     {   // The other context's frame may still be running on another stream.  Two single-chunk frames share nothing they
@@ -959,7 +990,9 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
             return H;
         };
         // cnt[0] counts the primary rays that reach the scene's root box; index0 lists them
-        { Range r("xrt raygen"); launch_raygen(gp, S, rays[0], W.lvlB.p, W.index0.p, cnt, Pc, pathBase, heavy_for(0), st, startEvent ? e0 : nullptr, (int)rayCap); startEvent = false; }
+        RayGenParams gb = gp;
+        if (gp.batch && heap) gb.batchRef = refOf[0];
+        { Range r("xrt raygen"); launch_raygen(gb, S, rays[0], W.lvlB.p, W.index0.p, cnt, Pc, pathBase, heavy_for(0), st, startEvent ? e0 : nullptr, (int)rayCap); startEvent = false; }
         // (one buffer serves every generation: the closest-hit answers of launch #k are read by part A of k_shade #k alone -- part B works from the
         // slot records -- and launch #k+1 starts after it on the frame's stream)
         xrt_hit *hitsOf[2] = {W.hits.p, W.hits.p};
@@ -1058,7 +1091,8 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
             X.maxReflections = R; X.P = (int)lvlStride; X.lvl = gp.lvl; X.heap = heap ? 1 : 0; X.overflow = overflowFlag;
             X.rays = rays[cur]; X.hits = hitsOf[cur]; X.hitFlags = flagsOf[cur]; X.shadowFlags = shadowFlagsOf[(k + 1) & 1]; X.nDev = nClosest; X.nHost = Pc; X.cap = (int)rayCap;
             X.index = nullptr; X.rayPath = k == 0 ? W.index0.p : paths[cur];   // (generation 0: the j-th live ray belongs to path index0[j])
-            X.rayNode = (heap && k > 0) ? nodesOf[cur] : nullptr; X.rayRef = (heap && k > 0) ? refOf[cur] : nullptr;
+            X.rayNode = (heap && k > 0) ? nodesOf[cur] : nullptr;
+            X.rayRef = (heap && (k > 0 || gp.batch)) ? refOf[cur] : nullptr;   // (a batch's generation 0 carries the caller's currentRefIndex, k_ingest)
             X.slotOut = slotOf[cur]; X.slotNodeOut = heap ? slotNodeOf[cur] : nullptr; X.scnt = scnt + k; X.shadowCap = (int)shadowCap; X.shadowRays = W.shadowRays.p;
             X.nextRays = rays[prv]; X.nextPath = paths[prv]; X.nextNode = heap ? nodesOf[prv] : nullptr; X.nextRef = heap ? refOf[prv] : nullptr;
             X.nextCnt = cnt + k + 1; X.nextCap = (int)rayCap;
@@ -1074,12 +1108,16 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
             }
         }
         Range rc_("xrt compose");
+        // a batch: path p of the chunk is ray pathBase + p, and the compose kernel writes its colour straight into the caller's arrays (a ray-tree chunk
+        // that overflowed is retried over the same range: the retry overwrites what the discarded attempt wrote)
+        uint32_t *const colorOut = gp.batch ? d_out + pathBase : (sampleOut ? sampleOut : W.sampleColor.p);
+        float *const f32Out = gp.batch ? (d_outF32 ? d_outF32 + 3 * (size_t)pathBase : nullptr) : (wantF32 ? W.sampleF32.p : nullptr);
         StampFold fold;
         fold.src = W.stamps.p; fold.host = F.stampHostDev; fold.row0 = chunkRow0; fold.row1 = F.stampRows;
         if (heap) {
             FrameEpilogue E;
             if (fast) { E.cntSrc = cnt; E.hostCnt = F.pinnedDev; E.cntWords = cntStride; E.zeroWords = cntStride + qStride; E.flagSrc = overflowFlag; }
-            launch_compose_tree(W.lvlA.p, W.lvlB.p, W.lvlAlpha.p, Pc, P, R, W.sampleColor.p, wantF32 ? W.sampleF32.p : nullptr, fold, E, st);
+            launch_compose_tree(W.lvlA.p, W.lvlB.p, W.lvlAlpha.p, Pc, P, R, colorOut, f32Out, fold, E, st);
         }
         else {
             ResolveArgs RA;
@@ -1087,7 +1125,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
             RA.stamps = fold;
             if (epi) { RA.cntSrc = epi->cntSrc; RA.hostCnt = epi->hostCnt; RA.cntWords = epi->cntWords; RA.zeroWords = epi->zeroWords; RA.zeroFrom = epi->zeroFrom; }
             else if (fast && !adaptive) { RA.cntSrc = cnt; RA.hostCnt = F.pinnedDev; RA.cntWords = cntStride; RA.zeroWords = cntStride + qStride; }
-            launch_compose(W.lvlA.p, W.lvlB.p, Pc, (int)lvlStride, R, sampleOut ? sampleOut : W.sampleColor.p, (wantF32 && !fuseResolve) ? W.sampleF32.p : nullptr, RA, st,
+            launch_compose(W.lvlA.p, W.lvlB.p, Pc, (int)lvlStride, R, colorOut, fuseResolve ? nullptr : f32Out, RA, st,
                            (fast && fuseResolve) ? e1 : nullptr);
         }
         return XRT_OK;
@@ -1198,6 +1236,16 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     // valid pixels of this shard
     unsigned long long &validPixels = F.validPixels;
     validPixels = 0;
+    if (batch) {   // path p is ray p: the compose kernels write the caller's arrays themselves (enqueue_chunk), nothing to do after a chunk
+        validPixels = (unsigned long long)batch->n;
+        livePaths = validPixels;
+        rc = run_pass(g, firstPaths, [&](int, long long) -> int { return XRT_OK; }, 0.0f, 1.0f, true);
+        if (rc != XRT_OK) return rc;
+        HIPCHECK(hipEventRecord(F.done, st));
+        HIPCHECK(hipGetLastError());
+        F.pending = true;
+        return XRT_OK;
+    }
     const long long slot0 = partStart / (512LL * g.samples), slot1 = (partStart + firstPaths + 512LL * g.samples - 1) / (512LL * g.samples);   // tile slots of this part
     for (long long sl = slot0; sl < slot1; sl++) {
         const long long t = tile_of_slot(sl);
@@ -1862,6 +1910,35 @@ int run_intersect(xrt_scene *s, const xrt_ray *d_rays, int64_t n, xrt_hit *d_hit
 
 // Host arrays of scene->host -> HBM of scene->device, launch geometry and scheduling defaults (second half of
 // xrt_scene_build; also what puts a replica of the scene on another device).
+// RayTracer.CastRay (RT:506-737) on n rays already in HBM: the pass of frame_begin with the batch as its ray source, MaxReflections - iteration
+// generations deep, then the pass's counters.  The caller holds the scene (BusyGuard, no frame in flight).
+int cast_rays_impl(xrt_scene *s, const xrt_ray *d_rays, int64_t n, int32_t iteration, float refIndex, const xrt_light *lights, int32_t nLights,
+                   const xrt_render_opts *opts, uint32_t *d_out, float *d_outF32, hipStream_t st, xrt_stats *stats) {
+    if (!opts) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: null opts");
+    if (opts->use_multisampling != XRT_MS_OFF) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: use_multisampling must be XRT_MS_OFF (one ray, one colour)");
+    if (opts->shard_count < 0 || opts->shard_count > 1) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: shard_count must be 0 or 1");
+    if (opts->n_gpus < 0 || opts->n_gpus > 1) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: n_gpus must be 0 or 1");
+    if (opts->max_reflections < 0) return fail(XRT_E_INVALID_ARG, "max_reflections out of range");
+    // CastRay(.., iteration, ..) reflects while iteration < MaxReflections (RT:545): a frame's recursion of max(0, M - iteration) generations
+    const long long depth = std::max(0LL, (long long)opts->max_reflections - (long long)iteration);
+    if (depth > 64) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: max_reflections - iteration = %lld is above 64", depth);
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n == 0) return XRT_OK;
+    xrt_render_opts o = *opts;
+    o.max_reflections = (int32_t)depth;
+    o.use_multisampling = XRT_MS_OFF; o.shard_count = 0; o.shard_rank = 0; o.n_gpus = 0; o.balance_tiles = 0;
+    BatchSrc b;
+    b.rays = d_rays; b.n = n; b.refIndex = refIndex;
+    xrt_scene::FrameCtx &F = s->frames[0];
+    Range rf("xrt cast rays (%lld)", (long long)n);
+    int rc = frame_begin(s, F, nullptr, lights, nLights, &o, d_out, d_outF32, st, 0, 1, false, &b);
+    if (rc != XRT_OK) {
+        if (F.pending) (void)frame_finish(s, F, nullptr);
+        return rc;
+    }
+    return frame_finish(s, F, stats);
+}
+
 int scene_upload(xrt_scene *scene) {
     const SceneArrays &A = scene->host->arrays;
     scene->stackNeeded = (A.sceneDepth + 1) + (A.meshDepth + 1);
@@ -2334,6 +2411,59 @@ int xrt_split_stats(xrt_scene *scene, uint64_t out[4], int32_t reset) {
         if (packet_split_stats(v, reset != 0) != 0) return fail(XRT_E_HIP, "xrt_split_stats: %s", hipGetErrorString(hipGetLastError()));
         for (int i = 0; i < 4; i++) out[i] = v[i];
         return XRT_OK;
+    });
+}
+
+int xrt_cast_rays(xrt_scene *scene, const xrt_ray *rays, int64_t n, int32_t iteration, float current_ref_index, const xrt_light *lights, int32_t n_lights,
+                  const xrt_render_opts *opts, uint32_t *rgba_out, float *rgb_f32_out, xrt_stats *stats_out) {
+    return guarded("xrt_cast_rays", [&]() -> int {
+        int rc = need_device(scene, "xrt_cast_rays");
+        if (rc != XRT_OK) return rc;
+        if (n < 0 || n > 0x7fffffff / 2) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: n = %lld out of range", (long long)n);
+        if (!opts || (n > 0 && (!rays || !rgba_out)) || (!lights && n_lights > 0) || n_lights < 0) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: null argument");
+        // an origin is (mesh id, index in Mesh.Triangles[]) of a triangle of the scene, or null (ignore_tri < 0)
+        const auto &meshes = scene->host->arrays.meshes;
+        for (int64_t i = 0; i < n; i++) {
+            const xrt_ray &r = rays[i];
+            if (r.ignore_tri < 0) continue;
+            if (r.ignore_mesh < 0 || r.ignore_mesh >= (int)meshes.size() || r.ignore_tri >= meshes[(size_t)r.ignore_mesh].ntri)
+                return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: ray %lld names triangle %d of mesh %d, which does not exist", (long long)i, r.ignore_tri, r.ignore_mesh);
+        }
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        if (n > 0) {
+            if ((rc = scene->castRays.ensure((size_t)n)) || (rc = scene->castRGBA.ensure((size_t)n)) || (rgb_f32_out && (rc = scene->castF32.ensure((size_t)n * 3)))) return rc;
+            HIPCHECK(hipMemcpyAsync(scene->castRays.p, rays, (size_t)n * sizeof(xrt_ray), hipMemcpyHostToDevice, scene->stream));
+        }
+        if ((rc = cast_rays_impl(scene, scene->castRays.p, n, iteration, current_ref_index, lights, n_lights, opts, scene->castRGBA.p,
+                                 rgb_f32_out ? scene->castF32.p : nullptr, scene->stream, stats_out)))
+            return rc;
+        if (n > 0) {
+            HIPCHECK(hipMemcpyAsync(rgba_out, scene->castRGBA.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, scene->stream));
+            if (rgb_f32_out) HIPCHECK(hipMemcpyAsync(rgb_f32_out, scene->castF32.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, scene->stream));
+            HIPCHECK(hipStreamSynchronize(scene->stream));
+        }
+        return guards_check("end of a ray batch");
+    });
+}
+
+int xrt_cast_rays_device(xrt_scene *scene, const void *d_rays, int64_t n, int32_t iteration, float current_ref_index, const xrt_light *lights,
+                         int32_t n_lights, const xrt_render_opts *opts, void *d_rgba_out, void *d_rgb_f32_out, void *stream, xrt_stats *stats_out) {
+    return guarded("xrt_cast_rays_device", [&]() -> int {
+        int rc = need_device(scene, "xrt_cast_rays_device");
+        if (rc != XRT_OK) return rc;
+        if (n < 0 || n > 0x7fffffff / 2) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_device: n = %lld out of range", (long long)n);
+        if (!opts || (n > 0 && (!d_rays || !d_rgba_out)) || (!lights && n_lights > 0) || n_lights < 0) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_device: null argument");
+        if (((uintptr_t)d_rays & 15) || ((uintptr_t)d_rgba_out & 15) || ((uintptr_t)d_rgb_f32_out & 15))
+            return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        hipStream_t st = (hipStream_t)stream;
+        if (!st) st = scene->stream;
+        if ((rc = cast_rays_impl(scene, (const xrt_ray *)d_rays, n, iteration, current_ref_index, lights, n_lights, opts, (uint32_t *)d_rgba_out,
+                                 (float *)d_rgb_f32_out, st, stats_out)))
+            return rc;
+        return guards_check("end of a ray batch");
     });
 }
 

@@ -468,6 +468,11 @@ struct RayGenParams {
     // min(*pathsDev, pathsCap) * pathsMul paths; null: the host's count
     const int *pathsDev;
     int   pathsMul, pathsCap;
+    // A caller's ray list instead of the camera (xrt_cast_rays, RT:506 on every ray; kernels.hip k_ingest): path p of the pass is the
+    // 32-byte xrt_ray record batch[2 * (pathBase + p)], batch[2 * (pathBase + p) + 1].  null: the camera above
+    const f4 *batch;
+    float *batchRef;               // ray-tree passes: the curRef of every live ray of generation 0 (ShadeArgs::rayRef) -- batchRefIndex; null: not written
+    float batchRefIndex;
 };
 XRT_HD int pass_paths(const RayGenParams &g, int hostCount) {
     if (!g.pathsDev) return hostCount;
