@@ -699,3 +699,28 @@ def test_rccl_load_failure_is_an_error_code_not_a_crash(xrt, tmp_path):
         assert out.returncode == 0, out.stderr[-2000:]
         rc, _, msg = out.stdout.strip().partition(" ")
         assert int(rc) == xrt.abi.XRT_E_RCCL and needle in msg and len(msg) > len(needle), out.stdout
+
+
+def test_env_switches_read_in_one_place_and_documented():
+    """libxrt reads its per-scene environment switches in csrc/settings.h only (read_settings, once per scene); elsewhere only the two
+    process-wide ones are read.  INTEGRATION.md's "Environment switches" table lists exactly the names the library reads."""
+    csrc = os.path.join(ROOT, "xna-ray-trace_amd", "csrc")
+    process_wide = {"XRT_ROCTX", "XRT_RCCL_LIB"}
+    read = set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".cpp", ".h", ".hip")):
+            continue
+        src = open(os.path.join(csrc, f)).read()
+        if f == "settings.h":
+            read |= set(re.findall(r'"(XRT_[A-Z0-9_]+)"', src))    # every name there is an argument of getenv or of a reader helper
+            continue
+        calls = re.findall(r"\bgetenv\s*\(([^)]*)\)", src)
+        others = [c for c in calls if c.strip('" ') not in process_wide]
+        assert not others, "%s reads the environment outside settings.h: %s" % (f, others)
+        read |= {c.strip('" ') for c in calls}
+    assert process_wide <= read and len(read) > 40, sorted(read)
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    table = doc.split("## Environment switches", 1)[1].split("\n## ", 1)[0]
+    listed = re.findall(r"^\| `(XRT_[A-Z0-9_]+)` \|", table, re.M)
+    assert len(listed) == len(set(listed)), sorted(listed)
+    assert set(listed) == read, {"undocumented": sorted(read - set(listed)), "not read": sorted(set(listed) - read)}

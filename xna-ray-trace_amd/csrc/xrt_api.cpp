@@ -26,6 +26,7 @@
 #include "kernels.h"
 #include "rccl_gather.h"
 #include "scene_host.h"
+#include "settings.h"
 
 using namespace xrt;
 
@@ -48,12 +49,6 @@ int fail(int code, const char *fmt, ...) {
             return fail(e_ == hipErrorOutOfMemory ? XRT_E_OOM : XRT_E_HIP, "%s failed: %s (%s:%d)", #expr,     \
                         hipGetErrorString(e_), __FILE__, __LINE__);                                            \
     } while (0)
-
-// Paths in flight per chunk (multiple of 512 * 16).  ~400 bytes of work buffers per path: 1920x1080 at 16 samples per
-// pixel (33.2 M paths) is one chunk of 13 GB per frame context -- sized for 288 GB of HBM, so that whole frames take the
-// single-chunk path (no host round trips, two frames overlapping).
-constexpr int MAX_CHUNK_PATHS = 1 << 25;
-constexpr int HEAP_RAY_CAP = 1 << 22;      // rays per generation of a ray-tree chunk
 
 // roctx ranges around the stages of a frame, for `rocprofv3 --marker-trace --kernel-trace`: XRT_ROCTX=1 loads the
 // marker library on first use (no load-time dependency, nothing is called otherwise).  The ranges bracket the ENQUEUE of a
@@ -200,7 +195,6 @@ struct RankWorker {
     }
 };
 
-constexpr int MAX_STAMP_ROWS = 256;   // traversal launches of one frame that can time themselves (kernels.h STAMP_*)
 struct xrt_scene {
     int device = -1;   // -1: host-only scene (inspection of the built trees; every compute call fails)
     HostScene hs;
@@ -220,46 +214,18 @@ struct xrt_scene {
     int stackNeeded = 2;
     int blocksPerCU = 1, blocksPerCUMesh = 1, blocksPerCUPacket = 1;
     bool packetOk = false;   // the scene's rays can take the wave-packet kernel (one body, one mesh with a real octree)
-    // Which ray populations take the wave-packet kernel.  -1 (default): all three of a frame with 16 sub-rays per pixel -- a wave
-    // then holds 4 pixels x 16 samples, rays that visit the same leaves (measured on the 1M-triangle frame: 7.3 against 11.1 ms);
-    // none otherwise (64 pixels of a 1-sample frame fan out over too many leaves: 5 x slower than the per-lane kernel).
-    // XRT_PACKET=<mask> forces it: bit 0 primary rays, 1 shadow rays, 2 closest-hit rays of later generations, 3 seam-1 batches,
-    // 4 bits 1 and 2 also apply beyond generation 1 (default: the first two generations and the first shadow rays only).
-    int packetMask = -1;
-    int packetMaskHeap = -1;   // the same for ray-tree frames (XRT_PACKET_HEAP; -1: by image size)
-    // Largest guided batch of k_intersect (XRT_BATCH_MAX).  Round 1 let a wave reserve up to 512 rays per atomic; per-wave clocks
-    // (make WAVE_TIMES=1, tools/wave_times.py) showed the median wave of a C3 / C4 launch leaving at 57 % of the launch and the
-    // tail growing with the frame size -- waves stuck with eight expensive rays per lane while the queue was empty.  64: C3 3.9 ->
-    // 3.4 ms, C4 11.4 -> 9.4 ms per blocking frame; 32 and 16 lose to contention on the queue word.
-    int batchMax = 64;
+    Settings cfg;   // the environment switches (settings.h): set once by xrt_scene_create (a replica's by ensure_replicas)
+    // Knobs of k_intersect that scene_upload derives from the scene where cfg does not name them (refill threshold: see there)
+    int refillMin = 24;
+    int heavyShift = 3;        // listed long rays are dealt one in 2^n work items (0: 64 to a wave); scene_upload: 0 for two-level scenes; XRT_HEAVY_SHIFT
+    int firstBatch = 64;
     // Sizes of the last finished single-chunk frame's generations (rays of traversal step k, work items of shade step k): the
     // launches of the next frame of the same geometry are sized for four times that instead of for the whole chip -- a generation
     // of a few thousand rays costs its kernels' launch floor (5-6 us each with full grids, C2: 0.119 -> 0.11 ms).  Sizing only.
     long long genKey = -1, genRays[68], genShade[68];
-    int batchMin = 64;         // XRT_BATCH_MIN (development)
-    // A launch of fewer rays than 64 per resident wave is dealt evenly over all waves in multiples of spreadMin instead of 64 to a
-    // wave: a batch takes as long as its slowest ray and longer the more rays diverge in it, and idle waves cost nothing -- the ten
-    // launches of a ray-tree frame of the reference's default scene: 1.05 -> 0.65 ms (XRT_SPREAD_MIN=64: as before).
-    int spreadMin = 4;
-    int heavyShift = 3;        // listed long rays are dealt one in 2^n work items (0: 64 to a wave); scene_upload: 0 for two-level scenes; XRT_HEAVY_SHIFT
-    bool heavyShiftGiven = false;
-    bool packetMerge = true;   // the closest-hit and the shadow packets of a step share one launch (XRT_PK_MERGE=0: two launches, as round 2)
-    bool noAnswerAtEmission = false;   // XRT_AE=0: k_shade emits every ray (kernels.h ShadeArgs::ae off)
-    int packetPrefetch = -1;   // XRT_PK_PREFETCH: -1 launches of fewer than packetPrefetchBelow packets per resident wave prefetch (kernels.h PacketArgs::prefetch), 0 never, 1 always
-    int packetPrefetchBelow = 12;
-    bool packetBundle = true;  // XRT_PK_BUNDLE=0: no bundle prefilter (kernels.h PacketArgs::bundle)
-    int packetCullMin = 4;     // XRT_PK_CULL_MIN (development): leaves with fewer references skip the tight-box test
-    // Split walks (packet.hip): one-body scenes; a packet / an item that has walked for this many microseconds looks for pending subtrees to hand to other waves
-    // (XRT_PK_SPLIT=0: off; XRT_PK_BUDGET / XRT_PK_BUDGET_ITEM in microseconds; XRT_PK_SPLIT_ITEMS: capacity of a frame context's arena)
     int lvlCheckedTilesX = 0; long long lvlCheckedTiles = 0;   // (LvlMap::inv verified for this frame geometry)
-    bool noLevelMap = false;   // XRT_LEVEL_MAP=0: level records for every path of the frame (as before round 4's last build)
-    bool packetSplit = false;   // (measured: no gain yet -- profiles/r04/split_walks.txt; XRT_PK_SPLIT=1 switches the split-walk variant of the packet kernel on)
-    int packetBudgetUs = 350, packetBudgetItemUs = 150, packetSplitItems = 8192;
-    int packetLongUs = 0, packetBudgetLongUs = 8;    // XRT_PK_LONG / XRT_PK_BUDGET_LONG (block entries, whatever the names say): a packet that made more than the first in the context's last frame hands subtrees over every <second> block entries from the start (XRT_PK_LONG=0: no prediction)
     unsigned splitSerial = 0;
     std::map<int, std::pair<DevBuf<unsigned>, DevBuf<unsigned>>> apiSplit;   // seam 1 (testing aid, XRT_PACKET & 8): an arena per stream
-    int packetGrabMax = 2;     // XRT_PK_GRAB (development): 8 -> 2 shortened the tail of a launch (C5 blocking 9.0 -> 7.8 ms); 1 loses to contention on the queue word
-    int packetStaticDiv = 4;   // XRT_PK_STATIC (development): 1/2 .. 1/8 measured within 2 % of each other on C5
     int sceneMode = MODE_SCENE;   // MODE_SINGLE when the scene is one SceneObject with one Mesh
     hipStream_t stream = nullptr;
     // per-frame work buffers
@@ -318,12 +284,9 @@ struct xrt_scene {
     size_t costMapPaths = 0;
     unsigned epoch = 100;
     int costT[66];            // per generation: rays that cost more than this are started first; steered in frame_finish
-    int longFracLo = 2, longFracHi = 6;   // percent of a generation's rays the list is steered to (XRT_LONG_FRAC=lo,hi)
     bool deepMeshes = false;  // some mesh has a real octree: rays can be long
-    float heavyPath = 0.0f;   // rays longer than this inside the root box are traced first (0: off); XRT_HEAVY=<fraction of the box diagonal>
-    std::string waveTimesPath;
-    std::string stampDumpPath;   // XRT_STAMP_DUMP=<file>: the stamp rows of the last frame (start, waves, every wave's end) -- how long a launch's waves lived
-    DevBuf<unsigned long long> waveTimes;   // XRT_WAVE_TIMES=<file>: per-wave clocks of the last frame's launches (development aid)
+    float heavyPath = 0.0f;   // rays longer than this inside the root box are traced first (0: off; cfg.heavy)
+    DevBuf<unsigned long long> waveTimes;   // cfg.waveTimesPath
     // Per-frame host state.  Two contexts so that the next frame can be enqueued while the previous one's counters
     // and timings are still on their way back (xrt_render_device_begin / _end).
     struct FrameCtx {
@@ -357,46 +320,21 @@ struct xrt_scene {
         WorkBufs w;
     } frames[8];   // context of ticket `slot`, part j of its frame: frames[slot + 2 * j] (a frame may be split into up to four bands on as many streams)
     std::vector<hipEvent_t> events;   // xrt_scene_intersect timing
-    int firstBatch = 64;
-    long long heapRayCap = HEAP_RAY_CAP;         // XRT_HEAP_RAY_CAP=<n> forces small ray buffers (tests of the overflow / retry path)
-    long long shadowBytes = 8LL << 30;   // budget of a frame context's shadow rays / hits / words (XRT_SHADOW_BYTES): many lights shrink the chunk
-    long long maxChunkPaths = MAX_CHUNK_PATHS;   // XRT_CHUNK_PATHS=<n> (multiple of 8192) forces smaller chunks (tests of the multi-chunk path)
     float lastFrameMs = 0.0f;    // GPU time of the last finished frame
-    float overlapMinMs = 0.05f;  // frames at least this long run on per-context streams
-    // A launch of persistent waves leaves the machine half empty while its last rays finish; a blocking single frame (what the
-    // C# host's RenderInternal asks for) has no other frame to fill the gaps, so it is rendered as two halves of its tiles on
-    // two streams.  XRT_SPLIT=0 never, 1 frames nobody else overlaps (default), 2 also pipelined frames.  It paid while a launch's
-    // waves were alive 55-60 % of its duration (C4 13.3 -> 10.9 ms), did not in rounds 2 and 3 (the second set of launches cost what the
-    // overlap gained: C3 2.74 vs 2.91 ms, C4 7.1 vs 6.9, C5 7.9 vs 8.0), and pays again now that the kernels are faster and a launch's tail
-    // is a larger share of it (round 4, one box: C3 1.95 -> 1.72 ms per blocking frame, C4 4.26 -> 4.13, C5 4.48 -> 4.43; three or four
-    // bands no better; profiles/r04/frame_split.txt).  By default only two-level scenes: the two extra frame contexts cost a one-body scene like C5
-    // 6 GB of work buffers for 1 %.
-    int splitMode = 1, splitParts = 2;
-    bool splitGiven = false;     // XRT_SPLIT was set: else only two-level scenes are split (a one-body scene gains 1-2 % for two more frame contexts' work buffers)
-    bool launchEvents = false;   // XRT_LAUNCH_EVENTS=1: single-chunk frames time their traversal launches with events on the dispatch packets, too
-    int maxStampRows = MAX_STAMP_ROWS;   // XRT_STAMP_ROWS=<n> (tests): launches of a frame beyond the n-th carry events instead
-    bool adaptiveFastOk = true;  // adaptive frames are enqueued whole (level buffers sized optimistically) until a level overflows; XRT_ADAPTIVE_FAST=0
-    long long adaptiveCap = 0;   // XRT_ADAPTIVE_CAP=<quadrants> (tests): capacity of the deeper levels instead of one quadrant per pixel
-    bool heapFastOk = true;      // single-chunk ray-tree frames go the optimistic way (no host round trip) until one overflows; XRT_HEAP_FAST=0
-    bool noGridHints = false;    // XRT_GRID_HINTS=0: every launch is sized for the whole chip
-    bool noLaunchTiming = false; // XRT_LAUNCH_TIMING=0: single-chunk frames do not time their traversal launches (xrt_stats.ms_intersect = 0)
+    bool adaptiveFastOk = true;  // no adaptive frame has overflowed its optimistically sized level buffers (cfg.adaptiveFast)
+    bool heapFastOk = true;      // no single-chunk ray-tree frame has overflowed on the optimistic way (cfg.heapFast)
     int wallClockKHz = 0;        // rate of the device clock the launches stamp (hipDeviceAttributeWallClockRate)
-    float splitMinMs = 1.0f;
-    int tune[4] = {24, 16, 48, 32};   // refill threshold (idle lanes), octree-child steps and leaf steps per outer iteration
-    bool tuneGiven = false;           // XRT_TUNE was set: keep it
     std::atomic<bool> busy{false};
     std::atomic<float> progress{0.0f};
     // Seam 1 (xrt_scene_intersect / xrt_mesh_intersect / xrt_generate_primary_rays) is re-entrant like the reference's
     // ISpatialManager.GetRayIntersection (ISM:15, called from N render threads, RT:105-113): the host-buffer calls share
     // one staging area and are serialised by this mutex; every stream has its own work-queue word.
     // In-library multi-GPU (xrt_render_opts.n_gpus): copies of the scene on devices device+1 .. (owned), the RCCL
-    // communicators, and per ticket the buffer the tile shards are gathered into.  XRT_FAKE_GPUS=1 (test boxes with one
-    // GPU): the replicas live on the scene's own device and the exchange is RCCL send-to-self.
+    // communicators, and per ticket the buffer the tile shards are gathered into (cfg.fakeGpus: all on the scene's own device).
     std::vector<xrt_scene *> replicas;
     std::vector<std::unique_ptr<RankWorker>> workers;   // workers[i - 1] drives replica i
     int visibleDevices = 0;                             // hipGetDeviceCount at xrt_scene_create
     RcclGather rccl;
-    bool fakeGpus = false;
     DevBuf<uint32_t> gathered[2];    // primary: n * tiles_per_rank * 512 pixels, rank-major
     DevBuf<uint32_t> tileOut[2];     // replica: its tiles of the frame in slot 0 / 1
     DevBuf<uint32_t> frameOut[2];    // W*H frame of a host-output ticket
@@ -416,8 +354,6 @@ struct xrt_scene {
     struct OpenFrame { int nGpus = 0, nParts = 1; bool tail = false, balance = false; uint32_t *hostOut = nullptr, *devOut = nullptr; size_t px = 0; hipStream_t st0 = nullptr; } open[2];
     std::mutex apiMutex;
     std::unordered_map<hipStream_t, int> queueOfStream;
-    // development switches, read once at xrt_scene_create (never per frame)
-    bool noRectCull = false, oneStream = false, noFeedback = false;
 
     ~xrt_scene() {
         workers.clear();   // (joins the threads)
@@ -490,6 +426,12 @@ int persistent_grid(xrt_scene *s, long long nHost, int raysPerBlock = 256) {
         if (want < full) return (int)want;
     }
     return full;
+}
+
+// The scheduling knobs of a k_intersect launch: the scene's where it derives them (scene_upload), else the switches'.
+void set_knobs(IntersectArgs &a, const xrt_scene *s) {
+    a.refillMin = s->refillMin; a.nodeBurst = s->cfg.tune[1]; a.leafBurst = s->cfg.tune[2]; a.coopMax = s->cfg.tune[3];
+    a.batchMax = s->cfg.batchMax; a.batchMin = s->cfg.batchMin; a.spreadMin = s->cfg.spreadMin; a.heavyShift = s->heavyShift; a.firstBatch = s->firstBatch;
 }
 
 void fill_stats(xrt_stats *st, const unsigned long long *c /* 2*C_COUNT: closest, shadow */, unsigned long long shaded, unsigned long long pixels) {
@@ -691,7 +633,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         g.cullX1 = g.width - 1;
         g.batch = reinterpret_cast<const f4 *>(batch->rays); g.batchRefIndex = batch->refIndex;
     } else {
-        rc = make_raygen(cam, opts, g, (haveRoot && !s->noRectCull) ? rootBox : nullptr);
+        rc = make_raygen(cam, opts, g, (haveRoot && !s->cfg.noRectCull) ? rootBox : nullptr);
         if (rc != XRT_OK) return rc;
         if (adaptive) g.samples = 4;
         g.cullSkipsRecord = heap ? 0 : 1;   // (k_compose_tree reads every root record)
@@ -717,7 +659,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     // 2^k in generation k, but few paths do: chunks are sized optimistically (ray buffers of HEAP_RAY_CAP rays,
     // level records bounded by 8 GB) and a chunk whose generation overflows is retried with a quarter of the paths.
     const size_t nodes = heap ? (((size_t)1 << (R + 1)) - 1) : (size_t)(R + 1);
-    long long maxPaths = s->maxChunkPaths;
+    long long maxPaths = s->cfg.maxChunkPaths;
     // The reference iterates a List<ILight> of any length (RT:534-542).  The shadow rays of one generation are counted in an int
     // (at most 2^30): many lights shrink the chunk, they are not refused -- until not even 8192 paths fit a generation.
     const long long lightBound = (1LL << 30) / (nL > 0 ? nL : 1);
@@ -726,7 +668,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     // the chunk to what XRT_SHADOW_BYTES (default 8 GB per context) holds -- the frame then takes the multi-chunk path -- instead of
     // failing with XRT_E_OOM (a 1080p frame with 100 lights would want 17 GB).
     if (nL > 0) {
-        const long long byBytes = ((long long)s->shadowBytes / (84LL * nL)) & ~8191LL;
+        const long long byBytes = ((long long)s->cfg.shadowBytes / (84LL * nL)) & ~8191LL;
         if (byBytes < maxPaths) maxPaths = byBytes < 8192 ? 8192 : byBytes;
     }
     if (maxPaths < 8192) return fail(XRT_E_UNSUPPORTED, "%d lights: the shadow rays of 8192 paths do not fit one generation (2^30 rays)", nL);
@@ -753,7 +695,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     // LvlMap): plain unsharded frames of one chunk and one part, whose tiles are numbered row by row.  (C5: 3.2 -> 1.7 GB per frame context.)
     size_t lvlStride = (size_t)P;
     std::memset(&g.lvl, 0, sizeof(g.lvl));
-    if (!heap && !adaptive && firstPaths <= chunkPaths && nParts == 1 && partStart == 0 && g.shardCount == 1 && !tabled && g.cullSkipsRecord && !s->noLevelMap &&
+    if (!heap && !adaptive && firstPaths <= chunkPaths && nParts == 1 && partStart == 0 && g.shardCount == 1 && !tabled && g.cullSkipsRecord && s->cfg.levelMap &&
         g.cullX1 >= g.cullX0 && g.cullY1 >= g.cullY0) {
         const int shift = 9 + (g.samples == 16 ? 4 : (g.samples == 4 ? 2 : 0));
         const int tx0 = g.cullX0 / XRT_TILE_W, tx1 = g.cullX1 / XRT_TILE_W, ty0 = g.cullY0 / XRT_TILE_H, ty1 = g.cullY1 / XRT_TILE_H;
@@ -771,7 +713,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         }
     }
     if (heap) {
-        const size_t capL = (size_t)std::min<long long>(s->heapRayCap, lightBound);   // (>= 8192 >= ... see above; P <= lightBound as well)
+        const size_t capL = (size_t)std::min<long long>(s->cfg.heapRayCap, lightBound);   // (>= 8192 >= ... see above; P <= lightBound as well)
         rayCap = (R < 20 && ((size_t)P << R) < capL) ? ((size_t)P << R) : capL;
         if (rayCap < (size_t)P) rayCap = (size_t)P;
     }
@@ -788,7 +730,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         (rc = W.lvlB.ensure(lvlStride * nodes)) || (rc = W.sampleColor.ensure(P)) || (rc = W.lights.ensure(nL > 0 ? nL : 1)) ||
         (rc = s->counters.ensure(2 * C_COUNT + 8)))
         return rc;
-    if (!s->waveTimesPath.empty() && !s->waveTimes.p) {
+    if (!s->cfg.waveTimesPath.empty() && !s->waveTimes.p) {
         if ((rc = s->waveTimes.ensure((size_t)16 * 3 * 8192))) return rc;
         HIPCHECK(hipMemset(s->waveTimes.p, 0, (size_t)16 * 3 * 8192 * sizeof(unsigned long long)));
     }
@@ -806,18 +748,18 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     // "a generation did not fit"; frame_finish then renders it again the careful way (chunks, checks, retries) and the scene's later
     // ray-tree frames take that way from the start.  Not where something is enqueued behind the frame that a redo cannot recall
     // (the in-library gather of n_gpus > 1).
-    const bool heapFast = heap && heapFastAllowed && s->heapFastOk && nParts == 1;
+    const bool heapFast = heap && heapFastAllowed && s->cfg.heapFast && s->heapFastOk && nParts == 1;
     // ... and an adaptive frame (RT:170-311) whose passes are one chunk each: the sizes of the deeper quadrant levels stay on the device
     // (k_ms_decide counts, the next level's kernels read the count), the level buffers are sized optimistically -- one quadrant per
     // pixel and level -- and a level that does not fit sets the same kind of word.
-    const bool adaptiveFast = adaptive && !heap && heapFastAllowed && s->adaptiveFastOk && nParts == 1 && !opts->collect_stats && totalPixels * 4 <= chunkPaths &&
+    const bool adaptiveFast = adaptive && !heap && heapFastAllowed && s->cfg.adaptiveFast && s->adaptiveFastOk && nParts == 1 && !opts->collect_stats && totalPixels * 4 <= chunkPaths &&
                               (quality + 2) * (R + 2) * 2 + 2 <= MAX_STAMP_ROWS;
     const bool fast = (adaptive ? adaptiveFast : (!heap || heapFast)) && firstPaths <= chunkPaths && !opts->collect_stats && !batch;
     // Answered at emission (kernels.h ShadeArgs::ae): plain one-chunk frames of one-body scenes whose mesh CAN face away from a ray as a whole (its normal
     // box does not hold the origin).  Not with the counting pass -- it counts the reference's work for every query from the ray lists --, not for ray trees.
     // (a batch of one chunk too: what part A answers depends on the hits alone, not on where generation 0 came from)
     bool ae = (fast || (batch && firstPaths <= chunkPaths && !opts->collect_stats)) && !heap && !adaptive && nParts == 1 && s->sceneMode == MODE_SINGLE &&
-              s->view.nodeCull != 0 && !s->noAnswerAtEmission;
+              s->view.nodeCull != 0 && s->cfg.answerAtEmission;
     if (ae) {
         const MeshRec &m0 = s->host->arrays.meshes[0];
         ae = m0.nbMin[3] == 0.0f && (m0.nbMin[0] > 0.0f || m0.nbMax[0] < 0.0f || m0.nbMin[1] > 0.0f || m0.nbMax[1] < 0.0f || m0.nbMin[2] > 0.0f || m0.nbMax[2] < 0.0f);
@@ -837,7 +779,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     F.frameW = g.width; F.frameH = g.height;
     // the traversal launches time themselves on the device clock instead of carrying events (device_util.h); a frame of more
     // than MAX_STAMP_ROWS launches (many chunks or supersampling levels) goes on with events
-    const bool useStamps = !s->launchEvents && !s->noLaunchTiming && s->wallClockKHz > 0;
+    const bool useStamps = !s->cfg.launchEvents && s->cfg.launchTiming && s->wallClockKHz > 0;
     F.stampRows = 0;
     if (useStamps) {
         if ((rc = W.stamps.ensure((size_t)MAX_STAMP_ROWS * STAMP_STRIDE))) return rc;
@@ -852,7 +794,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         // scene's one stream.  (While every traversal launch carried two events, enqueueing on a stream that had gone idle cost
         // ~15 us a launch and alternating streams made the host the bottleneck of 0.2 ms frames; the launches time themselves
         // now, device_util.h.)
-        if (fast && s->lastFrameMs >= s->overlapMinMs && !s->oneStream) {
+        if (fast && s->lastFrameMs >= s->cfg.overlapMinMs && !s->cfg.oneStream) {
             if (!W.stream) HIPCHECK(hipStreamCreateWithFlags(&W.stream, hipStreamNonBlocking));
             st = W.stream;
         } else st = s->stream;
@@ -883,14 +825,14 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     // (ray-tree frames -- Transparent materials -- of two-level scenes: the first two generations and the first shadow rays, where the image
     // is big enough for a launch to be more than its floor: G2 at 720p 1.12 -> 0.97 ms, the reference's default scene at 512x512 0.31 ->
     // 0.40 with packets, so not there; packets in every generation of a ray tree are 1.5-3 x slower (profiles/r03/packet_masks_ray_trees.txt))
-    const int pkHeap = s->packetMaskHeap >= 0 ? s->packetMaskHeap : ((s->sceneMode == MODE_SCENE && (long long)g.width * g.height * g.samples >= 600000LL) ? 7 : 0);
-    int pkMask = !s->packetOk ? 0 : (heap ? pkHeap : (s->packetMask >= 0 ? s->packetMask : pkAuto));
+    const int pkHeap = s->cfg.packetMaskHeap >= 0 ? s->cfg.packetMaskHeap : ((s->sceneMode == MODE_SCENE && (long long)g.width * g.height * g.samples >= 600000LL) ? 7 : 0);
+    int pkMask = !s->packetOk ? 0 : (heap ? pkHeap : (s->cfg.packetMask >= 0 ? s->cfg.packetMask : pkAuto));
     // A batch's generation 0 is in the caller's order, which nothing says is coherent: 64 consecutive rays need not be a patch of the same
     // surface, and a packet of scattered rays walks the union of their paths.  It goes to the per-lane kernel unless XRT_PACKET / XRT_PACKET_HEAP
     // name the packet kernel for it (bit 0; both kernels give the same answers).  Its later generations follow the hits as a frame's do.
-    if (batch && (heap ? s->packetMaskHeap : s->packetMask) < 0) pkMask &= ~1;
+    if (batch && (heap ? s->cfg.packetMaskHeap : s->cfg.packetMask) < 0) pkMask &= ~1;
     const bool laneClosest = (pkMask & 5) != 5;   // some closest-hit generation is traced ray by ray: the long-ray feedback has a reader
-    const bool wantFeedback = fast && !heap && !adaptive && s->deepMeshes && !s->noFeedback && laneClosest;   // (the paths of a deeper quadrant level are a list: no stable key)
+    const bool wantFeedback = fast && !heap && !adaptive && s->deepMeshes && !s->cfg.noFeedback && laneClosest;   // (the paths of a deeper quadrant level are a list: no stable key)
     {   // The other context's frame may still be running on another stream.  Two single-chunk frames share nothing they
         // write except scheduling hints; anything else (counting pass, supersampling levels, ray tree, a cost map
         // about to be reallocated or released) runs alone.
@@ -978,7 +920,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         // (generation 0 and 1 and the shadow rays of generation 0 are the big coherent populations; after two bounces the 64 rays
         // of a packet have little in common and a few packets take three times as long as the rest of their launch: bit 4)
         auto packet_closest = [&](int k) { return (k == 0 ? (pkMask & 1) : (k == 1 ? (pkMask & 4) : ((pkMask & 4) && (pkMask & 16)))) != 0; };
-        const bool hinted = fast && nParts == 1 && s->genKey == firstPaths * 64 + nL && !s->noGridHints;
+        const bool hinted = fast && nParts == 1 && s->genKey == firstPaths * 64 + nL && s->cfg.gridHints;
         auto hint = [&](const long long *v, int k) -> long long { return (hinted && k < 68 && v[k] >= 0) ? 4 * v[k] + 4096 : -1; };
         auto packet_shadow = [&](int k) { return (pkMask & 2) != 0 && (k <= 1 || (pkMask & 16) != 0); };   // shadow rays of generation k-1
         auto heavy_for = [&](int k) {
@@ -1016,7 +958,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
             B.nCap = (int)((long long)shadowCap * nL);
             for (IntersectArgs *a : {&C, &B}) {
                 a->queue = q + QW * k; a->mode = s->sceneMode; a->meshId = 0;
-                a->refillMin = s->tune[0]; a->nodeBurst = s->tune[1]; a->leafBurst = s->tune[2]; a->coopMax = s->tune[3]; a->batchMax = s->batchMax; a->heavyShift = s->heavyShift; a->batchMin = s->batchMin; a->spreadMin = s->spreadMin; a->firstBatch = s->firstBatch;
+                set_knobs(*a, s);
             }
             // segments of coherent rays go to the wave-packet kernel, the others (together, one launch) to the per-lane kernel
             const bool pkC = hasClosest && packet_closest(k), pkB = hasShadow && packet_shadow(k);
@@ -1032,10 +974,10 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
                     else PA.pathOf1 = k == 0 ? W.index0.p : paths[cur];
                     if (I2) { PA.slotOf2 = slotOf[prv]; PA.nL2 = nL; }
                 }
-                PA.queue = q + QW * k + 1 + PACKET_QUEUE_WORDS * word; PA.mode = s->sceneMode; PA.meshId = 0; PA.unmark = 0; PA.staticDiv = s->packetStaticDiv; PA.grabMax = s->packetGrabMax; PA.cullMin = s->packetCullMin; PA.bundle = s->packetBundle ? 1 : 0;
-                if (s->packetSplit && s->sceneMode != MODE_SCENE) {
+                PA.queue = q + QW * k + 1 + PACKET_QUEUE_WORDS * word; PA.mode = s->sceneMode; PA.meshId = 0; PA.unmark = 0; PA.staticDiv = s->cfg.packetStaticDiv; PA.grabMax = s->cfg.packetGrabMax; PA.cullMin = s->cfg.packetCullMin; PA.bundle = s->cfg.packetBundle ? 1 : 0;
+                if (s->cfg.packetSplit && s->sceneMode != MODE_SCENE) {
                     if ((rc = split_arena(s, W.splitItems, W.splitRecs, PA, st))) return rc;
-                    if (fast && !adaptive && !heap && s->packetLongUs > 0) {   // plain frames: the packets of launch #k are the same from frame to frame while the camera stands still, and nearly so while it moves
+                    if (fast && !adaptive && !heap && s->cfg.packetLongUs > 0) {   // plain frames: the packets of launch #k are the same from frame to frame while the camera stands still, and nearly so while it moves
                         const size_t stride = (rayCap + 63) / 64 + ((size_t)shadowCap * (size_t)(nL > 0 ? nL : 1) + 63) / 64 + 2;
                         if (W.splitCostStride != stride || !W.splitCost.p) {
                             if ((rc = W.splitCost.ensure(stride * 2 * (size_t)(R + 2)))) return rc;
@@ -1043,7 +985,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
                             W.splitCostStride = stride;
                         }
                         PA.splitCost = W.splitCost.p + stride * (size_t)(2 * k + word);
-                        PA.splitLong = s->packetLongUs; PA.splitBudgetLong = std::max(1, s->packetBudgetLongUs);
+                        PA.splitLong = s->cfg.packetLongUs; PA.splitBudgetLong = std::max(1, s->cfg.packetBudgetLongUs);
                     }
                 }
                 hipEvent_t a0 = get_event(F.events, ev), a1 = get_event(F.events, ev + 1);
@@ -1052,16 +994,16 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
                 if (nHost >= 0) { const long long want = (nHost + 255) / 256; if (want < grid) grid = (int)(want < 1 ? 1 : want); }
                 // a small launch -- a tile shard of a frame, a late generation -- walks parts of the octree no other wave keeps warm: it prefetches (packet.hip pk_prefetch);
                 // a launch of many packets per wave has its neighbours for that and would only pay for the extra loads (C5's primary launch: +4 %)
-                PA.prefetch = s->packetPrefetch >= 0 ? s->packetPrefetch : ((nHost >= 0 && nHost / 64 < (long long)s->packetPrefetchBelow * grid * 4) ? 1 : 0);
-                if (useStamps && grid * 4 <= STAMP_SLOTS && F.stampRows < s->maxStampRows) { PA.stamps = W.stamps.p + (size_t)F.stampRows++ * STAMP_STRIDE; a0 = a1 = nullptr; }
-                else if (s->noLaunchTiming) a0 = a1 = nullptr;
+                PA.prefetch = s->cfg.packetPrefetch >= 0 ? s->cfg.packetPrefetch : ((nHost >= 0 && nHost / 64 < (long long)s->cfg.packetPrefetchBelow * grid * 4) ? 1 : 0);
+                if (useStamps && grid * 4 <= STAMP_SLOTS && F.stampRows < s->cfg.maxStampRows) { PA.stamps = W.stamps.p + (size_t)F.stampRows++ * STAMP_STRIDE; a0 = a1 = nullptr; }
+                else if (!s->cfg.launchTiming) a0 = a1 = nullptr;
                 else { pairs.push_back({ev, ev + 1}); ev += 2; }
                 launch_packet(S, PA, grid, st, a0, a1);
                 return XRT_OK;
             };
             Range ri("xrt intersect #%d", k);
             // both populations of a step in ONE packet launch where both go to the packet kernel: one launch's tail instead of two
-            if (pkC && pkB && s->packetMerge) { if ((rc = launch_pk(C, 0, hint(s->genRays, k), &B))) return rc; }
+            if (pkC && pkB && s->cfg.packetMerge) { if ((rc = launch_pk(C, 0, hint(s->genRays, k), &B))) return rc; }
             else {
                 if (pkC && (rc = launch_pk(C, 0, k == 0 ? Pc : hint(s->genRays, k)))) return rc;
                 if (pkB && (rc = launch_pk(B, 1, hint(s->genRays, k)))) return rc;
@@ -1073,8 +1015,8 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
                 hipEvent_t a0 = get_event(F.events, ev), a1 = get_event(F.events, ev + 1);
                 if (!a0 || !a1) return fail(XRT_E_HIP, "hipEventCreate failed");
                 const int grid = k == 0 ? persistent_grid(s, Pc) : persistent_grid(s, hint(s->genRays, k), 16);
-                if (useStamps && grid * 4 <= STAMP_SLOTS && F.stampRows < s->maxStampRows) { A.stamps = W.stamps.p + (size_t)F.stampRows++ * STAMP_STRIDE; a0 = a1 = nullptr; }
-                else if (s->noLaunchTiming) a0 = a1 = nullptr;
+                if (useStamps && grid * 4 <= STAMP_SLOTS && F.stampRows < s->cfg.maxStampRows) { A.stamps = W.stamps.p + (size_t)F.stampRows++ * STAMP_STRIDE; a0 = a1 = nullptr; }
+                else if (!s->cfg.launchTiming) a0 = a1 = nullptr;
                 else { pairs.push_back({ev, ev + 1}); ev += 2; }
                 if (s->waveTimes.p && k < 16) A.debugTimes = s->waveTimes.p + (size_t)k * 3 * 8192;
                 launch_intersect(S, A, s->stackNeeded, grid, st, a0, a1);
@@ -1272,7 +1214,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         // overflow word and frame_finish renders the frame again the careful way below.
         const int nPass = quality + 1;
         constexpr int LW = 16;   // words in front of the per-pass counters: lvlCnt[0 .. quality], overflow word at LW - 1
-        const long long capDeep = s->adaptiveCap > 0 ? std::min(s->adaptiveCap, totalPixels) : totalPixels;
+        const long long capDeep = s->cfg.adaptiveCap > 0 ? std::min(s->cfg.adaptiveCap, totalPixels) : totalPixels;
         auto cap_of = [&](int l) { return l == 0 ? totalPixels : capDeep; };
         const size_t words = (size_t)LW + (size_t)nPass * cntStride + (size_t)nPass * qStride;
         const int *cntsBefore = W.cnts.p;
@@ -1380,12 +1322,12 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
     if (s->waveTimes.p) {   // development aid: launch k of the frame occupies rows [k*8192, (k+1)*8192) x 3 clocks
         std::vector<unsigned long long> h((size_t)16 * 3 * 8192);
         HIPCHECK(hipMemcpy(h.data(), s->waveTimes.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(s->waveTimesPath.c_str(), "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
+        if (FILE *f = fopen(s->cfg.waveTimesPath.c_str(), "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
     }
-    if (!s->stampDumpPath.empty() && F.stampRows > 0) {   // development aid (tools/stamp_lives.py)
+    if (!s->cfg.stampDumpPath.empty() && F.stampRows > 0) {   // development aid (tools/stamp_lives.py)
         std::vector<unsigned long long> h((size_t)F.stampRows * STAMP_STRIDE);
         HIPCHECK(hipMemcpy(h.data(), F.w.stamps.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(s->stampDumpPath.c_str(), "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
+        if (FILE *f = fopen(s->cfg.stampDumpPath.c_str(), "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
     }
     const int R = F.R;
     if (F.fast && F.adaptiveFast && ((const int *)F.pinned)[F.cntBase - 1] != 0) {
@@ -1460,8 +1402,8 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
             for (int k = 0; k <= R && k < 66; k++) {
                 const long long rays = k == 0 ? hc[0] : hc[(R + 2) + k - 1], listed = hc[2 * (R + 2) + k];
                 if (rays < 4096) continue;
-                if (listed * 100 > rays * s->longFracHi) s->costT[k] = s->costT[k] + s->costT[k] / 4 + 1;
-                else if (listed * 100 < rays * s->longFracLo && s->costT[k] > 1) s->costT[k] = s->costT[k] - s->costT[k] / 5 - (s->costT[k] < 5 ? 1 : 0);
+                if (listed * 100 > rays * s->cfg.longFracHi) s->costT[k] = s->costT[k] + s->costT[k] / 4 + 1;
+                else if (listed * 100 < rays * s->cfg.longFracLo && s->costT[k] > 1) s->costT[k] = s->costT[k] - s->costT[k] / 5 - (s->costT[k] < 5 ? 1 : 0);
                 if (s->costT[k] < 1) s->costT[k] = 1;
                 if (s->costT[k] > 60000) s->costT[k] = 60000;
             }
@@ -1527,16 +1469,14 @@ int ensure_replicas(xrt_scene *s, int n) {
     while ((int)s->replicas.size() < n - 1) {
         const int i = (int)s->replicas.size() + 1;
         std::unique_ptr<xrt_scene> r(new xrt_scene());
-        r->device = s->fakeGpus ? s->device : s->device + i;
+        r->device = s->cfg.fakeGpus ? s->device : s->device + i;
         r->host = s->host;
-        r->noRectCull = s->noRectCull; r->oneStream = s->oneStream; r->noFeedback = s->noFeedback; r->overlapMinMs = s->overlapMinMs;
-        r->heapRayCap = s->heapRayCap; r->maxChunkPaths = s->maxChunkPaths; r->shadowBytes = s->shadowBytes; r->packetMask = s->packetMask; r->packetMaskHeap = s->packetMaskHeap; r->packetCullMin = s->packetCullMin; r->packetBundle = s->packetBundle; r->packetPrefetch = s->packetPrefetch; r->packetPrefetchBelow = s->packetPrefetchBelow; r->noAnswerAtEmission = s->noAnswerAtEmission; r->packetMerge = s->packetMerge; r->packetSplit = s->packetSplit; r->noLevelMap = s->noLevelMap; r->packetBudgetUs = s->packetBudgetUs; r->packetBudgetItemUs = s->packetBudgetItemUs; r->packetSplitItems = s->packetSplitItems; r->packetLongUs = s->packetLongUs; r->packetBudgetLongUs = s->packetBudgetLongUs; r->batchMax = s->batchMax; r->heavyShift = s->heavyShift; r->heavyShiftGiven = s->heavyShiftGiven; r->batchMin = s->batchMin; r->spreadMin = s->spreadMin; r->tuneGiven = s->tuneGiven;
-        for (int k = 0; k < 4; k++) r->tune[k] = s->tune[k];
+        r->cfg = s->cfg;
+        r->cfg.waveTimesPath.clear(); r->cfg.stampDumpPath.clear();   // (the dumps are the primary's: a replica's frames would overwrite its files)
         HIPCHECK(hipSetDevice(r->device));
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, r->device) == hipSuccess) r->numCUs = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
         if (hipDeviceGetAttribute(&r->wallClockKHz, hipDeviceAttributeWallClockRate, r->device) != hipSuccess) { r->wallClockKHz = 0; (void)hipGetLastError(); }
-        r->launchEvents = s->launchEvents; r->noLaunchTiming = s->noLaunchTiming; r->noGridHints = s->noGridHints; r->heapFastOk = s->heapFastOk; r->maxStampRows = s->maxStampRows; r->adaptiveFastOk = s->adaptiveFastOk; r->adaptiveCap = s->adaptiveCap;
         HIPCHECK(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
         int rc = scene_upload(r.get());
         if (rc != XRT_OK) return rc;
@@ -1578,13 +1518,13 @@ int multi_begin(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_light *
     if (opts->shard_count > 1) return fail(XRT_E_INVALID_ARG, "n_gpus > 1 shards the frame inside the library: shard_count must be 0 or 1");
     if (n > XRT_MAX_GPUS) return fail(XRT_E_INVALID_ARG, "n_gpus %d exceeds %d", n, XRT_MAX_GPUS);
     if (!cam || cam->vp_width <= 0 || cam->vp_height <= 0) return fail(XRT_E_INVALID_ARG, "viewport must be positive");
-    if (!s->fakeGpus && s->device + n > s->visibleDevices)
+    if (!s->cfg.fakeGpus && s->device + n > s->visibleDevices)
         return fail(XRT_E_NO_DEVICE, "n_gpus %d from device %d needs %d visible devices, %d present", n, s->device, s->device + n, s->visibleDevices);
     int rc;
     if ((rc = ensure_replicas(s, n))) return rc;
     {
         std::vector<int> devs;
-        if (s->fakeGpus) devs.push_back(s->device);
+        if (s->cfg.fakeGpus) devs.push_back(s->device);
         else for (int i = 0; i < n; i++) devs.push_back(s->device + i);
         std::string err;
         if (!s->rccl.init(devs, err)) return fail(XRT_E_RCCL, "%s", err.c_str());
@@ -1619,7 +1559,7 @@ int multi_begin(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_light *
         xrt_scene *r = rank_scene(s, i);
         HIPCHECK(hipSetDevice(r->device));
         if ((rc = r->tileOut[slot].ensure(count))) { (void)hipSetDevice(s->device); return rc; }
-        if (s->fakeGpus && !r->tilesReady[slot]) HIPCHECK(hipEventCreateWithFlags(&r->tilesReady[slot], hipEventDisableTiming));
+        if (s->cfg.fakeGpus && !r->tilesReady[slot]) HIPCHECK(hipEventCreateWithFlags(&r->tilesReady[slot], hipEventDisableTiming));
     }
     HIPCHECK(hipSetDevice(s->device));
     // every device's share is enqueued by its own (persistent) host thread
@@ -1672,12 +1612,12 @@ int multi_begin(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_light *
         for (int i = 1; i < n; i++) {
             xrt_scene *r = rank_scene(s, i);
             hipStream_t sti = r->frames[slot].w.lastStream;
-            if (s->fakeGpus) {   // same device, one communicator: rank 0's stream waits for the tiles, then sends to itself
+            if (s->cfg.fakeGpus) {   // same device, one communicator: rank 0's stream waits for the tiles, then sends to itself
                 HIPCHECK(hipEventRecord(r->tilesReady[slot], sti));
                 HIPCHECK(hipStreamWaitEvent(st0, r->tilesReady[slot], 0));
                 sti = st0;
             }
-            src.push_back(r->tileOut[slot].p); srcRank.push_back(s->fakeGpus ? 0 : i); srcStream.push_back(sti);
+            src.push_back(r->tileOut[slot].p); srcRank.push_back(s->cfg.fakeGpus ? 0 : i); srcStream.push_back(sti);
             dst.push_back(s->gathered[slot].p + (size_t)i * count);
         }
         {
@@ -1764,9 +1704,9 @@ int open_frame_impl(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_lig
         const bool plain = opts->use_multisampling != XRT_MS_ADAPTIVE && !(s->host->arrays.anyTransparent && opts->max_reflections > 0) && !opts->collect_stats;
         const long long px64 = (long long)px * (opts->use_multisampling == XRT_MS_FIXED16 ? 16 : 1) / (opts->shard_count > 1 ? opts->shard_count : 1);
         const bool alone = !s->frames[slot ^ 1].pending;
-        if (!st && plain && !s->oneStream && s->splitMode > 0 && (s->splitGiven || s->sceneMode == MODE_SCENE) && (s->splitMode == 2 || alone) && s->lastFrameMs >= s->splitMinMs &&
-            s->lastFrameMs >= s->overlapMinMs && px64 >= 8 * 8192 && px64 <= (long long)s->maxChunkPaths)
-            nParts = s->splitParts;
+        if (!st && plain && !s->cfg.oneStream && s->cfg.splitMode.value_or(1) > 0 && (s->cfg.splitMode || s->sceneMode == MODE_SCENE) && (s->cfg.splitMode == 2 || alone) && s->lastFrameMs >= s->cfg.splitMinMs &&
+            s->lastFrameMs >= s->cfg.overlapMinMs && px64 >= 8 * 8192 && px64 <= (long long)s->cfg.maxChunkPaths)
+            nParts = s->cfg.splitParts;
         for (int j = 0; j < nParts; j++)
             if ((rc = frame_begin(s, s->frames[slot + 2 * j], cam, lights, nLights, opts, d_out, d_outF32, st, j, nParts))) {
                 for (int i = 0; i < j; i++) (void)frame_finish(s, s->frames[slot + 2 * i], nullptr);
@@ -1829,7 +1769,7 @@ int close_frame_impl(xrt_scene *s, int slot, xrt_stats *stats) {
 // The arena is cleared once, when it is made: an item counts as written when its first word holds the launch's serial number.
 int split_arena(xrt_scene *s, DevBuf<unsigned> &items, DevBuf<unsigned> &recs, PacketArgs &PA, hipStream_t st) {
     int rc;
-    const size_t NI = ((size_t)s->packetSplitItems + 7) / 8 * 8, NR = NI / 4 + 1;   // (an eighth of the items per XCD)
+    const size_t NI = ((size_t)s->cfg.packetSplitItems + 7) / 8 * 8, NR = NI / 4 + 1;   // (an eighth of the items per XCD)
     if (!items.p || items.cap < NI * SPLIT_ITEM_WORDS) {
         if ((rc = items.ensure(NI * SPLIT_ITEM_WORDS)) || (rc = recs.ensure(NR * SPLIT_REC_WORDS))) return rc;
         HIPCHECK(hipMemsetAsync(items.p, 0, NI * SPLIT_ITEM_WORDS * sizeof(unsigned), st));
@@ -1838,7 +1778,7 @@ int split_arena(xrt_scene *s, DevBuf<unsigned> &items, DevBuf<unsigned> &recs, P
     PA.splitItems = items.p; PA.splitRecs = recs.p; PA.splitNI = (int)NI; PA.splitNR = (int)NR;
     if (++s->splitSerial == 0u) s->splitSerial = 1u;
     PA.splitSerial = s->splitSerial;
-    PA.splitBudget = std::max(1, s->packetBudgetUs * 100); PA.splitBudgetItem = std::max(1, s->packetBudgetItemUs * 100);   // ticks of the 100 MHz device clock (0 would mean "off")
+    PA.splitBudget = std::max(1, s->cfg.packetBudgetUs * 100); PA.splitBudgetItem = std::max(1, s->cfg.packetBudgetItemUs * 100);   // ticks of the 100 MHz device clock (0 would mean "off")
     PA.splitCtl = reinterpret_cast<unsigned *>((reinterpret_cast<uintptr_t>(PA.queue + PACKET_QUEUE_HEADS * PACKET_HEAD_STRIDE) + 127) & ~(uintptr_t)127);
     return XRT_OK;
 }
@@ -1870,7 +1810,7 @@ int run_intersect(xrt_scene *s, const xrt_ray *d_rays, int64_t n, xrt_hit *d_hit
     HIPCHECK(hipMemsetAsync(queue, 0, (1 + PACKET_QUEUE_WORDS) * sizeof(unsigned), st));
     IntersectArgs A;
     A.rays = d_rays; A.hits = d_hits; A.index = nullptr; A.nDev = nullptr; A.nMul = 1; A.n = (int)n; A.nCap = 0; A.queue = queue; A.mode = mode; A.meshId = meshId;
-    A.refillMin = s->tune[0]; A.nodeBurst = s->tune[1]; A.leafBurst = s->tune[2]; A.coopMax = s->tune[3]; A.batchMax = s->batchMax; A.heavyShift = s->heavyShift; A.batchMin = s->batchMin; A.spreadMin = s->spreadMin; A.firstBatch = s->firstBatch;
+    set_knobs(A, s);
     hipEvent_t a0 = nullptr, a1 = nullptr;
     if (stats) {
         a0 = get_event(s, 0); a1 = get_event(s, 1);
@@ -1878,10 +1818,10 @@ int run_intersect(xrt_scene *s, const xrt_ray *d_rays, int64_t n, xrt_hit *d_hit
         HIPCHECK(hipMemsetAsync(s->counters.p, 0, 2 * C_COUNT * sizeof(unsigned long long), st));
     }
     const bool meshOk = mode != MODE_MESH || (meshId >= 0 && meshId < (int)s->host->meshTrees.size() && !s->host->meshTrees[(size_t)meshId].rootIsLeaf);
-    if (n > 0 && s->packetMask >= 0 && (s->packetMask & 8) && packet_supported(mode, s->host->arrays.meshDepth, s->host->arrays.sceneDepth) && meshOk) {   // (testing aid: arbitrary batches through the packet kernel)
+    if (n > 0 && s->cfg.packetMask >= 0 && (s->cfg.packetMask & 8) && packet_supported(mode, s->host->arrays.meshDepth, s->host->arrays.sceneDepth) && meshOk) {   // (testing aid: arbitrary batches through the packet kernel)
         PacketArgs PA;
-        PA.rays = d_rays; PA.hits = d_hits; PA.n = (int)n; PA.queue = queue + 1; PA.mode = mode; PA.meshId = meshId; PA.bundle = s->packetBundle ? 1 : 0;
-        if (s->packetSplit && mode != MODE_SCENE) {
+        PA.rays = d_rays; PA.hits = d_hits; PA.n = (int)n; PA.queue = queue + 1; PA.mode = mode; PA.meshId = meshId; PA.bundle = s->cfg.packetBundle ? 1 : 0;
+        if (s->cfg.packetSplit && mode != MODE_SCENE) {
             auto &ar = s->apiSplit[(int)((queue - s->queues.p) / (1 + PACKET_QUEUE_WORDS))];
             if ((rc = split_arena(s, ar.first, ar.second, PA, st))) return rc;
         }
@@ -1958,11 +1898,10 @@ int scene_upload(xrt_scene *scene) {
     S.objects = scene->objects.p; S.objMesh = scene->objMesh.p;
     S.nMeshes = (int)scene->host->meshes.size(); S.nObjects = (int)scene->host->objects.size();
     S.sceneDepth = A.sceneDepth + 1; S.meshDepth = A.meshDepth + 1;
-    S.nodeCull = 1;
-    if (const char *e = getenv("XRT_NODE_CULL")) { const int v = atoi(e); if (v >= 0 && v <= 2) S.nodeCull = v; }   // (tools: a scheduling-free switch, results never change)
-    scene->sceneMode = (scene->host->objects.size() == 1 && scene->host->objects[0].meshes.size() == 1 && scene->host->meshes.size() == 1 &&
+    const Settings &cfg = scene->cfg;
+    S.nodeCull = cfg.nodeCull;
+    scene->sceneMode = (!cfg.noSingle && scene->host->objects.size() == 1 && scene->host->objects[0].meshes.size() == 1 && scene->host->meshes.size() == 1 &&
                         scene->host->sceneTree.nodeCount == 1) ? MODE_SINGLE : MODE_SCENE;
-    if (getenv("XRT_NO_SINGLE")) scene->sceneMode = MODE_SCENE;
     scene->blocksPerCU = intersect_blocks_per_cu(scene->stackNeeded, scene->sceneMode);
     scene->blocksPerCUMesh = intersect_blocks_per_cu(scene->stackNeeded, MODE_MESH);
     scene->packetOk = packet_supported(scene->sceneMode, A.meshDepth, A.sceneDepth);
@@ -1970,24 +1909,21 @@ int scene_upload(xrt_scene *scene) {
     // scene phase while the others are deep in a mesh, and every partial refill made the wave run that phase for a few lanes
     // (measured with 8x8-pixel waves, whose rays take about equally long: C3 3.1 -> 2.45 ms, C4 8.9 -> 6.2 ms of traversal per frame).
     // One-body scenes have no such phase and keep refilling at 24 idle lanes (64 costs them 6 %).
-    if (!scene->tuneGiven) scene->tune[0] = scene->sceneMode == MODE_SCENE ? 64 : 24;
+    scene->refillMin = cfg.tune[0] > 0 ? cfg.tune[0] : (scene->sceneMode == MODE_SCENE ? 64 : 24);
     // Listed long rays: mixed one in eight into the first batches where waves refill lane by lane (a wave full of them takes five
     // times as long as one of them: C5 at one sample per pixel 1.58 -> 1.42 ms); 64 to a wave where waves refill as a whole -- there
     // a mixed wave idles 56 lanes until its long rays are done (C3 2.71 -> 2.97 ms when mixed).
-    if (!scene->heavyShiftGiven) scene->heavyShift = scene->sceneMode == MODE_SCENE ? 0 : 3;
+    scene->heavyShift = cfg.heavyShift.value_or(scene->sceneMode == MODE_SCENE ? 0 : 3);
     scene->blocksPerCUPacket = packet_blocks_per_cu(scene->sceneMode);
-    scene->firstBatch = (A.meshDepth == 0) ? 256 : 64;   // every mesh is a single leaf: rays are cheap, avoid queue traffic
-    if (const char *e = getenv("XRT_FIRST_BATCH")) { int v = atoi(e); if (v >= 64 && v <= 4096 && v % 64 == 0) scene->firstBatch = v; }
+    scene->firstBatch = cfg.firstBatch.value_or(A.meshDepth == 0 ? 256 : 64);   // every mesh is a single leaf: rays are cheap, avoid queue traffic
     {   // "long ray first": worth it only where rays can be long, i.e. where some mesh has a real octree
-        float frac = 0.25f;
-        if (const char *e = getenv("XRT_HEAVY")) frac = (float)atof(e);
+        const float frac = cfg.heavy.value_or(0.25f);
         scene->heavyPath = 0.0f;
         scene->deepMeshes = A.meshDepth > 0;
         for (int &t : scene->costT) t = 24;
-        if (const char *e = getenv("XRT_LONG_FRAC")) { int lo = 0, hi = 0; if (sscanf(e, "%d,%d", &lo, &hi) == 2 && lo >= 0 && hi > lo && hi <= 100) { scene->longFracLo = lo; scene->longFracHi = hi; } }
         // (measured: +24 % on the 1M-triangle heightfield, whose stragglers are rays skimming the terrain; nothing on the
         //  instanced grid, whose rays are all about as long as the box -- XRT_HEAVY forces it on for any scene)
-        const bool wanted = getenv("XRT_HEAVY") != nullptr || scene->sceneMode == MODE_SINGLE;
+        const bool wanted = cfg.heavy.has_value() || scene->sceneMode == MODE_SINGLE;
         if (wanted && frac > 0.0f && A.meshDepth > 0 && A.snodes.size() >= 2) {
             const f4 lo = A.snodes[0], hi = A.snodes[1];
             const double dx = (double)hi.x - lo.x, dy = (double)hi.y - lo.y, dz = (double)hi.z - lo.z;
@@ -2027,7 +1963,8 @@ int xrt_device_count(int *count_out) {
 int xrt_scene_create(int device, xrt_scene **scene_out) {
     if (!scene_out) return fail(XRT_E_INVALID_ARG, "xrt_scene_create: null argument");
     *scene_out = nullptr;
-    if (const char *e = getenv("XRT_GUARD")) g_guardMode.store(atoi(e) != 0 ? 1 : 0);
+    const Settings cfg = read_settings();
+    if (cfg.guard) g_guardMode.store(*cfg.guard ? 1 : 0);
     if (device < -1) return fail(XRT_E_INVALID_ARG, "xrt_scene_create: bad device index");
     if (device >= 0) {
         int n = 0;
@@ -2038,58 +1975,12 @@ int xrt_scene_create(int device, xrt_scene **scene_out) {
     xrt_scene *s = new xrt_scene();
     s->device = device;
     if (device >= 0 && hipGetDeviceCount(&s->visibleDevices) != hipSuccess) { (void)hipGetLastError(); s->visibleDevices = 0; }
-    s->waveTimesPath = getenv("XRT_WAVE_TIMES") ? getenv("XRT_WAVE_TIMES") : "";
-    s->stampDumpPath = getenv("XRT_STAMP_DUMP") ? getenv("XRT_STAMP_DUMP") : "";
-    s->fakeGpus = getenv("XRT_FAKE_GPUS") != nullptr;
-    if (const char *e = getenv("XRT_SPREAD_MIN")) { const int v = atoi(e); if (v >= 4 && v <= 64 && v % 4 == 0) s->spreadMin = v; }
-    if (const char *e = getenv("XRT_BATCH_MIN")) { const int v = atoi(e); if (v >= 16 && v <= 64 && v % 16 == 0) s->batchMin = v; }
-    if (const char *e = getenv("XRT_HEAVY_SHIFT")) { const int v = atoi(e); if (v >= 0 && v <= 6) { s->heavyShift = v; s->heavyShiftGiven = true; } }
-    if (const char *e = getenv("XRT_BATCH_MAX")) { const int v = atoi(e); if (v >= 16 && v <= 4096 && v % 16 == 0) s->batchMax = v; }
-    if (const char *e = getenv("XRT_PK_SPLIT")) s->packetSplit = atoi(e) != 0;
-    if (const char *e = getenv("XRT_LEVEL_MAP")) s->noLevelMap = atoi(e) == 0;
-    if (const char *e = getenv("XRT_PK_BUDGET")) { const int v = atoi(e); if (v >= 0 && v <= 1000000) s->packetBudgetUs = v; }   // (0: a walk looks for pending subtrees at every block it enters)
-    if (const char *e = getenv("XRT_PK_BUDGET_ITEM")) { const int v = atoi(e); if (v >= 0 && v <= 1000000) s->packetBudgetItemUs = v; }
-    if (const char *e = getenv("XRT_PK_LONG")) { const int v = atoi(e); if (v >= 0 && v <= 1000000) s->packetLongUs = v; }
-    if (const char *e = getenv("XRT_PK_BUDGET_LONG")) { const int v = atoi(e); if (v >= 0 && v <= 1000000) s->packetBudgetLongUs = v; }
-    if (const char *e = getenv("XRT_PK_SPLIT_ITEMS")) { const int v = atoi(e); if (v >= 1 && v <= (1 << 20)) s->packetSplitItems = v; }
-    if (const char *e = getenv("XRT_PK_GRAB")) { const int v = atoi(e); if (v >= 1 && v <= 64) s->packetGrabMax = v; }
-    if (const char *e = getenv("XRT_PK_STATIC")) { const int v = atoi(e); if (v >= 0 && v <= 64) s->packetStaticDiv = v; }
-    if (const char *e = getenv("XRT_PACKET")) { const int v = atoi(e); if (v >= -1 && v <= 31) s->packetMask = v; }
-    if (const char *e = getenv("XRT_PACKET_HEAP")) { const int v = atoi(e); if (v >= -1 && v <= 31) s->packetMaskHeap = v; }
-    if (const char *e = getenv("XRT_SPLIT")) { const int v = atoi(e); if (v >= 0 && v <= 2) { s->splitMode = v; s->splitGiven = true; } }
-    if (const char *e = getenv("XRT_LAUNCH_EVENTS")) s->launchEvents = atoi(e) != 0;
-    if (const char *e = getenv("XRT_HEAP_FAST")) s->heapFastOk = atoi(e) != 0;
-    if (const char *e = getenv("XRT_ADAPTIVE_FAST")) s->adaptiveFastOk = atoi(e) != 0;
-    if (const char *e = getenv("XRT_ADAPTIVE_CAP")) { const long long v = atoll(e); if (v >= 1) s->adaptiveCap = v; }
-    if (const char *e = getenv("XRT_GRID_HINTS")) s->noGridHints = atoi(e) == 0;
-    if (const char *e = getenv("XRT_STAMP_ROWS")) { const int v = atoi(e); if (v >= 0 && v <= MAX_STAMP_ROWS) s->maxStampRows = v; }
-    if (const char *e = getenv("XRT_LAUNCH_TIMING")) s->noLaunchTiming = atoi(e) == 0;
-    if (const char *e = getenv("XRT_SPLIT_MS")) s->splitMinMs = (float)atof(e);
-    if (const char *e = getenv("XRT_SPLIT_PARTS")) { const int v = atoi(e); if (v >= 2 && v <= 4) s->splitParts = v; }
-    if (const char *e = getenv("XRT_PK_BUNDLE")) s->packetBundle = atoi(e) != 0;
-    if (const char *e = getenv("XRT_PK_PREFETCH")) { const int v = atoi(e); if (v >= -1 && v <= 1) s->packetPrefetch = v; }
-    if (const char *e = getenv("XRT_PK_PREFETCH_BELOW")) { const int v = atoi(e); if (v >= 0 && v <= 100000) s->packetPrefetchBelow = v; }
-    if (const char *e = getenv("XRT_PK_CULL_MIN")) s->packetCullMin = atoi(e);
-    if (const char *e = getenv("XRT_AE")) s->noAnswerAtEmission = atoi(e) == 0;
-    if (const char *e = getenv("XRT_PK_MERGE")) s->packetMerge = atoi(e) != 0;
-    if (const char *e = getenv("XRT_LEAF_ORDER")) s->hs.spatialRuns = atoi(e) != 0;   // 0: the references of big leaves in list order (tools: A/B of the storage order, results never change)
-#ifdef XRT_DEV   // (make DEV=1) the two margin factors are the only switches that can change a result: below their proven values the skips
-                 // are no longer exact.  A shipped library does not read them from the environment of its host process.
-    if (const char *e = getenv("XRT_LEAF_CULL")) { const double v = atof(e); if (v >= 0.0 && v <= 1e6) s->hs.leafCullSafety = v; }   // 0 = no tight leaf boxes, 1 = the proven margin
-    if (const char *e = getenv("XRT_CULL_SAFETY")) { const double v = atof(e); if (v >= 0.0 && v <= 1e6) s->hs.cullSafety = v; }   // factor S of the object pre-cull margin (below 2 the bound is no longer proven)
+    s->cfg = cfg;
+    if (cfg.spatialRuns) s->hs.spatialRuns = *cfg.spatialRuns;
+#ifdef XRT_DEV
+    if (cfg.leafCullSafety) s->hs.leafCullSafety = *cfg.leafCullSafety;
+    if (cfg.cullSafety) s->hs.cullSafety = *cfg.cullSafety;
 #endif
-    s->noRectCull = getenv("XRT_NO_RECT_CULL") != nullptr; s->oneStream = getenv("XRT_ONE_STREAM") != nullptr; s->noFeedback = getenv("XRT_NO_FEEDBACK") != nullptr;
-    if (const char *e = getenv("XRT_OVERLAP_MS")) s->overlapMinMs = (float)atof(e);   // 0: every single-chunk frame gets its context's stream
-    if (const char *e = getenv("XRT_HEAP_RAY_CAP")) { long long v = atoll(e); if (v >= 1024 && v <= HEAP_RAY_CAP) s->heapRayCap = v; }
-    if (const char *e = getenv("XRT_SHADOW_BYTES")) { long long v = atoll(e); if (v >= (1LL << 20)) s->shadowBytes = v; }
-    if (const char *e = getenv("XRT_CHUNK_PATHS")) { long long v = atoll(e); if (v >= 8192 && v <= MAX_CHUNK_PATHS && v % 8192 == 0) s->maxChunkPaths = v; }
-    if (const char *t = getenv("XRT_TUNE")) {   // "refill,nodeBurst,leafBurst[,coopMax]" — scheduling only, never results
-        int v[4] = {0, 0, 0, s->tune[3]};
-        if (sscanf(t, "%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3]) >= 3 && v[0] >= 1 && v[0] <= 64 && v[1] >= 1 && v[2] >= 1 && v[3] >= 0 && v[3] <= 64) {
-            for (int i = 0; i < 4; i++) s->tune[i] = v[i];
-            s->tuneGiven = true;
-        }
-    }
     if (device >= 0) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess) s->numCUs = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
