@@ -124,6 +124,13 @@ namespace RayTraceProject.Native
                                                                       XrtLight[] lights, int nLights, ref XrtRenderOpts opts, uint* rgbaOut, float* rgbF32Out, IntPtr stats);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_cast_rays_device(IntPtr scene, IntPtr dRays, long n, int iteration, float currentRefIndex,
                                                                       XrtLight[] lights, int nLights, ref XrtRenderOpts opts, IntPtr dRgbaOut, IntPtr dRgbF32Out, IntPtr stream, IntPtr stats);
+        // SceneObject.Position / Rotation / Scale (SO:51-88) between frames: the dirty bodies' World / InverseWorld / WorldBoundingBox
+        // (16 + 16 + 6 floats per id), also while RenderAsync tickets are open; the scene octree stays until xrt_scene_build_tree
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_poses(IntPtr scene, [In] int[] objectIds, int n,
+                                                                     [In] float[] world, [In] float[] invWorld, [In] float[] worldBbox);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_poses_device(IntPtr scene, IntPtr dObjectIds, int n,
+                                                                     IntPtr dWorld, IntPtr dInvWorld, IntPtr dWorldBbox, IntPtr stream);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_build_tree(IntPtr scene, int sceneThreshold);
         // can n_gpus > 1 load RCCL?  OK or E_RCCL (-6) with the loader's message; no device is touched
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_rccl_probe();
         // diagnostics of the split walks of long packets (results never depend on them): subtrees handed over, taken, packets split, packets written by a taker

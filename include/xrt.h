@@ -410,6 +410,39 @@ int xrt_cast_rays_device(xrt_scene *scene, const void *d_rays, int64_t n, int32_
                          const xrt_light *lights, int32_t n_lights, const xrt_render_opts *opts,
                          void *d_rgba_out, void *d_rgb_f32_out, void *stream, xrt_stats *stats_out /* nullable */);
 
+/* ---- moving bodies between frames: SceneObject.Position / Rotation / Scale (SO:52-89) ------------------------------------------
+ * Added within ABI 203: these three exports are additive; no existing struct, field or entry point changed.
+ * The setters of the reference only mark a body dirty; its World, InverseWorld and WorldBoundingBox are recomputed lazily (SO:183-199)
+ * and read by the next query (OSM:349-364, 441-443).  xrt_scene_set_poses is that, batched: for i < n, body object_ids[i] takes
+ * world[16i..], inv_world[16i..] and world_bbox[6i..] (the arguments xrt_scene_add_object takes; BoundingBox stays as added).  The scene
+ * octree is NOT rebuilt: OctreeSpatialManager.Build (OSM:64-99) is the only code of the reference that files bodies into it, so a moved body
+ * stays in the nodes of the last xrt_scene_build / xrt_scene_build_tree and the root box keeps its bounds -- as in the reference's own game
+ * loop (a body moved out of the root box is not seen until the tree is built again).
+ *   - object ids out of range, n < 0, or a NULL array with n > 0: XRT_E_INVALID_ARG; n == 0 does nothing.  A body listed twice takes its
+ *     last entry.
+ *   - before the first xrt_scene_build the pose is simply what the build uses; on a host-only scene (device -1) the host copy is
+ *     updated (xrt_scene_save writes it) and the call returns XRT_OK.
+ *   - non-finite or singular transforms are accepted; the body's pre-cull record is then switched off, as at build time.
+ *   - xrt_scene_save writes the current poses (the file format is unchanged).
+ * Pipelining: the call may be made while one or two begin/end tickets are open, and neither synchronises the device nor waits for the
+ * frames in flight.  A frame renders with the poses set before its _begin, never with later ones; seam-1 calls (xrt_scene_intersect,
+ * xrt_cast_rays, ...) use the latest poses.  XRT_E_BUSY only while another thread is inside a render call on the scene. */
+int xrt_scene_set_poses(xrt_scene *scene, const int32_t *object_ids, int32_t n, const float *world, const float *inv_world,
+                        const float *world_bbox);
+
+/* The same with HBM arrays (int32 ids, 16n + 16n + 6n floats), read in order after the work enqueued on `stream` (a hipStream_t; NULL = the
+ * scene's stream); work enqueued on `stream` afterwards follows the update.  Every array 16-byte aligned, else XRT_E_INVALID_ARG.  The ids
+ * are not looked at on the host: ids out of range are skipped, and the ids of one call must be distinct.  Host-only scene:
+ * XRT_E_NO_DEVICE; before xrt_scene_build: XRT_E_NOT_BUILT. */
+int xrt_scene_set_poses_device(xrt_scene *scene, const void *d_object_ids, int32_t n, const void *d_world, const void *d_inv_world,
+                               const void *d_world_bbox, void *stream);
+
+/* OctreeSpatialManager.Build alone (OSM:64-99, 218-248) over the current poses: the scene octree, its root box and the pre-cull records in
+ * scene-leaf order are made again; meshes, mesh octrees, triangles and textures are untouched.  scene_threshold 0 = the reference
+ * default (20, OSM:50).  The frame that follows equals that of a scene built from scratch with the same poses.  XRT_E_BUSY while a
+ * begin/end ticket is open; XRT_E_NOT_BUILT before xrt_scene_build. */
+int xrt_scene_build_tree(xrt_scene *scene, int32_t scene_threshold);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,9 @@ SYMBOLS = {
                                 _P(C.c_uint32), _F, _P(xrt_stats)]),
     "xrt_cast_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, _P(xrt_light), C.c_int32, _P(xrt_render_opts),
                                        C.c_void_p, C.c_void_p, C.c_void_p, _P(xrt_stats)]),
+    "xrt_scene_set_poses": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int32, _F, _F, _F]),
+    "xrt_scene_set_poses_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "xrt_scene_build_tree": (C.c_int, [C.c_void_p, C.c_int32]),
 }
 
 _lib = None

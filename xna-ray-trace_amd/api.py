@@ -183,10 +183,12 @@ class Mesh:
 
 
 class SceneObject:
-    """SceneObject.cs:12 — transform + shared mesh list (SO:126-127); BuildWorld is SO:183-199."""
+    """SceneObject.cs:12 — transform + shared mesh list (SO:126-127); BuildWorld is SO:183-199.  Position / Rotation / Scale mark the
+    body dirty (SO:52-89): the OctreeSpatialManager it is in hands the new pose to the library before its next query or frame."""
 
     def __init__(self, meshes, pos=(0, 0, 0), rot=(0, 0, 0), name=None):
         self.Meshes = list(meshes)
+        self._pose_serial = 0
         self.Position = tuple(pos)
         self.Rotation = tuple(rot)
         self.Scale = (1.0, 1.0, 1.0)
@@ -196,6 +198,33 @@ class SceneObject:
             bb[:3] = np.minimum(bb[:3], m.MeshBoundingBox[:3])
             bb[3:] = np.maximum(bb[3:], m.MeshBoundingBox[3:])
         self.BoundingBox = bb
+
+    @property
+    def Position(self):
+        return self._position
+
+    @Position.setter
+    def Position(self, value):   # SO:51-62
+        self._position = tuple(value)
+        self._pose_serial += 1
+
+    @property
+    def Rotation(self):
+        return self._rotation
+
+    @Rotation.setter
+    def Rotation(self, value):   # SO:64-75
+        self._rotation = tuple(value)
+        self._pose_serial += 1
+
+    @property
+    def Scale(self):
+        return self._scale
+
+    @Scale.setter
+    def Scale(self, value):   # SO:77-88
+        self._scale = tuple(value)
+        self._pose_serial += 1
 
     def _build_world(self):
         world, inv, wbb = xna.build_world(self.Scale, self.Rotation, self.Position, self.BoundingBox)
@@ -235,8 +264,18 @@ class OctreeSpatialManager(ISpatialManager):
         self._scene = None
         self._mesh_ids = {}
         self.meshes = []
+        self._built_key = None   # the bodies and meshes of the last Build
+        self._pushed = []        # per body: the pose serial the library has
+
+    def _key(self):
+        return (self.meshItemTreshold, tuple((id(b), tuple(id(m) for m in b.Meshes)) for b in self.Bodies))
 
     def Build(self):   # OSM:64-99 (+ Mesh.Init of every distinct mesh, SO:132)
+        if self._scene is not None and self._built_key == self._key():
+            # same bodies and meshes: OctreeSpatialManager.Build alone over the current poses (xrt_scene_build_tree)
+            self._push_poses()
+            abi.check(abi.lib().xrt_scene_build_tree(self._scene.handle, self.itemTreshold))
+            return
         self._scene = _Scene(self.device)
         self._mesh_ids = {}
         self.meshes = []
@@ -253,6 +292,41 @@ class OctreeSpatialManager(ISpatialManager):
             abi.check(abi.lib().xrt_scene_add_object(self._scene.handle, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids),
                                                      _fp(world), _fp(inv), _fp(bb), _fp(wbb), C.byref(oid)))
         abi.check(abi.lib().xrt_scene_build(self._scene.handle, self.meshItemTreshold, self.itemTreshold))
+        self._built_key = self._key()
+        self._pushed = [b._pose_serial for b in self.Bodies]
+
+    def _push_poses(self):
+        """The poses of the bodies moved since the last push, in one xrt_scene_set_poses (before every query and frame)."""
+        if self._scene is None or self._built_key is None:
+            return
+        moved = [i for i, b in enumerate(self.Bodies) if b._pose_serial != self._pushed[i]]
+        if moved:
+            self.SetPoses(moved, *zip(*(self.Bodies[i]._build_world() for i in moved)))
+            for i in moved:
+                self._pushed[i] = self.Bodies[i]._pose_serial
+
+    def SetPoses(self, ids, world, inv, wbb):
+        """xrt_scene_set_poses: body ids[i] takes world[i] (16 floats), inv[i] (16) and wbb[i] (6); the scene octree stays as built."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        w = np.ascontiguousarray(world, dtype=np.float32).reshape(-1)
+        iw = np.ascontiguousarray(inv, dtype=np.float32).reshape(-1)
+        bb = np.ascontiguousarray(wbb, dtype=np.float32).reshape(-1)
+        n = ids.shape[0]
+        if w.size != 16 * n or iw.size != 16 * n or bb.size != 6 * n:
+            raise ValueError("SetPoses: 16 + 16 + 6 floats per id")
+        abi.check(abi.lib().xrt_scene_set_poses(self.handle, ids.ctypes.data_as(C.POINTER(C.c_int32)), n, _fp(w), _fp(iw), _fp(bb)))
+
+    def SetPosesDevice(self, ids, world, inv, wbb, stream=None):
+        """xrt_scene_set_poses_device on CUDA tensors (int32 ids; float32 world / inv with 16 and wbb with 6 values per id, contiguous),
+        ordered after `stream` (a torch stream; default: the current one)."""
+        import torch
+        n = ids.numel()
+        for t, k, dt in ((ids, 1, torch.int32), (world, 16, torch.float32), (inv, 16, torch.float32), (wbb, 6, torch.float32)):
+            if not t.is_cuda or not t.is_contiguous() or t.dtype != dt or t.numel() != k * n:
+                raise ValueError("SetPosesDevice: contiguous CUDA tensors, int32 ids and float32 poses (16 + 16 + 6 per id)")
+        s = stream if stream is not None else torch.cuda.current_stream(ids.device)
+        abi.check(abi.lib().xrt_scene_set_poses_device(self.handle, C.c_void_p(ids.data_ptr()), n, C.c_void_p(world.data_ptr()),
+                                                       C.c_void_p(inv.data_ptr()), C.c_void_p(wbb.data_ptr()), C.c_void_p(s.cuda_stream)))
 
     def Save(self, path):
         """xrt_scene_save: the built scene's meshes, materials, texels and bodies as one file (the reference's .xnb content)."""
@@ -289,6 +363,7 @@ class OctreeSpatialManager(ISpatialManager):
         rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
         hits = np.zeros(rays.shape[0], dtype=HIT_DTYPE)
         st = abi.xrt_stats()
+        self._push_poses()
         abi.check(abi.lib().xrt_scene_intersect(self.handle, rays.ctypes.data_as(C.POINTER(abi.xrt_ray)), None, rays.shape[0],
                                                 hits.ctypes.data_as(C.POINTER(abi.xrt_hit)), C.byref(st) if stats else None))
         return (hits, st.as_dict()) if stats else hits
@@ -407,6 +482,13 @@ class RayTracer:
         self._target = value
         self.renderTargetData = np.zeros(value.Width * value.Height, dtype=np.uint32)     # RT:29
 
+    def _scene_handle(self):
+        """The current scene's handle, after the bodies moved since the last frame have been handed over (SO:52-89)."""
+        sc = self.CurrentScene
+        if hasattr(sc, "_push_poses"):
+            sc._push_poses()
+        return sc.handle
+
     @property
     def Progress(self):   # RT:43-46
         return float(abi.lib().xrt_progress(self.CurrentScene.handle))
@@ -445,7 +527,7 @@ class RayTracer:
         cam, opts, lights = self._camera_abi(), self._opts_abi(), self._lights_abi()
         st = abi.xrt_stats()
         rgbf = np.zeros(self._target.Width * self._target.Height * 3, dtype=np.float32) if want_float else None
-        abi.check(abi.lib().xrt_render(self.CurrentScene.handle, C.byref(cam), lights, len(self.Lights), C.byref(opts),
+        abi.check(abi.lib().xrt_render(self._scene_handle(), C.byref(cam), lights, len(self.Lights), C.byref(opts),
                                        self.renderTargetData.ctypes.data_as(C.POINTER(C.c_uint32)),
                                        _fp(rgbf) if want_float else None, C.byref(st)))
         self.last_stats = st.as_dict()
@@ -482,6 +564,7 @@ class RayTracer:
         args = (handle, C.byref(cam), lights, n, C.byref(opts), C.c_void_p(d_rgba_ptr), C.c_void_p(stream or 0), C.byref(st))
 
         def frame():
+            self._scene_handle()
             abi.check(fn(*args))
             self.last_stats = st.as_dict()
             return self.last_stats
@@ -493,6 +576,7 @@ class RayTracer:
         bargs = args[:-1] + (C.byref(ticket),)
 
         def begin():
+            self._scene_handle()
             abi.check(lib.xrt_render_device_begin(*bargs))
             return ticket.value
 
@@ -531,6 +615,7 @@ class RayTracer:
         ptr = host_array.ctypes.data_as(C.POINTER(C.c_uint32))
 
         def begin():
+            self._scene_handle()
             abi.check(lib.xrt_render_begin(handle, C.byref(cam), lights, n, C.byref(opts), ptr, C.byref(ticket)))
             return ticket.value
 
@@ -559,7 +644,7 @@ class RayTracer:
             rgba = torch.empty(n, dtype=torch.int32, device=rays.device)
             rgbf = torch.empty((n, 3), dtype=torch.float32, device=rays.device) if want_float else None
             s = stream if stream is not None else torch.cuda.current_stream(rays.device)
-            abi.check(lib.xrt_cast_rays_device(self.CurrentScene.handle, C.c_void_p(rays.data_ptr()), n, int(iteration), float(currentRefIndex),
+            abi.check(lib.xrt_cast_rays_device(self._scene_handle(), C.c_void_p(rays.data_ptr()), n, int(iteration), float(currentRefIndex),
                                                lights, len(self.Lights), C.byref(opts), C.c_void_p(rgba.data_ptr()),
                                                C.c_void_p(rgbf.data_ptr()) if want_float else None, C.c_void_p(s.cuda_stream), C.byref(st)))
         else:
@@ -567,7 +652,7 @@ class RayTracer:
             n = rays.shape[0]
             rgba = np.zeros(n, dtype=np.uint32)
             rgbf = np.zeros((n, 3), dtype=np.float32) if want_float else None
-            abi.check(lib.xrt_cast_rays(self.CurrentScene.handle, rays.ctypes.data_as(C.POINTER(abi.xrt_ray)), n, int(iteration), float(currentRefIndex),
+            abi.check(lib.xrt_cast_rays(self._scene_handle(), rays.ctypes.data_as(C.POINTER(abi.xrt_ray)), n, int(iteration), float(currentRefIndex),
                                         lights, len(self.Lights), C.byref(opts), rgba.ctypes.data_as(C.POINTER(C.c_uint32)),
                                         _fp(rgbf) if want_float else None, C.byref(st)))
         self.last_stats = st.as_dict()
@@ -584,5 +669,5 @@ class RayTracer:
         """The rays of RT:410-421 for the whole target."""
         cam = self._camera_abi()
         rays = np.zeros(self._target.Width * self._target.Height, dtype=RAY_DTYPE)
-        abi.check(abi.lib().xrt_generate_primary_rays(self.CurrentScene.handle, C.byref(cam), rays.ctypes.data_as(C.POINTER(abi.xrt_ray))))
+        abi.check(abi.lib().xrt_generate_primary_rays(self._scene_handle(), C.byref(cam), rays.ctypes.data_as(C.POINTER(abi.xrt_ray))))
         return rays

@@ -226,4 +226,25 @@ void launch_ms_fold(uint32_t *quadColor, const uint32_t *childColor, const int *
 void launch_detile(int width, int height, int shardCount, int tilesPerRank, const uint32_t *gathered, long long rankStride, uint32_t *out,
                    hipStream_t st, const int *table = nullptr);
 
+// xrt_scene_set_poses[_device]: entry i gives body ids[i] the pose world[16i..] / inv[16i..] / wbb[6i..] (SO:52-89, 183-199).  k_pose writes
+// the body's ObjRec in `objects` (world, inverse, the pre-cull record of pose.h from its meshes' boxes), its records in `scull` at every
+// scene-leaf position posStart[id] .. posStart[id + 1] of pos, and wbb into wbbOut[6 id..] (what xrt_scene_build_tree reads back).
+// Ids outside [0, nObjects) are skipped; the ids of one call must be distinct.  One kernel launch: with copyObjects the version is first
+// made a copy of another (one workgroup: copy, barrier, update), so a pose update is a single dispatch however the versions rotate.
+struct PoseArgs {
+    const int *ids = nullptr;
+    const float *world = nullptr, *inv = nullptr, *wbb = nullptr;
+    int n = 0, nObjects = 0;
+    ObjRec *objects = nullptr;
+    f4 *scull = nullptr;
+    const int *posStart = nullptr, *pos = nullptr, *objMesh = nullptr;
+    const MeshRec *meshes = nullptr;
+    float *wbbOut = nullptr;
+    double safety = 2.0;
+    const ObjRec *copyObjects = nullptr;   // non-null: objects / scull start as a copy of these (nCopyObjects / nCopyScull records)
+    const f4 *copyScull = nullptr;
+    int nCopyObjects = 0, nCopyScull = 0;
+};
+void launch_pose(const PoseArgs &P, hipStream_t st);
+
 }  // namespace xrt

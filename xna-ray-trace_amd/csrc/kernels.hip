@@ -18,6 +18,7 @@
 // Built with -ffp-contract=off: every result must be bit-identical to the oracle.
 #include "kernels.h"
 #include "device_util.h"
+#include "pose.h"
 
 #include <hip/hip_ext.h>
 
@@ -1367,6 +1368,49 @@ void launch_detile(int width, int height, int shardCount, int tilesPerRank, cons
                    const int *table) {
     int tilesX = (width + XRT_TILE_W - 1) / XRT_TILE_W, tilesY = (height + XRT_TILE_H - 1) / XRT_TILE_H;
     hipLaunchKernelGGL(k_detile, dim3(2048), dim3(256), 0, st, width, height, shardCount, tilesPerRank, tilesX, tilesY, gathered, rankStride, out, table);
+}
+
+// ---- poses (xrt_scene_set_poses): one thread per entry ----------------------------------------------------------------
+struct PoseMeshBoxes {   // the AABBs of a body's meshes (MeshRec: Mesh.MeshBoundingBox) for pose.h object_cull_box
+    const int *ids;
+    const MeshRec *meshes;
+    XRT_HD void operator()(int k, float bb[6]) const {
+        const MeshRec &m = meshes[ids[k]];
+        bb[0] = m.bmin[0]; bb[1] = m.bmin[1]; bb[2] = m.bmin[2]; bb[3] = m.bmax[0]; bb[4] = m.bmax[1]; bb[5] = m.bmax[2];
+    }
+};
+__device__ __forceinline__ void pose_one(const PoseArgs &P, int i) {
+    const int o = P.ids[i];
+    if (o < 0 || o >= P.nObjects) return;
+    ObjRec r = P.objects[o];
+    for (int k = 0; k < 16; k++) { r.world[k] = P.world[16 * (size_t)i + k]; r.invWorld[k] = P.inv[16 * (size_t)i + k]; }
+    object_cull_box(r.invWorld, r.meshCount, PoseMeshBoxes{P.objMesh + r.meshStart, P.meshes}, r, P.safety);
+    P.objects[o] = r;
+    for (int k = 0; k < 6; k++) P.wbbOut[6 * (size_t)o + k] = P.wbb[6 * (size_t)i + k];
+    f4 rec[4];
+    scull_record(r, o, rec);
+    for (int k = P.posStart[o]; k < P.posStart[o + 1]; k++) {
+        f4 *q = P.scull + 4 * (size_t)P.pos[k];
+        q[0] = rec[0]; q[1] = rec[1]; q[2] = rec[2]; q[3] = rec[3];
+    }
+}
+__global__ __launch_bounds__(256) void k_pose(PoseArgs P) {
+    if (P.copyObjects) {   // one workgroup: the version starts as a copy of the source version, then the entries are applied
+        const f4 *src = reinterpret_cast<const f4 *>(P.copyObjects);
+        f4 *dst = reinterpret_cast<f4 *>(P.objects);
+        const int nObjF4 = P.nCopyObjects * (int)(sizeof(ObjRec) / sizeof(f4));
+        for (int k = threadIdx.x; k < nObjF4; k += blockDim.x) dst[k] = src[k];
+        for (int k = threadIdx.x; k < P.nCopyScull; k += blockDim.x) P.scull[k] = P.copyScull[k];
+        __syncthreads();
+        for (int i = threadIdx.x; i < P.n; i += blockDim.x) pose_one(P, i);
+        return;
+    }
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < P.n) pose_one(P, i);
+}
+void launch_pose(const PoseArgs &P, hipStream_t st) {
+    if (P.n <= 0) return;
+    hipLaunchKernelGGL(k_pose, dim3(P.copyObjects ? 1 : (P.n + 255) / 256), dim3(256), 0, st, P);
 }
 
 }  // namespace xrt

@@ -21,6 +21,7 @@ struct SceneArrays {
     std::vector<f4> runTB;                                 // 4 per run of LEAF_RUN references of a big leaf: the run's tight box (same record as leafTB)
     std::vector<int> runBase;                              // per node: index of the leaf's first run in runTB / 4, or -1 (small leaf, interior, empty)
     std::vector<f4> scull;                                 // 4 per scene leaf reference (traverse.h SceneView::scull)
+    std::vector<int> scullPosStart, scullPos;              // body o's records in scull: positions scullPos[scullPosStart[o] .. scullPosStart[o + 1])
     std::vector<f4> leafTB;                                // 4 per node: the leaf's tight box (xrt_core.h leaf_certainly_missed)
     std::vector<g3> refG;
     // The wave-packet kernel's copies (packet.hip: everything it walks arrives through scalar loads from THREE arrays -- pblocks, lrec, refT):
@@ -58,11 +59,19 @@ struct HostScene {
     int add_object(const int *meshIds, int n, const float *world, const float *invWorld, const float *bbox,
                    const float *worldBbox, std::string &err);
     bool build(int meshThreshold, int sceneThreshold, std::string &err);
+    // SceneObject.World / InverseWorld / WorldBoundingBox setters (SO:52-89, 183-199): after a build also the body's ObjRec and its records
+    // in scull; the scene octree stays as built (OSM:64-99 runs only in Build).
+    bool set_pose(int id, const float *world, const float *invWorld, const float *worldBbox, std::string &err);
+    // OctreeSpatialManager.Build alone over the current poses (0 = OSM:50's 20): meshes, their octrees and the ObjRecs are untouched.
+    bool build_tree(int sceneThreshold, std::string &err);
     // Scene file (xrt_scene_save / xrt_scene_load): the meshes, materials, texels and bodies exactly as they were added --
     // what the reference keeps in .xnb files (Model.Tag, TMP:113-117) -- little-endian, no pointers.  The trees are rebuilt on load.
     bool save(const char *path, std::string &err) const;
     bool load(const char *path, std::string &err);
-    SceneView host_view() const;   // pointers into `arrays` (CPU single-stepping in tests/emul only)
+    SceneView host_view() const;
+  private:
+    bool scene_part(int sceneThreshold, std::string &err);
+  public:   // pointers into `arrays` (CPU single-stepping in tests/emul only)
 };
 
 }  // namespace xrt

@@ -209,6 +209,28 @@ struct xrt_scene {
     DevBuf<MaterialRec> materials;
     DevBuf<uint32_t> texels;
     SceneView view{};
+    // Pose versions (xrt_scene_set_poses): a frame reads the ObjRecs and pre-cull records of ONE version, the one that was current at its
+    // begin (FrameCtx::pose).  Version 0 is `objects` / `scull`, versions 1 and 2 are made when a pose update must not overwrite a version
+    // an open ticket reads: with at most two tickets open one of the three is always free, so an update never waits for a frame.
+    struct PoseVer {
+        DevBuf<ObjRec> objects;   // (version 0: the scene's own `objects` / `scull`)
+        DevBuf<f4> scull;
+        hipEvent_t ready = nullptr;        // recorded behind the version's last write; null while it holds the build's records
+        unsigned long long serial = 0;     // which write it holds (a replica copies the primary's version when the serials differ)
+        std::vector<std::pair<hipStream_t, hipEvent_t>> readers;   // the last asynchronous seam-1 read on each stream (xrt_scene_intersect_device)
+    } pose[3];
+    int poseCur = 0;                       // the version new frames and seam-1 calls read
+    int slotPose[2] = {-1, -1};            // the version of the open ticket `slot`
+    unsigned long long poseSerial = 0;     // writes since the build
+    bool posesOnDevice = false;            // hs's poses are behind: the last update came from device arrays (xrt_scene_set_poses_device)
+    hipStream_t poseStream = nullptr;      // pose updates run here
+    hipEvent_t poseInput = nullptr;        // the caller's stream -> poseStream
+    DevBuf<int> scullPosStart, scullPos;   // HostScene scullPosStart / scullPos
+    DevBuf<float> wbbDev;                  // WorldBoundingBox of every body, 6 floats (kept by k_pose for the read-back)
+    DevBuf<float> poseIn;                  // the host form's arrays on the device: ids | world | inv | wbb
+    void *posePinned = nullptr;            // ... and their page-locked staging
+    size_t posePinnedBytes = 0;
+    hipEvent_t poseStaged = nullptr;       // the staging copy is done (the staging may be refilled)
     bool resident = false;
     int numCUs = 256;
     int stackNeeded = 2;
@@ -297,6 +319,7 @@ struct xrt_scene {
         size_t ev = 0;
         hipEvent_t done = nullptr;   // recorded after the frame's last copy
         std::vector<LightRec> hostLights;
+        int pose = 0;                // the pose version the frame reads (xrt_scene::pose)
         bool pending = false;
         bool fast = false;           // no copy / fill / event-record commands: k_compose hands the counters over, events ride on kernels
         int *pinnedDev = nullptr;    // device view of `pinned`
@@ -364,6 +387,16 @@ struct xrt_scene {
             tileTableDev.release(); tileCost.release();
             for (int i = 0; i < 2; i++) { if (tilesReady[i]) (void)hipEventDestroy(tilesReady[i]); if (tailDone[i]) (void)hipEventDestroy(tailDone[i]); gathered[i].release(); tileOut[i].release(); frameOut[i].release(); }
             for (auto e : events) (void)hipEventDestroy(e);
+            for (auto &v : pose) {
+                if (v.ready) (void)hipEventDestroy(v.ready);
+                for (auto &rd : v.readers) (void)hipEventDestroy(rd.second);
+                v.objects.release(); v.scull.release();
+            }
+            if (poseInput) (void)hipEventDestroy(poseInput);
+            if (poseStaged) (void)hipEventDestroy(poseStaged);
+            if (posePinned) (void)hipHostFree(posePinned);
+            if (poseStream) (void)hipStreamDestroy(poseStream);
+            scullPosStart.release(); scullPos.release(); wbbDev.release(); poseIn.release();
             for (auto &f : frames) {
                 for (auto e : f.events) (void)hipEventDestroy(e);
                 if (f.done) (void)hipEventDestroy(f.done);
@@ -417,6 +450,34 @@ hipEvent_t get_event(std::vector<hipEvent_t> &pool, size_t i) {
     return pool[i];
 }
 hipEvent_t get_event(xrt_scene *s, size_t i) { return get_event(s->events, i); }
+
+// ---- pose versions (xrt_scene_set_poses) ---------------------------------------------------------------------------------
+ObjRec *pose_objects(xrt_scene *s, int v) { return v == 0 ? s->objects.p : s->pose[v].objects.p; }
+f4 *pose_scull(xrt_scene *s, int v) { return v == 0 ? s->scull.p : s->pose[v].scull.p; }
+SceneView pose_view(xrt_scene *s, int v) {
+    SceneView S = s->view;
+    S.objects = pose_objects(s, v); S.scull = pose_scull(s, v);
+    return S;
+}
+// Work on `st` that reads version v starts after the version's last write.
+int pose_wait(xrt_scene *s, int v, hipStream_t st) {
+    if (s->pose[v].ready) HIPCHECK(hipStreamWaitEvent(st, s->pose[v].ready, 0));
+    return XRT_OK;
+}
+// An asynchronous read of version v on `st` was enqueued: the next write of v waits for it.
+int pose_reader(xrt_scene *s, int v, hipStream_t st) {
+    auto &rd = s->pose[v].readers;
+    size_t i = 0;
+    while (i < rd.size() && rd[i].first != st) i++;
+    if (i == rd.size()) {
+        hipEvent_t e = nullptr;
+        HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        rd.emplace_back(st, e);
+    }
+    HIPCHECK(hipEventRecord(rd[i].second, st));
+    return XRT_OK;
+}
+bool pose_referenced(const xrt_scene *s, int v) { return s->slotPose[0] == v || s->slotPose[1] == v; }
 
 int persistent_grid(xrt_scene *s, long long nHost, int raysPerBlock = 256) {
     int full = s->numCUs * s->blocksPerCU;
@@ -799,6 +860,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
             st = W.stream;
         } else st = s->stream;
     }
+    if ((rc = pose_wait(s, F.pose, st))) return rc;   // (the poses set before the frame's begin)
     // Tile costs (xrt.h xrt_scene_tile_costs): the packets of plain one-chunk frames add their device-clock ticks to the tile of their first
     // ray.  The words belong to the scene (both frame contexts add to them); a frame of another geometry or tile table starts them afresh.
     unsigned *tileCostDev = nullptr;
@@ -872,7 +934,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     ShadeView V;
     V.shade = s->shade.p; V.materials = s->materials.p; V.texels = s->texels.p; V.meshes = s->meshes.p;
     V.lights = W.lights.p; V.nLights = nL; V.addressMode = opts->address_mode; V.filtering = opts->filtering;
-    const SceneView &S = s->view;
+    const SceneView S = pose_view(s, F.pose);   // every kernel of the frame reads one pose version
     xrt_ray *rays[2] = {W.rays0.p, W.rays1.p};
     int *paths[2] = {W.path0.p, W.path1.p};
     int *nodesOf[2] = {W.node0.p, W.node1.p};
@@ -1480,6 +1542,9 @@ int ensure_replicas(xrt_scene *s, int n) {
         HIPCHECK(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
         int rc = scene_upload(r.get());
         if (rc != XRT_OK) return rc;
+        // the replica's version 0 holds the host's records: the primary's version 0 only while no pose was set since the build
+        for (auto &v : r->pose) v.serial = ~0ull;
+        if (s->poseSerial == 0) r->pose[0].serial = 0;
         s->workers.emplace_back(new RankWorker(r->device));
         s->replicas.push_back(r.release());
     }
@@ -1505,6 +1570,29 @@ int read_tile_costs(xrt_scene *r, int w, int h, float *cost, bool reset) {
     const int tiles = ((w + XRT_TILE_W - 1) / XRT_TILE_W) * ((h + XRT_TILE_H - 1) / XRT_TILE_H);
     for (size_t sl = 0; sl < ticks.size(); sl++) { const int t = r->costTiles[sl]; if (t >= 0 && t < tiles) cost[t] += (float)ticks[sl]; }
     if (reset) HIPCHECK(hipMemset(r->tileCost.p, 0, ticks.size() * sizeof(unsigned)));
+    return XRT_OK;
+}
+
+// Replica r renders version v of the primary's poses: copied from the primary's version v when r's copy is of another write.
+// Stream-ordered on r's stream behind the primary's write; the replica's frame waits for the copy (frame_begin, pose_wait).
+int replica_pose(xrt_scene *s, xrt_scene *r, int v) {
+    xrt_scene::PoseVer &P = s->pose[v], &R = r->pose[v];
+    if (R.serial == P.serial) return XRT_OK;
+    const size_t nObj = s->host->arrays.objects.size(), nCull = s->host->arrays.scull.size();
+    int rc;
+    HIPCHECK(hipSetDevice(r->device));
+    if (v != 0 && ((rc = R.objects.ensure(nObj)) || (rc = R.scull.ensure(nCull)))) return rc;
+    if (P.ready) HIPCHECK(hipStreamWaitEvent(r->stream, P.ready, 0));
+    if (r->device == s->device) {
+        HIPCHECK(hipMemcpyAsync(pose_objects(r, v), pose_objects(s, v), nObj * sizeof(ObjRec), hipMemcpyDeviceToDevice, r->stream));
+        HIPCHECK(hipMemcpyAsync(pose_scull(r, v), pose_scull(s, v), nCull * sizeof(f4), hipMemcpyDeviceToDevice, r->stream));
+    } else {
+        HIPCHECK(hipMemcpyPeerAsync(pose_objects(r, v), r->device, pose_objects(s, v), s->device, nObj * sizeof(ObjRec), r->stream));
+        HIPCHECK(hipMemcpyPeerAsync(pose_scull(r, v), r->device, pose_scull(s, v), s->device, nCull * sizeof(f4), r->stream));
+    }
+    if (!R.ready) HIPCHECK(hipEventCreateWithFlags(&R.ready, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(R.ready, r->stream));
+    R.serial = P.serial;
     return XRT_OK;
 }
 
@@ -1561,6 +1649,8 @@ int multi_begin(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_light *
         if ((rc = r->tileOut[slot].ensure(count))) { (void)hipSetDevice(s->device); return rc; }
         if (s->cfg.fakeGpus && !r->tilesReady[slot]) HIPCHECK(hipEventCreateWithFlags(&r->tilesReady[slot], hipEventDisableTiming));
     }
+    for (int i = 1; i < n; i++)
+        if ((rc = replica_pose(s, rank_scene(s, i), s->slotPose[slot]))) { (void)hipSetDevice(s->device); return rc; }
     HIPCHECK(hipSetDevice(s->device));
     // every device's share is enqueued by its own (persistent) host thread
     std::vector<int> rcs((size_t)n, XRT_OK);
@@ -1571,6 +1661,7 @@ int multi_begin(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_light *
         xrt_render_opts o = *opts;
         o.n_gpus = 0; o.shard_rank = i; o.shard_count = n;
         uint32_t *dst = i == 0 ? s->gathered[slot].p : r->tileOut[slot].p;
+        r->frames[slot].pose = s->slotPose[slot];   // (every rank renders the primary's version)
         rcs[(size_t)i] = frame_begin(r, r->frames[slot], cam, lights, nLights, &o, dst, nullptr, nullptr, 0, 1, false);   // (the gather is enqueued behind the frame: no redo)
         if (rcs[(size_t)i] != XRT_OK) errs[(size_t)i] = g_err;
     };
@@ -1698,6 +1789,12 @@ int open_frame_impl(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_lig
     }
     hipStream_t st0 = nullptr;
     int nParts = 1;
+    s->slotPose[slot] = s->poseCur;   // the frame renders the poses set before its begin, whatever is set while it is open
+    struct PoseRelease {   // (an open that fails leaves no ticket)
+        xrt_scene *s; int slot; bool keep = false;
+        ~PoseRelease() { if (!keep) s->slotPose[slot] = -1; }
+    } poseRelease{s, slot};
+    for (int j = 0; j < 4; j++) s->frames[slot + 2 * j].pose = s->poseCur;
     if (n == 1) {
         // Two halves on two streams?  Only plain single-pass frames that run long enough for the drain of their launches to
         // matter, on streams of the library's choosing; by default only when no other frame is in flight to fill the gaps.
@@ -1728,6 +1825,7 @@ int open_frame_impl(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_lig
         if (!s->tailDone[slot]) HIPCHECK(hipEventCreateWithFlags(&s->tailDone[slot], hipEventDisableTiming));
         HIPCHECK(hipEventRecord(s->tailDone[slot], st0));
     }
+    poseRelease.keep = true;
     return XRT_OK;
 }
 
@@ -1761,6 +1859,7 @@ int close_frame_impl(xrt_scene *s, int slot, xrt_stats *stats) {
         if (e != hipSuccess && rc == XRT_OK) rc = fail(XRT_E_HIP, "hipEventSynchronize: %s", hipGetErrorString(e));
     }
     O = xrt_scene::OpenFrame();
+    s->slotPose[slot] = -1;
     if (rc == XRT_OK) rc = guards_check("end of frame");
     return rc;
 }
@@ -1817,6 +1916,8 @@ int run_intersect(xrt_scene *s, const xrt_ray *d_rays, int64_t n, xrt_hit *d_hit
         if (!a0 || !a1) return fail(XRT_E_HIP, "hipEventCreate failed");
         HIPCHECK(hipMemsetAsync(s->counters.p, 0, 2 * C_COUNT * sizeof(unsigned long long), st));
     }
+    const SceneView S = pose_view(s, s->poseCur);   // seam 1 reads the latest poses
+    if ((rc = pose_wait(s, s->poseCur, st))) return rc;
     const bool meshOk = mode != MODE_MESH || (meshId >= 0 && meshId < (int)s->host->meshTrees.size() && !s->host->meshTrees[(size_t)meshId].rootIsLeaf);
     if (n > 0 && s->cfg.packetMask >= 0 && (s->cfg.packetMask & 8) && packet_supported(mode, s->host->arrays.meshDepth, s->host->arrays.sceneDepth) && meshOk) {   // (testing aid: arbitrary batches through the packet kernel)
         PacketArgs PA;
@@ -1828,10 +1929,10 @@ int run_intersect(xrt_scene *s, const xrt_ray *d_rays, int64_t n, xrt_hit *d_hit
         int grid = s->numCUs * packet_blocks_per_cu(mode);
         const long long want = (n + 255) / 256;
         if (want < grid) grid = (int)want;
-        launch_packet(s->view, PA, grid, st, a0, a1);
-    } else if (n > 0) launch_intersect(s->view, A, s->stackNeeded, persistent_grid(s, n), st, a0, a1);
+        launch_packet(S, PA, grid, st, a0, a1);
+    } else if (n > 0) launch_intersect(S, A, s->stackNeeded, persistent_grid(s, n), st, a0, a1);
     if (stats) {
-        if (n > 0) launch_count(s->view, A, s->counters.p, st);
+        if (n > 0) launch_count(S, A, s->counters.p, st);
     }
     HIPCHECK(hipGetLastError());
     if (sync || stats) HIPCHECK(hipStreamSynchronize(st));
@@ -1870,6 +1971,7 @@ int cast_rays_impl(xrt_scene *s, const xrt_ray *d_rays, int64_t n, int32_t itera
     BatchSrc b;
     b.rays = d_rays; b.n = n; b.refIndex = refIndex;
     xrt_scene::FrameCtx &F = s->frames[0];
+    F.pose = s->poseCur;
     Range rf("xrt cast rays (%lld)", (long long)n);
     int rc = frame_begin(s, F, nullptr, lights, nLights, &o, d_out, d_outF32, st, 0, 1, false, &b);
     if (rc != XRT_OK) {
@@ -1879,19 +1981,37 @@ int cast_rays_impl(xrt_scene *s, const xrt_ray *d_rays, int64_t n, int32_t itera
     return frame_finish(s, F, stats);
 }
 
-int scene_upload(xrt_scene *scene) {
+int pose_upload(xrt_scene *scene);
+
+// What is made from the scene octree and the poses (snodes, srefs, objects, scull, the positions of every body's records in scull, the
+// bodies' world boxes) -> HBM; the pose versions start again from version 0 (xrt_scene_build, xrt_scene_build_tree).  No frame in flight.
+int tree_upload(xrt_scene *scene) {
     const SceneArrays &A = scene->host->arrays;
-    scene->stackNeeded = (A.sceneDepth + 1) + (A.meshDepth + 1);
-    if (intersect_stack_capacity(scene->stackNeeded) < 0) return fail(XRT_E_UNSUPPORTED, "octree too deep for the LDS stack (%d levels)", scene->stackNeeded);
-    if (scene->device < 0) return XRT_OK;   // host-only scene: trees can be inspected, nothing can be traced
-    HIPCHECK(hipSetDevice(scene->device));
     int rc;
-    if ((rc = upload(scene->blocks, A.blocks)) || (rc = upload(scene->leafNB, A.leafNB)) || (rc = upload(scene->leafTB, A.leafTB)) || (rc = upload(scene->refT, A.refT)) || (rc = upload(scene->pblocks, A.pblocks)) || (rc = upload(scene->lrec, A.lrec)) || (rc = upload(scene->refN, A.refN)) || (rc = upload(scene->refG, A.refG)) ||
-        (rc = upload(scene->snodes, A.snodes)) || (rc = upload(scene->shade, A.shade)) || (rc = upload(scene->childDfs, A.childDfs)) ||
-        (rc = upload(scene->srefs, A.srefs)) || (rc = upload(scene->scull, A.scull)) || (rc = upload(scene->runTB, A.runTB)) || (rc = upload(scene->triTB, A.triTB)) || (rc = upload(scene->runBase, A.runBase)) || (rc = upload(scene->objMesh, A.objMesh)) ||
-        (rc = upload(scene->meshes, A.meshes)) || (rc = upload(scene->objects, A.objects)) || (rc = upload(scene->materials, A.materials)) ||
-        (rc = upload(scene->texels, A.texels)))
+    if ((rc = upload(scene->snodes, A.snodes)) || (rc = upload(scene->srefs, A.srefs)) || (rc = upload(scene->scull, A.scull)) || (rc = upload(scene->objects, A.objects)))
         return rc;
+    return pose_upload(scene);
+}
+
+// The bodies' positions in scull and their world boxes -> HBM; the pose versions start again from version 0.
+int pose_upload(xrt_scene *scene) {
+    const SceneArrays &A = scene->host->arrays;
+    int rc;
+    if ((rc = upload(scene->scullPosStart, A.scullPosStart)) || (rc = upload(scene->scullPos, A.scullPos))) return rc;
+    std::vector<float> wbb(6 * (scene->host->objects.size() + 1), 0.0f);
+    for (size_t o = 0; o < scene->host->objects.size(); o++) std::memcpy(&wbb[6 * o], scene->host->objects[o].worldBbox, 6 * sizeof(float));
+    if ((rc = upload(scene->wbbDev, wbb))) return rc;
+    for (auto &v : scene->pose) {
+        if (v.ready) (void)hipEventDestroy(v.ready);
+        v.ready = nullptr; v.serial = 0;
+    }
+    scene->poseCur = 0; scene->poseSerial = 0; scene->posesOnDevice = false;
+    return XRT_OK;
+}
+
+// Launch geometry and scheduling defaults that scene_upload derives from the scene (again after xrt_scene_build_tree).
+int scene_derive(xrt_scene *scene) {
+    const SceneArrays &A = scene->host->arrays;
     SceneView &S = scene->view;
     S.blocks = scene->blocks.p; S.childDfs = scene->childDfs.p; S.leafNB = scene->leafNB.p; S.leafTB = scene->leafTB.p; S.refT = scene->refT.p; S.pblocks = scene->pblocks.p; S.lrec = scene->lrec.p; S.refN = scene->refN.p; S.refG = scene->refG.p;
     S.meshes = scene->meshes.p; S.snodes = scene->snodes.p; S.srefs = scene->srefs.p; S.scull = scene->scull.p; S.runTB = scene->runTB.p; S.triTB = scene->triTB.p; S.runBase = scene->runBase.p;
@@ -1932,6 +2052,83 @@ int scene_upload(xrt_scene *scene) {
         }
     }
     scene->resident = true;
+    return XRT_OK;
+}
+
+int scene_upload(xrt_scene *scene) {
+    const SceneArrays &A = scene->host->arrays;
+    const int stackNeeded = (A.sceneDepth + 1) + (A.meshDepth + 1);
+    if (intersect_stack_capacity(stackNeeded) < 0) return fail(XRT_E_UNSUPPORTED, "octree too deep for the LDS stack (%d levels)", stackNeeded);
+    scene->stackNeeded = stackNeeded;
+    if (scene->device < 0) return XRT_OK;   // host-only scene: trees can be inspected, nothing can be traced
+    HIPCHECK(hipSetDevice(scene->device));
+    int rc;
+    if ((rc = upload(scene->blocks, A.blocks)) || (rc = upload(scene->leafNB, A.leafNB)) || (rc = upload(scene->leafTB, A.leafTB)) || (rc = upload(scene->refT, A.refT)) || (rc = upload(scene->pblocks, A.pblocks)) || (rc = upload(scene->lrec, A.lrec)) || (rc = upload(scene->refN, A.refN)) || (rc = upload(scene->refG, A.refG)) ||
+        (rc = upload(scene->snodes, A.snodes)) || (rc = upload(scene->shade, A.shade)) || (rc = upload(scene->childDfs, A.childDfs)) ||
+        (rc = upload(scene->srefs, A.srefs)) || (rc = upload(scene->scull, A.scull)) || (rc = upload(scene->runTB, A.runTB)) || (rc = upload(scene->triTB, A.triTB)) || (rc = upload(scene->runBase, A.runBase)) || (rc = upload(scene->objMesh, A.objMesh)) ||
+        (rc = upload(scene->meshes, A.meshes)) || (rc = upload(scene->objects, A.objects)) || (rc = upload(scene->materials, A.materials)) ||
+        (rc = upload(scene->texels, A.texels)) || (rc = pose_upload(scene)))
+        return rc;
+    return scene_derive(scene);
+}
+
+// Enqueue one pose update: entries [0, n) of the device arrays ids / world / inv / wbb, ready on `st`, become the newest version.  The version
+// written is the current one unless an open ticket reads it; then a free one, made a copy of the current one first.  Nothing here waits
+// for the device: the update runs on poseStream behind `st` and behind the asynchronous seam-1 reads of the version it overwrites, and
+// `st` continues behind the update (the caller may refill its arrays there).  Caller holds apiMutex and the scene (BusyGuard).
+int poses_enqueue(xrt_scene *s, const int *ids, int n, const float *world, const float *inv, const float *wbb, hipStream_t st) {
+    const int cur = s->poseCur;
+    int v = cur;
+    if (pose_referenced(s, v))
+        for (int x = 0; x < 3; x++) if (x != cur && !pose_referenced(s, x)) { v = x; break; }
+    if (pose_referenced(s, v)) return fail(XRT_E_INTERNAL, "xrt_scene_set_poses: no free pose version");
+    xrt_scene::PoseVer &P = s->pose[v];
+    const SceneArrays &A = s->host->arrays;
+    int rc;
+    if (!s->poseStream) HIPCHECK(hipStreamCreateWithFlags(&s->poseStream, hipStreamNonBlocking));
+    if (!s->poseInput) HIPCHECK(hipEventCreateWithFlags(&s->poseInput, hipEventDisableTiming));
+    hipStream_t ps = s->poseStream;
+    if (st != ps) {
+        HIPCHECK(hipEventRecord(s->poseInput, st));
+        HIPCHECK(hipStreamWaitEvent(ps, s->poseInput, 0));
+    }
+    for (auto &rd : P.readers) HIPCHECK(hipStreamWaitEvent(ps, rd.second, 0));
+    PoseArgs PA;
+    if (v != cur) {   // (k_pose copies the current version first)
+        if ((rc = P.objects.ensure(A.objects.size())) || (rc = P.scull.ensure(A.scull.size()))) return rc;
+        PA.copyObjects = pose_objects(s, cur); PA.copyScull = pose_scull(s, cur);
+        PA.nCopyObjects = (int)A.objects.size(); PA.nCopyScull = (int)A.scull.size();
+    }
+    PA.ids = ids; PA.world = world; PA.inv = inv; PA.wbb = wbb; PA.n = n; PA.nObjects = (int)s->host->objects.size();
+    PA.objects = pose_objects(s, v); PA.scull = pose_scull(s, v);
+    PA.posStart = s->scullPosStart.p; PA.pos = s->scullPos.p; PA.objMesh = s->objMesh.p; PA.meshes = s->meshes.p;
+    PA.wbbOut = s->wbbDev.p; PA.safety = s->host->cullSafety;
+    launch_pose(PA, ps);
+    HIPCHECK(hipGetLastError());
+    if (!P.ready) HIPCHECK(hipEventCreateWithFlags(&P.ready, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(P.ready, ps));
+    if (st != ps) HIPCHECK(hipStreamWaitEvent(st, P.ready, 0));
+    P.serial = ++s->poseSerial;
+    s->poseCur = v;
+    return XRT_OK;
+}
+
+// hs's poses <- the device's current version (after xrt_scene_set_poses_device): what xrt_scene_build_tree and xrt_scene_save read.
+int pull_poses(xrt_scene *s) {
+    if (!s->posesOnDevice) return XRT_OK;
+    HIPCHECK(hipSetDevice(s->device));
+    if (s->poseStream) HIPCHECK(hipStreamSynchronize(s->poseStream));
+    const size_t nObj = s->hs.objects.size();
+    std::vector<ObjRec> recs(nObj);
+    std::vector<float> wbb(6 * nObj);
+    if (nObj) {
+        HIPCHECK(hipMemcpy(recs.data(), pose_objects(s, s->poseCur), nObj * sizeof(ObjRec), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(wbb.data(), s->wbbDev.p, 6 * nObj * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    std::string err;
+    for (size_t o = 0; o < nObj; o++)
+        if (!s->hs.set_pose((int)o, recs[o].world, recs[o].invWorld, &wbb[6 * o], err)) return fail(XRT_E_INTERNAL, "%s", err.c_str());
+    s->posesOnDevice = false;
     return XRT_OK;
 }
 
@@ -2041,10 +2238,116 @@ int xrt_scene_build(xrt_scene *scene, int32_t mesh_threshold, int32_t scene_thre
     });
 }
 
+int xrt_scene_set_poses(xrt_scene *scene, const int32_t *object_ids, int32_t n, const float *world, const float *inv_world,
+                        const float *world_bbox) {
+    if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_scene_set_poses: null scene");
+    if (n < 0 || (n > 0 && (!object_ids || !world || !inv_world || !world_bbox))) return fail(XRT_E_INVALID_ARG, "xrt_scene_set_poses: null argument");
+    const int nObj = (int)scene->hs.objects.size();
+    for (int i = 0; i < n; i++)
+        if (object_ids[i] < 0 || object_ids[i] >= nObj) return fail(XRT_E_INVALID_ARG, "xrt_scene_set_poses: object id %d out of range (%d bodies)", object_ids[i], nObj);
+    if (n == 0) return XRT_OK;
+    std::lock_guard<std::mutex> lock(scene->apiMutex);
+    BusyGuard guard(scene);
+    if (!guard.owned) return fail(XRT_E_BUSY, "xrt_scene_set_poses: another call is rendering on the scene");
+    return guarded("xrt_scene_set_poses", [&]() -> int {
+        // the last entry of a body wins (the setters called one after the other); the host copy first: save and the next build read it
+        // (after an update from device arrays the other bodies' host poses stay behind until pull_poses: the device's version has them all)
+        std::vector<int> last((size_t)nObj, -1), order;
+        for (int i = 0; i < n; i++) last[(size_t)object_ids[i]] = i;
+        for (int i = 0; i < n; i++) if (last[(size_t)object_ids[i]] == i) order.push_back(i);
+        const bool onDevice = scene->device >= 0 && scene->hs.built && scene->resident;
+        std::string err;
+        for (int i : order)
+            if (!scene->hs.set_pose(object_ids[i], world + 16 * (size_t)i, inv_world + 16 * (size_t)i, world_bbox + 6 * (size_t)i, err))
+                return fail(XRT_E_INVALID_ARG, "%s", err.c_str());
+        if (!onDevice) return XRT_OK;
+        HIPCHECK(hipSetDevice(scene->device));
+        // staging: ids | world | inv | wbb in page-locked memory, one asynchronous copy to the device
+        const size_t m = order.size(), idWords = (m + 3) / 4 * 4, words = idWords + m * (16 + 16 + 6);
+        if (scene->poseStaged) HIPCHECK(hipEventSynchronize(scene->poseStaged));   // (the previous update's copy of a few KB)
+        if (scene->posePinnedBytes < words * 4) {
+            if (scene->posePinned) HIPCHECK(hipHostFree(scene->posePinned));
+            scene->posePinned = nullptr; scene->posePinnedBytes = 0;
+            HIPCHECK(hipHostMalloc(&scene->posePinned, words * 4, hipHostMallocDefault));
+            scene->posePinnedBytes = words * 4;
+        }
+        int rc;
+        if ((rc = scene->poseIn.ensure(words))) return rc;
+        int *hid = (int *)scene->posePinned;
+        float *hw = (float *)scene->posePinned + idWords, *hi = hw + 16 * m, *hb = hi + 16 * m;
+        for (size_t k = 0; k < m; k++) {
+            const size_t i = (size_t)order[k];
+            hid[k] = object_ids[i];
+            std::memcpy(hw + 16 * k, world + 16 * i, 64); std::memcpy(hi + 16 * k, inv_world + 16 * i, 64); std::memcpy(hb + 6 * k, world_bbox + 6 * i, 24);
+        }
+        if (!scene->poseStream) HIPCHECK(hipStreamCreateWithFlags(&scene->poseStream, hipStreamNonBlocking));
+        if (!scene->poseStaged) HIPCHECK(hipEventCreateWithFlags(&scene->poseStaged, hipEventDisableTiming));
+        HIPCHECK(hipMemcpyAsync(scene->poseIn.p, scene->posePinned, words * 4, hipMemcpyHostToDevice, scene->poseStream));
+        HIPCHECK(hipEventRecord(scene->poseStaged, scene->poseStream));
+        const float *dw = scene->poseIn.p + idWords;
+        return poses_enqueue(scene, (const int *)scene->poseIn.p, (int)m, dw, dw + 16 * m, dw + 32 * m, scene->poseStream);
+    });
+}
+
+int xrt_scene_set_poses_device(xrt_scene *scene, const void *d_object_ids, int32_t n, const void *d_world, const void *d_inv_world,
+                               const void *d_world_bbox, void *stream) {
+    if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_scene_set_poses_device: null scene");
+    if (n < 0 || (n > 0 && (!d_object_ids || !d_world || !d_inv_world || !d_world_bbox))) return fail(XRT_E_INVALID_ARG, "xrt_scene_set_poses_device: null argument");
+    if (((uintptr_t)d_object_ids & 15) || ((uintptr_t)d_world & 15) || ((uintptr_t)d_inv_world & 15) || ((uintptr_t)d_world_bbox & 15))
+        return fail(XRT_E_INVALID_ARG, "xrt_scene_set_poses_device: device arrays must be 16-byte aligned");
+    int rc = need_device(scene, "xrt_scene_set_poses_device");
+    if (rc != XRT_OK) return rc;
+    if (n == 0) return XRT_OK;
+    std::lock_guard<std::mutex> lock(scene->apiMutex);
+    BusyGuard guard(scene);
+    if (!guard.owned) return fail(XRT_E_BUSY, "xrt_scene_set_poses_device: another call is rendering on the scene");
+    return guarded("xrt_scene_set_poses_device", [&]() -> int {
+        hipStream_t st = stream ? (hipStream_t)stream : scene->stream;
+        if ((rc = poses_enqueue(scene, (const int *)d_object_ids, n, (const float *)d_world, (const float *)d_inv_world, (const float *)d_world_bbox, st)))
+            return rc;
+        scene->posesOnDevice = true;
+        return XRT_OK;
+    });
+}
+
+int xrt_scene_build_tree(xrt_scene *scene, int32_t scene_threshold) {
+    if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_scene_build_tree: null scene");
+    if (in_flight(scene)) return fail(XRT_E_BUSY, "xrt_scene_build_tree: a frame is in flight");
+    if (!scene->hs.built) return fail(XRT_E_NOT_BUILT, "xrt_scene_build_tree: call xrt_scene_build first");
+    std::lock_guard<std::mutex> lock(scene->apiMutex);
+    BusyGuard guard(scene);
+    if (!guard.owned) return fail(XRT_E_BUSY, "xrt_scene_build_tree: a frame is in flight");
+    return guarded("xrt_scene_build_tree", [&]() -> int {
+        int rc;
+        if (scene->device >= 0 && scene->resident && (rc = pull_poses(scene))) return rc;
+        std::string err;
+        scene->resident = false;
+        if (!scene->hs.build_tree(scene_threshold, err)) return fail(XRT_E_UNSUPPORTED, "%s", err.c_str());
+        scene->workers.clear();
+        for (xrt_scene *r : scene->replicas) delete r;   // (copies of the previous tree: made again on the next n_gpus > 1 frame)
+        scene->replicas.clear();
+        const SceneArrays &A = scene->hs.arrays;
+        const int stackNeeded = (A.sceneDepth + 1) + (A.meshDepth + 1);
+        if (intersect_stack_capacity(stackNeeded) < 0) return fail(XRT_E_UNSUPPORTED, "octree too deep for the LDS stack (%d levels)", stackNeeded);
+        scene->stackNeeded = stackNeeded;
+        if (scene->device < 0) return XRT_OK;
+        HIPCHECK(hipSetDevice(scene->device));
+        if (scene->poseStream) HIPCHECK(hipStreamSynchronize(scene->poseStream));
+        if ((rc = tree_upload(scene))) return rc;
+        return scene_derive(scene);
+    });
+}
+
 int xrt_scene_save(const xrt_scene *scene, const char *path) {
     if (!scene || !path) return fail(XRT_E_INVALID_ARG, "xrt_scene_save: null argument");
     return guarded("xrt_scene_save", [&]() -> int {
         std::string err;
+        xrt_scene *s = const_cast<xrt_scene *>(scene);   // (the poses last set on the device are read back first)
+        if (s->device >= 0 && s->resident) {
+            std::lock_guard<std::mutex> lock(s->apiMutex);
+            int rc = pull_poses(s);
+            if (rc != XRT_OK) return rc;
+        }
         if (!scene->hs.save(path, err)) return fail(XRT_E_INVALID_ARG, "%s (%s)", err.c_str(), path);
         return XRT_OK;
     });
@@ -2108,7 +2411,8 @@ int xrt_scene_intersect_device(xrt_scene *scene, const void *d_rays, int64_t n, 
     if (n < 0 || (n > 0 && (!d_rays || !d_hits_out))) return fail(XRT_E_INVALID_ARG, "xrt_scene_intersect_device: null argument");
     if (((uintptr_t)d_rays & 15) || ((uintptr_t)d_hits_out & 15)) return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
     std::lock_guard<std::mutex> lock(scene->apiMutex);   // (held for the enqueue only: the call is asynchronous)
-    return run_intersect(scene, (const xrt_ray *)d_rays, n, (xrt_hit *)d_hits_out, scene->sceneMode, 0, (hipStream_t)stream, nullptr, false);
+    if ((rc = run_intersect(scene, (const xrt_ray *)d_rays, n, (xrt_hit *)d_hits_out, scene->sceneMode, 0, (hipStream_t)stream, nullptr, false))) return rc;
+    return pose_reader(scene, scene->poseCur, (hipStream_t)stream);
 }
 
 int xrt_mesh_intersect(xrt_scene *scene, int32_t mesh_id, const xrt_ray *rays, int64_t n, xrt_hit *hits_out) {
@@ -2371,7 +2675,8 @@ int xrt_generate_primary_rays(xrt_scene *scene, const xrt_camera *camera, xrt_ra
     std::lock_guard<std::mutex> lock(scene->apiMutex);
     if ((rc = scene->apiRays.ensure((size_t)slots))) return rc;
     hipStream_t st = scene->stream;
-    launch_raygen(g, scene->view, scene->apiRays.p, nullptr, nullptr, nullptr, (int)slots, 0, HeavyArgs(), st);
+    if ((rc = pose_wait(scene, scene->poseCur, st))) return rc;
+    launch_raygen(g, pose_view(scene, scene->poseCur), scene->apiRays.p, nullptr, nullptr, nullptr, (int)slots, 0, HeavyArgs(), st);
     HIPCHECK(hipGetLastError());
     std::vector<xrt_ray> tmp((size_t)slots);
     HIPCHECK(hipMemcpyAsync(tmp.data(), scene->apiRays.p, (size_t)slots * sizeof(xrt_ray), hipMemcpyDeviceToHost, st));
