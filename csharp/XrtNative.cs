@@ -53,6 +53,12 @@ namespace RayTraceProject.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public struct XrtPathVertex                     // xrt_path_vertex: VertexPositionColor (Vector3 position, packed Color) -- one end of a segment of RayTracer.points
+    {
+        public float x, y, z; public uint color;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public struct XrtStats
     {
         public ulong raysClosest, raysShadow, hitsClosest, hitsShadow, sceneNodeTests, instanceVisits, meshAabbTests, meshQueries,
@@ -124,6 +130,14 @@ namespace RayTraceProject.Native
                                                                       XrtLight[] lights, int nLights, ref XrtRenderOpts opts, uint* rgbaOut, float* rgbF32Out, IntPtr stats);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_cast_rays_device(IntPtr scene, IntPtr dRays, long n, int iteration, float currentRefIndex,
                                                                       XrtLight[] lights, int nLights, ref XrtRenderOpts opts, IntPtr dRgbaOut, IntPtr dRgbF32Out, IntPtr stream, IntPtr stats);
+        // ... with RayTracer.points (RT:543, 701: the segments every call appends, vertices[vertexStart[i] .. vertexStart[i + 1]) for ray i) and the ray as CastRay leaves its
+        // `ref Ray ray` (RT:692-694).  nVerticesOut is what the batch needs; a capacity that is too small is not an error (the first whole segments are written)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern unsafe int xrt_cast_rays_paths(IntPtr scene, [In] XrtRay[] rays, long n, int iteration, float currentRefIndex,
+                                                                      XrtLight[] lights, int nLights, ref XrtRenderOpts opts, uint* rgbaOut, float* rgbF32Out, [Out] XrtRay[] raysBack,
+                                                                      [Out] long[] vertexStart, [Out] XrtPathVertex[] vertices, long vertexCapacity, out long nVerticesOut, IntPtr stats);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_cast_rays_paths_device(IntPtr scene, IntPtr dRays, long n, int iteration, float currentRefIndex,
+                                                                      XrtLight[] lights, int nLights, ref XrtRenderOpts opts, IntPtr dRgbaOut, IntPtr dRgbF32Out, IntPtr dRaysBack,
+                                                                      IntPtr dVertexStart, IntPtr dVertices, long vertexCapacity, IntPtr stream, out long nVerticesOut, IntPtr stats);
         // SceneObject.Position / Rotation / Scale (SO:51-88) between frames: the dirty bodies' World / InverseWorld / WorldBoundingBox
         // (16 + 16 + 6 floats per id), also while RenderAsync tickets are open; the scene octree stays until xrt_scene_build_tree
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_poses(IntPtr scene, [In] int[] objectIds, int n,

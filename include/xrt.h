@@ -410,6 +410,56 @@ int xrt_cast_rays_device(xrt_scene *scene, const void *d_rays, int64_t n, int32_
                          const xrt_light *lights, int32_t n_lights, const xrt_render_opts *opts,
                          void *d_rgba_out, void *d_rgb_f32_out, void *stream, xrt_stats *stats_out /* nullable */);
 
+/* ---- seam 3, second half: RayTracer.points (RT:504, 543, 701, 740-747) and CastRay's `ref Ray ray` (RT:692-694) ---------------------
+ * Added within ABI 203: one struct and two exports, additive; no existing struct, field or entry point changed.
+ * Every CastRay appends line segments to the public list RayTracer.points -- the reference's host draws it over its preview (G1:403-413) --
+ * and overwrites the ray it was given where it refracts.  For one call C(ray, it), in this order:
+ *   miss: nothing.   hit: the segment (ray.Position, hit position) in Color.White, whether or not it < MaxReflections (RT:543);
+ *   if it < MaxReflections: the segments of the reflection, cast with a fresh ray (RT:547-559);
+ *   if the material is also Transparent: ray = (hit position, refracted direction) (RT:692-694), the segments of C(ray, it + 1) on that
+ *   same variable (RT:698), then (ray.Position, ray.Direction * 100) in Color.Red (RT:701) with ray as the nested call left it -- the second
+ *   vertex is the direction times 100.0f, a vector, not a point on the ray; every red segment of an unbroken refraction chain therefore
+ *   carries the chain's last ray (the deepest one assigned at RT:692-694, whether or not it hit anything).
+ * xrt_path_vertex is VertexPositionColor: position, then the colour packed as rgba_out packs colours (White 0xFFFFFFFF, Red 0xFF0000FF);
+ * a segment is two consecutive vertices (PrimitiveType.LineList).  Non-finite values (total internal reflection, RT:676) are recorded as they are.
+ *
+ * xrt_cast_rays_paths is xrt_cast_rays -- every word said there holds, and rgba_out / rgb_f32_out / stats_out are bit for bit what it
+ * returns for the same arguments -- and additionally:
+ *   vertices[vertex_start[i] .. vertex_start[i + 1]) = the vertices of ray i in the reference's order, rays in the caller's order (as if the
+ *   reference had made the n calls one after the other on one thread); vertex_start (may be NULL) has n + 1 entries, vertex_start[n] ==
+ *   *n_vertices_out, always even.
+ *   *n_vertices_out (not NULL) = the number of vertices the batch NEEDS.  vertices == NULL with vertex_capacity == 0, or a capacity that is
+ *   too small, is no error: the first vertex_capacity vertices (rounded down to whole segments) are written, nothing at or behind
+ *   vertices[vertex_capacity], vertex_start is complete and the call returns XRT_OK -- compare the count with the capacity.  A call with
+ *   vertices == NULL counts; nothing is traced twice within one call.  vertex_capacity < 0, or > 0 with vertices == NULL: XRT_E_INVALID_ARG.
+ *   rays_back (may be NULL; may be `rays` itself): rays_back[i].o / .d = the ray as CastRay leaves its `ref ray` -- the last ray of the
+ *   refraction chain that starts at the root, or the ray as given when the root misses, is not Transparent or iteration >= max_reflections;
+ *   ignore_mesh / ignore_tri are copied from rays[i].
+ * n == 0: *n_vertices_out = 0 and vertex_start[0] = 0.
+ * Frames record nothing: the reference's Render clears the list (RT:61) and then appends every pixel's segments under one lock, which
+ * nobody wants at 1080p; xrt_render* stay as they are. */
+typedef struct xrt_path_vertex {
+    float    position[3];
+    uint32_t color;
+} xrt_path_vertex;
+
+int xrt_cast_rays_paths(xrt_scene *scene, const xrt_ray *rays, int64_t n, int32_t iteration, float current_ref_index,
+                        const xrt_light *lights, int32_t n_lights, const xrt_render_opts *opts,
+                        uint32_t *rgba_out, float *rgb_f32_out /* nullable */,
+                        xrt_ray *rays_back /* nullable, n */, int64_t *vertex_start /* nullable, n + 1 */,
+                        xrt_path_vertex *vertices /* nullable */, int64_t vertex_capacity, int64_t *n_vertices_out,
+                        xrt_stats *stats_out /* nullable */);
+
+/* The same on HBM buffers, as xrt_cast_rays_device: d_rays_back (NULL or n xrt_ray; NOT d_rays itself), d_vertex_start (NULL or n + 1
+ * int64), d_vertices (NULL or vertex_capacity xrt_path_vertex), each 16-byte aligned, else XRT_E_INVALID_ARG.  Enqueued on `stream` and
+ * synchronised once before it returns; n_vertices_out is host memory.  Nothing is written at or behind d_vertices[vertex_capacity]. */
+int xrt_cast_rays_paths_device(xrt_scene *scene, const void *d_rays, int64_t n, int32_t iteration, float current_ref_index,
+                               const xrt_light *lights, int32_t n_lights, const xrt_render_opts *opts,
+                               void *d_rgba_out, void *d_rgb_f32_out /* nullable */,
+                               void *d_rays_back /* nullable */, void *d_vertex_start /* nullable */,
+                               void *d_vertices /* nullable */, int64_t vertex_capacity, void *stream,
+                               int64_t *n_vertices_out /* host */, xrt_stats *stats_out /* nullable */);
+
 /* ---- moving bodies between frames: SceneObject.Position / Rotation / Scale (SO:52-89) ------------------------------------------
  * Added within ABI 203: these three exports are additive; no existing struct, field or entry point changed.
  * The setters of the reference only mark a body dirty; its World, InverseWorld and WorldBoundingBox are recomputed lazily (SO:183-199)

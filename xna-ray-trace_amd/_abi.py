@@ -92,6 +92,11 @@ class xrt_node_info(C.Structure):
                 ("dfs_index", C.c_int32), ("depth", C.c_int32), ("first_ref", C.c_int32), ("reserved", C.c_int32)]
 
 
+class xrt_path_vertex(C.Structure):   # VertexPositionColor: one end of a segment of RayTracer.points
+    _fields_ = [("position", C.c_float * 3), ("color", C.c_uint32)]
+
+
+assert C.sizeof(xrt_path_vertex) == 16
 assert C.sizeof(xrt_ray) == 32 and C.sizeof(xrt_hit) == 48 and C.sizeof(xrt_render_opts) == 48
 XRT_VERSION = 203
 
@@ -135,6 +140,10 @@ SYMBOLS = {
                                 _P(C.c_uint32), _F, _P(xrt_stats)]),
     "xrt_cast_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, _P(xrt_light), C.c_int32, _P(xrt_render_opts),
                                        C.c_void_p, C.c_void_p, C.c_void_p, _P(xrt_stats)]),
+    "xrt_cast_rays_paths": (C.c_int, [C.c_void_p, _P(xrt_ray), C.c_int64, C.c_int32, C.c_float, _P(xrt_light), C.c_int32, _P(xrt_render_opts),
+                                      _P(C.c_uint32), _F, _P(xrt_ray), _P(C.c_int64), _P(xrt_path_vertex), C.c_int64, _P(C.c_int64), _P(xrt_stats)]),
+    "xrt_cast_rays_paths_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, _P(xrt_light), C.c_int32, _P(xrt_render_opts),
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, _P(C.c_int64), _P(xrt_stats)]),
     "xrt_scene_set_poses": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int32, _F, _F, _F]),
     "xrt_scene_set_poses_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "xrt_scene_build_tree": (C.c_int, [C.c_void_p, C.c_int32]),

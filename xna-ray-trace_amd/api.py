@@ -112,6 +112,8 @@ HIT_DTYPE = np.dtype([("hit", np.int32), ("object", np.int32), ("mesh", np.int32
                       ("u", np.float32), ("v", np.float32), ("d", np.float32), ("w", np.float32, 3), ("reserved", np.int32)])
 NODE_DTYPE = np.dtype([("bmin", np.float32, 3), ("bmax", np.float32, 3), ("is_leaf", np.int32), ("count", np.int32),
                        ("dfs_index", np.int32), ("depth", np.int32), ("first_ref", np.int32), ("reserved", np.int32)])
+VERTEX_DTYPE = np.dtype([("position", np.float32, 3), ("color", np.uint32)])   # xrt_path_vertex: VertexPositionColor of RayTracer.points
+assert VERTEX_DTYPE.itemsize == C.sizeof(abi.xrt_path_vertex)
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 48 and NODE_DTYPE.itemsize == C.sizeof(abi.xrt_node_info)
 
 
@@ -468,6 +470,13 @@ class RayTracer:
         self.renderTargetData = None
         self.last_stats = None
         self.collect_stats = False
+        # RT:504: the debugging list of ray paths (VERTEX_DTYPE records, two per segment).  Off by default: CastRay / CastRays cost and return
+        # what they did; with RecordPoints they append to it.  Render* clears it (RT:61) and records nothing -- the reference's frame appends every
+        # pixel's segments under one lock.
+        self.points = []
+        self.RecordPoints = False
+        self.last_ray = None            # with RecordPoints: (position, direction) as the last CastRay left its `ref Ray ray` (RT:692-694)
+        self.last_n_vertices = 0        # vertices the last recording call needed
         self.NumGpus = 1                # xrt_render_opts.n_gpus: one process, the frame's tiles dealt to this many devices
         self.BalanceTiles = False       # xrt_render_opts.balance_tiles (with NumGpus > 1): tiles dealt by the last frame's costs instead of round-robin
 
@@ -526,6 +535,7 @@ class RayTracer:
         """Blocking RenderInternal (RT:103-126).  Returns the packed Color[] (and the float colorVector)."""
         cam, opts, lights = self._camera_abi(), self._opts_abi(), self._lights_abi()
         st = abi.xrt_stats()
+        self.points.clear()   # RT:61
         rgbf = np.zeros(self._target.Width * self._target.Height * 3, dtype=np.float32) if want_float else None
         abi.check(abi.lib().xrt_render(self._scene_handle(), C.byref(cam), lights, len(self.Lights), C.byref(opts),
                                        self.renderTargetData.ctypes.data_as(C.POINTER(C.c_uint32)),
@@ -565,6 +575,7 @@ class RayTracer:
 
         def frame():
             self._scene_handle()
+            self.points.clear()   # RT:61
             abi.check(fn(*args))
             self.last_stats = st.as_dict()
             return self.last_stats
@@ -577,6 +588,7 @@ class RayTracer:
 
         def begin():
             self._scene_handle()
+            self.points.clear()   # RT:61
             abi.check(lib.xrt_render_device_begin(*bargs))
             return ticket.value
 
@@ -616,6 +628,7 @@ class RayTracer:
 
         def begin():
             self._scene_handle()
+            self.points.clear()   # RT:61
             abi.check(lib.xrt_render_begin(handle, C.byref(cam), lights, n, C.byref(opts), ptr, C.byref(ticket)))
             return ticket.value
 
@@ -627,15 +640,26 @@ class RayTracer:
         begin.begin, begin.end = begin, end
         return begin
 
-    # ---- RayTracer.CastRay (RT:506-737) on caller-given rays: xrt_cast_rays ----
-    def CastRays(self, rays, iteration=0, currentRefIndex=1.0, want_float=False, device=False, stream=None):
+    # ---- RayTracer.CastRay (RT:506-737) on caller-given rays: xrt_cast_rays, xrt_cast_rays_paths ----
+    def CastRays(self, rays, iteration=0, currentRefIndex=1.0, want_float=False, device=False, stream=None, paths=False, vertex_capacity=None):
         """CastRay(ref rays[i], out color, iteration, origin_i, null, currentRefIndex) for every ray of a batch, origin_i = the ray's
         (ignore_mesh, ignore_tri).  Host form: `rays` an xrt_ray array (RAY_DTYPE) -> uint32 colours (and float32 (n, 3) colour vectors
         with want_float).  device=True: `rays` a contiguous CUDA tensor of n 32-byte records (e.g. (n, 8) float32) -> torch tensors on
-        its device (int32 holding the packed colours; float32 (n, 3)), enqueued on `stream` (a torch stream, default: the current one)."""
+        its device (int32 holding the packed colours; float32 (n, 3)), enqueued on `stream` (a torch stream, default: the current one).
+
+        paths=True (xrt_cast_rays_paths): additionally returns (vertices, vertex_start, rays_back) -- the segments every call appends to
+        RayTracer.points (RT:543, 701), vertices[vertex_start[i]:vertex_start[i + 1]] being ray i's, and every ray as CastRay leaves its
+        `ref ray` (RT:692-694).  Host form: a VERTEX_DTYPE array (`position`, `color`), int64[n + 1], RAY_DTYPE[n]; device form: torch tensors
+        (float32 (m, 4) whose last column holds the colour's bits, int64 (n + 1), float32 (n, 8)).  How the vertex array is sized: with
+        vertex_capacity=None a first call counts (no vertex array) and a second call of exactly that capacity fills it -- the batch is traced
+        twice; a caller who knows a bound passes vertex_capacity and gets one call, the array cut to what fitted; last_n_vertices is what
+        the batch needs either way.
+        With RecordPoints the segments are also appended to `points` and last_ray is the last ray's (position, direction) as left."""
         opts, lights = self._opts_abi(shard_count=0), self._lights_abi()
         opts.n_gpus = 0
         st, lib = abi.xrt_stats(), abi.lib()
+        record = paths or self.RecordPoints
+        need = C.c_int64(0)
         if device:
             import torch
             if not rays.is_contiguous() or rays.numel() * rays.element_size() % 32:
@@ -644,23 +668,72 @@ class RayTracer:
             rgba = torch.empty(n, dtype=torch.int32, device=rays.device)
             rgbf = torch.empty((n, 3), dtype=torch.float32, device=rays.device) if want_float else None
             s = stream if stream is not None else torch.cuda.current_stream(rays.device)
-            abi.check(lib.xrt_cast_rays_device(self._scene_handle(), C.c_void_p(rays.data_ptr()), n, int(iteration), float(currentRefIndex),
-                                               lights, len(self.Lights), C.byref(opts), C.c_void_p(rgba.data_ptr()),
-                                               C.c_void_p(rgbf.data_ptr()) if want_float else None, C.c_void_p(s.cuda_stream), C.byref(st)))
+            if not record:
+                abi.check(lib.xrt_cast_rays_device(self._scene_handle(), C.c_void_p(rays.data_ptr()), n, int(iteration), float(currentRefIndex),
+                                                   lights, len(self.Lights), C.byref(opts), C.c_void_p(rgba.data_ptr()),
+                                                   C.c_void_p(rgbf.data_ptr()) if want_float else None, C.c_void_p(s.cuda_stream), C.byref(st)))
+            else:
+                vstart = torch.empty(n + 1, dtype=torch.int64, device=rays.device)
+                back = torch.empty((n, 8), dtype=torch.float32, device=rays.device)
+
+                def call(verts, cap):
+                    abi.check(lib.xrt_cast_rays_paths_device(self._scene_handle(), C.c_void_p(rays.data_ptr()), n, int(iteration), float(currentRefIndex),
+                                                             lights, len(self.Lights), C.byref(opts), C.c_void_p(rgba.data_ptr()),
+                                                             C.c_void_p(rgbf.data_ptr()) if want_float else None, C.c_void_p(back.data_ptr()),
+                                                             C.c_void_p(vstart.data_ptr()), C.c_void_p(verts.data_ptr()) if cap > 0 else None, cap,
+                                                             C.c_void_p(s.cuda_stream), C.byref(need), C.byref(st)))
+                cap = vertex_capacity
+                if cap is None:
+                    call(None, 0)
+                    cap = need.value
+                vertices = torch.empty((max(int(cap), 1), 4), dtype=torch.float32, device=rays.device)
+                call(vertices, int(cap))
+                vertices = vertices[:min(need.value, int(cap) & ~1)]
         else:
             rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
             n = rays.shape[0]
             rgba = np.zeros(n, dtype=np.uint32)
             rgbf = np.zeros((n, 3), dtype=np.float32) if want_float else None
-            abi.check(lib.xrt_cast_rays(self._scene_handle(), rays.ctypes.data_as(C.POINTER(abi.xrt_ray)), n, int(iteration), float(currentRefIndex),
-                                        lights, len(self.Lights), C.byref(opts), rgba.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                        _fp(rgbf) if want_float else None, C.byref(st)))
+            if not record:
+                abi.check(lib.xrt_cast_rays(self._scene_handle(), rays.ctypes.data_as(C.POINTER(abi.xrt_ray)), n, int(iteration), float(currentRefIndex),
+                                            lights, len(self.Lights), C.byref(opts), rgba.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            _fp(rgbf) if want_float else None, C.byref(st)))
+            else:
+                vstart = np.zeros(n + 1, dtype=np.int64)
+                back = np.zeros(n, dtype=RAY_DTYPE)
+
+                def call(verts, cap):
+                    abi.check(lib.xrt_cast_rays_paths(self._scene_handle(), rays.ctypes.data_as(C.POINTER(abi.xrt_ray)), n, int(iteration), float(currentRefIndex),
+                                                      lights, len(self.Lights), C.byref(opts), rgba.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                      _fp(rgbf) if want_float else None, back.ctypes.data_as(C.POINTER(abi.xrt_ray)),
+                                                      vstart.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                      verts.ctypes.data_as(C.POINTER(abi.xrt_path_vertex)) if cap > 0 else None, cap, C.byref(need), C.byref(st)))
+                cap = vertex_capacity
+                if cap is None:
+                    call(None, 0)
+                    cap = need.value
+                vertices = np.zeros(max(int(cap), 1), dtype=VERTEX_DTYPE)
+                call(vertices, int(cap))
+                vertices = vertices[:min(need.value, int(cap) & ~1)]
         self.last_stats = st.as_dict()
-        return (rgba, rgbf) if want_float else rgba
+        if record:
+            self.last_n_vertices = need.value
+            if self.RecordPoints:   # RT:740-747: the public list grows call by call
+                host_v = np.ascontiguousarray(vertices.cpu().numpy()).view(VERTEX_DTYPE).reshape(-1) if device else vertices
+                self.points.extend(host_v)
+                if n > 0:
+                    b = back[n - 1].cpu().numpy() if device else np.frombuffer(back[n - 1].tobytes(), dtype=np.float32)
+                    self.last_ray = (b[0:3].copy(), b[3:6].copy())
+        out = (rgba, rgbf) if want_float else (rgba,)
+        if paths:
+            out = out + (vertices, vstart, back)
+        return out if len(out) > 1 else out[0]
 
     def CastRay(self, ray, iteration=0, origin=None, currentRefIndex=1.0, want_float=False):
         """RT:506: one ray = (position, direction) -> the packed Color (and its float colour vector with want_float).  origin: the
-        triangle the ray leaves, (mesh, index in Mesh.Triangles[]) as GetRayIntersection's ignoreTriangle, or None."""
+        triangle the ray leaves, (mesh, index in Mesh.Triangles[]) as GetRayIntersection's ignoreTriangle, or None.
+        With RecordPoints the call appends its segments to `points` and leaves the ray as the reference's `ref Ray ray` holds it
+        afterwards in last_ray = (position, direction)."""
         im, it = (-1, -1) if origin is None else (self.CurrentScene.mesh_id(origin[0]), int(origin[1]))
         out = self.CastRays(rays_array([ray[0]], [ray[1]], im, it), iteration, currentRefIndex, want_float)
         return (int(out[0][0]), out[1][0]) if want_float else int(out[0])

@@ -247,4 +247,32 @@ struct PoseArgs {
 };
 void launch_pose(const PoseArgs &P, hipStream_t st);
 
+// ---- RayTracer.points: the ray paths of xrt_cast_rays_paths (paths.hip; the order of the segments is paths.h's) --------------------------
+// Staging records of one chunk, addressed like the level records (node * P + path): hitRec = (world position of the node's hit, tag),
+// dirRec = (direction a refraction child was cast with, tag) -- ray trees only.  A record belongs to this attempt of the chunk when its
+// tag is `epoch` (every attempt gets a number of its own; the memory is cleared when it is allocated and never again).
+struct PathsCaptureArgs {
+    // the hits of generation `level`: what part A of k_shade #level left at their slots
+    const SlotRec *slots = nullptr; const int *slotNode = nullptr /* ray trees */; const int *scnt = nullptr; int slotCap = 0, level = 0;
+    // the rays of generation level + 1 (ray trees): the refraction children among them
+    const xrt_ray *nextRays = nullptr; const int *nextNode = nullptr, *nextPath = nullptr, *nextCnt = nullptr; int nextCap = 0;
+    f4 *hitRec = nullptr, *dirRec = nullptr;
+    int P = 0; unsigned epoch = 0;
+};
+void launch_paths_capture(const PathsCaptureArgs &A, int blocks, hipStream_t st);
+// order + emit of one chunk of Pc paths (ray pathBase + p of the batch): per-path vertex counts, their exclusive scan behind
+// vertexStart[pathBase] (what the chunk before left there; 0 for the first), then the segments into vertices[0 .. capacity) -- nothing at or
+// behind `capacity` -- and the ray every root call left into raysBack (nullable).
+struct PathsEmitArgs {
+    const xrt_ray *batch = nullptr;   // the caller's rays
+    long long pathBase = 0; int Pc = 0, P = 0, depth = 0, tree = 0; unsigned epoch = 0;
+    const f4 *hitRec = nullptr, *dirRec = nullptr;
+    int *local = nullptr, *blockSum = nullptr; long long *blockBase = nullptr;   // work: [Pc], [blocks], [blocks] (blocks of PATHS_BLOCK paths)
+    long long *vertexStart = nullptr;      // [n + 1]
+    xrt_path_vertex *vertices = nullptr; long long capacity = 0;
+    xrt_ray *raysBack = nullptr;
+};
+constexpr int PATHS_BLOCK = 256;
+void launch_paths_emit(const PathsEmitArgs &A, hipStream_t st);
+
 }  // namespace xrt

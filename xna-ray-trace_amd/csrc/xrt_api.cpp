@@ -24,6 +24,7 @@
 
 #include "../../include/xrt.h"
 #include "kernels.h"
+#include "paths.h"
 #include "rccl_gather.h"
 #include "scene_host.h"
 #include "settings.h"
@@ -256,6 +257,15 @@ struct xrt_scene {
     DevBuf<xrt_ray> castRays;     // xrt_cast_rays: the host's rays and their colours
     DevBuf<uint32_t> castRGBA;
     DevBuf<float> castF32;
+    // xrt_cast_rays_paths (paths.hip): staging records of a chunk -- (hit position, tag) and (refraction direction, tag) per (node, path), allocated
+    // only when a paths call is made --, the work arrays of the ordering pass, and the host form's copies of the caller's arrays
+    DevBuf<f4> pathHit, pathDir;
+    DevBuf<int> pathLocal, pathBlockSum;
+    DevBuf<long long> pathBlockBase, pathStart;
+    DevBuf<xrt_path_vertex> pathVerts;
+    DevBuf<xrt_ray> pathBack;
+    unsigned pathEpoch = 0;            // number of the last attempt of a chunk (the tag of its records; 0 is "never written")
+    long long *pathPinned = nullptr;   // the batch's vertex count on its way to the host
     DevBuf<unsigned> queues;
     DevBuf<uint32_t> outRGBA;
     DevBuf<float> outF32;
@@ -409,6 +419,8 @@ struct xrt_scene {
             childDfs.release(); srefs.release(); scull.release(); runTB.release(); triTB.release(); runBase.release(); pblocks.release(); lrec.release(); objMesh.release(); meshes.release();
             objects.release(); materials.release(); texels.release();
             apiRays.release(); apiHits.release(); castRays.release(); castRGBA.release(); castF32.release();
+            pathHit.release(); pathDir.release(); pathLocal.release(); pathBlockSum.release(); pathBlockBase.release(); pathStart.release(); pathVerts.release(); pathBack.release();
+            if (pathPinned) (void)hipHostFree(pathPinned);
 
             queues.release(); outRGBA.release(); outF32.release(); counters.release(); costMap.release(); waveTimes.release();
         }
@@ -651,6 +663,14 @@ struct BatchSrc {
     const xrt_ray *rays = nullptr;
     long long n = 0;
     float refIndex = 1.0f;
+    // xrt_cast_rays_paths: where the ray paths go (HBM; kernels.h PathsEmitArgs), or null
+    struct Paths {
+        xrt_path_vertex *vertices = nullptr;
+        long long capacity = 0;
+        long long *vertexStart = nullptr;   // [n + 1], never null
+        xrt_ray *raysBack = nullptr;
+    };
+    const Paths *paths = nullptr;
 };
 
 // Enqueues one frame on `st`.  On return the frame's kernels and its counter read-back are in flight (F.pending);
@@ -800,6 +820,8 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
                  (rc = W.lvlAlpha.ensure((size_t)P * nodes))))
         return rc;
     if (wantF32 && !batch && (rc = W.sampleF32.ensure((size_t)P * 3))) return rc;   // (a batch's compose writes the caller's arrays)
+    const BatchSrc::Paths *const pout = batch ? batch->paths : nullptr;   // the pass also records its ray paths (paths.hip)
+    unsigned pathEpoch = 0;                                               // ... the tag of the chunk attempt being enqueued
     const int cntStride = 4 * (R + 2);          // per chunk: cnt[R+2], scnt[R+2], the long-ray list lengths [R+2], the shadow rays really emitted [R+2] (ShadeArgs::ae)
     constexpr int QW = 1 + 2 * PACKET_QUEUE_WORDS;   // per launch step k: the lane kernel's queue word and the heads of each packet launch (closest, shadow)
     const int qStride = QW * (R + 2);
@@ -861,6 +883,20 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         } else st = s->stream;
     }
     if ((rc = pose_wait(s, F.pose, st))) return rc;   // (the poses set before the frame's begin)
+    if (pout) {   // staging records like the level records: one per node and path of a chunk; cleared when allocated, told apart by tag afterwards
+        auto ensure_cleared = [&](DevBuf<f4> &b, size_t n) -> int {
+            const f4 *before = b.p; const size_t capBefore = b.cap;
+            int rc2 = b.ensure(n);
+            if (rc2 != XRT_OK) return rc2;
+            if (b.p != before || b.cap != capBefore) HIPCHECK(hipMemsetAsync(b.p, 0, b.cap * sizeof(f4), st));
+            return XRT_OK;
+        };
+        const size_t pathBlocks = ((size_t)P + PATHS_BLOCK - 1) / PATHS_BLOCK;
+        if ((rc = ensure_cleared(s->pathHit, lvlStride * nodes)) || (heap && (rc = ensure_cleared(s->pathDir, lvlStride * nodes))) || (rc = s->pathLocal.ensure((size_t)P)) ||
+            (rc = s->pathBlockSum.ensure(pathBlocks)) || (rc = s->pathBlockBase.ensure(pathBlocks)))
+            return rc;
+        if (!s->pathPinned) HIPCHECK(hipHostMalloc((void **)&s->pathPinned, 64, hipHostMallocDefault));
+    }
     // Tile costs (xrt.h xrt_scene_tile_costs): the packets of plain one-chunk frames add their device-clock ticks to the tile of their first
     // ray.  The words belong to the scene (both frame contexts add to them); a frame of another geometry or tile table starts them afresh.
     unsigned *tileCostDev = nullptr;
@@ -976,6 +1012,14 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
                              const FrameEpilogue *epi = nullptr) -> int {
         int *scnt = cnt + (R + 2), *hcnt = cnt + 2 * (R + 2), *acnt = cnt + 3 * (R + 2);   // (acnt[k]: shadow rays of generation k that were really emitted, ShadeArgs::ae)
         const int chunkRow0 = F.stampRows;
+        if (pout) {   // this attempt's records carry a number no earlier attempt had
+            if (++s->pathEpoch == 0) {
+                HIPCHECK(hipMemsetAsync(s->pathHit.p, 0, s->pathHit.cap * sizeof(f4), st));
+                if (s->pathDir.p) HIPCHECK(hipMemsetAsync(s->pathDir.p, 0, s->pathDir.cap * sizeof(f4), st));
+                s->pathEpoch = 1;
+            }
+            pathEpoch = s->pathEpoch;
+        }
         // "long ray first" (kernels.hip): the producer of generation k lists its long rays, launch #k takes them first
         const bool feedback = fast && s->deepMeshes && s->costMap.p != nullptr;
         const bool listLong = s->heavyPath > 0.0f || feedback;
@@ -1110,6 +1154,13 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
                 if (h >= 0 && h < 4 * 131072 + 4096) launch_shade(S, V, X, st, (int)((h + 255) / 256), 256);
                 else launch_shade(S, V, X, st, h < 0 ? 1024 : (int)((h + 1023) / 1024 < 1024 ? (h + 1023) / 1024 : 1024));
             }
+            if (pout && hasClosest) {   // the generation's hits and the refraction rays it cast, before slots and ray buffers are reused
+                PathsCaptureArgs Cp;
+                Cp.slots = slotOf[cur]; Cp.slotNode = heap ? slotNodeOf[cur] : nullptr; Cp.scnt = scnt + k; Cp.slotCap = (int)shadowCap; Cp.level = k;
+                if (heap && k < R) { Cp.nextRays = rays[prv]; Cp.nextNode = nodesOf[prv]; Cp.nextPath = paths[prv]; Cp.nextCnt = cnt + k + 1; Cp.nextCap = (int)rayCap; }
+                Cp.hitRec = s->pathHit.p; Cp.dirRec = s->pathDir.p; Cp.P = (int)lvlStride; Cp.epoch = pathEpoch;
+                launch_paths_capture(Cp, (int)((rayCap + 255) / 256), st);
+            }
         }
         Range rc_("xrt compose");
         // a batch: path p of the chunk is ray pathBase + p, and the compose kernel writes its colour straight into the caller's arrays (a ray-tree chunk
@@ -1243,8 +1294,17 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     if (batch) {   // path p is ray p: the compose kernels write the caller's arrays themselves (enqueue_chunk), nothing to do after a chunk
         validPixels = (unsigned long long)batch->n;
         livePaths = validPixels;
-        rc = run_pass(g, firstPaths, [&](int, long long) -> int { return XRT_OK; }, 0.0f, 1.0f, true);
+        rc = run_pass(g, firstPaths, [&](int Pc, long long pathBase) -> int {
+            if (!pout) return XRT_OK;
+            PathsEmitArgs E;   // the chunk's segments in the recursion's order, behind those of the rays before it
+            E.batch = batch->rays; E.pathBase = pathBase; E.Pc = Pc; E.P = (int)lvlStride; E.depth = R; E.tree = heap ? 1 : 0; E.epoch = pathEpoch;
+            E.hitRec = s->pathHit.p; E.dirRec = s->pathDir.p; E.local = s->pathLocal.p; E.blockSum = s->pathBlockSum.p; E.blockBase = s->pathBlockBase.p;
+            E.vertexStart = pout->vertexStart; E.vertices = pout->vertices; E.capacity = pout->capacity; E.raysBack = pout->raysBack;
+            launch_paths_emit(E, st);
+            return XRT_OK;
+        }, 0.0f, 1.0f, true);
         if (rc != XRT_OK) return rc;
+        if (pout) HIPCHECK(hipMemcpyAsync(s->pathPinned, pout->vertexStart + batch->n, sizeof(long long), hipMemcpyDeviceToHost, st));
         HIPCHECK(hipEventRecord(F.done, st));
         HIPCHECK(hipGetLastError());
         F.pending = true;
@@ -1954,7 +2014,7 @@ int run_intersect(xrt_scene *s, const xrt_ray *d_rays, int64_t n, xrt_hit *d_hit
 // RayTracer.CastRay (RT:506-737) on n rays already in HBM: the pass of frame_begin with the batch as its ray source, MaxReflections - iteration
 // generations deep, then the pass's counters.  The caller holds the scene (BusyGuard, no frame in flight).
 int cast_rays_impl(xrt_scene *s, const xrt_ray *d_rays, int64_t n, int32_t iteration, float refIndex, const xrt_light *lights, int32_t nLights,
-                   const xrt_render_opts *opts, uint32_t *d_out, float *d_outF32, hipStream_t st, xrt_stats *stats) {
+                   const xrt_render_opts *opts, uint32_t *d_out, float *d_outF32, hipStream_t st, xrt_stats *stats, const BatchSrc::Paths *paths = nullptr) {
     if (!opts) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: null opts");
     if (opts->use_multisampling != XRT_MS_OFF) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: use_multisampling must be XRT_MS_OFF (one ray, one colour)");
     if (opts->shard_count < 0 || opts->shard_count > 1) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: shard_count must be 0 or 1");
@@ -1969,7 +2029,7 @@ int cast_rays_impl(xrt_scene *s, const xrt_ray *d_rays, int64_t n, int32_t itera
     o.max_reflections = (int32_t)depth;
     o.use_multisampling = XRT_MS_OFF; o.shard_count = 0; o.shard_rank = 0; o.n_gpus = 0; o.balance_tiles = 0;
     BatchSrc b;
-    b.rays = d_rays; b.n = n; b.refIndex = refIndex;
+    b.rays = d_rays; b.n = n; b.refIndex = refIndex; b.paths = paths;
     xrt_scene::FrameCtx &F = s->frames[0];
     F.pose = s->poseCur;
     Range rf("xrt cast rays (%lld)", (long long)n);
@@ -2658,6 +2718,99 @@ int xrt_cast_rays_device(xrt_scene *scene, const void *d_rays, int64_t n, int32_
         if ((rc = cast_rays_impl(scene, (const xrt_ray *)d_rays, n, iteration, current_ref_index, lights, n_lights, opts, (uint32_t *)d_rgba_out,
                                  (float *)d_rgb_f32_out, st, stats_out)))
             return rc;
+        return guards_check("end of a ray batch");
+    });
+}
+
+// Most vertices a batch of n rays can need (paths.h path_vertex_bound), or -1 where cast_rays_impl refuses the depth anyway.
+static long long paths_bound(const xrt_scene *scene, const xrt_render_opts *opts, int32_t iteration, int64_t n) {
+    const long long depth = std::max(0LL, (long long)opts->max_reflections - (long long)iteration);
+    const bool tree = scene->host->arrays.anyTransparent && depth > 0;
+    if (opts->max_reflections < 0 || depth > 64 || (tree && depth > PATH_TREE_DEPTH)) return -1;
+    return path_vertex_bound((int)depth, tree) * (long long)n;
+}
+
+int xrt_cast_rays_paths(xrt_scene *scene, const xrt_ray *rays, int64_t n, int32_t iteration, float current_ref_index, const xrt_light *lights, int32_t n_lights,
+                        const xrt_render_opts *opts, uint32_t *rgba_out, float *rgb_f32_out, xrt_ray *rays_back, int64_t *vertex_start, xrt_path_vertex *vertices,
+                        int64_t vertex_capacity, int64_t *n_vertices_out, xrt_stats *stats_out) {
+    return guarded("xrt_cast_rays_paths", [&]() -> int {
+        if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths: null scene");
+        int rc;
+        if (n < 0 || n > 0x7fffffff / 2) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths: n = %lld out of range", (long long)n);
+        if (!opts || !n_vertices_out || (n > 0 && (!rays || !rgba_out)) || (!lights && n_lights > 0) || n_lights < 0) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths: null argument");
+        if (vertex_capacity < 0 || (vertex_capacity > 0 && !vertices)) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths: vertex_capacity = %lld with%s vertices", (long long)vertex_capacity, vertices ? "" : " null");
+        if ((rc = need_device(scene, "xrt_cast_rays_paths"))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
+        const auto &meshes = scene->host->arrays.meshes;
+        for (int64_t i = 0; i < n; i++) {   // (an origin names a triangle of the scene, as for xrt_cast_rays)
+            const xrt_ray &r = rays[i];
+            if (r.ignore_tri < 0) continue;
+            if (r.ignore_mesh < 0 || r.ignore_mesh >= (int)meshes.size() || r.ignore_tri >= meshes[(size_t)r.ignore_mesh].ntri)
+                return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths: ray %lld names triangle %d of mesh %d, which does not exist", (long long)i, r.ignore_tri, r.ignore_mesh);
+        }
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        BatchSrc::Paths P;
+        if (n > 0) {
+            // the device never needs more room than the deepest recursion of every ray could fill, whatever capacity the caller names
+            const long long bound = paths_bound(scene, opts, iteration, n);
+            P.capacity = vertices ? std::min<long long>(vertex_capacity, std::max(0LL, bound)) : 0;
+            if ((rc = scene->castRays.ensure((size_t)n)) || (rc = scene->castRGBA.ensure((size_t)n)) || (rgb_f32_out && (rc = scene->castF32.ensure((size_t)n * 3))) ||
+                (rc = scene->pathStart.ensure((size_t)n + 1)) || (rays_back && (rc = scene->pathBack.ensure((size_t)n))) || (P.capacity > 0 && (rc = scene->pathVerts.ensure((size_t)P.capacity))))
+                return rc;
+            P.vertices = P.capacity > 0 ? scene->pathVerts.p : nullptr; P.vertexStart = scene->pathStart.p; P.raysBack = rays_back ? scene->pathBack.p : nullptr;
+            HIPCHECK(hipMemcpyAsync(scene->castRays.p, rays, (size_t)n * sizeof(xrt_ray), hipMemcpyHostToDevice, scene->stream));
+        }
+        if ((rc = cast_rays_impl(scene, scene->castRays.p, n, iteration, current_ref_index, lights, n_lights, opts, scene->castRGBA.p,
+                                 rgb_f32_out ? scene->castF32.p : nullptr, scene->stream, stats_out, &P)))
+            return rc;
+        *n_vertices_out = 0;
+        if (n == 0 && vertex_start) vertex_start[0] = 0;
+        if (n > 0) {
+            const long long need = *scene->pathPinned;   // (arrived with the pass: cast_rays_impl waited for it)
+            *n_vertices_out = need;
+            const long long wrote = std::min(need, P.capacity & ~1LL);
+            HIPCHECK(hipMemcpyAsync(rgba_out, scene->castRGBA.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, scene->stream));
+            if (rgb_f32_out) HIPCHECK(hipMemcpyAsync(rgb_f32_out, scene->castF32.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, scene->stream));
+            if (vertex_start) HIPCHECK(hipMemcpyAsync(vertex_start, scene->pathStart.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, scene->stream));
+            if (rays_back) HIPCHECK(hipMemcpyAsync(rays_back, scene->pathBack.p, (size_t)n * sizeof(xrt_ray), hipMemcpyDeviceToHost, scene->stream));
+            if (wrote > 0) HIPCHECK(hipMemcpyAsync(vertices, scene->pathVerts.p, (size_t)wrote * sizeof(xrt_path_vertex), hipMemcpyDeviceToHost, scene->stream));
+            HIPCHECK(hipStreamSynchronize(scene->stream));
+        }
+        return guards_check("end of a ray batch");
+    });
+}
+
+int xrt_cast_rays_paths_device(xrt_scene *scene, const void *d_rays, int64_t n, int32_t iteration, float current_ref_index, const xrt_light *lights,
+                               int32_t n_lights, const xrt_render_opts *opts, void *d_rgba_out, void *d_rgb_f32_out, void *d_rays_back, void *d_vertex_start,
+                               void *d_vertices, int64_t vertex_capacity, void *stream, int64_t *n_vertices_out, xrt_stats *stats_out) {
+    return guarded("xrt_cast_rays_paths_device", [&]() -> int {
+        if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths_device: null scene");
+        int rc;
+        if (n < 0 || n > 0x7fffffff / 2) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths_device: n = %lld out of range", (long long)n);
+        if (!opts || !n_vertices_out || (n > 0 && (!d_rays || !d_rgba_out)) || (!lights && n_lights > 0) || n_lights < 0) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths_device: null argument");
+        if (vertex_capacity < 0 || (vertex_capacity > 0 && !d_vertices)) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths_device: vertex_capacity = %lld with%s vertices", (long long)vertex_capacity, d_vertices ? "" : " null");
+        if ((rc = need_device(scene, "xrt_cast_rays_paths_device"))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
+        if (((uintptr_t)d_rays & 15) || ((uintptr_t)d_rgba_out & 15) || ((uintptr_t)d_rgb_f32_out & 15) || ((uintptr_t)d_rays_back & 15) || ((uintptr_t)d_vertex_start & 15) || ((uintptr_t)d_vertices & 15))
+            return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
+        if (d_rays_back && d_rays_back == d_rays) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths_device: d_rays_back must not be d_rays (a chunk that is redone reads its rays again)");
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        hipStream_t st = (hipStream_t)stream;
+        if (!st) st = scene->stream;
+        BatchSrc::Paths P;
+        P.vertices = vertex_capacity > 0 ? (xrt_path_vertex *)d_vertices : nullptr; P.capacity = vertex_capacity; P.vertexStart = (long long *)d_vertex_start; P.raysBack = (xrt_ray *)d_rays_back;
+        if (n > 0 && !P.vertexStart) {   // the ordering pass needs the running offsets whether or not the caller wants them
+            if ((rc = scene->pathStart.ensure((size_t)n + 1))) return rc;
+            P.vertexStart = scene->pathStart.p;
+        }
+        if ((rc = cast_rays_impl(scene, (const xrt_ray *)d_rays, n, iteration, current_ref_index, lights, n_lights, opts, (uint32_t *)d_rgba_out,
+                                 (float *)d_rgb_f32_out, st, stats_out, &P)))
+            return rc;
+        *n_vertices_out = n > 0 ? *scene->pathPinned : 0;
+        if (n == 0 && d_vertex_start) {
+            HIPCHECK(hipMemsetAsync(d_vertex_start, 0, sizeof(int64_t), st));
+            HIPCHECK(hipStreamSynchronize(st));
+        }
         return guards_check("end of a ray batch");
     });
 }
