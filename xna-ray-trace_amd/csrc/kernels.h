@@ -172,6 +172,12 @@ struct ShadeArgs {
     // rays at shadowRays[0 .. *shadowCnt) with shadowOut[i] = slot * nLights + light (where their answers go), reflections at nextRays[0 .. *nextCnt).
     int ae = 0;
     int *shadowCnt = nullptr, *shadowOut = nullptr, *shadowFlagsOut = nullptr;
+    // Finished in part A (plain reflection-chain frames with `ae`, at most 32 lights, no path capture; decided by the host, grid-uniform): a hit none of
+    // whose shadow rays has to be emitted -- every light answered above, or no lights -- has its light sum now, with every lightAmount 0, and writes its
+    // lvlA record itself: no slot, no SlotRec, no shadowFlagsOut words, nothing for part B of the next step to read back.  *scnt then counts the slots
+    // really taken (the hits that wait for shadow answers), *finishCnt the hits that took none: hits of the generation = *scnt + *finishCnt.
+    int finish = 0;
+    int *finishCnt = nullptr;
 };
 
 int  intersect_stack_capacity(int needed);   // smallest compiled capacity >= needed, or -1

@@ -849,182 +849,243 @@ __device__ __forceinline__ bool faces_away_single(const SceneView &S, v3 o, v3 d
 //                            depend on the hit alone, not on the lighting -- the rays of generation k+1 (RT:545-559,
 //                            RT:656-698); and everything else that depends on the hit alone goes into the level record
 //                            now: fragment normal, surface colour (RT:568-581 / 711-724), Reflectiveness.  Launch #k+1 traces
-//                            both ray sets together.
+//                            both ray sets together.  (ShadeArgs::finish: a hit with no shadow ray to emit takes no slot and
+//                            has its light sum here.)
 //   part B, generation k-1 : the shadow answers of launch #k: light accumulation (RT:534-542) into the level record the return
 //                            path (k_compose) needs.  It reads the hit's 32-byte slot record (world position, path, normal, Reflectiveness:
 //                            left by part A) where it used to read the 48-byte hit, the material and the shading record a second time.
+// The light sum of a shaded hit (RT:534-542): with the shadow answers of slot s (fromSlot: part B), or with every lightAmount 0 (a hit part A finished).
+// It holds the double-precision division of light_for_fragment (SPOT:54): each instantiation of k_shade forms it at ONE place.
+__device__ __forceinline__ v3 shade_light_sum(const ShadeView &V, const ShadeArgs &X, bool fromSlot, int s, v3 w, v3 normal) {
+    v3 lightResult = mk(0, 0, 0);
+    for (int l = 0; l < V.nLights; l++) {
+        const LightRec &Lt = V.lights[l];
+        float lightAmount = 0.0f;   // RT:485-501
+        if (fromSlot) {
+            v3 dir; float dist;
+            light_dir(Lt, w, dir, dist);
+            int sh, sobj, smesh, stri; float su, sv, sd; v3 sw;
+            load_hit(X.shadowHits + (size_t)s * V.nLights + l, sh, sobj, smesh, stri, su, sv, sd, sw,
+                     X.shadowFlags ? X.shadowFlags + (size_t)s * V.nLights + l : nullptr);
+            if (sh && sd < dist) {
+                const MaterialRec SM = V.materials[V.meshes[smesh].material];
+                if (SM.flags & MAT_TRANSPARENT) lightAmount = V.shade[(size_t)(V.meshes[smesh].triBase + stri) * 6 + 3].w;
+                else lightAmount = 1.0f;
+            }
+        }
+        if (lightAmount != 1.0f) lightResult = add(lightResult, scale(light_for_fragment(Lt, w, normal), 1.0f - lightAmount));   // RT:538-541
+    }
+    return lightResult;
+}
+// FIN (ShadeArgs::finish): one loop takes a thread through its part-B items and then through its part-A items, and both end in the same light sum -- a
+// part-B item with the shadow answers of its slot, a part-A item that finished with every lightAmount 0.  Without it part B is a loop of its own in front
+// of part A, as it always was (frames that finish nothing pay nothing for the other arrangement).
+template <bool FIN>
 __global__ __launch_bounds__(APPEND_BLOCK) void k_shade(SceneView S, ShadeView V, ShadeArgs X) {
     __shared__ int ldsCounts[17];
     const int stride = (int)(gridDim.x * blockDim.x);
     const int tid = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     const size_t P = (size_t)X.P;
-    if (X.doB) {
-        // Generation k-1: everything that depends on the hit alone (fragment normal, surface colour, Reflectiveness) was computed by
-        // part A of the previous step; what is left is the light sum, which needs the shadow answers: one dense 32-byte slot record in
-        // (kernels.h SlotRec) and one 16-byte level record out, instead of the 48-byte hit, the material and the shading record again.
-        int n = *X.scntPrev;
-        if (n > X.shadowCap) n = X.shadowCap;
-        for (int s = tid; s < n; s += stride) {
+    // Generation k-1 (part B): everything that depends on the hit alone (fragment normal, surface colour, Reflectiveness) was computed by
+    // part A of the previous step; what is left is the light sum, which needs the shadow answers: one dense 32-byte slot record in
+    // (kernels.h SlotRec) and one 16-byte level record out, instead of the 48-byte hit, the material and the shading record again.
+    int nB = X.doB ? *X.scntPrev : 0;
+    if (nB > X.shadowCap) nB = X.shadowCap;
+    if constexpr (!FIN) {
+        for (int s = tid; s < nB; s += stride) {
             const SlotRec rec = X.slotPrev[s];   // left by part A of the previous step
             const int node = X.heap ? X.slotNodePrev[s] : X.level - 1;
             const size_t at = (size_t)node * P + lvl_at(X.lvl, rec.path);
-            const v3 normal = mk(rec.nx, rec.ny, rec.nz), w = mk(rec.wx, rec.wy, rec.wz);
-            v3 lightResult = mk(0, 0, 0);
-            for (int l = 0; l < V.nLights; l++) {
-                const LightRec &Lt = V.lights[l];
-                v3 dir; float dist;
-                light_dir(Lt, w, dir, dist);
-                int sh, sobj, smesh, stri; float su, sv, sd; v3 sw;
-                load_hit(X.shadowHits + (size_t)s * V.nLights + l, sh, sobj, smesh, stri, su, sv, sd, sw,
-                         X.shadowFlags ? X.shadowFlags + (size_t)s * V.nLights + l : nullptr);
-                float lightAmount = 0.0f;   // RT:485-501
-                if (sh && sd < dist) {
-                    const MaterialRec SM = V.materials[V.meshes[smesh].material];
-                    if (SM.flags & MAT_TRANSPARENT) lightAmount = V.shade[(size_t)(V.meshes[smesh].triBase + stri) * 6 + 3].w;
-                    else lightAmount = 1.0f;
-                }
-                if (lightAmount != 1.0f) lightResult = add(lightResult, scale(light_for_fragment(Lt, w, normal), 1.0f - lightAmount));   // RT:538-541
-            }
+            const v3 lightResult = shade_light_sum(V, X, true, s, mk(rec.wx, rec.wy, rec.wz), mk(rec.nx, rec.ny, rec.nz));
             X.lvlA[at] = f4{lightResult.x, lightResult.y, lightResult.z, rec.refl};
         }
+        if (!X.doA) return;
     }
-    if (!X.doA) return;
-    int n = X.nDev ? *X.nDev : X.nHost;
+    int n = X.doA ? (X.nDev ? *X.nDev : X.nHost) : 0;
     if (n > X.cap) n = X.cap;
     const bool emitNext = X.level < X.maxReflections;   // grid-uniform
-    const int rounds = (n + stride - 1) / stride;
+    const int roundsB = FIN ? (nB + stride - 1) / stride : 0, rounds = roundsB + (n + stride - 1) / stride;
+    int nFinished = 0;   // part-A items of this thread that finished
+#pragma unroll 1
     for (int it = 0; it < rounds; it++) {
-        const int j = it * stride + tid;
-        int i = j, hit = 0, object, mesh = 0, tri = 0, p = 0, node = X.level;
-        float u = 0, v = 0, d = 0, curRef = 1.0f, n2 = 1.0f;
-        v3 w = mk(0, 0, 0), rdir = mk(0, 0, 0), tdir = mk(0, 0, 0);
-        bool refracts = false;
-        if (j < n) {
-            if (X.index) i = X.index[j];   // generation 0: only the rays that reached the scene's root box were traced
-            load_hit(X.hits + i, hit, object, mesh, tri, u, v, d, w, X.hitFlags ? X.hitFlags + i : nullptr);
-            p = X.rayPath ? X.rayPath[i] : i;
-            if (X.costOut) {   // (launches whose cost words are read write a record for every ray: IntersectArgs::missRecords)
-                const int c = reinterpret_cast<const Hit16 *>(X.hits + i)[2].i3;
-                X.costOut[p] = (X.epoch << 16) | (unsigned)(c > 0xffff ? 0xffff : (c < 0 ? 0 : c));
+        bool sum = false, fromSlot = false;   // FIN: this item has a light sum to form; ... from the shadow answers of slot s
+        int s = 0;
+        size_t at = 0;
+        v3 w = mk(0, 0, 0), normal = mk(0, 0, 0);
+        float refl = 0.0f;
+        if (FIN && it < roundsB) {   // (grid-uniform)
+            s = it * stride + tid;
+            if (s < nB) {
+                const SlotRec rec = X.slotPrev[s];   // left by part A of the previous step
+                const int node = X.heap ? X.slotNodePrev[s] : X.level - 1;
+                at = (size_t)node * P + lvl_at(X.lvl, rec.path);
+                normal = mk(rec.nx, rec.ny, rec.nz); w = mk(rec.wx, rec.wy, rec.wz);
+                refl = rec.refl;
+                sum = fromSlot = true;
             }
-            if (X.heap) { node = X.rayNode ? X.rayNode[i] : 0; curRef = X.rayRef ? X.rayRef[i] : 1.0f; }   // generation 0: root, in vacuum (RT:424)
-            if (!hit) X.lvlB[(size_t)node * P + lvl_at(X.lvl, p)] = f4{0, 0, 0, i2f(FLAG_MISS)};
-        }
-        const int slot = block_append(X.scnt, hit != 0, ldsCounts);
-        if (hit && slot >= X.shadowCap) { *X.overflow = 1; hit = 0; }   // more rays than the chunk's buffers hold: the host retries with fewer paths
-        if (X.ae) {   // (grid-uniform) shadow rays: answered here where the whole mesh faces away, else appended to the compact list
-            for (int l = 0; l < V.nLights; l++) {
-                v3 dir = mk(0, 0, 0); float dist;
-                bool emit = false;
-                if (hit) {
+        } else {
+            const int j = (it - roundsB) * stride + tid;
+            int i = j, hit = 0, object, mesh = 0, tri = 0, p = 0, node = X.level;
+            float u = 0, v = 0, d = 0, curRef = 1.0f, n2 = 1.0f;
+            v3 rdir = mk(0, 0, 0), tdir = mk(0, 0, 0);
+            bool refracts = false;
+            if (j < n) {
+                if (X.index) i = X.index[j];   // generation 0: only the rays that reached the scene's root box were traced
+                load_hit(X.hits + i, hit, object, mesh, tri, u, v, d, w, X.hitFlags ? X.hitFlags + i : nullptr);
+                p = X.rayPath ? X.rayPath[i] : i;
+                if (X.costOut) {   // (launches whose cost words are read write a record for every ray: IntersectArgs::missRecords)
+                    const int c = reinterpret_cast<const Hit16 *>(X.hits + i)[2].i3;
+                    X.costOut[p] = (X.epoch << 16) | (unsigned)(c > 0xffff ? 0xffff : (c < 0 ? 0 : c));
+                }
+                if (X.heap) { node = X.rayNode ? X.rayNode[i] : 0; curRef = X.rayRef ? X.rayRef[i] : 1.0f; }   // generation 0: root, in vacuum (RT:424)
+                if (!hit) X.lvlB[(size_t)node * P + lvl_at(X.lvl, p)] = f4{0, 0, 0, i2f(FLAG_MISS)};
+            }
+            // ShadeArgs::finish (grid-uniform; at most 32 lights): which lights' shadow rays have to be emitted is decided BEFORE the hit takes a slot
+            unsigned emitMask = 0;
+            if (FIN && hit) {
+                for (int l = 0; l < V.nLights; l++) {
+                    v3 dir; float dist;
                     light_dir(V.lights[l], w, dir, dist);
-                    emit = !faces_away_single(S, w, dir);
-                    if (!emit) X.shadowFlagsOut[(size_t)slot * V.nLights + l] = 0;   // IsLightPathObstructed's query finds nothing (RT:482-485)
-                }
-                const int pos = block_append(X.shadowCnt, emit, ldsCounts);
-                if (emit) {
-                    store_ray(X.shadowRays + pos, w, dir, mesh, tri);   // ignore = shaded triangle (RT:485)
-                    X.shadowOut[pos] = slot * V.nLights + l;
+                    if (!faces_away_single(S, w, dir)) emitMask |= 1u << l;
                 }
             }
-        }
-        if (hit) {
-            for (int l = 0; l < V.nLights && !X.ae; l++) {
-                v3 dir; float dist;
-                light_dir(V.lights[l], w, dir, dist);
-                store_ray(X.shadowRays + (size_t)slot * V.nLights + l, w, dir, mesh, tri);   // ignore = shaded triangle (RT:485)
-            }
-            // the hit's own share of RT:516-581: fragment normal (RT:520-531), surface colour (RT:568-581 / 711-724), Reflectiveness -- the colour final
-            // in lvlB, (normal, Reflectiveness) in the slot record until part B of the next step has the shadow answers for the light sum
-            const int gtri = V.meshes[mesh].triBase + tri;
-            const MaterialRec M = V.materials[V.meshes[mesh].material];
-            const v3 normal = fragment_normal(V, gtri, M.flags, u, v);
-            {
-                v3 surf;
-                const f4 *sr = V.shade + (size_t)gtri * 6;
-                if (M.flags & MAT_TEXTURE) {   // RT:568-575
-                    f4 s0 = sr[0], s1 = sr[1], s2 = sr[2], s4 = sr[4];
-                    float uv1x = s0.w, uv1y = s1.w, uv2x = s2.w, uv2y = s4.x, uv3x = s4.y, uv3y = s4.z;
-                    float ax = uv2x - uv1x, ay = uv2y - uv1y, bx = uv3x - uv1x, by = uv3y - uv1y;
-                    float ix = (uv1x + ax * u) + bx * v, iy = (uv1y + ay * u) + by * v;
-                    surf = lookup_uv(V, M, ix, iy);
-                } else {
-                    f4 c = sr[3];
-                    surf = mk(c.x, c.y, c.z);
-                }
-                const bool transparent = (M.flags & MAT_TRANSPARENT) != 0;
-                const size_t at = (size_t)node * P + lvl_at(X.lvl, p);
-                X.slotOut[slot] = SlotRec{w.x, w.y, w.z, p, normal.x, normal.y, normal.z, M.reflectiveness};
-                if (X.heap) X.slotNodeOut[slot] = node;
-                X.lvlB[at] = f4{surf.x, surf.y, surf.z, i2f(FLAG_HIT | (transparent ? FLAG_TRANSPARENT : 0))};
-                if (X.heap) X.lvlAlpha[at] = sr[3].w;   // triangle.color.W (RT:699)
-            }
-            if (emitNext) {
-                v3 o, dd; int im, itri;
-                load_ray(X.rays + i, o, dd, im, itri);
-                rdir = normalize(reflect(dd, normal));   // RT:549-550
-                if (X.heap && (M.flags & MAT_TRANSPARENT)) {   // RT:656-694: Snell refraction, the System.Math calls in double
-                    float n1;
-                    if (curRef == M.refractionIndex) { n1 = 1.0f; n2 = curRef; }
-                    else { n1 = M.refractionIndex; n2 = 1.0f; }
-                    const float cos1 = dot(normal, neg(dd));
-                    const double ratio = (double)(n1 / n2), c1 = (double)cos1;
-                    const float cos2 = (float)sqrt(1 - (ratio * ratio) * (1 - (c1 * c1)));   // Math.Pow(x, 2.0) == x*x exactly here
-                    const float q = n1 / n2;
-                    const v3 a = scale(dd, q), b = scale(normal, q * cos1 - cos2);
-                    tdir = normalize(cos1 >= 0 ? add(a, b) : sub(a, b));
-                    refracts = true;
+            const bool finished = FIN && hit && emitMask == 0;   // every shadow query answered (or no lights): no slot, the light sum below
+            const int slot = block_append(X.scnt, hit != 0 && !finished, ldsCounts);
+            if (hit && !finished && slot >= X.shadowCap) { *X.overflow = 1; hit = 0; }   // more rays than the chunk's buffers hold: the host retries with fewer paths
+            nFinished += finished ? 1 : 0;
+            if (X.ae) {   // (grid-uniform) shadow rays: answered here where the whole mesh faces away, else appended to the compact list
+                for (int l = 0; l < V.nLights; l++) {
+                    v3 dir = mk(0, 0, 0); float dist;
+                    bool emit = false;
+                    if (hit && !finished) {
+                        light_dir(V.lights[l], w, dir, dist);
+                        emit = FIN ? ((emitMask >> l) & 1u) != 0 : !faces_away_single(S, w, dir);
+                        if (!emit) X.shadowFlagsOut[(size_t)slot * V.nLights + l] = 0;   // IsLightPathObstructed's query finds nothing (RT:482-485)
+                    }
+                    const int pos = block_append(X.shadowCnt, emit, ldsCounts);
+                    if (emit) {
+                        store_ray(X.shadowRays + pos, w, dir, mesh, tri);   // ignore = shaded triangle (RT:485)
+                        X.shadowOut[pos] = slot * V.nLights + l;
+                    }
                 }
             }
-        }
-        if (!emitNext) continue;
-        if (!X.heap && X.ae) {   // chain of reflections, answered at emission: a reflection the whole mesh faces away from ends its path here
-            const bool emit = hit && !faces_away_single(S, w, rdir);
-            if (hit && !emit) X.lvlB[(size_t)(X.level + 1) * P + lvl_at(X.lvl, p)] = f4{0, 0, 0, i2f(FLAG_MISS)};   // what part A of the next step writes for a miss (RT:729-733)
-            const int pos = block_append(X.nextCnt, emit, ldsCounts);
-            const bool heavy = emit && X.heavy.list && pos < X.nextCap && long_ray(S, X.heavy, p, w, rdir);
-            if (emit && pos < X.nextCap) {   // (pos <= the parent's slot < cap: a guard, not a code path)
-                store_ray(X.nextRays + pos, w, rdir, mesh, heavy ? (tri ^ HEAVY_BIT) : tri);   // origin = result.triangle (RT:559)
-                X.nextPath[pos] = p;
-            }
-            if (X.heavy.list) {
-                const int hs = block_append(X.heavy.count, heavy, ldsCounts);
-                if (heavy) X.heavy.list[hs] = pos;
-            }
-            continue;
-        }
-        if (!X.heap) {   // chain of reflections: the ray of generation k+1 sits at its parent's slot
-            const bool heavy = hit && X.heavy.list && long_ray(S, X.heavy, p, w, rdir);
             if (hit) {
-                store_ray(X.nextRays + slot, w, rdir, mesh, heavy ? (tri ^ HEAVY_BIT) : tri);   // origin = result.triangle (RT:559)
-                X.nextPath[slot] = p;
+                for (int l = 0; l < V.nLights && !X.ae; l++) {
+                    v3 dir; float dist;
+                    light_dir(V.lights[l], w, dir, dist);
+                    store_ray(X.shadowRays + (size_t)slot * V.nLights + l, w, dir, mesh, tri);   // ignore = shaded triangle (RT:485)
+                }
+                // the hit's own share of RT:516-581: fragment normal (RT:520-531), surface colour (RT:568-581 / 711-724), Reflectiveness -- the colour final
+                // in lvlB, (normal, Reflectiveness) in the slot record until part B of the next step has the shadow answers for the light sum
+                const int gtri = V.meshes[mesh].triBase + tri;
+                const MaterialRec M = V.materials[V.meshes[mesh].material];
+                normal = fragment_normal(V, gtri, M.flags, u, v);
+                {
+                    v3 surf;
+                    const f4 *sr = V.shade + (size_t)gtri * 6;
+                    if (M.flags & MAT_TEXTURE) {   // RT:568-575
+                        f4 s0 = sr[0], s1 = sr[1], s2 = sr[2], s4 = sr[4];
+                        float uv1x = s0.w, uv1y = s1.w, uv2x = s2.w, uv2y = s4.x, uv3x = s4.y, uv3y = s4.z;
+                        float ax = uv2x - uv1x, ay = uv2y - uv1y, bx = uv3x - uv1x, by = uv3y - uv1y;
+                        float ix = (uv1x + ax * u) + bx * v, iy = (uv1y + ay * u) + by * v;
+                        surf = lookup_uv(V, M, ix, iy);
+                    } else {
+                        f4 c = sr[3];
+                        surf = mk(c.x, c.y, c.z);
+                    }
+                    const bool transparent = (M.flags & MAT_TRANSPARENT) != 0;
+                    at = (size_t)node * P + lvl_at(X.lvl, p);
+                    if (finished) { refl = M.reflectiveness; sum = true; }   // (the floats the slot record would have carried to part B)
+                    else {
+                        X.slotOut[slot] = SlotRec{w.x, w.y, w.z, p, normal.x, normal.y, normal.z, M.reflectiveness};
+                        if (X.heap) X.slotNodeOut[slot] = node;
+                    }
+                    X.lvlB[at] = f4{surf.x, surf.y, surf.z, i2f(FLAG_HIT | (transparent ? FLAG_TRANSPARENT : 0))};
+                    if (X.heap) X.lvlAlpha[at] = sr[3].w;   // triangle.color.W (RT:699)
+                }
+                if (emitNext) {
+                    v3 o, dd; int im, itri;
+                    load_ray(X.rays + i, o, dd, im, itri);
+                    rdir = normalize(reflect(dd, normal));   // RT:549-550
+                    if (X.heap && (M.flags & MAT_TRANSPARENT)) {   // RT:656-694: Snell refraction, the System.Math calls in double
+                        float n1;
+                        if (curRef == M.refractionIndex) { n1 = 1.0f; n2 = curRef; }
+                        else { n1 = M.refractionIndex; n2 = 1.0f; }
+                        const float cos1 = dot(normal, neg(dd));
+                        const double ratio = (double)(n1 / n2), c1 = (double)cos1;
+                        const float cos2 = (float)sqrt(1 - (ratio * ratio) * (1 - (c1 * c1)));   // Math.Pow(x, 2.0) == x*x exactly here
+                        const float q = n1 / n2;
+                        const v3 a = scale(dd, q), b = scale(normal, q * cos1 - cos2);
+                        tdir = normalize(cos1 >= 0 ? add(a, b) : sub(a, b));
+                        refracts = true;
+                    }
+                }
             }
-            if (X.heavy.list) {
-                const int hs = block_append(X.heavy.count, heavy, ldsCounts);
-                if (heavy) X.heavy.list[hs] = slot;
+            if (!emitNext) {
+            } else if (!X.heap && X.ae) {   // chain of reflections, answered at emission: a reflection the whole mesh faces away from ends its path here
+                const bool emit = hit && !faces_away_single(S, w, rdir);
+                if (hit && !emit) X.lvlB[(size_t)(X.level + 1) * P + lvl_at(X.lvl, p)] = f4{0, 0, 0, i2f(FLAG_MISS)};   // what part A of the next step writes for a miss (RT:729-733)
+                const int pos = block_append(X.nextCnt, emit, ldsCounts);
+                const bool heavy = emit && X.heavy.list && pos < X.nextCap && long_ray(S, X.heavy, p, w, rdir);
+                if (emit && pos < X.nextCap) {   // (reflections emitted <= rays of this generation <= cap: a guard, not a code path)
+                    store_ray(X.nextRays + pos, w, rdir, mesh, heavy ? (tri ^ HEAVY_BIT) : tri);   // origin = result.triangle (RT:559)
+                    X.nextPath[pos] = p;
+                }
+                if (X.heavy.list) {
+                    const int hs = block_append(X.heavy.count, heavy, ldsCounts);
+                    if (heavy) X.heavy.list[hs] = pos;
+                }
+            } else if (!X.heap) {   // chain of reflections: the ray of generation k+1 sits at its parent's slot
+                const bool heavy = hit && X.heavy.list && long_ray(S, X.heavy, p, w, rdir);
+                if (hit) {
+                    store_ray(X.nextRays + slot, w, rdir, mesh, heavy ? (tri ^ HEAVY_BIT) : tri);   // origin = result.triangle (RT:559)
+                    X.nextPath[slot] = p;
+                }
+                if (X.heavy.list) {
+                    const int hs = block_append(X.heavy.count, heavy, ldsCounts);
+                    if (heavy) X.heavy.list[hs] = slot;
+                }
+            } else {
+                const int slot1 = block_append(X.nextCnt, hit != 0, ldsCounts);
+                if (hit && slot1 >= X.nextCap) *X.overflow = 1;
+                else if (hit) {
+                    store_ray(X.nextRays + slot1, w, rdir, mesh, tri);
+                    X.nextPath[slot1] = p;
+                    X.nextNode[slot1] = 2 * node + 1; X.nextRef[slot1] = curRef;
+                }
+                const int slot2 = block_append(X.nextCnt, refracts, ldsCounts);   // the refracted ray of RT:698 continues in the medium with index n2
+                if (refracts && slot2 >= X.nextCap) *X.overflow = 1;
+                else if (refracts) {
+                    store_ray(X.nextRays + slot2, w, tdir, mesh, tri);
+                    X.nextPath[slot2] = p;
+                    X.nextNode[slot2] = 2 * node + 2; X.nextRef[slot2] = n2;
+                }
             }
-            continue;
         }
-        const int slot1 = block_append(X.nextCnt, hit != 0, ldsCounts);
-        if (hit && slot1 >= X.nextCap) *X.overflow = 1;
-        else if (hit) {
-            store_ray(X.nextRays + slot1, w, rdir, mesh, tri);
-            X.nextPath[slot1] = p;
-            X.nextNode[slot1] = 2 * node + 1; X.nextRef[slot1] = curRef;
+        if constexpr (FIN) {
+            if (sum) {
+                const v3 lightResult = shade_light_sum(V, X, fromSlot, s, w, normal);
+                X.lvlA[at] = f4{lightResult.x, lightResult.y, lightResult.z, refl};
+            }
         }
-        const int slot2 = block_append(X.nextCnt, refracts, ldsCounts);   // the refracted ray of RT:698 continues in the medium with index n2
-        if (refracts && slot2 >= X.nextCap) *X.overflow = 1;
-        else if (refracts) {
-            store_ray(X.nextRays + slot2, w, tdir, mesh, tri);
-            X.nextPath[slot2] = p;
-            X.nextNode[slot2] = 2 * node + 2; X.nextRef[slot2] = n2;
+    }
+    if constexpr (FIN) {   // the finished hits are only counted, they need no positions: one atomic per block
+        const int wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6), lane = lane_id();
+        const int mine = __builtin_amdgcn_readlane(wave_scan_add(nFinished), 63);
+        if (lane == 0) ldsCounts[wave] = mine;
+        __syncthreads();
+        if (wave == 0) {
+            const int total = __builtin_amdgcn_readlane(wave_scan_add(lane < nw ? ldsCounts[lane] : 0), 63);
+            if (lane == 0 && total) atomicAdd(X.finishCnt, total);
         }
     }
 }
 void launch_shade(const SceneView &S, const ShadeView &V, const ShadeArgs &X, hipStream_t st, int blocks, int threads) {
     if (threads != 256) threads = APPEND_BLOCK;   // 256-thread blocks spread a small generation over the CUs (block_append takes any block of whole waves)
     const int cap = threads == 256 ? 4096 : 1024;
-    hipLaunchKernelGGL(k_shade, dim3(blocks < 1 ? 1 : (blocks > cap ? cap : blocks)), dim3(threads), 0, st, S, V, X);
+    const dim3 grid(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
+    if (X.finish) hipLaunchKernelGGL(k_shade<true>, grid, dim3(threads), 0, st, S, V, X);
+    else hipLaunchKernelGGL(k_shade<false>, grid, dim3(threads), 0, st, S, V, X);
 }
 
 // Frame epilogue (kernels.h FrameEpilogue): every kernel that counts rays has finished -- hand the counters to the host, clear them

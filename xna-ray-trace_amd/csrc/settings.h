@@ -44,6 +44,7 @@ struct Settings {
     std::optional<int> firstBatch;   // XRT_FIRST_BATCH (unset: the scene's, xrt_scene::firstBatch)
     bool packetMerge = true;   // the closest-hit and the shadow packets of a step share one launch (XRT_PK_MERGE=0: two launches, as round 2)
     bool answerAtEmission = true;   // XRT_AE=0: k_shade emits every ray (kernels.h ShadeArgs::ae off)
+    bool finishInPartA = true;      // XRT_AE_FINISH=0: a hit whose shadow rays were all answered at emission still takes a slot and waits for part B (kernels.h ShadeArgs::finish off)
     int packetPrefetch = -1;   // XRT_PK_PREFETCH: -1 launches of fewer than packetPrefetchBelow packets per resident wave prefetch (kernels.h PacketArgs::prefetch), 0 never, 1 always
     int packetPrefetchBelow = 12;
     bool packetBundle = true;  // XRT_PK_BUNDLE=0: no bundle prefilter (kernels.h PacketArgs::bundle)
@@ -92,6 +93,7 @@ struct Settings {
                  // are no longer exact.  A shipped library does not read them from the environment of its host process.
     std::optional<double> leafCullSafety;   // XRT_LEAF_CULL: 0 = no tight leaf boxes, 1 = the proven margin (HostScene::leafCullSafety)
     std::optional<double> cullSafety;       // XRT_CULL_SAFETY: factor S of the object pre-cull margin (below 2 the bound is no longer proven)
+    bool finishCounts = false;              // XRT_FINISH_COUNTS=1: every single-pass frame prints its generations' hits and how many of them part A finished
 #endif
     std::optional<bool> guard;   // XRT_GUARD: process-wide (g_guardMode); unset leaves the mode as it is
 };
@@ -129,6 +131,7 @@ inline Settings read_settings() {
     env_int("XRT_FIRST_BATCH", c.firstBatch, 64, 4096, 64);
     env_flag("XRT_PK_MERGE", c.packetMerge);
     env_flag("XRT_AE", c.answerAtEmission);
+    env_flag("XRT_AE_FINISH", c.finishInPartA);
     env_int("XRT_PK_PREFETCH", c.packetPrefetch, -1, 1);
     env_int("XRT_PK_PREFETCH_BELOW", c.packetPrefetchBelow, 0, 100000);
     env_flag("XRT_PK_BUNDLE", c.packetBundle);
@@ -168,6 +171,7 @@ inline Settings read_settings() {
 #ifdef XRT_DEV
     if (const char *e = getenv("XRT_LEAF_CULL")) { const double v = atof(e); if (v >= 0.0 && v <= 1e6) c.leafCullSafety = v; }
     if (const char *e = getenv("XRT_CULL_SAFETY")) { const double v = atof(e); if (v >= 0.0 && v <= 1e6) c.cullSafety = v; }
+    env_flag("XRT_FINISH_COUNTS", c.finishCounts);
 #endif
     env_flag("XRT_GUARD", c.guard);
     return c;

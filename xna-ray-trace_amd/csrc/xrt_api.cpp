@@ -673,6 +673,9 @@ struct BatchSrc {
     const Paths *paths = nullptr;
 };
 
+// Hits of generation k in a chunk's counter block hc (frame_begin cntStride): the slots part A took plus the hits it finished itself (ShadeArgs::finish)
+static inline long long gen_hits(const int *hc, int R, int k) { return (long long)hc[(R + 2) + k] + (long long)hc[4 * (R + 2) + k]; }
+
 // Enqueues one frame on `st`.  On return the frame's kernels and its counter read-back are in flight (F.pending);
 // frame_finish waits for them.  Adaptive supersampling and ray-tree frames need host decisions between their passes and
 // are complete when this returns.
@@ -822,7 +825,8 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     if (wantF32 && !batch && (rc = W.sampleF32.ensure((size_t)P * 3))) return rc;   // (a batch's compose writes the caller's arrays)
     const BatchSrc::Paths *const pout = batch ? batch->paths : nullptr;   // the pass also records its ray paths (paths.hip)
     unsigned pathEpoch = 0;                                               // ... the tag of the chunk attempt being enqueued
-    const int cntStride = 4 * (R + 2);          // per chunk: cnt[R+2], scnt[R+2], the long-ray list lengths [R+2], the shadow rays really emitted [R+2] (ShadeArgs::ae)
+    const int cntStride = 5 * (R + 2);          // per chunk: cnt[R+2], scnt[R+2], the long-ray list lengths [R+2], the shadow rays really emitted [R+2] (ShadeArgs::ae),
+                                                // the hits that took no slot [R+2] (ShadeArgs::finish; hits of generation k = scnt[k] + fcnt[k])
     constexpr int QW = 1 + 2 * PACKET_QUEUE_WORDS;   // per launch step k: the lane kernel's queue word and the heads of each packet launch (closest, shadow)
     const int qStride = QW * (R + 2);
     // The common frame (one chunk, no supersampling levels, no ray tree, no counting pass) puts nothing but its kernels
@@ -848,6 +852,9 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         ae = m0.nbMin[3] == 0.0f && (m0.nbMin[0] > 0.0f || m0.nbMax[0] < 0.0f || m0.nbMin[1] > 0.0f || m0.nbMax[1] < 0.0f || m0.nbMin[2] > 0.0f || m0.nbMax[2] < 0.0f);
     }
     F.ae = ae;
+    // Finished in part A (kernels.h ShadeArgs::finish): such a frame's hits whose shadow rays are all answered at emission take no slot.  Not with path capture --
+    // k_paths_capture reads every hit's position from its slot record --, and the lights have to fit part A's bit mask.
+    const bool finishA = ae && !heap && !(batch && batch->paths) && nL <= 32 && s->cfg.finishInPartA;
     if (ae && ((rc = W.shadowOut.ensure(rayCap * (nL > 0 ? nL : 1))) || (rc = W.shadowFlags1.ensure(rayCap * (nL > 0 ? nL : 1))))) return rc;
     F.fast = fast;
     F.heap = heap;
@@ -1011,6 +1018,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     auto enqueue_chunk = [&](const RayGenParams &gp, int *cnt, unsigned *q, int Pc, long long pathBase, uint32_t *sampleOut = nullptr,
                              const FrameEpilogue *epi = nullptr) -> int {
         int *scnt = cnt + (R + 2), *hcnt = cnt + 2 * (R + 2), *acnt = cnt + 3 * (R + 2);   // (acnt[k]: shadow rays of generation k that were really emitted, ShadeArgs::ae)
+        int *fcnt = cnt + 4 * (R + 2);                                                      // (fcnt[k]: hits of generation k finished in part A, ShadeArgs::finish)
         const int chunkRow0 = F.stampRows;
         if (pout) {   // this attempt's records carry a number no earlier attempt had
             if (++s->pathEpoch == 0) {
@@ -1145,6 +1153,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
             X.nextRays = rays[prv]; X.nextPath = paths[prv]; X.nextNode = heap ? nodesOf[prv] : nullptr; X.nextRef = heap ? refOf[prv] : nullptr;
             X.nextCnt = cnt + k + 1; X.nextCap = (int)rayCap;
             if (ae) { X.ae = 1; X.shadowCnt = acnt + k; X.shadowOut = W.shadowOut.p; X.shadowFlagsOut = shadowFlagsOf[k & 1]; }
+            if (finishA) { X.finish = 1; X.finishCnt = fcnt + k; }
             X.slotPrev = slotOf[prv]; X.slotNodePrev = heap ? slotNodeOf[prv] : nullptr; X.scntPrev = k >= 1 ? scnt + (k - 1) : nullptr; X.shadowHits = W.shadowHits.p;
             X.lvlA = W.lvlA.p; X.lvlB = W.lvlB.p; X.lvlAlpha = heap ? W.lvlAlpha.p : nullptr;
             if (k < R) X.heavy = heavy_for(k + 1);
@@ -1199,8 +1208,8 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     };
     auto tally = [&](const int *hc) {
         for (int k = 0; k <= R; k++) {
-            shaded += (unsigned long long)hc[(R + 2) + k];
-            if (k > 0) closestDeep += (unsigned long long)(heap ? hc[k] : hc[(R + 2) + k - 1]);   // reflection chain: one ray per parent hit
+            shaded += (unsigned long long)gen_hits(hc, R, k);
+            if (k > 0) closestDeep += (unsigned long long)(heap ? hc[k] : gen_hits(hc, R, k - 1));   // reflection chain: one ray per parent hit
             else live0 += (unsigned long long)hc[0];
         }
     };
@@ -1493,21 +1502,29 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
             if (hc[0] < 0 || (size_t)hc[0] > F.liveCap)
                 return fail(XRT_E_INTERNAL, "%d primary rays reach the scene but the frame's ray arrays were sized for %zu (screen rectangle of the root box)", hc[0], F.liveCap);
             for (int k = 0; k <= R; k++) {
-                F.shaded += (unsigned long long)hc[(R + 2) + k];
-                if (k > 0) F.closestDeep += (unsigned long long)(F.heap ? hc[k] : hc[(R + 2) + k - 1]);   // reflection chain: one ray per parent hit
+                F.shaded += (unsigned long long)gen_hits(hc, R, k);
+                if (k > 0) F.closestDeep += (unsigned long long)(F.heap ? hc[k] : gen_hits(hc, R, k - 1));   // reflection chain: one ray per parent hit
                 else F.live0 += (unsigned long long)hc[0];
                 if (F.ae) {   // queries part A answered itself: the hits' shadow rays that were not emitted, and (not in the last generation) their reflections
-                    F.answered += (unsigned long long)hc[(R + 2) + k] * (unsigned long long)F.nL - (unsigned long long)hc[3 * (R + 2) + k];
-                    if (k < R) F.answered += (unsigned long long)(hc[(R + 2) + k] - hc[k + 1]);
+                    F.answered += (unsigned long long)gen_hits(hc, R, k) * (unsigned long long)F.nL - (unsigned long long)hc[3 * (R + 2) + k];
+                    if (k < R) F.answered += (unsigned long long)(gen_hits(hc, R, k) - hc[k + 1]);
                 }
             }
         }
+#ifdef XRT_DEV
+        if (s->cfg.finishCounts)   // (profiles/shade_finish: which share of a generation's hits part A finished; a frame not answered at emission emits every shadow ray)
+            for (int k = 0; k <= R; k++) {
+                const int *hc = (const int *)F.pinned + F.cntBase;
+                fprintf(stderr, "xrt finish: %s generation %d hits %lld finished %d shadow rays emitted %lld\n", F.ae ? "answered at emission," : "not answered at emission,", k,
+                        gen_hits(hc, R, k), hc[4 * (R + 2) + k], F.ae ? (long long)hc[3 * (R + 2) + k] : gen_hits(hc, R, k) * (long long)F.nL);
+            }
+#endif
         if (!F.fast) std::memcpy(F.hcnt, (char *)F.pinned + nb, sizeof(F.hcnt));
         // (adaptive frames in flight put the level-count words in front of the per-pass counters and have no framePaths key: no hints from them)
         if (F.fast && F.tallyChunks == 1 && !F.adaptiveFast) {   // sizes of this frame's generations: grid hints for the next one (sizing only)
             const int *hc = (const int *)F.pinned + F.cntBase;
             for (int k = 0; k <= R + 1 && k < 68; k++) {
-                const long long closest = (k == 0 || ((F.heap || F.ae) && k <= R)) ? hc[k] : (k <= R ? hc[(R + 2) + k - 1] : 0), shaded = k >= 1 ? hc[(R + 2) + k - 1] : 0;
+                const long long closest = (k == 0 || ((F.heap || F.ae) && k <= R)) ? hc[k] : (k <= R ? gen_hits(hc, R, k - 1) : 0), shaded = k >= 1 ? gen_hits(hc, R, k - 1) : 0;
                 // (a hint shrinks by an eighth per frame at most: a camera that looks away for a frame, or alternates between two views,
                 // must not leave the next full view with a grid of sixteen blocks)
                 const bool same = s->genKey == F.framePaths * 64 + F.nL;
@@ -1522,7 +1539,7 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
         if (F.fast && s->costMap.p && !F.adaptiveFast) {   // steer the "long ray" thresholds towards 2-6 % of each generation's rays
             const int *hc = (const int *)F.pinned + F.cntBase;
             for (int k = 0; k <= R && k < 66; k++) {
-                const long long rays = k == 0 ? hc[0] : hc[(R + 2) + k - 1], listed = hc[2 * (R + 2) + k];
+                const long long rays = k == 0 ? hc[0] : gen_hits(hc, R, k - 1), listed = hc[2 * (R + 2) + k];
                 if (rays < 4096) continue;
                 if (listed * 100 > rays * s->cfg.longFracHi) s->costT[k] = s->costT[k] + s->costT[k] / 4 + 1;
                 else if (listed * 100 < rays * s->cfg.longFracLo && s->costT[k] > 1) s->costT[k] = s->costT[k] - s->costT[k] / 5 - (s->costT[k] < 5 ? 1 : 0);
