@@ -149,6 +149,8 @@ namespace RayTraceProject.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_rccl_probe();
         // diagnostics of the split walks of long packets (results never depend on them): subtrees handed over, taken, packets split, packets written by a taker
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_split_stats(IntPtr scene, [Out] ulong[] out4, int reset);
+        // diagnostics of "end early" (results never depend on it): the last frame's paths coloured by the ray generation kernel, by the shading kernel, left to the compose list
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_debug_end_counts(IntPtr scene, [Out] ulong[] out3);
 
         // error convention of the reference: InvalidOperationException when busy (RayTracer.cs:26-27,62-63),
         // ArgumentException for bad arguments (SceneObject.cs:123-124, Material.cs:85,97)

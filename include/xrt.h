@@ -373,6 +373,14 @@ int xrt_rccl_probe(void);
  * whose results were written by a taker -- counted on the scene's device since the library was loaded or since the last call with reset != 0. */
 int xrt_split_stats(xrt_scene *scene, uint64_t out[4], int32_t reset);
 
+/* Diagnostics of "end early" (testing aid; XRT_END_EARLY, results never depend on it): plain one-chunk frames of one-body scenes that want no float
+ * colours give every path that ends at generation 0 its colour where it ends.  For the last finished frame of the scene: out[0] paths coloured by the
+ * ray generation kernel (they cannot reach the scene's root box, or have no pixel), out[1] paths coloured by the shading kernel (misses, and hits with
+ * no shadow ray and no reflection to trace), out[2] paths left to the compose kernel's list -- each counted on the device by the kernel that did it.
+ * They sum to the frame's paths; all zero: the frame did not take that way.  The output buffer of a frame is written by the frame's last kernel
+ * only, on this way as on every other. */
+int xrt_debug_end_counts(xrt_scene *scene, uint64_t out[3]);
+
 /* RayTracer.Progress (RT:43-46): fraction of the frame's ray generations completed; callable from
  * another thread during xrt_render. */
 float xrt_progress(const xrt_scene *scene);

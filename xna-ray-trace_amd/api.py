@@ -360,6 +360,12 @@ class OctreeSpatialManager(ISpatialManager):
         abi.check(abi.lib().xrt_split_stats(self.handle, out, 1 if reset else 0))
         return tuple(int(x) for x in out)
 
+    def EndCounts(self):
+        """xrt_debug_end_counts: the last finished frame's paths coloured by k_raygen, coloured by k_shade, left on k_compose's list (all zero: not engaged)."""
+        out = (C.c_uint64 * 3)()
+        abi.check(abi.lib().xrt_debug_end_counts(self.handle, out))
+        return tuple(int(x) for x in out)
+
     def IntersectBatch(self, rays, stats=False):
         """Batched ISpatialManager.GetRayIntersection (ISM:15): xrt_ray array -> xrt_hit array."""
         rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)

@@ -145,6 +145,25 @@ constexpr int FLAG_MISS = 0, FLAG_HIT = 1, FLAG_TRANSPARENT = 2;
 // What part B of k_shade needs of a shaded hit, left by part A at the hit's slot (the slots of a generation are dense, so both sides stream
 // 32 bytes per hit; the level record lvlA[node][path] is written once, by part B): world position, path, fragment normal, Reflectiveness.
 
+// End early (plain one-chunk frames that finish hits in part A and want no float samples; decided by the host, grid-uniform): whoever ends a
+// generation-0 path writes its sample colour -- k_raygen black for a path that cannot reach the root box (no lvlB record), part A of k_shade #0
+// black for a miss and the composed colour for a hit it finished that has no next ray (no lvlA / lvlB record at all) -- where k_compose would have
+// written it: sampleColor[p].  Only there: the caller's framebuffer is written by the frame's LAST kernel as it always was (the caller may still have work
+// of its own queued on that buffer when the frame begins), so a one-sample frame that ends paths early is not fused -- k_resolve copies its samples out.
+// Every other hit is appended to `list` and k_compose walks the list instead of the frame.
+// The counts (cnt[END_WORDS], in front of the list, not in the frame's counter block): cnt[END_LISTED] the entries of the list -- k_raygen clears it,
+// part A of k_shade #0 appends, EVERY block of k_compose reads it, which is why it cannot be a word that k_compose's epilogue clears (the blocks of a
+// grid start at different times; a late one would read zero) --; cnt[END_BY_RAYGEN], cnt[END_BY_SHADE] the paths the two kernels coloured, counted
+// there with one atomic per block (xrt_debug_end_counts).  Block 0 of k_compose hands all three to the host behind the counter block and clears the
+// last two (their writers ran in earlier kernels, nobody else reads them).
+enum { END_LISTED = 0, END_BY_RAYGEN, END_BY_SHADE, END_WORDS };
+struct EndArgs {
+    int on = 0;
+    uint32_t *sampleColor = nullptr;
+    int *list = nullptr, *cnt = nullptr;   // cnt[END_WORDS]
+    int listCap = 0;
+};
+
 // k_shade: part A works on generation `level`, part B on generation level-1 (kernels.hip).
 struct ShadeArgs {
     int level, doA, doB;
@@ -178,6 +197,8 @@ struct ShadeArgs {
     // really taken (the hits that wait for shadow answers), *finishCnt the hits that took none: hits of the generation = *scnt + *finishCnt.
     int finish = 0;
     int *finishCnt = nullptr;
+    // End early (EndArgs; step 0 of a `finish` frame only): part A colours the paths that end in it and lists the others for k_compose.
+    EndArgs end;
 };
 
 int  intersect_stack_capacity(int needed);   // smallest compiled capacity >= needed, or -1
@@ -186,7 +207,7 @@ void launch_intersect(const SceneView &S, const IntersectArgs &A, int stackNeede
 int  intersect_blocks_per_cu(int stackNeeded, int mode);
 void launch_count(const SceneView &S, const IntersectArgs &A, unsigned long long *counters, hipStream_t st);
 void launch_raygen(const RayGenParams &g, const SceneView &S, xrt_ray *rays, f4 *lvlB0, int *index, int *count, int P, long long pathBase,
-                   const HeavyArgs &H, hipStream_t st, hipEvent_t startEvent = nullptr, int liveCap = 0x7fffffff);
+                   const HeavyArgs &H, hipStream_t st, hipEvent_t startEvent = nullptr, int liveCap = 0x7fffffff, const EndArgs *end = nullptr);
 void launch_shade(const SceneView &S, const ShadeView &V, const ShadeArgs &X, hipStream_t st, int blocks = 1024, int threads = 1024);   // (any grid is correct: grid-stride loops)
 // Frame epilogue of the compose kernels: the clock stamps of traversal launches row0 .. row1-1 are folded into (start, latest
 // end) pairs in host-visible memory (device_util.h)
@@ -220,9 +241,14 @@ struct ResolveArgs {
     int *hostCnt = nullptr;
     int cntWords = 0, zeroWords = 0, zeroFrom = 0;
     StampFold stamps;
+    // End early (EndArgs): the paths to compose are list[0 .. endCnt[END_LISTED]); the END_WORDS counts go to hostCnt[cntWords ..]
+    const int *list = nullptr;
+    int *endCnt = nullptr;
+    int listCap = 0;
 };
+// (`blocks` > 0: the grid of a frame whose compose list was this long a frame ago -- any grid is correct)
 void launch_compose(const f4 *lvlA, const f4 *lvlB, int count, int P /* level stride */, int maxReflections, uint32_t *sampleColor, float *sampleF32,
-                    const ResolveArgs &RA, hipStream_t st, hipEvent_t stopEvent = nullptr);
+                    const ResolveArgs &RA, hipStream_t st, hipEvent_t stopEvent = nullptr, int blocks = 0);
 void launch_resolve(const RayGenParams &g, const uint32_t *sampleColor, const float *sampleF32, int pixels, long long pixelBase,
                     uint32_t *out, float *outF32, hipStream_t st, int *zeroPtr = nullptr, int zeroN = 0);
 void launch_ms_decide(const RayGenParams &g, const uint32_t *quadColor, const int *nQuadsDev, int nQuadsHost, long long pixelBase, int *childBase,

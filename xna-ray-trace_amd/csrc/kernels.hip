@@ -102,6 +102,40 @@ __device__ __forceinline__ int block_append(int *counter, bool flag, int *ldsCou
     return slot;
 }
 
+// Counting without positions: the block's sum of n goes to *counter with one atomic.  Must be called by all threads of the block.
+__device__ __forceinline__ void block_count(int *counter, int n, int *ldsCounts /* [17] */) {
+    const int wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6), lane = lane_id();
+    const int mine = __builtin_amdgcn_readlane(wave_scan_add(n), 63);
+    __syncthreads();   // (ldsCounts may still be read by the round before)
+    if (lane == 0) ldsCounts[wave] = mine;
+    __syncthreads();
+    if (wave == 0) {
+        const int total = __builtin_amdgcn_readlane(wave_scan_add(lane < nw ? ldsCounts[lane] : 0), 63);
+        if (lane == 0 && total) atomicAdd(counter, total);
+    }
+}
+// Two lists in one round of barriers: wave 0 reserves the block's range of the first, wave 1 of the second (blocks of at least two waves).
+__device__ __forceinline__ void block_append2(int *counterA, bool flagA, int *counterB, bool flagB, int *ldsCounts /* [34] */, int &slotA, int &slotB) {
+    const unsigned long long mA = __ballot(flagA), mB = __ballot(flagB);
+    const int wave = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6), lane = lane_id();
+    if (lane == 0) { ldsCounts[wave] = (int)__popcll(mA); ldsCounts[17 + wave] = (int)__popcll(mB); }
+    __syncthreads();
+    if (wave < 2) {
+        int *cells = ldsCounts + 17 * wave;
+        const int c = lane < nw ? cells[lane] : 0;
+        const int incl = wave_scan_add(c);
+        const int total = __builtin_amdgcn_readlane(incl, 63);
+        int base = 0;
+        if (lane == 0 && total) base = atomicAdd(wave == 0 ? counterA : counterB, total);
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (lane < nw) cells[lane] = base + incl - c;
+    }
+    __syncthreads();
+    slotA = ldsCounts[wave] + lanes_below(mA);
+    slotB = ldsCounts[17 + wave] + lanes_below(mB);
+    __syncthreads();   // ldsCounts is reused by the next round
+}
+
 // ---- the hot kernel ------------------------------------------------------------------------------------------
 
 // Scene mode keeps the scene-level half of every lane's query (SceneLane, 27 words: world ray, scene cursor, best answer
@@ -570,6 +604,37 @@ __device__ __forceinline__ bool path_pixel(const RayGenParams &g, long long pix,
     return x < g.width && y < g.height;
 }
 
+// The sample-buffer form of path_color_out below.  Whoever ends a path early (kernels.h EndArgs) calls this form alone: the caller's framebuffer belongs to the
+// frame's LAST kernel (the caller may still have work of its own queued on it when the frame begins), so the frames that end paths early are never fused.
+__device__ __forceinline__ void sample_color_out(uint32_t *sampleColor, float *sampleF32, int p, uint32_t col, v3 cv) {
+    sampleColor[p] = col;
+    if (sampleF32) { sampleF32[3 * (size_t)p] = cv.x; sampleF32[3 * (size_t)p + 1] = cv.y; sampleF32[3 * (size_t)p + 2] = cv.z; }
+}
+// "The colour of path p of the pass goes out": the ONE place that knows where a path's colour lives -- its word of the sample buffer (and the three
+// floats, where a frame wants them), or, with one sample per pixel (fused), the framebuffer itself (RT:425): the pixel of path pixelBase + p, or the
+// shard's tile-contiguous buffer, where a path without a pixel is cleared.  Called by k_compose.
+__device__ __forceinline__ void path_color_out(const RayGenParams &g, int fused, long long pixelBase, uint32_t *out, float *outF32, uint32_t *sampleColor,
+                                               float *sampleF32, int p, uint32_t col, v3 cv) {
+    if (fused) {   // one sample per pixel: write the framebuffer directly (RT:425), no sample buffer round trip
+        long long pix = pixelBase + p;
+        int x, y;
+        bool ok = path_pixel(g, pix, x, y);
+        if (g.shardCount > 1) out[pix] = ok ? col : 0u;
+        else if (ok) {
+            size_t o = (size_t)y * g.width + x;
+            out[o] = col;
+            if (outF32) { outF32[3 * o] = cv.x; outF32[3 * o + 1] = cv.y; outF32[3 * o + 2] = cv.z; }
+        }
+        return;
+    }
+    sample_color_out(sampleColor, sampleF32, p, col, cv);
+}
+// The return path of the CastRay recursion, one level: the deepest hit of a path that reached generation MaxReflections has no reflection term
+// (RT:708-727); every other level blends what came back from below -- quantised, RT:705 -- with its surface colour by its Reflectiveness (RT:584).
+// The caller quantises the result (pack_color).
+__device__ __forceinline__ v3 compose_last(v3 light, v3 surf) { return mul(light, surf); }
+__device__ __forceinline__ v3 compose_step(uint32_t below, v3 surf, float refl, v3 light) { return mul(lerp(unpack_color(below), surf, 1.0f - refl), light); }
+
 // Rays that miss the scene octree's root box are answered here (OSM:318-320: no cuboid collected -> return
 // false) and the others are appended, wave by wave, to a compact index list for the traversal kernel.
 // One global atomic per list covers RG_ROUNDS x 1024 consecutive paths of a block (2025 atomics on one word were 20 of
@@ -579,9 +644,14 @@ constexpr int RG_ROUNDS = 4;
 // -- what the traversal kernels read is one contiguous run, and every per-ray array of generation 0 needs room for the live rays only
 // (at most the paths inside the root box's screen rectangle, known on the host: `liveCap`), not for every path of the frame.  Without
 // a list (xrt_generate_primary_rays) ray p sits at rays[p].
+// END (kernels.h EndArgs; frames with a live list): a path that ends here -- outside the rectangle, past the root box, without a pixel -- gets its colour,
+// black (RT:732), where k_compose would have written it, and no record.
+template <bool END>
 __global__ __launch_bounds__(APPEND_BLOCK) void k_raygen(RayGenParams g, SceneView S, xrt_ray *rays, f4 *lvlB0, int *index, int *count, int Phost,
-                                                         long long pathBase, HeavyArgs H, int liveCap) {
+                                                         long long pathBase, HeavyArgs H, int liveCap, EndArgs E) {
     __shared__ int ldsLive[RG_ROUNDS * 16], ldsHeavy[RG_ROUNDS * 16];
+    if constexpr (END) { if (blockIdx.x == 0 && threadIdx.x == 0) E.cnt[END_LISTED] = 0; }   // the frame's compose list starts empty (k_shade #0 fills it, a launch later)
+    int nEnded = 0;   // END: paths of this thread that ended here
     const int P = pass_paths(g, Phost);
     const f4 rlo = S.snodes[0], rhi = S.snodes[1];
     const int span = RG_ROUNDS * APPEND_BLOCK;
@@ -630,7 +700,8 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_raygen(RayGenParams g, SceneVi
                     if (!index) store_ray(rays + p, nearP, dir, -1, -1);
                     keepO[r] = nearP; keepD[r] = dir;   // (a culled ray is never read: it gets no place)
                 }
-                if (index && !live && record) lvlB0[lvl_at(g.lvl, p)] = f4{0, 0, 0, i2f(FLAG_MISS)};   // generation 0 ends here (RT:729-733)
+                if constexpr (END) { if (!live) { sample_color_out(E.sampleColor, nullptr, p, pack_color(mk(0, 0, 0)), mk(0, 0, 0)); nEnded++; } }   // generation 0 ends here (RT:729-733), and so does the path
+                else if (index && !live && record) lvlB0[lvl_at(g.lvl, p)] = f4{0, 0, 0, i2f(FLAG_MISS)};   // generation 0 ends here (RT:729-733)
             }
             const unsigned long long ml = __ballot(live), mh = __ballot(heavy);
             liveAt[r] = live ? lanes_below(ml) : -1;
@@ -664,6 +735,7 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_raygen(RayGenParams g, SceneVi
         }
         __syncthreads();   // the cells are reused by the next group
     }
+    if constexpr (END) block_count(E.cnt + END_BY_RAYGEN, nEnded, ldsLive);
 }
 // Generation 0 from a caller's ray list (xrt_cast_rays: RayTracer.CastRay, RT:506, on every ray) instead of the camera: path p of the pass is
 // ray g.batch[pathBase + p], used as given (CastRay does not normalise it).  Everything else is k_raygen's: a ray that cannot reach the
@@ -735,13 +807,14 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_ingest(RayGenParams g, SceneVi
     }
 }
 void launch_raygen(const RayGenParams &g, const SceneView &S, xrt_ray *rays, f4 *lvlB0, int *index, int *count, int P, long long pathBase,
-                   const HeavyArgs &H, hipStream_t st, hipEvent_t startEvent, int liveCap) {
+                   const HeavyArgs &H, hipStream_t st, hipEvent_t startEvent, int liveCap, const EndArgs *end) {
     static_assert(RG_ROUNDS * 16 == 64, "one wave scans the block's cells");
     int blocks = (P + RG_ROUNDS * APPEND_BLOCK - 1) / (RG_ROUNDS * APPEND_BLOCK);
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
     if (g.batch) hipExtLaunchKernelGGL(k_ingest, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap);
-    else hipExtLaunchKernelGGL(k_raygen, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap);
+    else if (end && end->on && index) hipExtLaunchKernelGGL(k_raygen<true>, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap, *end);
+    else hipExtLaunchKernelGGL(k_raygen<false>, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap, EndArgs());
 }
 
 // ---- shading ----------------------------------------------------------------------------------------------------------
@@ -880,9 +953,14 @@ __device__ __forceinline__ v3 shade_light_sum(const ShadeView &V, const ShadeArg
 // FIN (ShadeArgs::finish): one loop takes a thread through its part-B items and then through its part-A items, and both end in the same light sum -- a
 // part-B item with the shadow answers of its slot, a part-A item that finished with every lightAmount 0.  Without it part B is a loop of its own in front
 // of part A, as it always was (frames that finish nothing pay nothing for the other arrangement).
-template <bool FIN>
+// END (ShadeArgs::end; with FIN, generation 0, a chain answered at emission): a miss gets its colour here, black, and no record; a hit that finished and has
+// no next ray -- the last generation, or its reflection was answered at emission -- is TERMINAL: its light sum, one step of the return path against what a
+// miss below it returns, its colour out -- no lvlA, no lvlB, no miss record of generation 1.  Every other hit leaves its records as always and its path in
+// the compose list.
+template <bool FIN, bool END = false>
 __global__ __launch_bounds__(APPEND_BLOCK) void k_shade(SceneView S, ShadeView V, ShadeArgs X) {
-    __shared__ int ldsCounts[17];
+    static_assert(FIN || !END, "a frame that ends paths early finishes hits in part A");
+    __shared__ int ldsCounts[END ? 34 : 17];
     const int stride = (int)(gridDim.x * blockDim.x);
     const int tid = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     const size_t P = (size_t)X.P;
@@ -906,6 +984,7 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_shade(SceneView S, ShadeView V
     const bool emitNext = X.level < X.maxReflections;   // grid-uniform
     const int roundsB = FIN ? (nB + stride - 1) / stride : 0, rounds = roundsB + (n + stride - 1) / stride;
     int nFinished = 0;   // part-A items of this thread that finished
+    int nEnded = 0;      // END: paths this thread coloured
 #pragma unroll 1
     for (int it = 0; it < rounds; it++) {
         bool sum = false, fromSlot = false;   // FIN: this item has a light sum to form; ... from the shadow answers of slot s
@@ -913,6 +992,10 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_shade(SceneView S, ShadeView V
         size_t at = 0;
         v3 w = mk(0, 0, 0), normal = mk(0, 0, 0);
         float refl = 0.0f;
+        // END: the path of this part-A item, its surface colour and flag word (the lvlB record, written once the hit is known not to be terminal)
+        int pathA = 0, flagA = 0;
+        v3 surfA = mk(0, 0, 0);
+        bool terminal = false;
         if (FIN && it < roundsB) {   // (grid-uniform)
             s = it * stride + tid;
             if (s < nB) {
@@ -938,7 +1021,8 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_shade(SceneView S, ShadeView V
                     X.costOut[p] = (X.epoch << 16) | (unsigned)(c > 0xffff ? 0xffff : (c < 0 ? 0 : c));
                 }
                 if (X.heap) { node = X.rayNode ? X.rayNode[i] : 0; curRef = X.rayRef ? X.rayRef[i] : 1.0f; }   // generation 0: root, in vacuum (RT:424)
-                if (!hit) X.lvlB[(size_t)node * P + lvl_at(X.lvl, p)] = f4{0, 0, 0, i2f(FLAG_MISS)};
+                if constexpr (END) { if (!hit) { sample_color_out(X.end.sampleColor, nullptr, p, pack_color(mk(0, 0, 0)), mk(0, 0, 0)); nEnded++; } }   // RT:732, and the path is over
+                else if (!hit) X.lvlB[(size_t)node * P + lvl_at(X.lvl, p)] = f4{0, 0, 0, i2f(FLAG_MISS)};
             }
             // ShadeArgs::finish (grid-uniform; at most 32 lights): which lights' shadow rays have to be emitted is decided BEFORE the hit takes a slot
             unsigned emitMask = 0;
@@ -1000,7 +1084,8 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_shade(SceneView S, ShadeView V
                         X.slotOut[slot] = SlotRec{w.x, w.y, w.z, p, normal.x, normal.y, normal.z, M.reflectiveness};
                         if (X.heap) X.slotNodeOut[slot] = node;
                     }
-                    X.lvlB[at] = f4{surf.x, surf.y, surf.z, i2f(FLAG_HIT | (transparent ? FLAG_TRANSPARENT : 0))};
+                    if constexpr (END) { surfA = surf; flagA = FLAG_HIT | (transparent ? FLAG_TRANSPARENT : 0); pathA = p; }
+                    else X.lvlB[at] = f4{surf.x, surf.y, surf.z, i2f(FLAG_HIT | (transparent ? FLAG_TRANSPARENT : 0))};
                     if (X.heap) X.lvlAlpha[at] = sr[3].w;   // triangle.color.W (RT:699)
                 }
                 if (emitNext) {
@@ -1021,11 +1106,16 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_shade(SceneView S, ShadeView V
                     }
                 }
             }
+            int lp = 0;   // END: the place of a listed path
             if (!emitNext) {
+                if constexpr (END) { terminal = finished; lp = block_append(X.end.cnt + END_LISTED, hit && !terminal, ldsCounts); }
             } else if (!X.heap && X.ae) {   // chain of reflections, answered at emission: a reflection the whole mesh faces away from ends its path here
                 const bool emit = hit && !faces_away_single(S, w, rdir);
-                if (hit && !emit) X.lvlB[(size_t)(X.level + 1) * P + lvl_at(X.lvl, p)] = f4{0, 0, 0, i2f(FLAG_MISS)};   // what part A of the next step writes for a miss (RT:729-733)
-                const int pos = block_append(X.nextCnt, emit, ldsCounts);
+                if constexpr (END) terminal = finished && !emit;
+                if (hit && !emit && !(END && terminal)) X.lvlB[(size_t)(X.level + 1) * P + lvl_at(X.lvl, p)] = f4{0, 0, 0, i2f(FLAG_MISS)};   // what part A of the next step writes for a miss (RT:729-733)
+                int pos;
+                if constexpr (END) block_append2(X.nextCnt, emit, X.end.cnt + END_LISTED, hit && !terminal, ldsCounts, pos, lp);   // (the list shares the reflections' round of barriers)
+                else pos = block_append(X.nextCnt, emit, ldsCounts);
                 const bool heavy = emit && X.heavy.list && pos < X.nextCap && long_ray(S, X.heavy, p, w, rdir);
                 if (emit && pos < X.nextCap) {   // (reflections emitted <= rays of this generation <= cap: a guard, not a code path)
                     store_ray(X.nextRays + pos, w, rdir, mesh, heavy ? (tri ^ HEAVY_BIT) : tri);   // origin = result.triangle (RT:559)
@@ -1061,11 +1151,22 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_shade(SceneView S, ShadeView V
                     X.nextNode[slot2] = 2 * node + 2; X.nextRef[slot2] = n2;
                 }
             }
+            if constexpr (END) {   // a hit that goes on, or waits for shadow answers: its lvlB record, and its path into the compose list
+                const bool listed = hit && !terminal;
+                if (listed) {
+                    X.lvlB[at] = f4{surfA.x, surfA.y, surfA.z, i2f(flagA)};
+                    if (lp < X.end.listCap) X.end.list[lp] = pathA;   // (listed <= hits <= live rays <= listCap: a guard, not a code path)
+                }
+            }
         }
         if constexpr (FIN) {
             if (sum) {
                 const v3 lightResult = shade_light_sum(V, X, fromSlot, s, w, normal);
-                X.lvlA[at] = f4{lightResult.x, lightResult.y, lightResult.z, refl};
+                if (END && terminal) {   // what k_compose forms for such a path: a miss below returns black (RT:732), or nothing is below (RT:708-727)
+                    const v3 cv = emitNext ? compose_step(pack_color(mk(0, 0, 0)), surfA, refl, lightResult) : compose_last(lightResult, surfA);
+                    sample_color_out(X.end.sampleColor, nullptr, pathA, pack_color(cv), cv);
+                    nEnded++;
+                } else X.lvlA[at] = f4{lightResult.x, lightResult.y, lightResult.z, refl};
             }
         }
     }
@@ -1079,13 +1180,15 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_shade(SceneView S, ShadeView V
             if (lane == 0 && total) atomicAdd(X.finishCnt, total);
         }
     }
+    if constexpr (END) block_count(X.end.cnt + END_BY_SHADE, nEnded, ldsCounts);
 }
 void launch_shade(const SceneView &S, const ShadeView &V, const ShadeArgs &X, hipStream_t st, int blocks, int threads) {
     if (threads != 256) threads = APPEND_BLOCK;   // 256-thread blocks spread a small generation over the CUs (block_append takes any block of whole waves)
     const int cap = threads == 256 ? 4096 : 1024;
     const dim3 grid(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-    if (X.finish) hipLaunchKernelGGL(k_shade<true>, grid, dim3(threads), 0, st, S, V, X);
-    else hipLaunchKernelGGL(k_shade<false>, grid, dim3(threads), 0, st, S, V, X);
+    if (X.finish && X.end.on) hipLaunchKernelGGL((k_shade<true, true>), grid, dim3(threads), 0, st, S, V, X);
+    else if (X.finish) hipLaunchKernelGGL((k_shade<true, false>), grid, dim3(threads), 0, st, S, V, X);
+    else hipLaunchKernelGGL((k_shade<false, false>), grid, dim3(threads), 0, st, S, V, X);
 }
 
 // Frame epilogue (kernels.h FrameEpilogue): every kernel that counts rays has finished -- hand the counters to the host, clear them
@@ -1128,9 +1231,21 @@ __device__ __forceinline__ void fold_stamps(const StampFold &F) {
 }
 
 // The return path of the CastRay recursion: deepest generation first, one RGBA8 quantisation per level.
+// LIST (kernels.h EndArgs): the paths that did not end at generation 0 are RA.list[0 .. *RA.listCnt) -- every one has its records --, the others have their
+// colours already.  The count is NOT one of the words the epilogue clears: the blocks of a grid start at different times, and a late one would read the
+// cleared word.
+template <bool LIST>
 __global__ __launch_bounds__(256) void k_compose(const f4 *lvlA, const f4 *lvlB, int countHost, int P, int maxReflections, uint32_t *sampleColor, float *sampleF32,
                                                  ResolveArgs RA) {
-    const int count = pass_paths(RA.g, countHost);   // (read before the epilogue below may clear the word it comes from)
+    int count = 0;
+    if constexpr (LIST) {
+        const int listed = RA.endCnt[END_LISTED];   // (nobody writes the word while this kernel runs: the next frame's k_raygen clears it)
+        if (blockIdx.x == 0 && threadIdx.x == 0 && RA.hostCnt) {   // behind the counters the epilogue hands over; its fence covers these words too
+            RA.hostCnt[RA.cntWords + END_LISTED] = listed;
+            for (int i = END_BY_RAYGEN; i <= END_BY_SHADE; i++) { RA.hostCnt[RA.cntWords + i] = RA.endCnt[i]; RA.endCnt[i] = 0; }   // (their writers ran in earlier kernels; block 0 is their only reader)
+        }
+        count = listed < RA.listCap ? listed : RA.listCap;
+    } else count = pass_paths(RA.g, countHost);   // (read before the epilogue below may clear the word it comes from)
     {
         FrameEpilogue E;
         E.cntSrc = RA.cntSrc; E.hostCnt = RA.hostCnt; E.cntWords = RA.cntWords; E.zeroWords = RA.zeroWords; E.zeroFrom = RA.zeroFrom;
@@ -1138,11 +1253,12 @@ __global__ __launch_bounds__(256) void k_compose(const f4 *lvlA, const f4 *lvlB,
     }
     fold_stamps(RA.stamps);
     const int sshift = RA.g.samples == 16 ? 4 : (RA.g.samples == 4 ? 2 : 0);
-    for (int p = (int)(blockIdx.x * blockDim.x + threadIdx.x); p < count; p += (int)(gridDim.x * blockDim.x)) {
+    for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < count; i += (int)(gridDim.x * blockDim.x)) {
+        const int p = LIST ? RA.list[i] : i;
         int kd = 0;
         int flag = FLAG_MISS;
         bool culled = false;
-        if (RA.g.cullSkipsRecord && RA.g.quadLevel <= 0) {   // k_raygen left no record for pixels that cannot reach the root box
+        if (!LIST && RA.g.cullSkipsRecord && RA.g.quadLevel <= 0) {   // k_raygen left no record for pixels that cannot reach the root box
             int cx, cy;
             if (path_pixel(RA.g, (RA.pixelBase + p) >> sshift, cx, cy))
                 culled = cx < RA.g.cullX0 || cx > RA.g.cullX1 || cy < RA.g.cullY0 || cy > RA.g.cullY1;
@@ -1159,28 +1275,15 @@ __global__ __launch_bounds__(256) void k_compose(const f4 *lvlA, const f4 *lvlB,
         if (!(flag & FLAG_HIT)) col = pack_color(mk(0, 0, 0));   // RT:732
         else {   // RT:708-727: generation MaxReflections has no reflection term
             f4 a = lvlA[(size_t)kd * P + lp], b = lvlB[(size_t)kd * P + lp];
-            cv = mul(mk(a.x, a.y, a.z), mk(b.x, b.y, b.z));
+            cv = compose_last(mk(a.x, a.y, a.z), mk(b.x, b.y, b.z));
             col = pack_color(cv);
         }
         for (int k = kd - 1; k >= 0; k--) {   // RT:584 + RT:705
             f4 a = lvlA[(size_t)k * P + lp], b = lvlB[(size_t)k * P + lp];
-            cv = mul(lerp(unpack_color(col), mk(b.x, b.y, b.z), 1.0f - a.w), mk(a.x, a.y, a.z));
+            cv = compose_step(col, mk(b.x, b.y, b.z), a.w, mk(a.x, a.y, a.z));
             col = pack_color(cv);
         }
-        if (RA.fused) {   // one sample per pixel: write the framebuffer directly (RT:425), no sample buffer round trip
-            long long pix = RA.pixelBase + p;
-            int x, y;
-            bool ok = path_pixel(RA.g, pix, x, y);
-            if (RA.g.shardCount > 1) RA.out[pix] = ok ? col : 0u;
-            else if (ok) {
-                size_t o = (size_t)y * RA.g.width + x;
-                RA.out[o] = col;
-                if (RA.outF32) { RA.outF32[3 * o] = cv.x; RA.outF32[3 * o + 1] = cv.y; RA.outF32[3 * o + 2] = cv.z; }
-            }
-            continue;
-        }
-        sampleColor[p] = col;
-        if (sampleF32) { sampleF32[3 * (size_t)p] = cv.x; sampleF32[3 * (size_t)p + 1] = cv.y; sampleF32[3 * (size_t)p + 2] = cv.z; }
+        path_color_out(RA.g, RA.fused, RA.pixelBase, RA.out, RA.outF32, sampleColor, sampleF32, p, col, cv);
     }
 }
 // The same return path over the binary ray tree of a scene with Transparent materials (RT:586-702): node i has
@@ -1246,11 +1349,13 @@ void launch_compose_tree(const f4 *lvlA, const f4 *lvlB, const float *lvlAlpha, 
                        stamps, epilogue);
 }
 void launch_compose(const f4 *lvlA, const f4 *lvlB, int count, int P, int maxReflections, uint32_t *sampleColor, float *sampleF32,
-                    const ResolveArgs &RA, hipStream_t st, hipEvent_t stopEvent) {
-    int blocks = (count + 255) / 256;
+                    const ResolveArgs &RA, hipStream_t st, hipEvent_t stopEvent, int blocksHint) {
+    int blocks = blocksHint > 0 ? blocksHint : (count + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipExtLaunchKernelGGL(k_compose, dim3(blocks < 1 ? 1 : blocks), dim3(256), 0, st, nullptr, stopEvent, 0, lvlA, lvlB, count, P, maxReflections,
-                          sampleColor, sampleF32, RA);
+    if (RA.list) hipExtLaunchKernelGGL(k_compose<true>, dim3(blocks < 1 ? 1 : blocks), dim3(256), 0, st, nullptr, stopEvent, 0, lvlA, lvlB, count, P, maxReflections,
+                                       sampleColor, sampleF32, RA);
+    else hipExtLaunchKernelGGL(k_compose<false>, dim3(blocks < 1 ? 1 : blocks), dim3(256), 0, st, nullptr, stopEvent, 0, lvlA, lvlB, count, P, maxReflections,
+                               sampleColor, sampleF32, RA);
 }
 
 // Supersample averaging (RT:309: mean of four quantised colours, re-quantised, twice for 16 samples) and the

@@ -45,6 +45,7 @@ struct Settings {
     bool packetMerge = true;   // the closest-hit and the shadow packets of a step share one launch (XRT_PK_MERGE=0: two launches, as round 2)
     bool answerAtEmission = true;   // XRT_AE=0: k_shade emits every ray (kernels.h ShadeArgs::ae off)
     bool finishInPartA = true;      // XRT_AE_FINISH=0: a hit whose shadow rays were all answered at emission still takes a slot and waits for part B (kernels.h ShadeArgs::finish off)
+    bool endEarly = true;           // XRT_END_EARLY=0: every generation-0 path leaves its records and k_compose colours it (kernels.h EndArgs off)
     int packetPrefetch = -1;   // XRT_PK_PREFETCH: -1 launches of fewer than packetPrefetchBelow packets per resident wave prefetch (kernels.h PacketArgs::prefetch), 0 never, 1 always
     int packetPrefetchBelow = 12;
     bool packetBundle = true;  // XRT_PK_BUNDLE=0: no bundle prefilter (kernels.h PacketArgs::bundle)
@@ -132,6 +133,7 @@ inline Settings read_settings() {
     env_flag("XRT_PK_MERGE", c.packetMerge);
     env_flag("XRT_AE", c.answerAtEmission);
     env_flag("XRT_AE_FINISH", c.finishInPartA);
+    env_flag("XRT_END_EARLY", c.endEarly);
     env_int("XRT_PK_PREFETCH", c.packetPrefetch, -1, 1);
     env_int("XRT_PK_PREFETCH_BELOW", c.packetPrefetchBelow, 0, 100000);
     env_flag("XRT_PK_BUNDLE", c.packetBundle);

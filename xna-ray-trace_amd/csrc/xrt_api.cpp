@@ -246,6 +246,8 @@ struct xrt_scene {
     // launches of the next frame of the same geometry are sized for four times that instead of for the whole chip -- a generation
     // of a few thousand rays costs its kernels' launch floor (5-6 us each with full grids, C2: 0.119 -> 0.11 ms).  Sizing only.
     long long genKey = -1, genRays[68], genShade[68];
+    long long genCompose = -1;   // ... and the length of its compose list (kernels.h EndArgs; -1: the frame had none)
+    unsigned long long endCounts[3] = {0, 0, 0};   // xrt_debug_end_counts: the last finished frame's paths coloured by k_raygen, by k_shade, and on the compose list
     int lvlCheckedTilesX = 0; long long lvlCheckedTiles = 0;   // (LvlMap::inv verified for this frame geometry)
     unsigned splitSerial = 0;
     std::map<int, std::pair<DevBuf<unsigned>, DevBuf<unsigned>>> apiSplit;   // seam 1 (testing aid, XRT_PACKET & 8): an arena per stream
@@ -276,6 +278,7 @@ struct xrt_scene {
         DevBuf<xrt_ray> rays0, rays1, shadowRays;
         DevBuf<xrt_hit> hits, shadowHits;
         DevBuf<int> path0, path1, index0, heavyList, cnts;
+        DevBuf<int> composeList;                // kernels.h EndArgs: [0 .. END_WORDS) the count words, [16 ..] the paths k_compose has to walk
         DevBuf<int> node0, node1, heapFlag;     // ray-tree frames: heap node of every ray; heapFlag[0]: a generation overflowed its buffers
         DevBuf<float> ref0, ref1, lvlAlpha;     // ... refraction index of the medium a ray travels in; alpha per level record
         DevBuf<int> hitFlags0, shadowFlags;   // hit / miss word per ray of hits, shadowHits (a miss has no record)
@@ -303,7 +306,7 @@ struct xrt_scene {
         hipStream_t lastStream = nullptr;       // the stream the context's last frame ran on
         void release() {
             rays0.release(); rays1.release(); shadowRays.release(); hits.release(); shadowHits.release();
-            path0.release(); path1.release(); index0.release(); heavyList.release(); cnts.release(); stamps.release(); hitFlags0.release(); shadowFlags.release(); shadowOut.release(); shadowFlags1.release();
+            path0.release(); path1.release(); index0.release(); heavyList.release(); cnts.release(); composeList.release(); stamps.release(); hitFlags0.release(); shadowFlags.release(); shadowOut.release(); shadowFlags1.release();
             node0.release(); node1.release(); heapFlag.release(); ref0.release(); ref1.release(); lvlAlpha.release(); slot0.release(); slot1.release(); slotNode0.release(); slotNode1.release();
             lvlA.release(); lvlB.release(); sampleColor.release(); sampleF32.release(); lights.release(); splitItems.release(); splitRecs.release(); splitCost.release(); splitCostStride = 0;
             for (auto &l : levels) { l.color.release(); l.childBase.release(); l.childMask.release(); l.cx.release(); l.cy.release(); }
@@ -345,6 +348,7 @@ struct xrt_scene {
         // deferred accounting
         int tallyChunks = 0, cntStride = 0, R = 0, nL = 0;
         bool ae = false;             // ShadeArgs::ae: rays answered at emission are not in the ray lists
+        bool endEarly = false;       // kernels.h EndArgs: generation-0 paths were coloured where they ended; its END_WORDS counts are pinned[cntStride ..]
         unsigned long long answered = 0;   // ... their number (frame_finish)
         bool collect = false;
         unsigned long long shaded = 0, closestDeep = 0, livePaths = 0, live0 = 0, validPixels = 0;
@@ -804,7 +808,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     if ((unsigned long long)rayCap * (unsigned long long)(nL > 0 ? nL : 1) > (1ull << 30)) return fail(XRT_E_UNSUPPORTED, "frame too large: %zu rays x %d lights per generation", rayCap, nL);
     const size_t shadowCap = rayCap;   // hits of one generation (each emits nL shadow rays)
     const bool wantF32 = d_outF32 != nullptr && !adaptive && g.samples == 1;
-    const bool fuseResolve = !adaptive && !heap && !batch && g.samples == 1;   // k_compose writes the framebuffer itself
+    bool fuseResolve = !adaptive && !heap && !batch && g.samples == 1;   // k_compose writes the framebuffer itself (not where paths end early, below)
     // buffers
     if ((rc = W.rays0.ensure(rayCap)) || (rc = W.rays1.ensure(rayCap)) || (rc = W.hits.ensure(rayCap)) || (rc = W.path0.ensure(rayCap)) ||
         (rc = W.path1.ensure(rayCap)) || (rc = W.hitFlags0.ensure(rayCap)) ||
@@ -856,6 +860,21 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     // k_paths_capture reads every hit's position from its slot record --, and the lights have to fit part A's bit mask.
     const bool finishA = ae && !heap && !(batch && batch->paths) && nL <= 32 && s->cfg.finishInPartA;
     if (ae && ((rc = W.shadowOut.ensure(rayCap * (nL > 0 ? nL : 1))) || (rc = W.shadowFlags1.ensure(rayCap * (nL > 0 ? nL : 1))))) return rc;
+    // End early (kernels.h EndArgs): the frames that finish hits in part A, when they put nothing but kernels on the stream (their counters come back with
+    // k_compose) and want no float colours -- every path that ends at generation 0 is coloured where it ends, k_compose walks a list of the others.
+    const bool endEarly = finishA && fast && !batch && !d_outF32 && s->cfg.endEarly;
+    if (endEarly) {
+        // The early writers go through the context's sample buffer and k_resolve copies it out: d_out stays what it was until the frame's last kernel,
+        // as in every other frame (a caller may have queued work of its own on it that is still running when k_raygen starts).
+        fuseResolve = false;
+        const int *before = W.composeList.p;
+        if ((rc = W.composeList.ensure(rayCap + 16))) return rc;
+        if (W.composeList.p != before) {   // the count words (kernels.h EndArgs::cnt) start at zero; a new allocation is rare, and the frame's stream is not chosen yet
+            HIPCHECK(hipMemsetAsync(W.composeList.p, 0, 16 * sizeof(int), s->stream));
+            HIPCHECK(hipStreamSynchronize(s->stream));
+        }
+    }
+    F.endEarly = endEarly;
     F.fast = fast;
     F.heap = heap;
     F.redone = false;
@@ -1015,8 +1034,9 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     bool startEvent = fast;   // the frame's first raygen launch carries its start event (fast frames put nothing but kernels on the stream)
     // (sampleOut: where the chunk's quantised colours go -- the context's sample buffer, or a quadrant level's colour array; epi: the
     // frame epilogue this chunk's compose kernel carries, if any)
+    // (listCnt: the chunk ends generation-0 paths early, kernels.h EndArgs -- the count word of its compose list)
     auto enqueue_chunk = [&](const RayGenParams &gp, int *cnt, unsigned *q, int Pc, long long pathBase, uint32_t *sampleOut = nullptr,
-                             const FrameEpilogue *epi = nullptr) -> int {
+                             const FrameEpilogue *epi = nullptr, int *listCnt = nullptr) -> int {
         int *scnt = cnt + (R + 2), *hcnt = cnt + 2 * (R + 2), *acnt = cnt + 3 * (R + 2);   // (acnt[k]: shadow rays of generation k that were really emitted, ShadeArgs::ae)
         int *fcnt = cnt + 4 * (R + 2);                                                      // (fcnt[k]: hits of generation k finished in part A, ShadeArgs::finish)
         const int chunkRow0 = F.stampRows;
@@ -1048,7 +1068,12 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         // cnt[0] counts the primary rays that reach the scene's root box; index0 lists them
         RayGenParams gb = gp;
         if (gp.batch && heap) gb.batchRef = refOf[0];
-        { Range r("xrt raygen"); launch_raygen(gb, S, rays[0], W.lvlB.p, W.index0.p, cnt, Pc, pathBase, heavy_for(0), st, startEvent ? e0 : nullptr, (int)rayCap); startEvent = false; }
+        EndArgs endArgs;
+        if (listCnt) {
+            endArgs.on = 1; endArgs.sampleColor = sampleOut ? sampleOut : W.sampleColor.p;
+            endArgs.list = W.composeList.p + 16; endArgs.cnt = listCnt; endArgs.listCap = (int)rayCap;
+        }
+        { Range r("xrt raygen"); launch_raygen(gb, S, rays[0], W.lvlB.p, W.index0.p, cnt, Pc, pathBase, heavy_for(0), st, startEvent ? e0 : nullptr, (int)rayCap, &endArgs); startEvent = false; }
         // (one buffer serves every generation: the closest-hit answers of launch #k are read by part A of k_shade #k alone -- part B works from the
         // slot records -- and launch #k+1 starts after it on the frame's stream)
         xrt_hit *hitsOf[2] = {W.hits.p, W.hits.p};
@@ -1154,6 +1179,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
             X.nextCnt = cnt + k + 1; X.nextCap = (int)rayCap;
             if (ae) { X.ae = 1; X.shadowCnt = acnt + k; X.shadowOut = W.shadowOut.p; X.shadowFlagsOut = shadowFlagsOf[k & 1]; }
             if (finishA) { X.finish = 1; X.finishCnt = fcnt + k; }
+            if (listCnt && k == 0) X.end = endArgs;
             X.slotPrev = slotOf[prv]; X.slotNodePrev = heap ? slotNodeOf[prv] : nullptr; X.scntPrev = k >= 1 ? scnt + (k - 1) : nullptr; X.shadowHits = W.shadowHits.p;
             X.lvlA = W.lvlA.p; X.lvlB = W.lvlB.p; X.lvlAlpha = heap ? W.lvlAlpha.p : nullptr;
             if (k < R) X.heavy = heavy_for(k + 1);
@@ -1189,8 +1215,13 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
             RA.stamps = fold;
             if (epi) { RA.cntSrc = epi->cntSrc; RA.hostCnt = epi->hostCnt; RA.cntWords = epi->cntWords; RA.zeroWords = epi->zeroWords; RA.zeroFrom = epi->zeroFrom; }
             else if (fast && !adaptive) { RA.cntSrc = cnt; RA.hostCnt = F.pinnedDev; RA.cntWords = cntStride; RA.zeroWords = cntStride + qStride; }
+            int blocks = 0;
+            if (listCnt) {
+                RA.list = W.composeList.p + 16; RA.endCnt = listCnt; RA.listCap = (int)rayCap;
+                if (hinted && s->genCompose >= 0) blocks = (int)((4 * s->genCompose + 4096 + 255) / 256);
+            }
             launch_compose(W.lvlA.p, W.lvlB.p, Pc, (int)lvlStride, R, colorOut, fuseResolve ? nullptr : f32Out, RA, st,
-                           (fast && fuseResolve) ? e1 : nullptr);
+                           (fast && fuseResolve) ? e1 : nullptr, blocks);
         }
         return XRT_OK;
     };
@@ -1270,7 +1301,8 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         for (int c = 0; c < nChunks; c++) {
             const long long localBase = (long long)c * chunkPaths, pathBase = partStart + localBase;
             const int Pc = (int)((total - localBase) < chunkPaths ? (total - localBase) : chunkPaths);
-            if ((rc2 = enqueue_chunk(gp, W.cnts.p + (size_t)c * cntStride, queuesBase + (size_t)c * qStride, Pc, pathBase))) return rc2;
+            if ((rc2 = enqueue_chunk(gp, W.cnts.p + (size_t)c * cntStride, queuesBase + (size_t)c * qStride, Pc, pathBase, nullptr, nullptr,
+                                     endEarly ? W.composeList.p : nullptr))) return rc2;
             if (!fuseResolve && (rc2 = post(Pc, pathBase))) return rc2;
             if (nChunks > 1) {   // frames of more than MAX_CHUNK_PATHS rays: xrt_progress follows the chunks
                 HIPCHECK(hipStreamSynchronize(st));
@@ -1501,6 +1533,8 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
             const int *hc = (const int *)F.pinned + F.cntBase + (size_t)c * F.cntStride;
             if (hc[0] < 0 || (size_t)hc[0] > F.liveCap)
                 return fail(XRT_E_INTERNAL, "%d primary rays reach the scene but the frame's ray arrays were sized for %zu (screen rectangle of the root box)", hc[0], F.liveCap);
+            if (F.endEarly && (hc[F.cntStride] < 0 || hc[F.cntStride] > hc[0]))
+                return fail(XRT_E_INTERNAL, "%d paths on the compose list of a frame with %d live primary rays", hc[F.cntStride], hc[0]);
             for (int k = 0; k <= R; k++) {
                 F.shaded += (unsigned long long)gen_hits(hc, R, k);
                 if (k > 0) F.closestDeep += (unsigned long long)(F.heap ? hc[k] : gen_hits(hc, R, k - 1));   // reflection chain: one ray per parent hit
@@ -1523,6 +1557,7 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
         // (adaptive frames in flight put the level-count words in front of the per-pass counters and have no framePaths key: no hints from them)
         if (F.fast && F.tallyChunks == 1 && !F.adaptiveFast) {   // sizes of this frame's generations: grid hints for the next one (sizing only)
             const int *hc = (const int *)F.pinned + F.cntBase;
+            const bool same0 = s->genKey == F.framePaths * 64 + F.nL;
             for (int k = 0; k <= R + 1 && k < 68; k++) {
                 const long long closest = (k == 0 || ((F.heap || F.ae) && k <= R)) ? hc[k] : (k <= R ? gen_hits(hc, R, k - 1) : 0), shaded = k >= 1 ? gen_hits(hc, R, k - 1) : 0;
                 // (a hint shrinks by an eighth per frame at most: a camera that looks away for a frame, or alternates between two views,
@@ -1534,6 +1569,10 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
                 s->genShade[k] = work > keepS ? work : keepS;
             }
             for (int k = R + 2; k < 68; k++) s->genRays[k] = s->genShade[k] = -1;
+            {
+                const long long listed = F.endEarly ? hc[F.cntStride] : -1, keep = same0 && s->genCompose > 0 ? s->genCompose - s->genCompose / 8 : 0;
+                s->genCompose = listed < 0 ? -1 : (listed > keep ? listed : keep);
+            }
             s->genKey = F.framePaths * 64 + F.nL;
         }
         if (F.fast && s->costMap.p && !F.adaptiveFast) {   // steer the "long ray" thresholds towards 2-6 % of each generation's rays
@@ -1549,6 +1588,10 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
         }
         F.tallyChunks = 0;
     }
+    if (F.endEarly) {   // (xrt_debug_end_counts: a frame that engaged has one chunk and its counters in `pinned`)
+        const int *hc = (const int *)F.pinned + F.cntBase;
+        s->endCounts[0] = (unsigned long long)hc[F.cntStride + END_BY_RAYGEN]; s->endCounts[1] = (unsigned long long)hc[F.cntStride + END_BY_SHADE]; s->endCounts[2] = (unsigned long long)hc[F.cntStride + END_LISTED];
+    } else s->endCounts[0] = s->endCounts[1] = s->endCounts[2] = 0;
     {
         float frameMs = 0;
         if (hipEventElapsedTime(&frameMs, F.events[0], F.events[1]) == hipSuccess) s->lastFrameMs = frameMs;
@@ -2671,6 +2714,16 @@ int xrt_rccl_probe(void) {
 }
 
 float xrt_progress(const xrt_scene *scene) { return scene ? scene->progress.load() : 0.0f; }
+
+int xrt_debug_end_counts(xrt_scene *scene, uint64_t out[3]) {
+    return guarded("xrt_debug_end_counts", [&]() -> int {
+        int rc = need_device(scene, "xrt_debug_end_counts");
+        if (rc != XRT_OK) return rc;
+        if (!out) return fail(XRT_E_INVALID_ARG, "xrt_debug_end_counts: null argument");
+        for (int i = 0; i < 3; i++) out[i] = scene->endCounts[i];
+        return XRT_OK;
+    });
+}
 
 int xrt_split_stats(xrt_scene *scene, uint64_t out[4], int32_t reset) {
     return guarded("xrt_split_stats", [&]() -> int {
