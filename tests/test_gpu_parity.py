@@ -505,7 +505,7 @@ def test_default_game_scene_as_the_reference_renders_it(xrt, orc):
 
 def test_work_buffers_under_guards(xrt, orc, monkeypatch):
     """XRT_GUARD=1: every device buffer of scenes created from now on ends in 4 KB of a known pattern that the end of every frame and
-    batched query checks (xrt_api.cpp guards_check) -- a kernel that writes past an array it was given is XRT_E_INTERNAL here instead
+    batched query checks (csrc/device_res.h guards_check) -- a kernel that writes past an array it was given is XRT_E_INTERNAL here instead
     of a corrupted neighbour or a process abort.  The frame modes whose arrays are sized tightly: generation-0 arrays sized by the root
     box's screen rectangle (a soup seen from close by: the case that aborted once during round 3, a camera inside the root box, a scene
     in the image's corner), 16 sub-rays, adaptive levels, ray trees, many lights, tile shards, two frames in flight."""
@@ -860,7 +860,7 @@ def test_launch_timing_mixed_stamps_and_events(xrt, monkeypatch):
 
 def test_grid_hints_follow_a_camera_that_looks_away(xrt):
     """The launches of a frame's later generations are sized for four times the generation sizes of the last finished frame
-    (xrt_api.cpp genRays / genShade).  A camera that looks away from the scene (every generation empty) and back again makes those
+    (csrc/scene_state.h genRays / genShade, read by frame_begin in xrt_api.cpp).  A camera that looks away from the scene (every generation empty) and back again makes those
     hints as wrong as they can be; sizing never touches a result: the frames equal the ones rendered without hints."""
     import torch
     spec = xrt.configs.config("C3", 0.25)

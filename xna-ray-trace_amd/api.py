@@ -73,9 +73,12 @@ class _Scene:
         abi.check(abi.lib().xrt_scene_create(int(device), C.byref(self.handle)))
 
     def close(self):
+        """xrt_scene_destroy now; returns its code (XRT_OK for a scene already closed).  The handle is given up either way."""
+        rc = abi.XRT_OK
         if self.handle:
-            abi.lib().xrt_scene_destroy(self.handle)
+            rc = abi.lib().xrt_scene_destroy(self.handle)
             self.handle = C.c_void_p()
+        return rc
 
     def __del__(self):
         try:

@@ -3,445 +3,23 @@
 // uses the HIP runtime API); all arithmetic of the path runs in kernels.hip.
 #include <hip/hip_runtime.h>
 
-#include <dlfcn.h>
-
-#include <atomic>
-#include <condition_variable>
-#include <functional>
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <mutex>
-#include <thread>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/xrt.h"
-#include "kernels.h"
-#include "paths.h"
-#include "rccl_gather.h"
-#include "scene_host.h"
-#include "settings.h"
+#include "device_res.h"    // the owners of device resources, fail / HIPCHECK, the XRT_GUARD registry, roctx ranges
 
 using namespace xrt;
 
-namespace {
-
-thread_local std::string g_err = "";
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-#define HIPCHECK(expr)                                                                                         \
-    do {                                                                                                       \
-        hipError_t e_ = (expr);                                                                                \
-        if (e_ != hipSuccess)                                                                                  \
-            return fail(e_ == hipErrorOutOfMemory ? XRT_E_OOM : XRT_E_HIP, "%s failed: %s (%s:%d)", #expr,     \
-                        hipGetErrorString(e_), __FILE__, __LINE__);                                            \
-    } while (0)
-
-// roctx ranges around the stages of a frame, for `rocprofv3 --marker-trace --kernel-trace`: XRT_ROCTX=1 loads the
-// marker library on first use (no load-time dependency, nothing is called otherwise).  The ranges bracket the ENQUEUE of a
-// stage on the host; the kernels they enqueue carry the same names in the kernel trace.
-struct Roctx {
-    int (*push)(const char *) = nullptr;
-    int (*pop)() = nullptr;
-    bool on = false;
-    Roctx() {
-        if (!getenv("XRT_ROCTX")) return;
-        for (const char *n : {"librocprofiler-sdk-roctx.so", "librocprofiler-sdk-roctx.so.1", "libroctx64.so", "libroctx64.so.4"}) {
-            if (void *h = dlopen(n, RTLD_NOW | RTLD_GLOBAL)) {
-                push = reinterpret_cast<int (*)(const char *)>(dlsym(h, "roctxRangePushA"));
-                pop = reinterpret_cast<int (*)()>(dlsym(h, "roctxRangePop"));
-                if (push && pop) { on = true; return; }
-            }
-        }
-    }
-};
-Roctx &roctx() { static Roctx r; return r; }
-struct Range {   // RAII: a named range for the enclosing scope
-    bool on;
-    explicit Range(const char *fmt, int k = 0) : on(roctx().on) {
-        if (!on) return;
-        char buf[64];
-        snprintf(buf, sizeof(buf), fmt, k);
-        roctx().push(buf);
-    }
-    ~Range() { if (on) roctx().pop(); }
-};
-
-// No C++ exception may cross the C boundary (a P/Invoke, ctypes or C host would be terminated): the entry points that
-// allocate host memory from caller-given sizes run inside this guard.
-template <class F>
-int guarded(const char *fn, F &&f) {
-    try { return f(); }
-    catch (const std::bad_alloc &) { return fail(XRT_E_OOM, "%s: out of host memory", fn); }
-    catch (const std::exception &e) { return fail(XRT_E_INVALID_ARG, "%s: %s", fn, e.what()); }
-    catch (...) { return fail(XRT_E_INTERNAL, "%s: unknown exception", fn); }
-}
-
-// XRT_GUARD=1 (read by xrt_scene_create / xrt_scene_load; a test and debugging mode): every device buffer allocated from then on gets
-// GUARD_BYTES of a known pattern behind its last element, and the end of every frame and of every batched query checks that the pattern
-// is intact -- a kernel that writes past an array it was given is then XRT_E_INTERNAL naming the buffer's size, not a corrupted
-// neighbour or a GPU fault somewhere else.  (Round 3 sized the generation-0 arrays by the root box's screen rectangle while one of them
-// was still indexed by path: a process abort in the GPU suite that the next edit hid.  tests/test_gpu_parity.py runs the frame modes
-// under the guards.)
-constexpr size_t GUARD_BYTES = 4096;
-constexpr unsigned char GUARD_PATTERN = 0xA5;
-std::atomic<int> g_guardMode{0};
-struct GuardRegistry {
-    std::mutex m;
-    std::unordered_map<void *, size_t> bytesOf;   // buffer -> payload bytes (the guard follows)
-} g_guards;
-inline int guard_alloc(void **p, size_t bytes) {
-    const bool on = g_guardMode.load() != 0;
-    HIPCHECK(hipMalloc(p, bytes + (on ? GUARD_BYTES : 0)));
-    if (on) {
-        HIPCHECK(hipMemset((char *)*p + bytes, GUARD_PATTERN, GUARD_BYTES));
-        std::lock_guard<std::mutex> lk(g_guards.m);
-        g_guards.bytesOf[*p] = bytes;
-    }
-    return XRT_OK;
-}
-inline void guard_free(void *p) {
-    if (g_guardMode.load() != 0) { std::lock_guard<std::mutex> lk(g_guards.m); g_guards.bytesOf.erase(p); }
-    (void)hipFree(p);
-}
-// All guards of the process (buffers of every scene on the CURRENT device are readable; others are skipped on error).
-int guards_check(const char *where) {
-    if (g_guardMode.load() == 0) return XRT_OK;
-    if (hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); return XRT_OK; }
-    std::lock_guard<std::mutex> lk(g_guards.m);
-    std::vector<unsigned char> tail(GUARD_BYTES);
-    for (const auto &kv : g_guards.bytesOf) {
-        if (hipMemcpy(tail.data(), (const char *)kv.first + kv.second, GUARD_BYTES, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); continue; }
-        for (size_t i = 0; i < GUARD_BYTES; i++)
-            if (tail[i] != GUARD_PATTERN)
-                return fail(XRT_E_INTERNAL, "%s: a kernel wrote %zu bytes past the end of a device buffer of %zu bytes (XRT_GUARD)", where, i + 1, kv.second);
-    }
-    return XRT_OK;
-}
-
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;   // elements
-    int ensure(size_t n) {
-        if (n <= cap && p) return XRT_OK;
-        if (p) { guard_free(p); p = nullptr; cap = 0; }
-        if (n == 0) n = 1;
-        int rc = guard_alloc((void **)&p, n * sizeof(T));
-        if (rc != XRT_OK) { p = nullptr; return rc; }
-        cap = n;
-        return XRT_OK;
-    }
-    void release() { if (p) guard_free(p); p = nullptr; cap = 0; }
-};
-
-template <class T>
-int upload(DevBuf<T> &b, const std::vector<T> &v) {
-    int rc = b.ensure(v.size());
-    if (rc != XRT_OK) return rc;
-    if (!v.empty()) HIPCHECK(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return XRT_OK;
-}
-
-}  // namespace
-
-// One host thread per replica device (in-library multi-GPU, xrt_render_opts.n_gpus), created with the replica and parked on a
-// condition variable between frames: it has made its device current once and enqueues that device's share of every frame.
-// (Round 2 spawned and joined n-1 std::threads per frame: tens of microseconds of host time on a 0.75 ms frame.)
-struct RankWorker {
-    std::thread th;
-    std::mutex m;
-    std::condition_variable cv;
-    std::function<void()> job;
-    bool posted = false, finished = false, quit = false;
-    explicit RankWorker(int device) {
-        th = std::thread([this, device] {
-            (void)hipSetDevice(device);
-            std::unique_lock<std::mutex> lk(m);
-            for (;;) {
-                cv.wait(lk, [this] { return posted || quit; });
-                if (quit) return;
-                posted = false;
-                lk.unlock();
-                job();
-                lk.lock();
-                finished = true;
-                cv.notify_all();
-            }
-        });
-    }
-    void post(std::function<void()> f) {
-        { std::lock_guard<std::mutex> lk(m); job = std::move(f); finished = false; posted = true; }
-        cv.notify_all();
-    }
-    void wait() { std::unique_lock<std::mutex> lk(m); cv.wait(lk, [this] { return finished; }); }
-    ~RankWorker() {
-        { std::lock_guard<std::mutex> lk(m); quit = true; }
-        cv.notify_all();
-        if (th.joinable()) th.join();
-    }
-};
-
-struct xrt_scene {
-    int device = -1;   // -1: host-only scene (inspection of the built trees; every compute call fails)
-    HostScene hs;
-    const HostScene *host = &hs;   // what the frame code reads; a replica on another device points at its primary's
-    // HBM-resident scene
-    DevBuf<f4> blocks, refN, snodes, shade, leafNB, leafTB, scull, runTB, triTB;
-    DevBuf<float> refT, pblocks, lrec;
-    DevBuf<g3> refG;
-    DevBuf<int> childDfs, srefs, objMesh, runBase;
-    DevBuf<MeshRec> meshes;
-    DevBuf<ObjRec> objects;
-    DevBuf<MaterialRec> materials;
-    DevBuf<uint32_t> texels;
-    SceneView view{};
-    // Pose versions (xrt_scene_set_poses): a frame reads the ObjRecs and pre-cull records of ONE version, the one that was current at its
-    // begin (FrameCtx::pose).  Version 0 is `objects` / `scull`, versions 1 and 2 are made when a pose update must not overwrite a version
-    // an open ticket reads: with at most two tickets open one of the three is always free, so an update never waits for a frame.
-    struct PoseVer {
-        DevBuf<ObjRec> objects;   // (version 0: the scene's own `objects` / `scull`)
-        DevBuf<f4> scull;
-        hipEvent_t ready = nullptr;        // recorded behind the version's last write; null while it holds the build's records
-        unsigned long long serial = 0;     // which write it holds (a replica copies the primary's version when the serials differ)
-        std::vector<std::pair<hipStream_t, hipEvent_t>> readers;   // the last asynchronous seam-1 read on each stream (xrt_scene_intersect_device)
-    } pose[3];
-    int poseCur = 0;                       // the version new frames and seam-1 calls read
-    int slotPose[2] = {-1, -1};            // the version of the open ticket `slot`
-    unsigned long long poseSerial = 0;     // writes since the build
-    bool posesOnDevice = false;            // hs's poses are behind: the last update came from device arrays (xrt_scene_set_poses_device)
-    hipStream_t poseStream = nullptr;      // pose updates run here
-    hipEvent_t poseInput = nullptr;        // the caller's stream -> poseStream
-    DevBuf<int> scullPosStart, scullPos;   // HostScene scullPosStart / scullPos
-    DevBuf<float> wbbDev;                  // WorldBoundingBox of every body, 6 floats (kept by k_pose for the read-back)
-    DevBuf<float> poseIn;                  // the host form's arrays on the device: ids | world | inv | wbb
-    void *posePinned = nullptr;            // ... and their page-locked staging
-    size_t posePinnedBytes = 0;
-    hipEvent_t poseStaged = nullptr;       // the staging copy is done (the staging may be refilled)
-    bool resident = false;
-    int numCUs = 256;
-    int stackNeeded = 2;
-    int blocksPerCU = 1, blocksPerCUMesh = 1, blocksPerCUPacket = 1;
-    bool packetOk = false;   // the scene's rays can take the wave-packet kernel (one body, one mesh with a real octree)
-    Settings cfg;   // the environment switches (settings.h): set once by xrt_scene_create (a replica's by ensure_replicas)
-    // Knobs of k_intersect that scene_upload derives from the scene where cfg does not name them (refill threshold: see there)
-    int refillMin = 24;
-    int heavyShift = 3;        // listed long rays are dealt one in 2^n work items (0: 64 to a wave); scene_upload: 0 for two-level scenes; XRT_HEAVY_SHIFT
-    int firstBatch = 64;
-    // Sizes of the last finished single-chunk frame's generations (rays of traversal step k, work items of shade step k): the
-    // launches of the next frame of the same geometry are sized for four times that instead of for the whole chip -- a generation
-    // of a few thousand rays costs its kernels' launch floor (5-6 us each with full grids, C2: 0.119 -> 0.11 ms).  Sizing only.
-    long long genKey = -1, genRays[68], genShade[68];
-    long long genCompose = -1;   // ... and the length of its compose list (kernels.h EndArgs; -1: the frame had none)
-    unsigned long long endCounts[3] = {0, 0, 0};   // xrt_debug_end_counts: the last finished frame's paths coloured by k_raygen, by k_shade, and on the compose list
-    int lvlCheckedTilesX = 0; long long lvlCheckedTiles = 0;   // (LvlMap::inv verified for this frame geometry)
-    unsigned splitSerial = 0;
-    std::map<int, std::pair<DevBuf<unsigned>, DevBuf<unsigned>>> apiSplit;   // seam 1 (testing aid, XRT_PACKET & 8): an arena per stream
-    int sceneMode = MODE_SCENE;   // MODE_SINGLE when the scene is one SceneObject with one Mesh
-    hipStream_t stream = nullptr;
-    // per-frame work buffers
-    DevBuf<xrt_ray> apiRays;
-    DevBuf<xrt_hit> apiHits;
-    DevBuf<xrt_ray> castRays;     // xrt_cast_rays: the host's rays and their colours
-    DevBuf<uint32_t> castRGBA;
-    DevBuf<float> castF32;
-    // xrt_cast_rays_paths (paths.hip): staging records of a chunk -- (hit position, tag) and (refraction direction, tag) per (node, path), allocated
-    // only when a paths call is made --, the work arrays of the ordering pass, and the host form's copies of the caller's arrays
-    DevBuf<f4> pathHit, pathDir;
-    DevBuf<int> pathLocal, pathBlockSum;
-    DevBuf<long long> pathBlockBase, pathStart;
-    DevBuf<xrt_path_vertex> pathVerts;
-    DevBuf<xrt_ray> pathBack;
-    unsigned pathEpoch = 0;            // number of the last attempt of a chunk (the tag of its records; 0 is "never written")
-    long long *pathPinned = nullptr;   // the batch's vertex count on its way to the host
-    DevBuf<unsigned> queues;
-    DevBuf<uint32_t> outRGBA;
-    DevBuf<float> outF32;
-    DevBuf<unsigned long long> counters;
-    // Work buffers of one frame in flight.  Two sets (FrameCtx) so that two frames on two streams can overlap: a launch
-    // of persistent waves leaves the machine half empty while its last rays finish, and the other frame's launches fill it.
-    struct WorkBufs {
-        DevBuf<xrt_ray> rays0, rays1, shadowRays;
-        DevBuf<xrt_hit> hits, shadowHits;
-        DevBuf<int> path0, path1, index0, heavyList, cnts;
-        DevBuf<int> composeList;                // kernels.h EndArgs: [0 .. END_WORDS) the count words, [16 ..] the paths k_compose has to walk
-        DevBuf<int> node0, node1, heapFlag;     // ray-tree frames: heap node of every ray; heapFlag[0]: a generation overflowed its buffers
-        DevBuf<float> ref0, ref1, lvlAlpha;     // ... refraction index of the medium a ray travels in; alpha per level record
-        DevBuf<int> hitFlags0, shadowFlags;   // hit / miss word per ray of hits, shadowHits (a miss has no record)
-        DevBuf<unsigned> splitCost;               // ... what every packet of every packet launch of the context's last plain frame cost (PacketArgs::splitCost)
-        size_t splitCostStride = 0;               // (packets a launch may have; a frame of another size starts the memory afresh)
-        DevBuf<unsigned> splitItems, splitRecs;   // split walks (kernels.h PacketArgs::splitItems): the arena of this context's packet launches (they run one after the other)
-        DevBuf<int> shadowOut;                // ShadeArgs::ae: where the answer of the i-th emitted shadow ray goes (slot * lights + light)
-        DevBuf<int> shadowFlags1;             // ShadeArgs::ae: part A of step k answers some shadow queries of generation k ITSELF while part B of the same launch still reads
-                                              // generation k-1's words: the generations alternate between shadowFlags and this
-        DevBuf<unsigned long long> stamps;      // device-clock stamps of the traversal launches (device_util.h), STAMP_STRIDE per launch
-        DevBuf<SlotRec> slot0, slot1;
-        DevBuf<int> slotNode0, slotNode1;   // ray-tree frames: the node of a slot's hit
-        DevBuf<f4> lvlA, lvlB;
-        DevBuf<uint32_t> sampleColor;
-        DevBuf<float> sampleF32;
-        DevBuf<LightRec> lights;
-        // adaptive supersampling in flight (RT:170-311 without host round trips): the quadrant levels' buffers belong to the frame context
-        struct Level { DevBuf<uint32_t> color; DevBuf<int> childBase, childMask; DevBuf<float> cx, cy; } levels[8];
-        bool levelWordsClean = false;           // the level-count words at the head of cnts are zero (k_resolve cleared them)
-        bool heapFlagClean = false;
-        bool cntsClean = false;                 // cnts is all zero (the previous frame's epilogue cleared what it counted)
-        std::vector<LightRec> lightsOnDevice;   // what `lights` holds
-        const void *lightsDevPtr = nullptr;
-        hipStream_t stream = nullptr;           // the context's own stream (used when the caller passes none)
-        hipStream_t lastStream = nullptr;       // the stream the context's last frame ran on
-        void release() {
-            rays0.release(); rays1.release(); shadowRays.release(); hits.release(); shadowHits.release();
-            path0.release(); path1.release(); index0.release(); heavyList.release(); cnts.release(); composeList.release(); stamps.release(); hitFlags0.release(); shadowFlags.release(); shadowOut.release(); shadowFlags1.release();
-            node0.release(); node1.release(); heapFlag.release(); ref0.release(); ref1.release(); lvlAlpha.release(); slot0.release(); slot1.release(); slotNode0.release(); slotNode1.release();
-            lvlA.release(); lvlB.release(); sampleColor.release(); sampleF32.release(); lights.release(); splitItems.release(); splitRecs.release(); splitCost.release(); splitCostStride = 0;
-            for (auto &l : levels) { l.color.release(); l.childBase.release(); l.childMask.release(); l.cx.release(); l.cy.release(); }
-            if (stream) (void)hipStreamDestroy(stream);
-            stream = nullptr;
-        }
-    };
-    // cost feedback (kernels.hip long_ray): per path and generation, what the ray cost in the last frames
-    DevBuf<unsigned> costMap;
-    size_t costMapPaths = 0;
-    unsigned epoch = 100;
-    int costT[66];            // per generation: rays that cost more than this are started first; steered in frame_finish
-    bool deepMeshes = false;  // some mesh has a real octree: rays can be long
-    float heavyPath = 0.0f;   // rays longer than this inside the root box are traced first (0: off; cfg.heavy)
-    DevBuf<unsigned long long> waveTimes;   // cfg.waveTimesPath
-    // Per-frame host state.  Two contexts so that the next frame can be enqueued while the previous one's counters
-    // and timings are still on their way back (xrt_render_device_begin / _end).
-    struct FrameCtx {
-        std::vector<hipEvent_t> events;
-        void *pinned = nullptr;      // host staging for the counter read-back
-        size_t pinnedBytes = 0;
-        std::vector<std::pair<size_t, size_t>> pairs;   // (start, stop) event indices of the k_intersect launches
-        size_t ev = 0;
-        hipEvent_t done = nullptr;   // recorded after the frame's last copy
-        std::vector<LightRec> hostLights;
-        int pose = 0;                // the pose version the frame reads (xrt_scene::pose)
-        bool pending = false;
-        bool fast = false;           // no copy / fill / event-record commands: k_compose hands the counters over, events ride on kernels
-        int *pinnedDev = nullptr;    // device view of `pinned`
-        long long framePaths = 0;    // paths of the frame (part) this context holds: key of the grid hints
-        int frameW = 0, frameH = 0;  // the frame's size in pixels
-        bool heap = false, redone = false;   // a ray-tree frame; ... that overflowed on the optimistic way and was rendered again
-        bool adaptiveFast = false;           // an adaptive frame enqueued without host round trips (level sizes stay on the device)
-        int cntBase = 0, levelCap = 0, quality = 0;   // words in front of the per-pass counters in `pinned`; quadrant capacity of a deeper level
-        xrt_camera redoCam; xrt_render_opts redoOpts; std::vector<xrt_light> redoLights;
-        uint32_t *redoOut = nullptr; float *redoOutF32 = nullptr; hipStream_t redoSt = nullptr;
-        int stampRows = 0;           // traversal launches of the frame that timed themselves (device_util.h)
-        unsigned long long *stampHost = nullptr, *stampHostDev = nullptr;   // their (start, end) clock pairs: mapped pinned memory and its device view
-        // deferred accounting
-        int tallyChunks = 0, cntStride = 0, R = 0, nL = 0;
-        bool ae = false;             // ShadeArgs::ae: rays answered at emission are not in the ray lists
-        bool endEarly = false;       // kernels.h EndArgs: generation-0 paths were coloured where they ended; its END_WORDS counts are pinned[cntStride ..]
-        unsigned long long answered = 0;   // ... their number (frame_finish)
-        bool collect = false;
-        unsigned long long shaded = 0, closestDeep = 0, livePaths = 0, live0 = 0, validPixels = 0;
-        size_t liveCap = 0;   // room of the generation-0 ray arrays (k_raygen writes no live ray past it: a count above it is a wrong bound, reported)
-        unsigned long long hcnt[2 * C_COUNT] = {0};
-        WorkBufs w;
-    } frames[8];   // context of ticket `slot`, part j of its frame: frames[slot + 2 * j] (a frame may be split into up to four bands on as many streams)
-    std::vector<hipEvent_t> events;   // xrt_scene_intersect timing
-    float lastFrameMs = 0.0f;    // GPU time of the last finished frame
-    bool adaptiveFastOk = true;  // no adaptive frame has overflowed its optimistically sized level buffers (cfg.adaptiveFast)
-    bool heapFastOk = true;      // no single-chunk ray-tree frame has overflowed on the optimistic way (cfg.heapFast)
-    int wallClockKHz = 0;        // rate of the device clock the launches stamp (hipDeviceAttributeWallClockRate)
-    std::atomic<bool> busy{false};
-    std::atomic<float> progress{0.0f};
-    // Seam 1 (xrt_scene_intersect / xrt_mesh_intersect / xrt_generate_primary_rays) is re-entrant like the reference's
-    // ISpatialManager.GetRayIntersection (ISM:15, called from N render threads, RT:105-113): the host-buffer calls share
-    // one staging area and are serialised by this mutex; every stream has its own work-queue word.
-    // In-library multi-GPU (xrt_render_opts.n_gpus): copies of the scene on devices device+1 .. (owned), the RCCL
-    // communicators, and per ticket the buffer the tile shards are gathered into (cfg.fakeGpus: all on the scene's own device).
-    std::vector<xrt_scene *> replicas;
-    std::vector<std::unique_ptr<RankWorker>> workers;   // workers[i - 1] drives replica i
-    int visibleDevices = 0;                             // hipGetDeviceCount at xrt_scene_create
-    RcclGather rccl;
-    DevBuf<uint32_t> gathered[2];    // primary: n * tiles_per_rank * 512 pixels, rank-major
-    DevBuf<uint32_t> tileOut[2];     // replica: its tiles of the frame in slot 0 / 1
-    DevBuf<uint32_t> frameOut[2];    // W*H frame of a host-output ticket
-    hipEvent_t tilesReady[2] = {nullptr, nullptr};   // replica (fake mode): its tiles are rendered
-    hipEvent_t tailDone[2] = {nullptr, nullptr};     // primary: gather + de-tile + host copy of the ticket are done
-    // Cost-aware tile assignment (xrt.h xrt_scene_set_tile_table / xrt_scene_tile_costs).  tileTable: the installed table (host copy and device
-    // copy) for frames of tableW x tableH pixels with tableCount shards, tableTpr slots per rank; tileCost: ticks per LOCAL tile slot of the
-    // frames rendered since the last reset, with the geometry they were rendered under (costKey) and their slots' tiles (costTiles).
-    std::vector<int> tileTable;
-    DevBuf<int> tileTableDev;
-    int tableW = 0, tableH = 0, tableCount = 0, tableTpr = 0;
-    DevBuf<unsigned> tileCost;
-    std::vector<int> costTiles;      // tile of every local slot the cost words belong to
-    int costW = 0, costH = 0;
-    std::vector<float> balanceCost;  // n_gpus > 1 with balance_tiles: the last frame's costs by tile (all ranks summed), its size
-    int balanceW = 0, balanceH = 0, balanceN = 0;
-    struct OpenFrame { int nGpus = 0, nParts = 1; bool tail = false, balance = false; uint32_t *hostOut = nullptr, *devOut = nullptr; size_t px = 0; hipStream_t st0 = nullptr; } open[2];
-    std::mutex apiMutex;
-    std::unordered_map<hipStream_t, int> queueOfStream;
-
-    ~xrt_scene() {
-        workers.clear();   // (joins the threads)
-        for (xrt_scene *r : replicas) delete r;
-        replicas.clear();
-        if (device >= 0) {
-            (void)hipSetDevice(device);
-            tileTableDev.release(); tileCost.release();
-            for (int i = 0; i < 2; i++) { if (tilesReady[i]) (void)hipEventDestroy(tilesReady[i]); if (tailDone[i]) (void)hipEventDestroy(tailDone[i]); gathered[i].release(); tileOut[i].release(); frameOut[i].release(); }
-            for (auto e : events) (void)hipEventDestroy(e);
-            for (auto &v : pose) {
-                if (v.ready) (void)hipEventDestroy(v.ready);
-                for (auto &rd : v.readers) (void)hipEventDestroy(rd.second);
-                v.objects.release(); v.scull.release();
-            }
-            if (poseInput) (void)hipEventDestroy(poseInput);
-            if (poseStaged) (void)hipEventDestroy(poseStaged);
-            if (posePinned) (void)hipHostFree(posePinned);
-            if (poseStream) (void)hipStreamDestroy(poseStream);
-            scullPosStart.release(); scullPos.release(); wbbDev.release(); poseIn.release();
-            for (auto &f : frames) {
-                for (auto e : f.events) (void)hipEventDestroy(e);
-                if (f.done) (void)hipEventDestroy(f.done);
-                if (f.pinned) (void)hipHostFree(f.pinned);
-                if (f.stampHost) (void)hipHostFree(f.stampHost);
-                f.w.release();
-            }
-            if (stream) (void)hipStreamDestroy(stream);
-            blocks.release(); leafNB.release(); leafTB.release(); refT.release(); refN.release(); refG.release(); snodes.release(); shade.release();
-            childDfs.release(); srefs.release(); scull.release(); runTB.release(); triTB.release(); runBase.release(); pblocks.release(); lrec.release(); objMesh.release(); meshes.release();
-            objects.release(); materials.release(); texels.release();
-            apiRays.release(); apiHits.release(); castRays.release(); castRGBA.release(); castF32.release();
-            pathHit.release(); pathDir.release(); pathLocal.release(); pathBlockSum.release(); pathBlockBase.release(); pathStart.release(); pathVerts.release(); pathBack.release();
-            if (pathPinned) (void)hipHostFree(pathPinned);
-
-            queues.release(); outRGBA.release(); outF32.release(); counters.release(); costMap.release(); waveTimes.release();
-        }
-    }
-};
+#include "scene_state.h"   // xrt_scene and its parts (global, as include/xrt.h declares it; its members' types are xrt's)
 
 namespace {
-
-struct BusyGuard {
-    xrt_scene *s;
-    bool owned;
-    explicit BusyGuard(xrt_scene *sc) : s(sc) {
-        bool expected = false;
-        owned = s->busy.compare_exchange_strong(expected, true);
-    }
-    ~BusyGuard() { if (owned) s->busy.store(false); }
-};
 
 bool in_flight(const xrt_scene *s) {
     if (s->busy.load()) return true;
@@ -457,11 +35,11 @@ int need_device(xrt_scene *s, const char *fn) {
     return XRT_OK;
 }
 
-hipEvent_t get_event(std::vector<hipEvent_t> &pool, size_t i) {
+hipEvent_t get_event(std::vector<Event> &pool, size_t i) {
     while (pool.size() <= i) {
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) return nullptr;
-        pool.push_back(e);
+        Event e;
+        if (hipEventCreate(&e.h) != hipSuccess) return nullptr;
+        pool.push_back(std::move(e));
     }
     return pool[i];
 }
@@ -486,9 +64,9 @@ int pose_reader(xrt_scene *s, int v, hipStream_t st) {
     size_t i = 0;
     while (i < rd.size() && rd[i].first != st) i++;
     if (i == rd.size()) {
-        hipEvent_t e = nullptr;
-        HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        rd.emplace_back(st, e);
+        Event e;
+        if (int rc = e.create()) return rc;
+        rd.emplace_back(st, std::move(e));
     }
     HIPCHECK(hipEventRecord(rd[i].second, st));
     return XRT_OK;
@@ -892,10 +470,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     F.stampRows = 0;
     if (useStamps) {
         if ((rc = W.stamps.ensure((size_t)MAX_STAMP_ROWS * STAMP_STRIDE))) return rc;
-        if (!F.stampHost) {
-            HIPCHECK(hipHostMalloc((void **)&F.stampHost, (size_t)MAX_STAMP_ROWS * 2 * sizeof(unsigned long long), hipHostMallocMapped));
-            HIPCHECK(hipHostGetDevicePointer((void **)&F.stampHostDev, F.stampHost, 0));
-        }
+        if ((rc = F.stampHost.ensure((size_t)MAX_STAMP_ROWS * 2 * sizeof(unsigned long long), hipHostMallocMapped))) return rc;
     }
     if (!st) {
         // No stream given.  Single-chunk frames get a stream per context, so that two frames in flight overlap on the GPU
@@ -904,7 +479,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         // ~15 us a launch and alternating streams made the host the bottleneck of 0.2 ms frames; the launches time themselves
         // now, device_util.h.)
         if (fast && s->lastFrameMs >= s->cfg.overlapMinMs && !s->cfg.oneStream) {
-            if (!W.stream) HIPCHECK(hipStreamCreateWithFlags(&W.stream, hipStreamNonBlocking));
+            if ((rc = W.stream.create())) return rc;
             st = W.stream;
         } else st = s->stream;
     }
@@ -921,7 +496,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         if ((rc = ensure_cleared(s->pathHit, lvlStride * nodes)) || (heap && (rc = ensure_cleared(s->pathDir, lvlStride * nodes))) || (rc = s->pathLocal.ensure((size_t)P)) ||
             (rc = s->pathBlockSum.ensure(pathBlocks)) || (rc = s->pathBlockBase.ensure(pathBlocks)))
             return rc;
-        if (!s->pathPinned) HIPCHECK(hipHostMalloc((void **)&s->pathPinned, 64, hipHostMallocDefault));
+        if ((rc = s->pathPinned.ensure(64, hipHostMallocDefault))) return rc;
     }
     // Tile costs (xrt.h xrt_scene_tile_costs): the packets of plain one-chunk frames add their device-clock ticks to the tile of their first
     // ray.  The words belong to the scene (both frame contexts add to them); a frame of another geometry or tile table starts them afresh.
@@ -974,7 +549,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         }
         if (part == 0) s->epoch++;
     } else if (s->costMap.p) {
-        s->costMap.release(); s->costMapPaths = 0;
+        s->costMap.release(); s->costMapPaths = 0;   // (freed early on purpose: a map of (R + 1) words per path that no frame of this kind reads)
     }
     if (!fast) {
         W.cntsClean = false;
@@ -1006,8 +581,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     std::vector<std::pair<size_t, size_t>> &pairs = F.pairs;
     pairs.clear();
     hipEvent_t e0 = get_event(F.events, ev++), e1 = get_event(F.events, ev++);
-    if (!F.done && hipEventCreateWithFlags(&F.done, hipEventDisableTiming) != hipSuccess) F.done = nullptr;
-    if (!e0 || !e1 || !F.done) return fail(XRT_E_HIP, "hipEventCreate failed");
+    if (!e0 || !e1 || F.done.create() != XRT_OK) return fail(XRT_E_HIP, "hipEventCreate failed");
     if (!fast) HIPCHECK(hipEventRecord(e0, st));
     s->progress.store(0.0f);
     unsigned long long &shaded = F.shaded, &closestDeep = F.closestDeep, &livePaths = F.livePaths, &live0 = F.live0;
@@ -1203,10 +777,10 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         uint32_t *const colorOut = gp.batch ? d_out + pathBase : (sampleOut ? sampleOut : W.sampleColor.p);
         float *const f32Out = gp.batch ? (d_outF32 ? d_outF32 + 3 * (size_t)pathBase : nullptr) : (wantF32 ? W.sampleF32.p : nullptr);
         StampFold fold;
-        fold.src = W.stamps.p; fold.host = F.stampHostDev; fold.row0 = chunkRow0; fold.row1 = F.stampRows;
+        fold.src = W.stamps.p; fold.host = F.stampHost.dev; fold.row0 = chunkRow0; fold.row1 = F.stampRows;
         if (heap) {
             FrameEpilogue E;
-            if (fast) { E.cntSrc = cnt; E.hostCnt = F.pinnedDev; E.cntWords = cntStride; E.zeroWords = cntStride + qStride; E.flagSrc = overflowFlag; }
+            if (fast) { E.cntSrc = cnt; E.hostCnt = F.pinned.dev; E.cntWords = cntStride; E.zeroWords = cntStride + qStride; E.flagSrc = overflowFlag; }
             launch_compose_tree(W.lvlA.p, W.lvlB.p, W.lvlAlpha.p, Pc, P, R, colorOut, f32Out, fold, E, st);
         }
         else {
@@ -1214,7 +788,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
             RA.fused = fuseResolve ? 1 : 0; RA.g = gp; RA.pixelBase = pathBase; RA.out = d_out; RA.outF32 = d_outF32;
             RA.stamps = fold;
             if (epi) { RA.cntSrc = epi->cntSrc; RA.hostCnt = epi->hostCnt; RA.cntWords = epi->cntWords; RA.zeroWords = epi->zeroWords; RA.zeroFrom = epi->zeroFrom; }
-            else if (fast && !adaptive) { RA.cntSrc = cnt; RA.hostCnt = F.pinnedDev; RA.cntWords = cntStride; RA.zeroWords = cntStride + qStride; }
+            else if (fast && !adaptive) { RA.cntSrc = cnt; RA.hostCnt = F.pinned.dev; RA.cntWords = cntStride; RA.zeroWords = cntStride + qStride; }
             int blocks = 0;
             if (listCnt) {
                 RA.list = W.composeList.p + 16; RA.endCnt = listCnt; RA.listCap = (int)rayCap;
@@ -1225,18 +799,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         }
         return XRT_OK;
     };
-    auto ensure_pinned = [&](size_t bytes) -> int {
-        if (F.pinnedBytes < bytes) {
-            if (F.pinned) (void)hipHostFree(F.pinned);
-            F.pinned = nullptr; F.pinnedBytes = 0;
-            HIPCHECK(hipHostMalloc(&F.pinned, bytes + 4096, hipHostMallocMapped));
-            F.pinnedBytes = bytes + 4096;
-            void *dv = nullptr;
-            HIPCHECK(hipHostGetDevicePointer(&dv, F.pinned, 0));
-            F.pinnedDev = (int *)dv;
-        }
-        return XRT_OK;
-    };
+    auto ensure_pinned = [&](size_t bytes) -> int { return F.pinned.bytes < bytes ? F.pinned.ensure(bytes + 4096, hipHostMallocMapped) : XRT_OK; };
     auto tally = [&](const int *hc) {
         for (int k = 0; k <= R; k++) {
             shaded += (unsigned long long)gen_hits(hc, R, k);
@@ -1264,7 +827,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
                 if ((rc2 = enqueue_chunk(gp, W.cnts.p, q, Pc, pathBase))) return rc2;
                 // the chunk's samples are consumed before the host has looked at the overflow flag: a retry overwrites them
                 if ((rc2 = post(Pc, pathBase))) return rc2;
-                char *pin = (char *)F.pinned;
+                char *pin = (char *)F.pinned.p;
                 const size_t cAt = ((size_t)cntStride * sizeof(int) + 7) & ~(size_t)7;   // counters + spare words (overflow flag) in one copy
                 HIPCHECK(hipMemcpyAsync(pin, W.cnts.p, (size_t)cntStride * sizeof(int), hipMemcpyDeviceToHost, st));
                 HIPCHECK(hipMemcpyAsync(pin + cAt, s->counters.p, nb2, hipMemcpyDeviceToHost, st));
@@ -1319,12 +882,12 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         if (stats) {   // per-pass ray accounting (the counter block is reused by the next pass): one pinned read-back
             const size_t nb = (size_t)nChunks * cntStride * sizeof(int);
             if ((rc2 = ensure_pinned(nb + nb2))) return rc2;
-            HIPCHECK(hipMemcpyAsync(F.pinned, W.cnts.p, nb, hipMemcpyDeviceToHost, st));
-            HIPCHECK(hipMemcpyAsync((char *)F.pinned + nb, s->counters.p, nb2, hipMemcpyDeviceToHost, st));
+            HIPCHECK(hipMemcpyAsync(F.pinned.p, W.cnts.p, nb, hipMemcpyDeviceToHost, st));
+            HIPCHECK(hipMemcpyAsync((char *)F.pinned.p + nb, s->counters.p, nb2, hipMemcpyDeviceToHost, st));
             if (finalPass) { F.tallyChunks = nChunks; return XRT_OK; }   // frame_finish tallies after the frame's done event
             HIPCHECK(hipStreamSynchronize(st));
-            for (int c = 0; c < nChunks; c++) tally((const int *)F.pinned + (size_t)c * cntStride);
-            std::memcpy(hcntHost, (char *)F.pinned + nb, nb2);
+            for (int c = 0; c < nChunks; c++) tally(F.pinned.p + (size_t)c * cntStride);
+            std::memcpy(hcntHost, (char *)F.pinned.p + nb, nb2);
         }
         return XRT_OK;
     };
@@ -1345,7 +908,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
             return XRT_OK;
         }, 0.0f, 1.0f, true);
         if (rc != XRT_OK) return rc;
-        if (pout) HIPCHECK(hipMemcpyAsync(s->pathPinned, pout->vertexStart + batch->n, sizeof(long long), hipMemcpyDeviceToHost, st));
+        if (pout) HIPCHECK(hipMemcpyAsync(s->pathPinned.p, pout->vertexStart + batch->n, sizeof(long long), hipMemcpyDeviceToHost, st));
         HIPCHECK(hipEventRecord(F.done, st));
         HIPCHECK(hipGetLastError());
         F.pending = true;
@@ -1402,7 +965,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
             if (l > 0) { gl.pathsDev = lvlCnt + l; gl.pathsMul = 4; gl.pathsCap = (int)cap_of(l); }
             FrameEpilogue E;
             const bool last = l == quality;
-            if (last) { E.cntSrc = W.cnts.p; E.hostCnt = F.pinnedDev; E.cntWords = LW + nPass * cntStride; E.zeroWords = (int)words; E.zeroFrom = LW; }
+            if (last) { E.cntSrc = W.cnts.p; E.hostCnt = F.pinned.dev; E.cntWords = LW + nPass * cntStride; E.zeroWords = (int)words; E.zeroFrom = LW; }
             if ((rc = enqueue_chunk(gl, cnt0 + (size_t)l * cntStride, q0 + (size_t)l * qStride, (int)(cap_of(l) * 4), 0, Lv.color.p, last ? &E : nullptr))) return rc;
             if (l < quality) {   // RT:279-306
                 auto &Nx = W.levels[l + 1];
@@ -1424,10 +987,9 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         // quadrants are the pixels (size 1); a level's
         // quadrants each cast four rays; corners that deviate are subdivided into the next level, down to
         // MultisampleQuality; results fold back up.
-        struct Level { DevBuf<uint32_t> color; DevBuf<int> childBase, childMask; DevBuf<float> cx, cy; long long n = 0; };
+        struct Level : xrt_scene::WorkBufs::Level { long long n = 0; };   // (the frame's own: freed when it is done, however it ends)
         std::vector<Level> lv((size_t)quality + 1);
         int *levelCount = reinterpret_cast<int *>(s->counters.p + 2 * C_COUNT);   // [quality+1] ints in the spare counter words
-        auto free_levels = [&]() { for (auto &l : lv) { l.color.release(); l.childBase.release(); l.childMask.release(); l.cx.release(); l.cy.release(); } };
         lv[0].n = totalPixels;
         float size = 1.0f;
         for (int l = 0; l <= quality && rc == XRT_OK; l++) {
@@ -1467,7 +1029,6 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
             if (e == hipSuccess) e = hipStreamSynchronize(st);
             if (e != hipSuccess) rc = fail(XRT_E_HIP, "adaptive resolve: %s", hipGetErrorString(e));
         }
-        free_levels();
         if (rc != XRT_OK) return rc;
     }
     if (!fast) HIPCHECK(hipEventRecord(F.done, st));
@@ -1493,7 +1054,7 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
         if (FILE *f = fopen(s->cfg.stampDumpPath.c_str(), "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
     }
     const int R = F.R;
-    if (F.fast && F.adaptiveFast && ((const int *)F.pinned)[F.cntBase - 1] != 0) {
+    if (F.fast && F.adaptiveFast && F.pinned.p[F.cntBase - 1] != 0) {
         // A quadrant level of the adaptive frame did not fit its optimistically sized buffers: the frame is rendered again the careful
         // way (a host read-back per level, exact sizes), and so are this scene's later adaptive frames from the start.
         s->adaptiveFastOk = false;
@@ -1509,11 +1070,11 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
         return rc;
     }
     if (F.fast && F.adaptiveFast) {   // rays of the frame: four per level-0 pixel and four per quadrant of every deeper level
-        const int *lw = (const int *)F.pinned;
+        const int *lw = F.pinned.p;
         F.livePaths = F.validPixels * 4ull;
         for (int l = 1; l <= F.quality; l++) F.livePaths += 4ull * (unsigned long long)std::min(lw[l], F.levelCap);
     }
-    if (F.fast && F.heap && F.tallyChunks == 1 && ((const int *)F.pinned)[F.cntStride] != 0) {
+    if (F.fast && F.heap && F.tallyChunks == 1 && F.pinned.p[F.cntStride] != 0) {
         // A generation of the ray tree did not fit the optimistically sized buffers: the frame is rendered again the careful way
         // (chunks, overflow checks, retries with fewer paths), and so are this scene's later ray-tree frames from the start.
         s->heapFastOk = false;
@@ -1530,7 +1091,7 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
     if (F.tallyChunks > 0) {   // single-pass frame: the read-back was left in flight
         const size_t nb = (size_t)F.tallyChunks * F.cntStride * sizeof(int);
         for (int c = 0; c < F.tallyChunks; c++) {
-            const int *hc = (const int *)F.pinned + F.cntBase + (size_t)c * F.cntStride;
+            const int *hc = F.pinned.p + F.cntBase + (size_t)c * F.cntStride;
             if (hc[0] < 0 || (size_t)hc[0] > F.liveCap)
                 return fail(XRT_E_INTERNAL, "%d primary rays reach the scene but the frame's ray arrays were sized for %zu (screen rectangle of the root box)", hc[0], F.liveCap);
             if (F.endEarly && (hc[F.cntStride] < 0 || hc[F.cntStride] > hc[0]))
@@ -1548,15 +1109,15 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
 #ifdef XRT_DEV
         if (s->cfg.finishCounts)   // (profiles/shade_finish: which share of a generation's hits part A finished; a frame not answered at emission emits every shadow ray)
             for (int k = 0; k <= R; k++) {
-                const int *hc = (const int *)F.pinned + F.cntBase;
+                const int *hc = F.pinned.p + F.cntBase;
                 fprintf(stderr, "xrt finish: %s generation %d hits %lld finished %d shadow rays emitted %lld\n", F.ae ? "answered at emission," : "not answered at emission,", k,
                         gen_hits(hc, R, k), hc[4 * (R + 2) + k], F.ae ? (long long)hc[3 * (R + 2) + k] : gen_hits(hc, R, k) * (long long)F.nL);
             }
 #endif
-        if (!F.fast) std::memcpy(F.hcnt, (char *)F.pinned + nb, sizeof(F.hcnt));
+        if (!F.fast) std::memcpy(F.hcnt, (char *)F.pinned.p + nb, sizeof(F.hcnt));
         // (adaptive frames in flight put the level-count words in front of the per-pass counters and have no framePaths key: no hints from them)
         if (F.fast && F.tallyChunks == 1 && !F.adaptiveFast) {   // sizes of this frame's generations: grid hints for the next one (sizing only)
-            const int *hc = (const int *)F.pinned + F.cntBase;
+            const int *hc = F.pinned.p + F.cntBase;
             const bool same0 = s->genKey == F.framePaths * 64 + F.nL;
             for (int k = 0; k <= R + 1 && k < 68; k++) {
                 const long long closest = (k == 0 || ((F.heap || F.ae) && k <= R)) ? hc[k] : (k <= R ? gen_hits(hc, R, k - 1) : 0), shaded = k >= 1 ? gen_hits(hc, R, k - 1) : 0;
@@ -1576,7 +1137,7 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
             s->genKey = F.framePaths * 64 + F.nL;
         }
         if (F.fast && s->costMap.p && !F.adaptiveFast) {   // steer the "long ray" thresholds towards 2-6 % of each generation's rays
-            const int *hc = (const int *)F.pinned + F.cntBase;
+            const int *hc = F.pinned.p + F.cntBase;
             for (int k = 0; k <= R && k < 66; k++) {
                 const long long rays = k == 0 ? hc[0] : gen_hits(hc, R, k - 1), listed = hc[2 * (R + 2) + k];
                 if (rays < 4096) continue;
@@ -1589,7 +1150,7 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
         F.tallyChunks = 0;
     }
     if (F.endEarly) {   // (xrt_debug_end_counts: a frame that engaged has one chunk and its counters in `pinned`)
-        const int *hc = (const int *)F.pinned + F.cntBase;
+        const int *hc = F.pinned.p + F.cntBase;
         s->endCounts[0] = (unsigned long long)hc[F.cntStride + END_BY_RAYGEN]; s->endCounts[1] = (unsigned long long)hc[F.cntStride + END_BY_SHADE]; s->endCounts[2] = (unsigned long long)hc[F.cntStride + END_LISTED];
     } else s->endCounts[0] = s->endCounts[1] = s->endCounts[2] = 0;
     {
@@ -1626,7 +1187,7 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
             if (t > longest) longest = t;
         }
         for (int j = 0; j < F.stampRows; j++) {
-            const unsigned long long *sp = F.stampHost;
+            const unsigned long long *sp = F.stampHost.p;
             if (sp[2 * j + 1] > sp[2 * j]) {
                 const double t = (double)(sp[2 * j + 1] - sp[2 * j]) / (double)s->wallClockKHz;
                 mi += t;
@@ -1659,19 +1220,18 @@ int ensure_replicas(xrt_scene *s, int n) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, r->device) == hipSuccess) r->numCUs = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
         if (hipDeviceGetAttribute(&r->wallClockKHz, hipDeviceAttributeWallClockRate, r->device) != hipSuccess) { r->wallClockKHz = 0; (void)hipGetLastError(); }
-        HIPCHECK(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
-        int rc = scene_upload(r.get());
-        if (rc != XRT_OK) return rc;
+        int rc;
+        if ((rc = r->stream.create()) || (rc = scene_upload(r.get()))) return rc;
         // the replica's version 0 holds the host's records: the primary's version 0 only while no pose was set since the build
         for (auto &v : r->pose) v.serial = ~0ull;
         if (s->poseSerial == 0) r->pose[0].serial = 0;
         s->workers.emplace_back(new RankWorker(r->device));
-        s->replicas.push_back(r.release());
+        s->replicas.push_back(std::move(r));
     }
     return hipSetDevice(s->device) == hipSuccess ? XRT_OK : fail(XRT_E_HIP, "hipSetDevice failed");
 }
 
-xrt_scene *rank_scene(xrt_scene *s, int i) { return i == 0 ? s : s->replicas[(size_t)i - 1]; }
+xrt_scene *rank_scene(xrt_scene *s, int i) { return i == 0 ? s : s->replicas[(size_t)i - 1].get(); }
 
 // Install / remove a tile table on one scene object (its device must be current).  Caller has checked the table.
 int install_tile_table(xrt_scene *r, int w, int h, int count, int tpr, const int *table) {
@@ -1710,7 +1270,7 @@ int replica_pose(xrt_scene *s, xrt_scene *r, int v) {
         HIPCHECK(hipMemcpyPeerAsync(pose_objects(r, v), r->device, pose_objects(s, v), s->device, nObj * sizeof(ObjRec), r->stream));
         HIPCHECK(hipMemcpyPeerAsync(pose_scull(r, v), r->device, pose_scull(s, v), s->device, nCull * sizeof(f4), r->stream));
     }
-    if (!R.ready) HIPCHECK(hipEventCreateWithFlags(&R.ready, hipEventDisableTiming));
+    if ((rc = R.ready.create())) return rc;
     HIPCHECK(hipEventRecord(R.ready, r->stream));
     R.serial = P.serial;
     return XRT_OK;
@@ -1767,7 +1327,7 @@ int multi_begin(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_light *
         xrt_scene *r = rank_scene(s, i);
         HIPCHECK(hipSetDevice(r->device));
         if ((rc = r->tileOut[slot].ensure(count))) { (void)hipSetDevice(s->device); return rc; }
-        if (s->cfg.fakeGpus && !r->tilesReady[slot]) HIPCHECK(hipEventCreateWithFlags(&r->tilesReady[slot], hipEventDisableTiming));
+        if (s->cfg.fakeGpus && (rc = r->tilesReady[slot].create())) return rc;
     }
     for (int i = 1; i < n; i++)
         if ((rc = replica_pose(s, rank_scene(s, i), s->slotPose[slot]))) { (void)hipSetDevice(s->device); return rc; }
@@ -1942,7 +1502,7 @@ int open_frame_impl(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_lig
             HIPCHECK(hipStreamWaitEvent(st0, Fj.fast ? Fj.events[1] : Fj.done, 0));
         }
         if (host_out && px) HIPCHECK(hipMemcpyAsync(host_out, d_out, px * sizeof(uint32_t), hipMemcpyDeviceToHost, st0));   // CurrentTarget.SetData (RT:123)
-        if (!s->tailDone[slot]) HIPCHECK(hipEventCreateWithFlags(&s->tailDone[slot], hipEventDisableTiming));
+        if ((rc = s->tailDone[slot].create())) return rc;
         HIPCHECK(hipEventRecord(s->tailDone[slot], st0));
     }
     poseRelease.keep = true;
@@ -2069,8 +1629,6 @@ int run_intersect(xrt_scene *s, const xrt_ray *d_rays, int64_t n, xrt_hit *d_hit
     return XRT_OK;
 }
 
-// Host arrays of scene->host -> HBM of scene->device, launch geometry and scheduling defaults (second half of
-// xrt_scene_build; also what puts a replica of the scene on another device).
 // RayTracer.CastRay (RT:506-737) on n rays already in HBM: the pass of frame_begin with the batch as its ray source, MaxReflections - iteration
 // generations deep, then the pass's counters.  The caller holds the scene (BusyGuard, no frame in flight).
 int cast_rays_impl(xrt_scene *s, const xrt_ray *d_rays, int64_t n, int32_t iteration, float refIndex, const xrt_light *lights, int32_t nLights,
@@ -2121,10 +1679,7 @@ int pose_upload(xrt_scene *scene) {
     std::vector<float> wbb(6 * (scene->host->objects.size() + 1), 0.0f);
     for (size_t o = 0; o < scene->host->objects.size(); o++) std::memcpy(&wbb[6 * o], scene->host->objects[o].worldBbox, 6 * sizeof(float));
     if ((rc = upload(scene->wbbDev, wbb))) return rc;
-    for (auto &v : scene->pose) {
-        if (v.ready) (void)hipEventDestroy(v.ready);
-        v.ready = nullptr; v.serial = 0;
-    }
+    for (auto &v : scene->pose) { v.ready.reset(); v.serial = 0; }
     scene->poseCur = 0; scene->poseSerial = 0; scene->posesOnDevice = false;
     return XRT_OK;
 }
@@ -2175,6 +1730,8 @@ int scene_derive(xrt_scene *scene) {
     return XRT_OK;
 }
 
+// Host arrays of scene->host -> HBM of scene->device, launch geometry and scheduling defaults (second half of
+// xrt_scene_build; also what puts a replica of the scene on another device).
 int scene_upload(xrt_scene *scene) {
     const SceneArrays &A = scene->host->arrays;
     const int stackNeeded = (A.sceneDepth + 1) + (A.meshDepth + 1);
@@ -2205,8 +1762,7 @@ int poses_enqueue(xrt_scene *s, const int *ids, int n, const float *world, const
     xrt_scene::PoseVer &P = s->pose[v];
     const SceneArrays &A = s->host->arrays;
     int rc;
-    if (!s->poseStream) HIPCHECK(hipStreamCreateWithFlags(&s->poseStream, hipStreamNonBlocking));
-    if (!s->poseInput) HIPCHECK(hipEventCreateWithFlags(&s->poseInput, hipEventDisableTiming));
+    if ((rc = s->poseStream.create()) || (rc = s->poseInput.create())) return rc;
     hipStream_t ps = s->poseStream;
     if (st != ps) {
         HIPCHECK(hipEventRecord(s->poseInput, st));
@@ -2225,7 +1781,7 @@ int poses_enqueue(xrt_scene *s, const int *ids, int n, const float *world, const
     PA.wbbOut = s->wbbDev.p; PA.safety = s->host->cullSafety;
     launch_pose(PA, ps);
     HIPCHECK(hipGetLastError());
-    if (!P.ready) HIPCHECK(hipEventCreateWithFlags(&P.ready, hipEventDisableTiming));
+    if ((rc = P.ready.create())) return rc;
     HIPCHECK(hipEventRecord(P.ready, ps));
     if (st != ps) HIPCHECK(hipStreamWaitEvent(st, P.ready, 0));
     P.serial = ++s->poseSerial;
@@ -2289,7 +1845,7 @@ int xrt_scene_create(int device, xrt_scene **scene_out) {
         if (device >= n) return fail(XRT_E_NO_DEVICE, "device %d not present (%d visible)", device, n);
         HIPCHECK(hipSetDevice(device));
     }
-    xrt_scene *s = new xrt_scene();
+    std::unique_ptr<xrt_scene> s(new xrt_scene());
     s->device = device;
     if (device >= 0 && hipGetDeviceCount(&s->visibleDevices) != hipSuccess) { (void)hipGetLastError(); s->visibleDevices = 0; }
     s->cfg = cfg;
@@ -2302,10 +1858,10 @@ int xrt_scene_create(int device, xrt_scene **scene_out) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess) s->numCUs = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
         if (hipDeviceGetAttribute(&s->wallClockKHz, hipDeviceAttributeWallClockRate, device) != hipSuccess) { s->wallClockKHz = 0; (void)hipGetLastError(); }
-        hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) { delete s; return fail(XRT_E_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
+        hipError_t e = hipStreamCreateWithFlags(&s->stream.h, hipStreamNonBlocking);
+        if (e != hipSuccess) return fail(XRT_E_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
     }
-    *scene_out = s;
+    *scene_out = s.release();
     return XRT_OK;
 }
 
@@ -2352,8 +1908,7 @@ int xrt_scene_build(xrt_scene *scene, int32_t mesh_threshold, int32_t scene_thre
         scene->resident = false;
         if (!scene->hs.build(mesh_threshold, scene_threshold, err)) return fail(XRT_E_UNSUPPORTED, "%s", err.c_str());
         scene->workers.clear();
-        for (xrt_scene *r : scene->replicas) delete r;   // copies of the previous build on other devices
-        scene->replicas.clear();
+        scene->replicas.clear();   // copies of the previous build on other devices
         return scene_upload(scene);
     });
 }
@@ -2385,24 +1940,17 @@ int xrt_scene_set_poses(xrt_scene *scene, const int32_t *object_ids, int32_t n, 
         // staging: ids | world | inv | wbb in page-locked memory, one asynchronous copy to the device
         const size_t m = order.size(), idWords = (m + 3) / 4 * 4, words = idWords + m * (16 + 16 + 6);
         if (scene->poseStaged) HIPCHECK(hipEventSynchronize(scene->poseStaged));   // (the previous update's copy of a few KB)
-        if (scene->posePinnedBytes < words * 4) {
-            if (scene->posePinned) HIPCHECK(hipHostFree(scene->posePinned));
-            scene->posePinned = nullptr; scene->posePinnedBytes = 0;
-            HIPCHECK(hipHostMalloc(&scene->posePinned, words * 4, hipHostMallocDefault));
-            scene->posePinnedBytes = words * 4;
-        }
         int rc;
-        if ((rc = scene->poseIn.ensure(words))) return rc;
-        int *hid = (int *)scene->posePinned;
-        float *hw = (float *)scene->posePinned + idWords, *hi = hw + 16 * m, *hb = hi + 16 * m;
+        if ((rc = scene->posePinned.ensure(words * 4, hipHostMallocDefault)) || (rc = scene->poseIn.ensure(words))) return rc;
+        int *hid = (int *)scene->posePinned.p;
+        float *hw = (float *)scene->posePinned.p + idWords, *hi = hw + 16 * m, *hb = hi + 16 * m;
         for (size_t k = 0; k < m; k++) {
             const size_t i = (size_t)order[k];
             hid[k] = object_ids[i];
             std::memcpy(hw + 16 * k, world + 16 * i, 64); std::memcpy(hi + 16 * k, inv_world + 16 * i, 64); std::memcpy(hb + 6 * k, world_bbox + 6 * i, 24);
         }
-        if (!scene->poseStream) HIPCHECK(hipStreamCreateWithFlags(&scene->poseStream, hipStreamNonBlocking));
-        if (!scene->poseStaged) HIPCHECK(hipEventCreateWithFlags(&scene->poseStaged, hipEventDisableTiming));
-        HIPCHECK(hipMemcpyAsync(scene->poseIn.p, scene->posePinned, words * 4, hipMemcpyHostToDevice, scene->poseStream));
+        if ((rc = scene->poseStream.create()) || (rc = scene->poseStaged.create())) return rc;
+        HIPCHECK(hipMemcpyAsync(scene->poseIn.p, scene->posePinned.p, words * 4, hipMemcpyHostToDevice, scene->poseStream));
         HIPCHECK(hipEventRecord(scene->poseStaged, scene->poseStream));
         const float *dw = scene->poseIn.p + idWords;
         return poses_enqueue(scene, (const int *)scene->poseIn.p, (int)m, dw, dw + 16 * m, dw + 32 * m, scene->poseStream);
@@ -2444,8 +1992,7 @@ int xrt_scene_build_tree(xrt_scene *scene, int32_t scene_threshold) {
         scene->resident = false;
         if (!scene->hs.build_tree(scene_threshold, err)) return fail(XRT_E_UNSUPPORTED, "%s", err.c_str());
         scene->workers.clear();
-        for (xrt_scene *r : scene->replicas) delete r;   // (copies of the previous tree: made again on the next n_gpus > 1 frame)
-        scene->replicas.clear();
+        scene->replicas.clear();   // (copies of the previous tree: made again on the next n_gpus > 1 frame)
         const SceneArrays &A = scene->hs.arrays;
         const int stackNeeded = (A.sceneDepth + 1) + (A.meshDepth + 1);
         if (intersect_stack_capacity(stackNeeded) < 0) return fail(XRT_E_UNSUPPORTED, "octree too deep for the LDS stack (%d levels)", stackNeeded);
@@ -2482,12 +2029,7 @@ int xrt_scene_load(int device, const char *path, xrt_scene **scene_out) {
         if (!(*scene_out)->hs.load(path, err)) return fail(XRT_E_INVALID_ARG, "%s (%s)", err.c_str(), path);
         return XRT_OK;
     });
-    if (rc != XRT_OK) {
-        const std::string keep = g_err;
-        delete *scene_out;
-        *scene_out = nullptr;
-        g_err = keep;
-    }
+    if (rc != XRT_OK) { delete *scene_out; *scene_out = nullptr; }   // (the owners' destructors report nothing: the load's error stays)
     return rc;
 }
 
@@ -2836,7 +2378,7 @@ int xrt_cast_rays_paths(xrt_scene *scene, const xrt_ray *rays, int64_t n, int32_
         *n_vertices_out = 0;
         if (n == 0 && vertex_start) vertex_start[0] = 0;
         if (n > 0) {
-            const long long need = *scene->pathPinned;   // (arrived with the pass: cast_rays_impl waited for it)
+            const long long need = *scene->pathPinned.p;   // (arrived with the pass: cast_rays_impl waited for it)
             *n_vertices_out = need;
             const long long wrote = std::min(need, P.capacity & ~1LL);
             HIPCHECK(hipMemcpyAsync(rgba_out, scene->castRGBA.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, scene->stream));
@@ -2876,7 +2418,7 @@ int xrt_cast_rays_paths_device(xrt_scene *scene, const void *d_rays, int64_t n, 
         if ((rc = cast_rays_impl(scene, (const xrt_ray *)d_rays, n, iteration, current_ref_index, lights, n_lights, opts, (uint32_t *)d_rgba_out,
                                  (float *)d_rgb_f32_out, st, stats_out, &P)))
             return rc;
-        *n_vertices_out = n > 0 ? *scene->pathPinned : 0;
+        *n_vertices_out = n > 0 ? *scene->pathPinned.p : 0;
         if (n == 0 && d_vertex_start) {
             HIPCHECK(hipMemsetAsync(d_vertex_start, 0, sizeof(int64_t), st));
             HIPCHECK(hipStreamSynchronize(st));
