@@ -1,3 +1,5 @@
+import functools
+
 import numpy as np
 
 
@@ -244,3 +246,140 @@ def coplanar_tie_scene(xrt):
     od = o.copy(); od[:, 0] -= 4.0                                               # 45 degrees in the x-y plane: |d| = (sqrt 1/2, sqrt 1/2, 0)
     sets.append(xrt.rays_array(od, np.tile(np.float32([np.sqrt(0.5), -np.sqrt(0.5), 0]), (len(o), 1))))
     return spec, sets
+
+
+# ---- magnitudes: the same scene and rays at another power-of-two scale (tests/test_magnitudes_cpu.py, tests/test_gpu_magnitudes.py) ----
+def _pow2(k):
+    """float32(2)**k, exact for -149 <= k <= 127."""
+    return np.ldexp(np.float32(1.0), int(k)).astype(np.float32)
+
+
+def scaled_mesh(md, k):
+    """md with every vertex multiplied by 2^k (exact in binary32 as long as nothing leaves the normal range).  The surface normals and the box
+    are MeshData's own, recomputed in binary32 from the scaled vertices as a host would; vertex normals, UVs and colours are untouched."""
+    with np.errstate(all="ignore"):   # (a squared edge that underflows gives a NaN normal: that is the point of the small scales)
+        return type(md)(md.v * _pow2(k), md.n, md.uv, md.color)
+
+
+def scaled_spec(spec, k):
+    """spec at scale 2^k: mesh vertices, body positions, camera pos / target / near / far and the positions of positionable lights are
+    multiplied by 2^k; directions, angles, intensities, thresholds and the image stay."""
+    import copy
+    s = copy.copy(spec)
+    f = float(_pow2(k))
+    mul = lambda p: tuple(float(np.float32(x) * _pow2(k)) for x in p)
+    s.name = "%s_2^%d" % (spec.name, k)
+    s.meshes = [(scaled_mesh(md, k), dict(m)) for md, m in spec.meshes]
+    s.objects = [(list(ids), mul(pos), tuple(rot), tuple(scale)) for ids, pos, rot, scale in spec.objects]
+    s.camera = dict(spec.camera)
+    s.camera["pos"], s.camera["target"] = mul(spec.camera["pos"]), mul(spec.camera["target"])
+    s.camera["near"], s.camera["far"] = spec.camera["near"] * f, spec.camera["far"] * f
+    s.lights = []
+    for l in spec.lights:
+        l = dict(l)
+        if any(l["position"]):   # (a directional light keeps position 0 and has nothing to scale)
+            l["position"] = mul(l["position"])
+        s.lights.append(l)
+    return s
+
+
+def scaled_rays(rays, k, j):
+    """A copy of rays with origins x 2^k and directions x 2^j (both exact)."""
+    r = rays.copy()
+    with np.errstate(all="ignore"):
+        r["o"] = rays["o"] * _pow2(k)
+        r["d"] = rays["d"] * _pow2(j)
+    return r
+
+
+def magnitude_rays(xrt, md, n, seed, radius=None, inside=False):
+    """n unit-direction rays at a mesh: origins on the sphere of `radius` (default: the box diagonal) around the centre of the mesh box -- or,
+    inside=True, uniform in 0.9 x the box -- towards targets uniform in the box."""
+    rng = np.random.default_rng(seed)
+    lo, hi = md.bbox[:3].astype(np.float64), md.bbox[3:].astype(np.float64)
+    c, half = (lo + hi) / 2, (hi - lo) / 2
+    if inside:
+        o = c + 0.9 * half * rng.uniform(-1, 1, size=(n, 3))
+    else:
+        o = rng.normal(size=(n, 3))
+        o = c + o / np.linalg.norm(o, axis=1, keepdims=True) * (float(np.linalg.norm(hi - lo)) if radius is None else radius)
+    t = c + half * rng.uniform(-1, 1, size=(n, 3))
+    d = t - o
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    return xrt.rays_array(o.astype(np.float32), d.astype(np.float32))
+
+
+@functools.lru_cache(maxsize=None)
+def magnitude_fixture(xrt, name):
+    """(unit mesh, one-body spec, 4000 unit rays from outside, 4000 from inside) of the two magnitude fixtures, made once and shared (callers
+    copy, never write): 'soup' = triangle_soup(900, 5, 0.3) with leaf threshold 12, 'hf' = fixtures.heightfield(48) with leaf threshold 50
+    (smooth: tight leaf boxes and normal boxes engage).  One body at the origin with the identity pose, 48 x 48 image."""
+    if name == "soup":
+        md, threshold, radius = triangle_soup(900, 5, 0.3), 12, 3.0
+        cam, light = xrt.configs.camera((0, 3, 3), (0, 0, 0)), xrt.configs.spot((0, 5, 5))
+    else:
+        md, threshold, radius = xrt.fixtures.heightfield(48), 50, None
+        cam, light = xrt.configs.camera((0, 60, 110), (0, 0, 0)), xrt.configs.spot((0, 120, 160))
+    s = xrt.configs.SceneSpec(name)
+    s.meshes.append((md, xrt.configs.material(0.5 if name == "soup" else 0.3)))
+    s.objects.append(([0], (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)))
+    s.camera, s.lights = cam, [light]
+    s.mesh_threshold = threshold
+    s.max_reflections = 2
+    s = s.with_size(48, 48)
+    return md, s, magnitude_rays(xrt, md, 4000, 31, radius=radius), magnitude_rays(xrt, md, 4000, 32, inside=True)
+
+
+def magnitude_frame_spec(xrt, name, k, transparent=False, multisampling=None, quality=0):
+    """The frame scene of a magnitude fixture at scale 2^k: the soup under its spot and a directional light (opaque, or transparent with
+    refraction index 1.32), the heightfield under its spot; MaxReflections 2, 48 x 48."""
+    import copy
+    md, spec, _, _ = magnitude_fixture(xrt, name)
+    s = copy.copy(spec)
+    if name == "soup":
+        s.lights = list(spec.lights) + [xrt.configs.directional((0.2, 0.9, 0.3), (0.5, 0.5, 0.4), 0.6)]
+    if transparent:
+        s.meshes = [(md, xrt.configs.material(0.5, transparent=True, refraction_index=float(np.float32(1.32))))]
+    if multisampling is not None:
+        s.multisampling, s.multisample_quality = multisampling, quality
+    return scaled_spec(s, k)
+
+
+def magnitude_pose_case(xrt, k=None, scale=None):
+    """Two bodies of the unit soup for xrt_scene_set_poses at magnitude -> (spec as built, pose of body 0 to set, rays at body 0, rays at
+    body 1).  Body 0 is built at the origin with the identity pose and then moved to rotation (0.3, 0.9, -0.4) and scale 2^k (or the
+    given scale triple); body 1 stands at unit scale 5 max(1, 2^k) along x.  The rays at body 0 are the fixture's unit rays scaled by 2^k
+    (a sphere of origins does not care about the rotation); for a body scaled up by 2^k, rays from its world box into the root box of the scene octree as built; for a
+    non-uniform scale the unit rays carried by the pose's world matrix (the plain unit rays when a scale component is zero: the matrix would
+    flatten them into the body's plane)."""
+    import copy
+    md, spec, rays, _ = magnitude_fixture(xrt, "soup")
+    sc = tuple(float(_pow2(k)) for _ in range(3)) if scale is None else tuple(float(x) for x in scale)
+    x1 = 5.0 * max(1.0, max(sc))
+    s = copy.copy(spec)
+    s.name = "poses"
+    s.objects = [([0], (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)), ([0], (x1, 0.0, 0.0), (0.0, 0.0, 0.0), (1.0, 1.0, 1.0))]
+    pose0 = ((0.0, 0.0, 0.0), (0.3, 0.9, -0.4), sc)
+    if scale is None and k > 0:
+        # A ray reaches the body only through the scene octree's root box -- until the tree is built again the box of the two unit bodies -- and
+        # through the body's WorldBoundingBox, which in the reference is the box of the two transformed corners Min and Max alone (SO:183-199):
+        # under this rotation a sliver beside the root box.  Rays from points of the sliver towards points of the stale root box cross both.
+        wbb = xrt.xna.as_array(xrt.xna.build_world(sc, pose0[1], pose0[0], md.bbox)[2]).astype(np.float64)
+        lo, hi = np.minimum(wbb[:3], wbb[3:]), np.maximum(wbb[:3], wbb[3:])
+        rlo, rhi = md.bbox[:3].astype(np.float64), md.bbox[3:].astype(np.float64) + np.array([x1, 0.0, 0.0])
+        rng = np.random.default_rng(33)
+        o = lo + (hi - lo) * rng.uniform(size=(len(rays), 3))
+        d = rlo + (rhi - rlo) * rng.uniform(size=(len(rays), 3)) - o
+        rays0 = xrt.rays_array(o.astype(np.float32), (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32))
+    elif scale is None:
+        rays0 = scaled_rays(rays, k, 0)
+    elif min(sc) == 0.0:
+        rays0 = rays.copy()
+    else:
+        W = xrt.xna.as_array(xrt.xna.build_world(sc, pose0[1], pose0[0], md.bbox)[0]).reshape(4, 4).astype(np.float64)[:3, :3]
+        o = rays["o"].astype(np.float64) @ W
+        d = (rays["o"].astype(np.float64) + 3.0 * rays["d"].astype(np.float64)) @ W - o
+        rays0 = xrt.rays_array(o.astype(np.float32), (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32))
+    rays1 = rays.copy()
+    rays1["o"][:, 0] += np.float32(x1)
+    return s, pose0, rays0, rays1
