@@ -91,6 +91,28 @@ namespace RayTraceProject.Spatial
             Xrt.Check(Xrt.xrt_scene_build(this.scene, 0, 0));
         }
 
+        // Material's setters (Material.cs:39, 234-268) between frames: the scalar properties of every mesh's material in one xrt_scene_set_materials,
+        // before the next RenderAsync (tickets may be open; nothing is rebuilt).  texArgb stays IntPtr.Zero: the library keeps the texels it was given
+        // by Build().  A host that assigns Material.Texture passes the new lock's Scan0 / Width / Height (and the pinned ColorData) for that mesh
+        // instead, as Build() does.
+        public void PushMaterials()
+        {
+            if (this.scene == IntPtr.Zero || this.meshesById.Count == 0) return;
+            int[] ids = new int[this.meshesById.Count];
+            XrtMaterial[] mats = new XrtMaterial[ids.Length];
+            for (int i = 0; i < ids.Length; i++)
+            {
+                Material mat = this.meshesById[i].MeshMaterial;
+                ids[i] = i;
+                mats[i] = new XrtMaterial
+                {
+                    reflectiveness = mat.Reflectiveness, transparent = mat.Transparent ? 1 : 0, refractionIndex = mat.RefractionIndex,
+                    interpolateNormals = mat.InterpolateNormals ? 1 : 0, useTexture = mat.UseTexture ? 1 : 0
+                };
+            }
+            Xrt.Check(Xrt.xrt_scene_set_materials(this.scene, ids, ids.Length, mats));
+        }
+
         static void Put3(float[] a, int o, Vector3 p) { a[o] = p.X; a[o + 1] = p.Y; a[o + 2] = p.Z; }
 
         // Batched form used by a wavefront renderer.

@@ -145,6 +145,10 @@ namespace RayTraceProject.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_poses_device(IntPtr scene, IntPtr dObjectIds, int n,
                                                                      IntPtr dWorld, IntPtr dInvWorld, IntPtr dWorldBbox, IntPtr stream);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_build_tree(IntPtr scene, int sceneThreshold);
+        // Material.Reflectiveness / Transparent / RefractionIndex / InterpolateNormals / UseTexture / Texture (Material.cs:39, 234-268) between frames: mesh
+        // meshIds[i] takes materials[i], also while RenderAsync tickets are open; texArgb == IntPtr.Zero keeps the texels the mesh has; nothing is rebuilt
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_materials(IntPtr scene, [In] int[] meshIds, int n,
+                                                                     [In] XrtMaterial[] materials);
         // can n_gpus > 1 load RCCL?  OK or E_RCCL (-6) with the loader's message; no device is touched
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_rccl_probe();
         // diagnostics of the split walks of long packets (results never depend on them): subtrees handed over, taken, packets split, packets written by a taker

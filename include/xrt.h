@@ -501,6 +501,34 @@ int xrt_scene_set_poses_device(xrt_scene *scene, const void *d_object_ids, int32
  * begin/end ticket is open; XRT_E_NOT_BUILT before xrt_scene_build. */
 int xrt_scene_build_tree(xrt_scene *scene, int32_t scene_threshold);
 
+/* ---- changing materials between frames: Material.Reflectiveness / Transparent / RefractionIndex / InterpolateNormals / UseTexture /
+ * Texture (MAT:39, 234-268) ----------------------------------------------------------------------------------------------------
+ * Added within ABI 203: this export is additive; no existing struct, field or entry point changed.
+ * The reference's Material has public setters and CastRay reads them at every hit (RT:515, 520, 568, 584, 586, 658): a host that turns
+ * the glass spheres opaque or slides a crate's reflectiveness sees it in the next frame.  xrt_scene_set_materials is that, batched: for
+ * i < n, mesh mesh_ids[i] takes materials[i] (the struct xrt_scene_add_mesh takes).
+ *   - scalar fields: reflectiveness, transparent, refraction_index, interpolate_normals, use_texture are taken as given.
+ *   - texels: use_texture != 0 with tex_argb != NULL replaces the mesh's texels (tex_width, tex_height, tex_pargb as in
+ *     xrt_scene_add_mesh; the size may differ from the old one).  use_texture != 0 with tex_argb == NULL keeps the texels the mesh
+ *     has: tex_width / tex_height must be 0 or the stored size, and a mesh that never had texels is XRT_E_INVALID_ARG (the reference:
+ *     UseTexture = true on a material whose bitmap was never locked, a null dereference).  use_texture == 0 switches the flag only:
+ *     the stored texels stay, as the reference's locked bitmap does, and a later use_texture = 1 with NULL texels brings them back;
+ *     texels passed with use_texture == 0 are stored.  tex_pargb is read only together with tex_argb.
+ *   - what xrt_scene_add_mesh rejects in a material is rejected here with the same code; mesh ids out of range, n < 0, or a NULL array
+ *     with n > 0: XRT_E_INVALID_ARG.  A failing call applies nothing.  n == 0 does nothing.  A mesh listed twice takes its last entry.
+ *   - before the first xrt_scene_build the call only edits what the build will use; on a host-only scene (device -1) the host copy is
+ *     updated and the call returns XRT_OK.
+ *   - xrt_scene_save writes the current materials and texels (the file format is unchanged; texels kept while use_texture is 0 are not
+ *     part of the file, as they are not part of what xrt_scene_add_mesh is given).
+ *   - mesh octrees, triangles, normal boxes, poses, the scene octree, tile tables and the geometry of replicas are not touched; nothing
+ *     is rebuilt.
+ * Pipelining, exactly as xrt_scene_set_poses: the call may be made while one or two begin/end tickets are open, and neither synchronises
+ * the device nor waits for the frames in flight.  A frame renders with the materials set before its _begin, never with later ones --
+ * including the choice between the plain and the ray-tree pipeline and the max_reflections <= 12 limit of Transparent materials, which
+ * follow the frame's own materials; xrt_cast_rays* use the latest materials.  XRT_E_BUSY only while another thread is inside a render
+ * call on the scene. */
+int xrt_scene_set_materials(xrt_scene *scene, const int32_t *mesh_ids, int32_t n, const xrt_material *materials);
+
 #ifdef __cplusplus
 }
 #endif

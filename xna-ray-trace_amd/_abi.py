@@ -148,6 +148,7 @@ SYMBOLS = {
     "xrt_scene_set_poses": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int32, _F, _F, _F]),
     "xrt_scene_set_poses_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "xrt_scene_build_tree": (C.c_int, [C.c_void_p, C.c_int32]),
+    "xrt_scene_set_materials": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int32, _P(xrt_material)]),
 }
 
 _lib = None

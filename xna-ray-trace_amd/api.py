@@ -23,8 +23,37 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _material_property(name, convert, texels=False):
+    """A reference property of Material with a public setter (MAT:39, 234-268): setting it bumps the serial the spatial manager compares
+    (and, for the texel arrays, the serial that says the library's texels are behind)."""
+    attr = "_" + name
+
+    def get(self):
+        return getattr(self, attr)
+
+    def set_(self, value):
+        setattr(self, attr, convert(value))
+        self._serial = getattr(self, "_serial", 0) + 1
+        if texels:
+            self._tex_serial = getattr(self, "_tex_serial", 0) + 1
+    return property(get, set_)
+
+
+def _texel_array(value):
+    return None if value is None else np.ascontiguousarray(value, dtype=np.uint32)
+
+
 class Material:
-    """Material.cs:25-269 (shading inputs; texels as the Format32bppArgb lock of MAT:65)."""
+    """Material.cs:25-269 (shading inputs; texels as the Format32bppArgb lock of MAT:65).  Reflectiveness, Transparent, RefractionIndex,
+    InterpolateNormals, UseTexture and Texture / TexturePArgb may be set after the scene is built: the OctreeSpatialManager the material's
+    meshes are in hands the change to the library before its next query or frame (xrt_scene_set_materials)."""
+    Reflectiveness = _material_property("Reflectiveness", float)
+    UseTexture = _material_property("UseTexture", bool)
+    Transparent = _material_property("Transparent", bool)
+    RefractionIndex = _material_property("RefractionIndex", float)
+    InterpolateNormals = _material_property("InterpolateNormals", bool)
+    Texture = _material_property("Texture", _texel_array, texels=True)
+    TexturePArgb = _material_property("TexturePArgb", _texel_array, texels=True)
 
     def __init__(self, reflectiveness=0.0, useTexture=False, transparent=False, refractionIndex=0.0, texture=None, texture_pargb=None, textureFilePath=None):
         self.Reflectiveness = float(reflectiveness)
@@ -62,6 +91,23 @@ class Material:
                 if self.TexturePArgb.shape != self.Texture.shape:
                     raise ValueError("Texture.ColorData must have the size of the bitmap")
                 m.tex_pargb = self.TexturePArgb.ctypes.data_as(C.POINTER(C.c_uint32))
+        return m
+
+    def _to_abi_update(self, texels):
+        """The xrt_material of an xrt_scene_set_materials entry: with the texel arrays, or with NULL texels (the library keeps the ones it has)."""
+        m = abi.xrt_material()
+        m.reflectiveness, m.transparent, m.refraction_index = self.Reflectiveness, int(self.Transparent), self.RefractionIndex
+        m.interpolate_normals, m.use_texture = int(self.InterpolateNormals), int(self.UseTexture)
+        if texels:
+            if self.Texture is None:
+                self.Init()   # (UseTexture without a bitmap: the file, or ValueError as Bitmap.FromFile(null), MAT:63)
+            if self.Texture is not None:
+                m.tex_height, m.tex_width = self.Texture.shape
+                m.tex_argb = self.Texture.ctypes.data_as(C.POINTER(C.c_uint32))
+                if self.TexturePArgb is not None:
+                    if self.TexturePArgb.shape != self.Texture.shape:
+                        raise ValueError("Texture.ColorData must have the size of the bitmap")
+                    m.tex_pargb = self.TexturePArgb.ctypes.data_as(C.POINTER(C.c_uint32))
         return m
 
 
@@ -271,6 +317,8 @@ class OctreeSpatialManager(ISpatialManager):
         self.meshes = []
         self._built_key = None   # the bodies and meshes of the last Build
         self._pushed = []        # per body: the pose serial the library has
+        self._pushed_mats = []   # per mesh: (its Material, the material's serial) the library has
+        self._pushed_tex = []    # per mesh: (Material, texel serial) of the texels the library has, or None
 
     def _key(self):
         return (self.meshItemTreshold, tuple((id(b), tuple(id(m) for m in b.Meshes)) for b in self.Bodies))
@@ -279,6 +327,7 @@ class OctreeSpatialManager(ISpatialManager):
         if self._scene is not None and self._built_key == self._key():
             # same bodies and meshes: OctreeSpatialManager.Build alone over the current poses (xrt_scene_build_tree)
             self._push_poses()
+            self._push_materials()
             abi.check(abi.lib().xrt_scene_build_tree(self._scene.handle, self.itemTreshold))
             return
         self._scene = _Scene(self.device)
@@ -299,6 +348,8 @@ class OctreeSpatialManager(ISpatialManager):
         abi.check(abi.lib().xrt_scene_build(self._scene.handle, self.meshItemTreshold, self.itemTreshold))
         self._built_key = self._key()
         self._pushed = [b._pose_serial for b in self.Bodies]
+        self._pushed_mats = [(m.MeshMaterial, m.MeshMaterial._serial) for m in self.meshes]
+        self._pushed_tex = [(m.MeshMaterial, m.MeshMaterial._tex_serial) if m.MeshMaterial.UseTexture else None for m in self.meshes]
 
     def _push_poses(self):
         """The poses of the bodies moved since the last push, in one xrt_scene_set_poses (before every query and frame)."""
@@ -321,6 +372,42 @@ class OctreeSpatialManager(ISpatialManager):
             raise ValueError("SetPoses: 16 + 16 + 6 floats per id")
         abi.check(abi.lib().xrt_scene_set_poses(self.handle, ids.ctypes.data_as(C.POINTER(C.c_int32)), n, _fp(w), _fp(iw), _fp(bb)))
 
+    def _push_materials(self):
+        """The materials changed since the last push -- a property set, or another Material assigned to Mesh.MeshMaterial -- in one
+        xrt_scene_set_materials (before every query, frame, Save and Build).  A Material shared by several meshes goes to each of them
+        (TMP:121-131).  Texels travel only when the library's are behind."""
+        if self._scene is None or self._built_key is None:
+            return
+        ids, mats, done = [], [], []
+        for i, mesh in enumerate(self.meshes):
+            mat = mesh.MeshMaterial
+            had, serial = self._pushed_mats[i]
+            if had is mat and serial == mat._serial:
+                continue
+            tex = self._pushed_tex[i]
+            need_tex = (mat.UseTexture or mat.Texture is not None) and not (tex is not None and tex[0] is mat and tex[1] == mat._tex_serial)
+            ids.append(i)
+            mats.append(mat._to_abi_update(need_tex))
+            done.append((i, mat, need_tex))
+        if ids:
+            self.SetMaterials(ids, mats)
+            for i, mat, sent in done:
+                self._pushed_mats[i] = (mat, mat._serial)
+                if sent:
+                    self._pushed_tex[i] = (mat, mat._tex_serial)
+
+    def SetMaterials(self, mesh_ids, materials):
+        """xrt_scene_set_materials: mesh mesh_ids[i] takes materials[i] -- a Material (its texels travel when it has any; without them the
+        library keeps the ones the mesh has) or an abi.xrt_material as the C-ABI takes it.  Nothing is rebuilt."""
+        ids = np.ascontiguousarray(mesh_ids, dtype=np.int32).reshape(-1)
+        materials = list(materials)
+        if len(materials) != ids.shape[0]:
+            raise ValueError("SetMaterials: one material per mesh id")
+        arr = (abi.xrt_material * max(len(materials), 1))()
+        for i, m in enumerate(materials):   # (the Materials own the texel arrays the structs point into)
+            arr[i] = m if isinstance(m, abi.xrt_material) else m._to_abi_update(m.Texture is not None)
+        abi.check(abi.lib().xrt_scene_set_materials(self.handle, ids.ctypes.data_as(C.POINTER(C.c_int32)), ids.shape[0], arr))
+
     def SetPosesDevice(self, ids, world, inv, wbb, stream=None):
         """xrt_scene_set_poses_device on CUDA tensors (int32 ids; float32 world / inv with 16 and wbb with 6 values per id, contiguous),
         ordered after `stream` (a torch stream; default: the current one)."""
@@ -335,6 +422,7 @@ class OctreeSpatialManager(ISpatialManager):
 
     def Save(self, path):
         """xrt_scene_save: the built scene's meshes, materials, texels and bodies as one file (the reference's .xnb content)."""
+        self._push_materials()
         abi.check(abi.lib().xrt_scene_save(self.handle, str(path).encode()))
 
     @classmethod
@@ -375,6 +463,7 @@ class OctreeSpatialManager(ISpatialManager):
         hits = np.zeros(rays.shape[0], dtype=HIT_DTYPE)
         st = abi.xrt_stats()
         self._push_poses()
+        self._push_materials()
         abi.check(abi.lib().xrt_scene_intersect(self.handle, rays.ctypes.data_as(C.POINTER(abi.xrt_ray)), None, rays.shape[0],
                                                 hits.ctypes.data_as(C.POINTER(abi.xrt_hit)), C.byref(st) if stats else None))
         return (hits, st.as_dict()) if stats else hits
@@ -501,10 +590,13 @@ class RayTracer:
         self.renderTargetData = np.zeros(value.Width * value.Height, dtype=np.uint32)     # RT:29
 
     def _scene_handle(self):
-        """The current scene's handle, after the bodies moved since the last frame have been handed over (SO:52-89)."""
+        """The current scene's handle, after the bodies moved and the materials changed since the last frame have been handed over
+        (SO:52-89; MAT:39, 234-268)."""
         sc = self.CurrentScene
         if hasattr(sc, "_push_poses"):
             sc._push_poses()
+        if hasattr(sc, "_push_materials"):
+            sc._push_materials()
         return sc.handle
 
     @property

@@ -158,6 +158,30 @@ static void spatial_runs_cut(const HostMesh &m, std::vector<int> &lr, int b0, in
     }
 }
 
+// The MaterialRec of mesh m when its texels (and behind them their premultiplied copy) start at word `off` of the arena; off moves past them.  The
+// texels a mesh holds have their place whether or not UseTexture is set: the flag alone decides what the kernels read (xrt_scene_set_materials).
+static MaterialRec material_record(const HostMesh &m, size_t &off) {
+    MaterialRec mat;
+    std::memset(&mat, 0, sizeof(mat));
+    mat.reflectiveness = m.reflectiveness;
+    mat.refractionIndex = m.refractionIndex;
+    mat.flags = (m.transparent ? MAT_TRANSPARENT : 0) | (m.interpolateNormals ? MAT_INTERP : 0) | (m.useTexture ? MAT_TEXTURE : 0);
+    mat.texOffset = (int)off;
+    mat.texWidth = m.texW; mat.texHeight = m.texH;
+    off += m.texels.size();
+    mat.texOffsetP = mat.texOffset;
+    if (!m.texelsP.empty()) { mat.texOffsetP = (int)off; off += m.texelsP.size(); }
+    return mat;
+}
+static void append_material(SceneArrays &A, const HostMesh &m) {
+    size_t off = A.texels.size();
+    A.materials.push_back(material_record(m, off));
+    A.texels.insert(A.texels.end(), m.texels.begin(), m.texels.end());
+    A.texels.insert(A.texels.end(), m.texelsP.begin(), m.texelsP.end());
+    A.anyTransparent = A.anyTransparent || m.transparent;
+    A.anyTexture = A.anyTexture || m.useTexture;
+}
+
 bool HostScene::build(int meshThreshold, int sceneThreshold, std::string &err) {
     if (meshThreshold <= 0) meshThreshold = 50;    // MO:42
     if (sceneThreshold <= 0) sceneThreshold = 20;  // OSM:50
@@ -341,19 +365,7 @@ bool HostScene::build(int meshThreshold, int sceneThreshold, std::string &err) {
             A.refG.push_back(g3{p[3] - p[0], p[4] - p[1], p[5] - p[2]});   // Edge1 = v2 - v1 (RE:54)
             A.refG.push_back(g3{p[6] - p[0], p[7] - p[1], p[8] - p[2]});   // Edge2 = v3 - v1 (RE:55)
         }
-        MaterialRec mat;
-        std::memset(&mat, 0, sizeof(mat));
-        mat.reflectiveness = m.reflectiveness;
-        mat.refractionIndex = m.refractionIndex;
-        mat.flags = (m.transparent ? MAT_TRANSPARENT : 0) | (m.interpolateNormals ? MAT_INTERP : 0) | (m.useTexture ? MAT_TEXTURE : 0);
-        mat.texOffset = (int)A.texels.size();
-        mat.texWidth = m.texW; mat.texHeight = m.texH;
-        A.texels.insert(A.texels.end(), m.texels.begin(), m.texels.end());
-        mat.texOffsetP = mat.texOffset;
-        if (!m.texelsP.empty()) { mat.texOffsetP = (int)A.texels.size(); A.texels.insert(A.texels.end(), m.texelsP.begin(), m.texelsP.end()); }
-        A.materials.push_back(mat);
-        A.anyTransparent = A.anyTransparent || m.transparent;
-        A.anyTexture = A.anyTexture || m.useTexture;
+        append_material(A, m);
         for (int i = 0; i < m.ntri; i++) {
             const float *n = &m.n[(size_t)i * 9], *uv = &m.uv[(size_t)i * 6], *c = &m.color[(size_t)i * 4], *sn = &m.sn[(size_t)i * 3];
             A.shade.push_back(f4{n[0], n[1], n[2], uv[0]});
@@ -470,6 +482,73 @@ bool HostScene::set_pose(int id, const float *world, const float *invWorld, cons
     return true;
 }
 
+bool HostScene::set_materials(const int *ids, int n, const xrt_material *mats, MaterialEdit &edit, std::string &err) {
+    edit = MaterialEdit();
+    if (n < 0 || (n > 0 && (!ids || !mats))) { err = "xrt_scene_set_materials: null argument"; return false; }
+    const int nMesh = (int)meshes.size();
+    for (int i = 0; i < n; i++)
+        if (ids[i] < 0 || ids[i] >= nMesh) { err = "xrt_scene_set_materials: mesh id " + std::to_string(ids[i]) + " out of range (" + std::to_string(nMesh) + " meshes)"; return false; }
+    // the last entry of a mesh wins (the setters called one after the other); everything is checked before anything is applied
+    std::vector<int> last((size_t)nMesh, -1), order;
+    for (int i = 0; i < n; i++) last[(size_t)ids[i]] = i;
+    for (int i = 0; i < n; i++) if (last[(size_t)ids[i]] == i) order.push_back(i);
+    for (int i : order) {
+        const xrt_material &m = mats[i];
+        const HostMesh &hm = meshes[(size_t)ids[i]];
+        if (m.tex_argb) {
+            if (m.tex_width <= 0 || m.tex_height <= 0 || (long long)m.tex_width * m.tex_height > (1LL << 30)) { err = "xrt_scene_set_materials: texels of " + std::to_string(m.tex_width) + " x " + std::to_string(m.tex_height); return false; }
+        } else if (m.use_texture) {
+            if (hm.texels.empty()) { err = "xrt_scene_set_materials: UseTexture without texels on a mesh that has none (the bitmap was never locked, MAT:65)"; return false; }
+            if (!((m.tex_width == 0 && m.tex_height == 0) || (m.tex_width == hm.texW && m.tex_height == hm.texH))) { err = "xrt_scene_set_materials: tex_width / tex_height differ from the texels the mesh keeps"; return false; }
+        }
+    }
+    bool repack = false;
+    for (int i : order) {
+        const xrt_material &m = mats[i];
+        HostMesh &hm = meshes[(size_t)ids[i]];
+        hm.reflectiveness = m.reflectiveness;
+        hm.refractionIndex = m.refraction_index;
+        hm.transparent = m.transparent != 0;
+        hm.interpolateNormals = m.interpolate_normals != 0;
+        hm.useTexture = m.use_texture != 0;
+        if (!m.tex_argb) continue;
+        const size_t count = (size_t)m.tex_width * (size_t)m.tex_height;
+        const bool sameShape = hm.texels.size() == count && hm.texelsP.empty() == (m.tex_pargb == nullptr);
+        hm.texW = m.tex_width; hm.texH = m.tex_height;
+        hm.texels.assign(m.tex_argb, m.tex_argb + count);
+        if (m.tex_pargb) hm.texelsP.assign(m.tex_pargb, m.tex_pargb + count); else hm.texelsP.clear();
+        edit.texels = true;
+        if (!built || repack) continue;
+        if (!sameShape) { repack = true; continue; }
+        // texels of the size the mesh had: written over the old ones where they lie in the arena
+        const MaterialRec &r = arrays.materials[(size_t)ids[i]];
+        std::copy(hm.texels.begin(), hm.texels.end(), arrays.texels.begin() + r.texOffset);
+        if (!hm.texelsP.empty()) std::copy(hm.texelsP.begin(), hm.texelsP.end(), arrays.texels.begin() + r.texOffsetP);
+        const size_t lo = (size_t)r.texOffset, hi = (size_t)(hm.texelsP.empty() ? r.texOffset : r.texOffsetP) + count;
+        if (edit.texHi == edit.texLo) { edit.texLo = lo; edit.texHi = hi; }
+        else { edit.texLo = std::min(edit.texLo, lo); edit.texHi = std::max(edit.texHi, hi); }
+    }
+    if (!built) return true;   // (the next build reads the materials)
+    SceneArrays &A = arrays;
+    A.anyTransparent = A.anyTexture = false;   // over ALL meshes: turning the last Transparent material opaque clears the flag
+    if (repack) {   // some texels changed their size: the arena is packed again, as build packs it
+        A.materials.clear();
+        A.texels.clear();
+        for (const HostMesh &hm : meshes) append_material(A, hm);
+        if (A.texels.empty()) A.texels.assign(1, 0u);
+        edit.texFull = true;
+    } else {        // the records again, the texels where they are
+        size_t off = 0;
+        for (size_t k = 0; k < meshes.size(); k++) {
+            A.materials[k] = material_record(meshes[k], off);
+            A.anyTransparent = A.anyTransparent || meshes[k].transparent;
+            A.anyTexture = A.anyTexture || meshes[k].useTexture;
+        }
+    }
+    if (edit.texFull) { edit.texLo = 0; edit.texHi = A.texels.size(); }
+    return true;
+}
+
 bool HostScene::build_tree(int sceneThreshold, std::string &err) {
     if (!built) { err = "xrt_scene_build_tree: call xrt_scene_build first"; return false; }
     if (sceneThreshold <= 0) sceneThreshold = 20;  // OSM:50
@@ -515,12 +594,13 @@ bool HostScene::save(const char *path, std::string &err) const {
     w.one<uint32_t>(1); w.one<uint32_t>((uint32_t)meshes.size()); w.one<uint32_t>((uint32_t)objects.size());
     for (const HostMesh &m : meshes) {
         w.one<int32_t>(m.ntri); w.put(m.bbox, 6); w.one<float>(m.reflectiveness); w.one<float>(m.refractionIndex);
-        w.one<int32_t>((m.transparent ? 1 : 0) | (m.interpolateNormals ? 2 : 0) | (m.useTexture ? 4 : 0) | (m.texelsP.empty() ? 0 : 8));
-        w.one<int32_t>(m.texW); w.one<int32_t>(m.texH);
+        // (texels a mesh keeps while UseTexture is off -- xrt_scene_set_materials -- are not part of the file: it holds what add_mesh would be given)
+        w.one<int32_t>((m.transparent ? 1 : 0) | (m.interpolateNormals ? 2 : 0) | (m.useTexture ? 4 : 0) | (m.useTexture && !m.texelsP.empty() ? 8 : 0));
+        w.one<int32_t>(m.useTexture ? m.texW : 0); w.one<int32_t>(m.useTexture ? m.texH : 0);
         w.put(m.v.data(), m.v.size()); w.put(m.n.data(), m.n.size()); w.put(m.uv.data(), m.uv.size()); w.put(m.sn.data(), m.sn.size());
         w.put(m.color.data(), m.color.size());
         if (m.useTexture) w.put(m.texels.data(), m.texels.size());
-        if (!m.texelsP.empty()) w.put(m.texelsP.data(), m.texelsP.size());
+        if (m.useTexture && !m.texelsP.empty()) w.put(m.texelsP.data(), m.texelsP.size());
     }
     for (const HostObject &o : objects) {
         w.one<int32_t>((int32_t)o.meshes.size()); w.put(o.meshes.data(), o.meshes.size());

@@ -64,6 +64,12 @@ struct HostScene {
     bool set_pose(int id, const float *world, const float *invWorld, const float *worldBbox, std::string &err);
     // OctreeSpatialManager.Build alone over the current poses (0 = OSM:50's 20): meshes, their octrees and the ObjRecs are untouched.
     bool build_tree(int sceneThreshold, std::string &err);
+    // Material's setters (MAT:39, 234-268), batched: mesh ids[i] takes mats[i] (xrt.h xrt_scene_set_materials: the texel cases, all or
+    // nothing, the last entry of a mesh wins).  After a build also the MaterialRecs, the texel arena and anyTransparent / anyTexture of
+    // `arrays`; nothing else of it is touched.  texLo / texHi: the words of arrays.texels that changed (texFull: the arena was packed again,
+    // every offset may have moved).
+    struct MaterialEdit { bool texels = false, texFull = false; size_t texLo = 0, texHi = 0; };
+    bool set_materials(const int *ids, int n, const xrt_material *mats, MaterialEdit &edit, std::string &err);
     // Scene file (xrt_scene_save / xrt_scene_load): the meshes, materials, texels and bodies exactly as they were added --
     // what the reference keeps in .xnb files (Model.Tag, TMP:113-117) -- little-endian, no pointers.  The trees are rebuilt on load.
     bool save(const char *path, std::string &err) const;

@@ -90,6 +90,32 @@ struct xrt_scene {
     DevBuf<float> poseIn;                  // the host form's arrays on the device: ids | world | inv | wbb
     Pinned<void> posePinned;               // ... and their page-locked staging
     Event poseStaged;                      // the staging copy is done (the staging may be refilled)
+    // Material versions (xrt_scene_set_materials), as the pose versions: a frame reads the MaterialRec table and the texel arena of ONE version,
+    // the one that was current at its begin (FrameCtx::mat), and takes the plain or the ray-tree pipeline by THAT version's anyTransparent.
+    // Version 0 is `materials` / `texels`; versions 1 and 2 are made when an update must not overwrite what an open ticket reads.  Every
+    // version holds a whole arena (DESIGN.md "Material versions": at most three copies of every texture).  An update only STAGES what the
+    // version lacks, in page-locked memory of the version's own; the copies to the device are enqueued by the first frame or ray batch that
+    // reads the version, on ITS stream ahead of its kernels (mat_acquire): an update has no stream and no dispatch of its own that would have
+    // to find room among the persistent waves of the frames in flight (profiles/materials).
+    struct MatVer {
+        DevBuf<MaterialRec> materials;   // (version 0: the scene's own `materials` / `texels`)
+        DevBuf<uint32_t> texels;
+        Pinned<void> staging;              // MaterialRecs | texels [stagedLo, stagedHi) of the newest write, until its copies have run
+        bool pending = false;              // staged, the copies not enqueued yet
+        size_t stagedRecBytes = 0, stagedMat = 0, stagedLo = 0, stagedHi = 0;
+        hipStream_t owner = nullptr;       // the stream the copies were enqueued on (work on it is behind them anyway) ...
+        Event ready;                       // ... and the event recorded behind them there, for readers on other streams; null while it holds the build's records
+        unsigned long long serial = 0;     // which write it holds (a replica copies the primary's version when the serials differ)
+        bool anyTransparent = false;       // SceneArrays::anyTransparent of the materials it holds
+        size_t texCount = 0;               // words of its arena
+        bool texFull = false;              // its arena is behind the host's as a whole (never written, or the host's was packed again) ...
+        size_t texLo = 0, texHi = 0;       // ... or in these words only
+    } mat[3];
+    int matCur = 0;                        // the version new frames and ray batches read
+    int slotMat[2] = {-1, -1};             // the version of the open ticket `slot`
+    unsigned long long matSerial = 0;      // writes since the build
+    Stream matStream;                      // (n_gpus > 1: the primary's copies run here when its replicas need the version before its own frame is enqueued)
+    std::vector<DevBuf<uint32_t>> matRetired;   // arenas that were outgrown while a ticket was open: freed when none is (hipFree waits for the device)
     bool resident = false;
     int numCUs = 256;
     int stackNeeded = 2;
@@ -104,6 +130,7 @@ struct xrt_scene {
     // launches of the next frame of the same geometry are sized for four times that instead of for the whole chip -- a generation
     // of a few thousand rays costs its kernels' launch floor (5-6 us each with full grids, C2: 0.119 -> 0.11 ms).  Sizing only.
     long long genKey = -1, genRays[68], genShade[68];
+    bool genHeap = false;        // ... made by a ray-tree frame (a frame of the other pipeline takes no hints from them: the counter words mean other things)
     long long genCompose = -1;   // ... and the length of its compose list (kernels.h EndArgs; -1: the frame had none)
     unsigned long long endCounts[3] = {0, 0, 0};   // xrt_debug_end_counts: the last finished frame's paths coloured by k_raygen, by k_shade, and on the compose list
     int lvlCheckedTilesX = 0; long long lvlCheckedTiles = 0;   // (LvlMap::inv verified for this frame geometry)
@@ -181,6 +208,7 @@ struct xrt_scene {
         Event done;                  // recorded after the frame's last copy
         std::vector<LightRec> hostLights;
         int pose = 0;                // the pose version the frame reads (xrt_scene::pose)
+        int mat = 0;                 // the material version the frame reads (xrt_scene::mat)
         bool pending = false;
         bool fast = false;           // no copy / fill / event-record commands: k_compose hands the counters over, events ride on kernels
         long long framePaths = 0;    // paths of the frame (part) this context holds: key of the grid hints

@@ -73,6 +73,38 @@ int pose_reader(xrt_scene *s, int v, hipStream_t st) {
 }
 bool pose_referenced(const xrt_scene *s, int v) { return s->slotPose[0] == v || s->slotPose[1] == v; }
 
+// ---- material versions (xrt_scene_set_materials) ---------------------------------------------------------------------------
+DevBuf<MaterialRec> &mat_records(xrt_scene *s, int v) { return v == 0 ? s->materials : s->mat[v].materials; }
+DevBuf<uint32_t> &mat_texels(xrt_scene *s, int v) { return v == 0 ? s->texels : s->mat[v].texels; }
+// Work enqueued on `st` after this call may read version v.  The first reader of a staged write enqueues its copies on `st` itself (they
+// are ahead of whatever it enqueues next) and records the version's event behind them; a reader on another stream waits for that event.
+int mat_acquire(xrt_scene *s, int v, hipStream_t st) {
+    xrt_scene::MatVer &M = s->mat[v];
+    if (M.pending) {
+        const char *src = (const char *)M.staging.p;
+        HIPCHECK(hipMemcpyAsync(mat_records(s, v).p, src, M.stagedMat * sizeof(MaterialRec), hipMemcpyHostToDevice, st));
+        if (M.stagedHi > M.stagedLo)
+            HIPCHECK(hipMemcpyAsync(mat_texels(s, v).p + M.stagedLo, src + M.stagedRecBytes, (M.stagedHi - M.stagedLo) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (int rc = M.ready.create()) return rc;
+        HIPCHECK(hipEventRecord(M.ready, st));
+        M.owner = st;
+        M.pending = false;
+        return XRT_OK;
+    }
+    if (M.ready && M.owner != st) HIPCHECK(hipStreamWaitEvent(st, M.ready, 0));
+    return XRT_OK;
+}
+bool mat_referenced(const xrt_scene *s, int v) { return s->slotMat[0] == v || s->slotMat[1] == v; }
+// Room for n texels in b.  An arena that is outgrown is set aside, not freed: hipFree would wait for the frames in flight.
+int mat_texel_room(xrt_scene *s, DevBuf<uint32_t> &b, size_t n) {
+    if (b.p && n <= b.cap) return XRT_OK;
+    DevBuf<uint32_t> fresh;
+    if (int rc = fresh.ensure(n + n / 2)) return rc;   // (half as much again: textures whose size changes a little do not allocate every time)
+    std::swap(b, fresh);
+    if (fresh.p) s->matRetired.push_back(std::move(fresh));
+    return XRT_OK;
+}
+
 int persistent_grid(xrt_scene *s, long long nHost, int raysPerBlock = 256) {
     int full = s->numCUs * s->blocksPerCU;
     if (nHost >= 0) {
@@ -274,7 +306,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         return fail(XRT_E_INVALID_ARG, "Value does not fall within the expected range: addressMode (MAT:85)");
     if (opts->filtering != XRT_FILTER_POINT && opts->filtering != XRT_FILTER_BILINEAR)
         return fail(XRT_E_INVALID_ARG, "Value does not fall within the expected range: filtering (MAT:97)");
-    const bool heap = s->host->arrays.anyTransparent && opts->max_reflections > 0;   // RT:586-702: binary ray tree
+    const bool heap = s->mat[F.mat].anyTransparent && opts->max_reflections > 0;   // RT:586-702: binary ray tree (by the materials of the frame's version)
     if (heap && opts->max_reflections > 12)
         return fail(XRT_E_UNSUPPORTED, "Transparent materials with MaxReflections > 12 (a ray tree of more than 8191 nodes per pixel)");
     const int msMode = opts->use_multisampling;
@@ -483,7 +515,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
             st = W.stream;
         } else st = s->stream;
     }
-    if ((rc = pose_wait(s, F.pose, st))) return rc;   // (the poses set before the frame's begin)
+    if ((rc = pose_wait(s, F.pose, st)) || (rc = mat_acquire(s, F.mat, st))) return rc;   // (the poses and materials set before the frame's begin)
     if (pout) {   // staging records like the level records: one per node and path of a chunk; cleared when allocated, told apart by tag afterwards
         auto ensure_cleared = [&](DevBuf<f4> &b, size_t n) -> int {
             const f4 *before = b.p; const size_t capBefore = b.cap;
@@ -569,9 +601,9 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         W.lightsDevPtr = W.lights.p;
     }
     ShadeView V;
-    V.shade = s->shade.p; V.materials = s->materials.p; V.texels = s->texels.p; V.meshes = s->meshes.p;
+    V.shade = s->shade.p; V.materials = mat_records(s, F.mat).p; V.texels = mat_texels(s, F.mat).p; V.meshes = s->meshes.p;
     V.lights = W.lights.p; V.nLights = nL; V.addressMode = opts->address_mode; V.filtering = opts->filtering;
-    const SceneView S = pose_view(s, F.pose);   // every kernel of the frame reads one pose version
+    const SceneView S = pose_view(s, F.pose);   // every kernel of the frame reads one pose version (and, above, one material version)
     xrt_ray *rays[2] = {W.rays0.p, W.rays1.p};
     int *paths[2] = {W.path0.p, W.path1.p};
     int *nodesOf[2] = {W.node0.p, W.node1.p};
@@ -628,7 +660,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         // (generation 0 and 1 and the shadow rays of generation 0 are the big coherent populations; after two bounces the 64 rays
         // of a packet have little in common and a few packets take three times as long as the rest of their launch: bit 4)
         auto packet_closest = [&](int k) { return (k == 0 ? (pkMask & 1) : (k == 1 ? (pkMask & 4) : ((pkMask & 4) && (pkMask & 16)))) != 0; };
-        const bool hinted = fast && nParts == 1 && s->genKey == firstPaths * 64 + nL && s->cfg.gridHints;
+        const bool hinted = fast && nParts == 1 && s->genKey == firstPaths * 64 + nL && s->genHeap == heap && s->cfg.gridHints;
         auto hint = [&](const long long *v, int k) -> long long { return (hinted && k < 68 && v[k] >= 0) ? 4 * v[k] + 4096 : -1; };
         auto packet_shadow = [&](int k) { return (pkMask & 2) != 0 && (k <= 1 || (pkMask & 16) != 0); };   // shadow rays of generation k-1
         auto heavy_for = [&](int k) {
@@ -1118,12 +1150,12 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
         // (adaptive frames in flight put the level-count words in front of the per-pass counters and have no framePaths key: no hints from them)
         if (F.fast && F.tallyChunks == 1 && !F.adaptiveFast) {   // sizes of this frame's generations: grid hints for the next one (sizing only)
             const int *hc = F.pinned.p + F.cntBase;
-            const bool same0 = s->genKey == F.framePaths * 64 + F.nL;
+            const bool same0 = s->genKey == F.framePaths * 64 + F.nL && s->genHeap == F.heap;
             for (int k = 0; k <= R + 1 && k < 68; k++) {
                 const long long closest = (k == 0 || ((F.heap || F.ae) && k <= R)) ? hc[k] : (k <= R ? gen_hits(hc, R, k - 1) : 0), shaded = k >= 1 ? gen_hits(hc, R, k - 1) : 0;
                 // (a hint shrinks by an eighth per frame at most: a camera that looks away for a frame, or alternates between two views,
                 // must not leave the next full view with a grid of sixteen blocks)
-                const bool same = s->genKey == F.framePaths * 64 + F.nL;
+                const bool same = same0;
                 const long long rays = closest + shaded * F.nL, work = closest > shaded ? closest : shaded;
                 const long long keepR = same && s->genRays[k] > 0 ? s->genRays[k] - s->genRays[k] / 8 : 0, keepS = same && s->genShade[k] > 0 ? s->genShade[k] - s->genShade[k] / 8 : 0;
                 s->genRays[k] = rays > keepR ? rays : keepR;
@@ -1135,6 +1167,7 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
                 s->genCompose = listed < 0 ? -1 : (listed > keep ? listed : keep);
             }
             s->genKey = F.framePaths * 64 + F.nL;
+            s->genHeap = F.heap;
         }
         if (F.fast && s->costMap.p && !F.adaptiveFast) {   // steer the "long ray" thresholds towards 2-6 % of each generation's rays
             const int *hc = F.pinned.p + F.cntBase;
@@ -1225,6 +1258,9 @@ int ensure_replicas(xrt_scene *s, int n) {
         // the replica's version 0 holds the host's records: the primary's version 0 only while no pose was set since the build
         for (auto &v : r->pose) v.serial = ~0ull;
         if (s->poseSerial == 0) r->pose[0].serial = 0;
+        // ... and the host's materials: the primary's CURRENT version (scene_upload read the host arrays); every frame's version arrives by replica_material
+        for (auto &v : r->mat) v.serial = ~0ull;
+        if (s->matCur == 0) r->mat[0].serial = s->mat[0].serial;
         s->workers.emplace_back(new RankWorker(r->device));
         s->replicas.push_back(std::move(r));
     }
@@ -1273,6 +1309,34 @@ int replica_pose(xrt_scene *s, xrt_scene *r, int v) {
     if ((rc = R.ready.create())) return rc;
     HIPCHECK(hipEventRecord(R.ready, r->stream));
     R.serial = P.serial;
+    return XRT_OK;
+}
+
+// Replica r renders version v of the primary's materials: its MaterialRecs, its texel arena and its anyTransparent, copied when r's copy is of
+// another write -- the route replica_pose takes.
+int replica_material(xrt_scene *s, xrt_scene *r, int v) {
+    xrt_scene::MatVer &P = s->mat[v], &R = r->mat[v];
+    if (R.serial == P.serial) return XRT_OK;
+    const size_t nMat = s->host->arrays.materials.size(), nTex = P.texCount;
+    int rc;
+    if (P.pending) {   // (the primary's own copies: its frame is enqueued after its replicas' copies are)
+        HIPCHECK(hipSetDevice(s->device));
+        if ((rc = s->matStream.create()) || (rc = mat_acquire(s, v, s->matStream))) return rc;
+    }
+    HIPCHECK(hipSetDevice(r->device));
+    if ((rc = mat_records(r, v).ensure(nMat)) || (rc = mat_texel_room(r, mat_texels(r, v), nTex))) return rc;
+    if (P.ready) HIPCHECK(hipStreamWaitEvent(r->stream, P.ready, 0));
+    if (r->device == s->device) {
+        HIPCHECK(hipMemcpyAsync(mat_records(r, v).p, mat_records(s, v).p, nMat * sizeof(MaterialRec), hipMemcpyDeviceToDevice, r->stream));
+        HIPCHECK(hipMemcpyAsync(mat_texels(r, v).p, mat_texels(s, v).p, nTex * sizeof(uint32_t), hipMemcpyDeviceToDevice, r->stream));
+    } else {
+        HIPCHECK(hipMemcpyPeerAsync(mat_records(r, v).p, r->device, mat_records(s, v).p, s->device, nMat * sizeof(MaterialRec), r->stream));
+        HIPCHECK(hipMemcpyPeerAsync(mat_texels(r, v).p, r->device, mat_texels(s, v).p, s->device, nTex * sizeof(uint32_t), r->stream));
+    }
+    if ((rc = R.ready.create())) return rc;
+    HIPCHECK(hipEventRecord(R.ready, r->stream));
+    R.owner = r->stream;
+    R.serial = P.serial; R.anyTransparent = P.anyTransparent; R.texCount = nTex;
     return XRT_OK;
 }
 
@@ -1330,7 +1394,7 @@ int multi_begin(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_light *
         if (s->cfg.fakeGpus && (rc = r->tilesReady[slot].create())) return rc;
     }
     for (int i = 1; i < n; i++)
-        if ((rc = replica_pose(s, rank_scene(s, i), s->slotPose[slot]))) { (void)hipSetDevice(s->device); return rc; }
+        if ((rc = replica_pose(s, rank_scene(s, i), s->slotPose[slot])) || (rc = replica_material(s, rank_scene(s, i), s->slotMat[slot]))) { (void)hipSetDevice(s->device); return rc; }
     HIPCHECK(hipSetDevice(s->device));
     // every device's share is enqueued by its own (persistent) host thread
     std::vector<int> rcs((size_t)n, XRT_OK);
@@ -1341,7 +1405,8 @@ int multi_begin(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_light *
         xrt_render_opts o = *opts;
         o.n_gpus = 0; o.shard_rank = i; o.shard_count = n;
         uint32_t *dst = i == 0 ? s->gathered[slot].p : r->tileOut[slot].p;
-        r->frames[slot].pose = s->slotPose[slot];   // (every rank renders the primary's version)
+        r->frames[slot].pose = s->slotPose[slot];   // (every rank renders the primary's versions)
+        r->frames[slot].mat = s->slotMat[slot];
         rcs[(size_t)i] = frame_begin(r, r->frames[slot], cam, lights, nLights, &o, dst, nullptr, nullptr, 0, 1, false);   // (the gather is enqueued behind the frame: no redo)
         if (rcs[(size_t)i] != XRT_OK) errs[(size_t)i] = g_err;
     };
@@ -1469,16 +1534,17 @@ int open_frame_impl(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_lig
     }
     hipStream_t st0 = nullptr;
     int nParts = 1;
-    s->slotPose[slot] = s->poseCur;   // the frame renders the poses set before its begin, whatever is set while it is open
+    s->slotPose[slot] = s->poseCur;   // the frame renders the poses and materials set before its begin, whatever is set while it is open
+    s->slotMat[slot] = s->matCur;
     struct PoseRelease {   // (an open that fails leaves no ticket)
         xrt_scene *s; int slot; bool keep = false;
-        ~PoseRelease() { if (!keep) s->slotPose[slot] = -1; }
+        ~PoseRelease() { if (!keep) s->slotPose[slot] = s->slotMat[slot] = -1; }
     } poseRelease{s, slot};
-    for (int j = 0; j < 4; j++) s->frames[slot + 2 * j].pose = s->poseCur;
+    for (int j = 0; j < 4; j++) { s->frames[slot + 2 * j].pose = s->poseCur; s->frames[slot + 2 * j].mat = s->matCur; }
     if (n == 1) {
         // Two halves on two streams?  Only plain single-pass frames that run long enough for the drain of their launches to
         // matter, on streams of the library's choosing; by default only when no other frame is in flight to fill the gaps.
-        const bool plain = opts->use_multisampling != XRT_MS_ADAPTIVE && !(s->host->arrays.anyTransparent && opts->max_reflections > 0) && !opts->collect_stats;
+        const bool plain = opts->use_multisampling != XRT_MS_ADAPTIVE && !(s->mat[s->matCur].anyTransparent && opts->max_reflections > 0) && !opts->collect_stats;
         const long long px64 = (long long)px * (opts->use_multisampling == XRT_MS_FIXED16 ? 16 : 1) / (opts->shard_count > 1 ? opts->shard_count : 1);
         const bool alone = !s->frames[slot ^ 1].pending;
         if (!st && plain && !s->cfg.oneStream && s->cfg.splitMode.value_or(1) > 0 && (s->cfg.splitMode || s->sceneMode == MODE_SCENE) && (s->cfg.splitMode == 2 || alone) && s->lastFrameMs >= s->cfg.splitMinMs &&
@@ -1539,7 +1605,7 @@ int close_frame_impl(xrt_scene *s, int slot, xrt_stats *stats) {
         if (e != hipSuccess && rc == XRT_OK) rc = fail(XRT_E_HIP, "hipEventSynchronize: %s", hipGetErrorString(e));
     }
     O = xrt_scene::OpenFrame();
-    s->slotPose[slot] = -1;
+    s->slotPose[slot] = s->slotMat[slot] = -1;
     if (rc == XRT_OK) rc = guards_check("end of frame");
     return rc;
 }
@@ -1650,6 +1716,7 @@ int cast_rays_impl(xrt_scene *s, const xrt_ray *d_rays, int64_t n, int32_t itera
     b.rays = d_rays; b.n = n; b.refIndex = refIndex; b.paths = paths;
     xrt_scene::FrameCtx &F = s->frames[0];
     F.pose = s->poseCur;
+    F.mat = s->matCur;   // (a ray batch reads the latest materials)
     Range rf("xrt cast rays (%lld)", (long long)n);
     int rc = frame_begin(s, F, nullptr, lights, nLights, &o, d_out, d_outF32, st, 0, 1, false, &b);
     if (rc != XRT_OK) {
@@ -1746,6 +1813,10 @@ int scene_upload(xrt_scene *scene) {
         (rc = upload(scene->meshes, A.meshes)) || (rc = upload(scene->objects, A.objects)) || (rc = upload(scene->materials, A.materials)) ||
         (rc = upload(scene->texels, A.texels)) || (rc = pose_upload(scene)))
         return rc;
+    // the material versions start again from version 0, which holds the host's materials
+    for (auto &v : scene->mat) { v.ready.reset(); v.owner = nullptr; v.pending = false; v.serial = 0; v.texFull = true; v.texLo = v.texHi = 0; v.texCount = 0; v.anyTransparent = A.anyTransparent; }
+    scene->mat[0].texFull = false; scene->mat[0].texCount = A.texels.size();
+    scene->matCur = 0; scene->matSerial = 0;
     return scene_derive(scene);
 }
 
@@ -1786,6 +1857,59 @@ int poses_enqueue(xrt_scene *s, const int *ids, int n, const float *world, const
     if (st != ps) HIPCHECK(hipStreamWaitEvent(st, P.ready, 0));
     P.serial = ++s->poseSerial;
     s->poseCur = v;
+    return XRT_OK;
+}
+
+// Stage one material update: the host's MaterialRecs and the texels version v lacks become the newest version.  The version written is the
+// current one unless an open ticket reads it; then a free one.  Every version is written from the HOST's arrays (which hold the newest
+// materials as a whole), so no version is copied from another: the records are a few bytes per mesh, and of the arena only the words the
+// version is behind in.  Nothing here touches a stream: the data is put into the version's page-locked staging and the first frame or ray
+// batch that reads the version enqueues the copies on its own stream (mat_acquire).  Caller holds apiMutex and the scene (BusyGuard).
+int materials_stage(xrt_scene *s, const HostScene::MaterialEdit &edit) {
+    const SceneArrays &A = s->host->arrays;
+    auto widen = [](xrt_scene::MatVer &m, size_t lo, size_t hi) {
+        if (hi <= lo) return;
+        if (m.texHi == m.texLo) { m.texLo = lo; m.texHi = hi; }
+        else { m.texLo = std::min(m.texLo, lo); m.texHi = std::max(m.texHi, hi); }
+    };
+    for (auto &m : s->mat) {   // what every version is behind in now
+        if (!edit.texels) break;
+        if (edit.texFull) m.texFull = true;
+        else widen(m, edit.texLo, edit.texHi);
+    }
+    if (!mat_referenced(s, 0) && !mat_referenced(s, 1) && !mat_referenced(s, 2)) {   // (no ticket open: freeing waits for nothing)
+        s->matRetired.clear();
+        for (auto &r : s->replicas) { (void)hipSetDevice(r->device); r->matRetired.clear(); }
+        HIPCHECK(hipSetDevice(s->device));
+    }
+    const int cur = s->matCur;
+    int v = cur;
+    if (mat_referenced(s, v))
+        for (int x = 0; x < 3; x++) if (x != cur && !mat_referenced(s, x)) { v = x; break; }
+    if (mat_referenced(s, v)) return fail(XRT_E_INTERNAL, "xrt_scene_set_materials: no free material version");
+    xrt_scene::MatVer &M = s->mat[v];
+    DevBuf<MaterialRec> &recs = mat_records(s, v);
+    DevBuf<uint32_t> &tex = mat_texels(s, v);
+    int rc;
+    const size_t nMat = A.materials.size(), nTex = A.texels.size();
+    // No open ticket reads v, so every reader of its last write has ended, and with it the copies out of the staging (they ran ahead of that
+    // reader on its stream); a write that nobody read yet was never copied and is staged again with this one.  (The wait is for a reader
+    // whose enqueue failed half way: the copies may have been enqueued with nothing behind them to wait for.)
+    if (M.pending) widen(M, M.stagedLo, M.stagedHi);
+    else if (M.ready) HIPCHECK(hipEventSynchronize(M.ready));
+    if (!tex.p || tex.cap < nTex || M.texCount != nTex) M.texFull = true;
+    if ((rc = recs.ensure(nMat)) || (rc = mat_texel_room(s, tex, nTex))) return rc;
+    const size_t lo = M.texFull ? 0 : std::min(M.texLo, nTex), hi = M.texFull ? nTex : std::min(M.texHi, nTex);
+    const size_t recBytes = (nMat * sizeof(MaterialRec) + 15) / 16 * 16, texWords = hi > lo ? hi - lo : 0;
+    if ((rc = M.staging.ensure(recBytes + texWords * sizeof(uint32_t), hipHostMallocDefault))) return rc;
+    std::memcpy(M.staging.p, A.materials.data(), nMat * sizeof(MaterialRec));
+    if (texWords) std::memcpy((char *)M.staging.p + recBytes, A.texels.data() + lo, texWords * sizeof(uint32_t));
+    M.stagedRecBytes = recBytes; M.stagedMat = nMat; M.stagedLo = lo; M.stagedHi = lo + texWords;
+    M.pending = true;
+    M.texFull = false; M.texLo = M.texHi = 0; M.texCount = nTex;
+    M.anyTransparent = A.anyTransparent;
+    M.serial = ++s->matSerial;
+    s->matCur = v;
     return XRT_OK;
 }
 
@@ -1975,6 +2099,25 @@ int xrt_scene_set_poses_device(xrt_scene *scene, const void *d_object_ids, int32
             return rc;
         scene->posesOnDevice = true;
         return XRT_OK;
+    });
+}
+
+int xrt_scene_set_materials(xrt_scene *scene, const int32_t *mesh_ids, int32_t n, const xrt_material *materials) {
+    if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_scene_set_materials: null scene");
+    if (n < 0 || (n > 0 && (!mesh_ids || !materials))) return fail(XRT_E_INVALID_ARG, "xrt_scene_set_materials: null argument");
+    if (n == 0) return XRT_OK;
+    std::lock_guard<std::mutex> lock(scene->apiMutex);
+    BusyGuard guard(scene);
+    if (!guard.owned) return fail(XRT_E_BUSY, "xrt_scene_set_materials: another call is rendering on the scene");
+    return guarded("xrt_scene_set_materials", [&]() -> int {
+        // the host copy first (checked as a whole before anything is applied): save and the next build read it, and the device's
+        // newest version is written from it
+        std::string err;
+        HostScene::MaterialEdit edit;
+        if (!scene->hs.set_materials(mesh_ids, n, materials, edit, err)) return fail(XRT_E_INVALID_ARG, "%s", err.c_str());
+        if (!(scene->device >= 0 && scene->hs.built && scene->resident)) return XRT_OK;
+        HIPCHECK(hipSetDevice(scene->device));
+        return materials_stage(scene, edit);
     });
 }
 
@@ -2337,7 +2480,7 @@ int xrt_cast_rays_device(xrt_scene *scene, const void *d_rays, int64_t n, int32_
 // Most vertices a batch of n rays can need (paths.h path_vertex_bound), or -1 where cast_rays_impl refuses the depth anyway.
 static long long paths_bound(const xrt_scene *scene, const xrt_render_opts *opts, int32_t iteration, int64_t n) {
     const long long depth = std::max(0LL, (long long)opts->max_reflections - (long long)iteration);
-    const bool tree = scene->host->arrays.anyTransparent && depth > 0;
+    const bool tree = scene->mat[scene->matCur].anyTransparent && depth > 0;
     if (opts->max_reflections < 0 || depth > 64 || (tree && depth > PATH_TREE_DEPTH)) return -1;
     return path_vertex_bound((int)depth, tree) * (long long)n;
 }
