@@ -162,6 +162,10 @@ struct EndArgs {
     uint32_t *sampleColor = nullptr;
     int *list = nullptr, *cnt = nullptr;   // cnt[END_WORDS]
     int listCap = 0;
+    // The frame has a level map (xrt_core.h LvlMap) and more than one sample per pixel: the tiles outside it take no part.  k_raygen walks the kept tiles alone and writes nothing for the others --
+    // their words of sampleColor keep what an earlier frame left --, and k_resolve writes the constant colour of a path that ended there, pack_color(0, 0, 0),
+    // for every pixel outside the rectangle without reading its samples.  The host counts the paths of the tiles that were never walked as coloured by k_raygen (xrt_debug_end_counts).
+    int skipTiles = 0;
 };
 
 // k_shade: part A works on generation `level`, part B on generation level-1 (kernels.hip).
@@ -250,7 +254,7 @@ struct ResolveArgs {
 void launch_compose(const f4 *lvlA, const f4 *lvlB, int count, int P /* level stride */, int maxReflections, uint32_t *sampleColor, float *sampleF32,
                     const ResolveArgs &RA, hipStream_t st, hipEvent_t stopEvent = nullptr, int blocks = 0);
 void launch_resolve(const RayGenParams &g, const uint32_t *sampleColor, const float *sampleF32, int pixels, long long pixelBase,
-                    uint32_t *out, float *outF32, hipStream_t st, int *zeroPtr = nullptr, int zeroN = 0);
+                    uint32_t *out, float *outF32, hipStream_t st, int *zeroPtr = nullptr, int zeroN = 0, int cullBlack = 0 /* EndArgs::skipTiles */);
 void launch_ms_decide(const RayGenParams &g, const uint32_t *quadColor, const int *nQuadsDev, int nQuadsHost, long long pixelBase, int *childBase,
                       int *childMask, float *nextCx, float *nextCy, int *nextCount, hipStream_t st, int nextCap = 0, int *overflow = nullptr);
 void launch_ms_fold(uint32_t *quadColor, const uint32_t *childColor, const int *childBase, const int *childMask, int n, hipStream_t st,

@@ -648,24 +648,34 @@ constexpr int RG_ROUNDS = 4;
 // black (RT:732), where k_compose would have written it, and no record.
 template <bool END>
 __global__ __launch_bounds__(APPEND_BLOCK) void k_raygen(RayGenParams g, SceneView S, xrt_ray *rays, f4 *lvlB0, int *index, int *count, int Phost,
-                                                         long long pathBase, HeavyArgs H, int liveCap, EndArgs E) {
+                                                         long long pathBase, HeavyArgs H, int liveCap, EndArgs E, int keptTiles) {
     __shared__ int ldsLive[RG_ROUNDS * 16], ldsHeavy[RG_ROUNDS * 16];
     if constexpr (END) { if (blockIdx.x == 0 && threadIdx.x == 0) E.cnt[END_LISTED] = 0; }   // the frame's compose list starts empty (k_shade #0 fills it, a launch later)
     int nEnded = 0;   // END: paths of this thread that ended here
     const int P = pass_paths(g, Phost);
     const f4 rlo = S.snodes[0], rhi = S.snodes[1];
     const int span = RG_ROUNDS * APPEND_BLOCK;
-    const int groups = (P + span - 1) / span;
+    // END with a level map (keptTiles > 0): the walk covers the tiles that overlap the rectangle and no others -- 4096 consecutive paths of the kept tiles per group
+    // (eight tiles of a one-sample frame, half a tile of a 16-sample one).  Nothing is written for the other tiles: no live ray, no record, and their colour is
+    // k_resolve's constant (kernels.h EndArgs::skipTiles).
+    const bool keptWalk = END && keptTiles > 0;
+    const int walk = keptWalk ? (keptTiles << g.lvl.shift) : P;
+    const int groups = (walk + span - 1) / span;
     const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
+    auto path_of = [&](int q) -> int {   // path of the frame at place q of the walk
+        if constexpr (END) { if (keptWalk) return lvl_walk_path(g.lvl, __builtin_amdgcn_readfirstlane((unsigned)q >> g.lvl.shift), (unsigned)q); }
+        return q;
+    };
     for (int grp = (int)blockIdx.x; grp < groups; grp += (int)gridDim.x) {
         int liveAt[RG_ROUNDS], heavyAt[RG_ROUNDS];   // rank among the flagged lanes of the wave, -1: not flagged
         v3 keepO[RG_ROUNDS], keepD[RG_ROUNDS];       // the live rays of this thread, written once their places in the list are known
 #pragma unroll
         for (int r = 0; r < RG_ROUNDS; r++) {
-            const int p = grp * span + r * APPEND_BLOCK + (int)threadIdx.x;
+            const int q = grp * span + r * APPEND_BLOCK + (int)threadIdx.x;
+            const int p = path_of(q);
             bool live = false, heavy = false, record = true;
             keepO[r] = mk(0, 0, 0); keepD[r] = mk(0, 0, 0);
-            if (p < P) {
+            if (q < walk && p < P) {
                 long long gp = pathBase + p;
                 const int sshift = g.samples == 16 ? 4 : (g.samples == 4 ? 2 : 0);   // samples is 1, 4 or 16
                 int s = (int)(gp & (long long)(g.samples - 1));
@@ -723,7 +733,7 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_raygen(RayGenParams g, SceneVi
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < RG_ROUNDS; r++) {
-            const int p = grp * span + r * APPEND_BLOCK + (int)threadIdx.x;
+            const int p = path_of(grp * span + r * APPEND_BLOCK + (int)threadIdx.x);
             if (liveAt[r] >= 0) {
                 const int slot = ldsLive[r * 16 + wave] + liveAt[r];
                 if (slot < liveCap) {   // (liveCap bounds the live rays by construction: the guard is against a wrong bound, not a code path)
@@ -809,12 +819,15 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_ingest(RayGenParams g, SceneVi
 void launch_raygen(const RayGenParams &g, const SceneView &S, xrt_ray *rays, f4 *lvlB0, int *index, int *count, int P, long long pathBase,
                    const HeavyArgs &H, hipStream_t st, hipEvent_t startEvent, int liveCap, const EndArgs *end) {
     static_assert(RG_ROUNDS * 16 == 64, "one wave scans the block's cells");
-    int blocks = (P + RG_ROUNDS * APPEND_BLOCK - 1) / (RG_ROUNDS * APPEND_BLOCK);
+    const bool ending = !g.batch && end && end->on && index;
+    const int kept = (ending && end->skipTiles) ? lvl_kept_tiles(g) : 0;   // (k_resolve colours the other tiles)
+    const long long walk = kept > 0 ? ((long long)kept << g.lvl.shift) : (long long)P;
+    int blocks = (int)((walk + RG_ROUNDS * APPEND_BLOCK - 1) / (RG_ROUNDS * APPEND_BLOCK));
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
     if (g.batch) hipExtLaunchKernelGGL(k_ingest, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap);
-    else if (end && end->on && index) hipExtLaunchKernelGGL(k_raygen<true>, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap, *end);
-    else hipExtLaunchKernelGGL(k_raygen<false>, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap, EndArgs());
+    else if (ending) hipExtLaunchKernelGGL(k_raygen<true>, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap, *end, kept);
+    else hipExtLaunchKernelGGL(k_raygen<false>, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap, EndArgs(), 0);
 }
 
 // ---- shading ----------------------------------------------------------------------------------------------------------
@@ -1361,7 +1374,7 @@ void launch_compose(const f4 *lvlA, const f4 *lvlB, int count, int P, int maxRef
 // Supersample averaging (RT:309: mean of four quantised colours, re-quantised, twice for 16 samples) and the
 // framebuffer write renderTargetData[y*W + x] = color (RT:425) — or the shard's tile-contiguous buffer.
 __global__ __launch_bounds__(256) void k_resolve(RayGenParams g, const uint32_t *sampleColor, const float *sampleF32, int pixels, long long pixelBase,
-                                                 uint32_t *out, float *outF32, int *zeroPtr, int zeroN) {
+                                                 uint32_t *out, float *outF32, int *zeroPtr, int zeroN, int cullBlack) {
     // (an adaptive frame in flight: the quadrant-level counts its fold kernels read are cleared here, by the frame's last kernel)
     if (zeroPtr && blockIdx.x == 0) for (int i = (int)threadIdx.x; i < zeroN; i += (int)blockDim.x) zeroPtr[i] = 0;
     for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < pixels; i += (int)(gridDim.x * blockDim.x)) {
@@ -1370,7 +1383,11 @@ __global__ __launch_bounds__(256) void k_resolve(RayGenParams g, const uint32_t 
         bool ok = path_pixel(g, pix, x, y);
         uint32_t col;
         v3 cv;
-        if (g.quadLevel == 0) {   // adaptive: the pixel's level-0 quadrant after all folds (RT:309)
+        if (cullBlack && (!ok || x < g.cullX0 || x > g.cullX1 || y < g.cullY0 || y > g.cullY1)) {
+            // kernels.h EndArgs::skipTiles: every sample of such a pixel is black (RT:732) and so are its means (RT:309) -- its samples may never have been written
+            col = pack_color(mk(0, 0, 0));
+            cv = unpack_color(col);
+        } else if (g.quadLevel == 0) {   // adaptive: the pixel's level-0 quadrant after all folds (RT:309)
             const uint32_t *s = sampleColor + (size_t)i * 4;
             v3 sum = add(add(add(unpack_color(s[0]), unpack_color(s[1])), unpack_color(s[2])), unpack_color(s[3]));
             col = pack_color(divf(sum, 4.0f));
@@ -1399,10 +1416,10 @@ __global__ __launch_bounds__(256) void k_resolve(RayGenParams g, const uint32_t 
     }
 }
 void launch_resolve(const RayGenParams &g, const uint32_t *sampleColor, const float *sampleF32, int pixels, long long pixelBase, uint32_t *out,
-                    float *outF32, hipStream_t st, int *zeroPtr, int zeroN) {
+                    float *outF32, hipStream_t st, int *zeroPtr, int zeroN, int cullBlack) {
     int blocks = (pixels + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_resolve, dim3(blocks < 1 ? 1 : blocks), dim3(256), 0, st, g, sampleColor, sampleF32, pixels, pixelBase, out, outF32, zeroPtr, zeroN);
+    hipLaunchKernelGGL(k_resolve, dim3(blocks < 1 ? 1 : blocks), dim3(256), 0, st, g, sampleColor, sampleF32, pixels, pixelBase, out, outF32, zeroPtr, zeroN, cullBlack);
 }
 
 // ---- adaptive supersampling (RT:170-311) ------------------------------------------------------------------------

@@ -224,6 +224,7 @@ struct xrt_scene {
         int tallyChunks = 0, cntStride = 0, R = 0, nL = 0;
         bool ae = false;             // ShadeArgs::ae: rays answered at emission are not in the ray lists
         bool endEarly = false;       // kernels.h EndArgs: generation-0 paths were coloured where they ended; its END_WORDS counts are pinned[cntStride ..]
+        unsigned long long endSkipped = 0;   // ... EndArgs::skipTiles: the paths of the tiles k_raygen never walked (they count as coloured by k_raygen)
         unsigned long long answered = 0;   // ... their number (frame_finish)
         bool collect = false;
         unsigned long long shaded = 0, closestDeep = 0, livePaths = 0, live0 = 0, validPixels = 0;

@@ -485,6 +485,10 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         }
     }
     F.endEarly = endEarly;
+    // ... and where such a frame has a level map, the tiles outside it take no part (kernels.h EndArgs::skipTiles).  Not with one sample per pixel: a group of the walk
+    // would cover eight kept tiles, and C5 at one sample measured 0.740 -> 0.752 ms per step with it (profiles/gen0_latency) -- such frames keep the old walk.
+    const bool skipTiles = endEarly && g.lvl.on != 0 && g.samples > 1;
+    F.endSkipped = skipTiles ? (unsigned long long)(totalTiles - lvl_kept_tiles(g)) << g.lvl.shift : 0;
     F.fast = fast;
     F.heap = heap;
     F.redone = false;
@@ -678,6 +682,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         if (listCnt) {
             endArgs.on = 1; endArgs.sampleColor = sampleOut ? sampleOut : W.sampleColor.p;
             endArgs.list = W.composeList.p + 16; endArgs.cnt = listCnt; endArgs.listCap = (int)rayCap;
+            endArgs.skipTiles = skipTiles ? 1 : 0;
         }
         { Range r("xrt raygen"); launch_raygen(gb, S, rays[0], W.lvlB.p, W.index0.p, cnt, Pc, pathBase, heavy_for(0), st, startEvent ? e0 : nullptr, (int)rayCap, &endArgs); startEvent = false; }
         // (one buffer serves every generation: the closest-hit answers of launch #k are read by part A of k_shade #k alone -- part B works from the
@@ -960,7 +965,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     if (!adaptive) {
         livePaths = validPixels * (unsigned long long)g.samples;
         rc = run_pass(g, firstPaths, [&](int Pc, long long pathBase) -> int {
-            launch_resolve(g, W.sampleColor.p, wantF32 ? W.sampleF32.p : nullptr, Pc / g.samples, pathBase / g.samples, d_out, d_outF32, st);
+            launch_resolve(g, W.sampleColor.p, wantF32 ? W.sampleF32.p : nullptr, Pc / g.samples, pathBase / g.samples, d_out, d_outF32, st, nullptr, 0, skipTiles ? 1 : 0);
             return XRT_OK;
         }, 0.0f, 1.0f, true);
         if (rc != XRT_OK) return rc;
@@ -1184,7 +1189,7 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
     }
     if (F.endEarly) {   // (xrt_debug_end_counts: a frame that engaged has one chunk and its counters in `pinned`)
         const int *hc = F.pinned.p + F.cntBase;
-        s->endCounts[0] = (unsigned long long)hc[F.cntStride + END_BY_RAYGEN]; s->endCounts[1] = (unsigned long long)hc[F.cntStride + END_BY_SHADE]; s->endCounts[2] = (unsigned long long)hc[F.cntStride + END_LISTED];
+        s->endCounts[0] = (unsigned long long)hc[F.cntStride + END_BY_RAYGEN] + F.endSkipped; s->endCounts[1] = (unsigned long long)hc[F.cntStride + END_BY_SHADE]; s->endCounts[2] = (unsigned long long)hc[F.cntStride + END_LISTED];
     } else s->endCounts[0] = s->endCounts[1] = s->endCounts[2] = 0;
     {
         float frameMs = 0;

@@ -474,6 +474,14 @@ struct RayGenParams {
     float *batchRef;               // ray-tree passes: the curRef of every live ray of generation 0 (ShadeArgs::rayRef) -- batchRefIndex; null: not written
     float batchRefIndex;
 };
+// The tiles a level map keeps (tx0 .. tx1 x ty0 .. ty1 of the rectangle), row by row: their number, and path q of a walk over them alone -- kept tile
+// q >> shift, the same place inside it -- as a path of the frame.  (q >> shift is the same for the 64 paths of a wavefront: a tile is a multiple of 512 paths.)
+XRT_HD int lvl_kept_tiles(const RayGenParams &g) { return g.lvl.on ? g.lvl.rw * (g.cullY1 / XRT_TILE_H - g.lvl.ty0 + 1) : 0; }
+XRT_HD int lvl_walk_path(const LvlMap &m, unsigned keptTile, unsigned q) {
+    const unsigned ky = keptTile / (unsigned)m.rw, kx = keptTile - ky * (unsigned)m.rw;
+    const unsigned t = ((unsigned)m.ty0 + ky) * (unsigned)m.tilesX + (unsigned)m.tx0 + kx;
+    return (int)((t << m.shift) | (q & ((1u << m.shift) - 1u)));
+}
 XRT_HD int pass_paths(const RayGenParams &g, int hostCount) {
     if (!g.pathsDev) return hostCount;
     int n = *g.pathsDev;
