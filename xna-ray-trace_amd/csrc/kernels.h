@@ -82,9 +82,8 @@ struct PacketArgs {
     int staticDiv = 4;            // 1/staticDiv of the packets are dealt statically (0: none)
     int grabMax = 2;              // most packets a wave takes per queue atomic
     int *flags = nullptr;         // inside a frame: hit / miss word per ray, no record for a miss (IntersectArgs::flags)
-    int prefetch = 0;             // small launches (a tile shard, a late generation): a block's children and a leaf's triangle records are asked for with one vector load each,
-                                  // a level ahead of the scalar loads that use them (packet.hip pk_prefetch) -- their walks go through parts of the tree no other wave keeps warm
-    int bundle = 1;               // one-body scenes: big leaves are scanned through the bundle prefilter (packet.hip; XRT_PK_BUNDLE=0: run by run as in round 3)
+    int splitLong = 0, splitBudgetLong = 0;   // (of the split walks, see splitCost below.  They sit here so that every other field keeps the kernel-argument offset k_packet was
+                                              // tuned at: with the struct eight bytes shorter from here on, its variants came out 1-3 instructions and one a register off)
     int cullMin = 4;              // leaves of at least this many references are tested against their tight box first (the test costs about two triangles)
     unsigned long long *stamps = nullptr;   // this launch's row of device-clock stamps (device_util.h), or null
     // optional second segment traced by the same launch (the shadow rays of generation k-1 beside the closest-hit rays of generation k, as
@@ -118,8 +117,7 @@ struct PacketArgs {
     // block entries from the start, as do the takers of its items.  (Waiting for a walk to PROVE long costs half of it; splitting every walk early is speculation --
     // the far siblings of a ray that is about to find a near hit would have been pruned; and a cost in TICKS is contagious: the speculative work slows every packet,
     // more of them count as long.  profiles/r04/split_walks.txt.)
-    unsigned *splitCost = nullptr;
-    int splitLong = 0, splitBudgetLong = 0;
+    unsigned *splitCost = nullptr;   // (splitLong, splitBudgetLong: above, behind `flags`)
 };
 constexpr int PACKET_QUEUE_HEADS = 8, PACKET_HEAD_STRIDE = 64;   // every head on a 256-byte line of its own: atomics on one line serialise whatever the word
 constexpr int PACKET_SPLIT_WORDS = 320;                          // ... and behind the heads the lines of the split-walk counters (PacketArgs::splitCtl: 9 x 128 bytes, aligned)

@@ -60,7 +60,7 @@ struct xrt_scene {
     // Declared in front of every stream: members are destroyed in reverse order, so the scene's streams go before the communicators (as they always did).
     RcclGather rccl;
     // HBM-resident scene
-    DevBuf<f4> blocks, refN, snodes, shade, leafNB, leafTB, scull, runTB, triTB;
+    DevBuf<f4> blocks, refN, snodes, shade, leafNB, leafTB, scull, runTB;
     DevBuf<float> refT, pblocks, lrec;
     DevBuf<g3> refG;
     DevBuf<int> childDfs, srefs, objMesh, runBase;

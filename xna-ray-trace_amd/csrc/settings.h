@@ -46,9 +46,6 @@ struct Settings {
     bool answerAtEmission = true;   // XRT_AE=0: k_shade emits every ray (kernels.h ShadeArgs::ae off)
     bool finishInPartA = true;      // XRT_AE_FINISH=0: a hit whose shadow rays were all answered at emission still takes a slot and waits for part B (kernels.h ShadeArgs::finish off)
     bool endEarly = true;           // XRT_END_EARLY=0: every generation-0 path leaves its records and k_compose colours it (kernels.h EndArgs off)
-    int packetPrefetch = -1;   // XRT_PK_PREFETCH: -1 launches of fewer than packetPrefetchBelow packets per resident wave prefetch (kernels.h PacketArgs::prefetch), 0 never, 1 always
-    int packetPrefetchBelow = 12;
-    bool packetBundle = true;  // XRT_PK_BUNDLE=0: no bundle prefilter (kernels.h PacketArgs::bundle)
     int packetCullMin = 4;     // XRT_PK_CULL_MIN (development): leaves with fewer references skip the tight-box test
     // Split walks (packet.hip): one-body scenes; a packet / an item that has walked for this many microseconds looks for pending subtrees to hand to other waves
     // (XRT_PK_SPLIT=0: off; XRT_PK_BUDGET / XRT_PK_BUDGET_ITEM in microseconds, XRT_PK_BUDGET=0: a walk looks for pending subtrees at every block it enters;
@@ -134,9 +131,6 @@ inline Settings read_settings() {
     env_flag("XRT_AE", c.answerAtEmission);
     env_flag("XRT_AE_FINISH", c.finishInPartA);
     env_flag("XRT_END_EARLY", c.endEarly);
-    env_int("XRT_PK_PREFETCH", c.packetPrefetch, -1, 1);
-    env_int("XRT_PK_PREFETCH_BELOW", c.packetPrefetchBelow, 0, 100000);
-    env_flag("XRT_PK_BUNDLE", c.packetBundle);
     env_int("XRT_PK_CULL_MIN", c.packetCullMin, INT_MIN, INT_MAX);
     env_flag("XRT_PK_SPLIT", c.packetSplit);
     env_int("XRT_PK_BUDGET", c.packetBudgetUs, 0, 1000000);

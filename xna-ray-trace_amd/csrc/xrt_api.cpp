@@ -724,7 +724,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
                     else PA.pathOf1 = k == 0 ? W.index0.p : paths[cur];
                     if (I2) { PA.slotOf2 = slotOf[prv]; PA.nL2 = nL; }
                 }
-                PA.queue = q + QW * k + 1 + PACKET_QUEUE_WORDS * word; PA.mode = s->sceneMode; PA.meshId = 0; PA.unmark = 0; PA.staticDiv = s->cfg.packetStaticDiv; PA.grabMax = s->cfg.packetGrabMax; PA.cullMin = s->cfg.packetCullMin; PA.bundle = s->cfg.packetBundle ? 1 : 0;
+                PA.queue = q + QW * k + 1 + PACKET_QUEUE_WORDS * word; PA.mode = s->sceneMode; PA.meshId = 0; PA.unmark = 0; PA.staticDiv = s->cfg.packetStaticDiv; PA.grabMax = s->cfg.packetGrabMax; PA.cullMin = s->cfg.packetCullMin;
                 if (s->cfg.packetSplit && s->sceneMode != MODE_SCENE) {
                     if ((rc = split_arena(s, W.splitItems, W.splitRecs, PA, st))) return rc;
                     if (fast && !adaptive && !heap && s->cfg.packetLongUs > 0) {   // plain frames: the packets of launch #k are the same from frame to frame while the camera stands still, and nearly so while it moves
@@ -742,9 +742,6 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
                 if (!a0 || !a1) return fail(XRT_E_HIP, "hipEventCreate failed");
                 int grid = s->numCUs * s->blocksPerCUPacket;
                 if (nHost >= 0) { const long long want = (nHost + 255) / 256; if (want < grid) grid = (int)(want < 1 ? 1 : want); }
-                // a small launch -- a tile shard of a frame, a late generation -- walks parts of the octree no other wave keeps warm: it prefetches (packet.hip pk_prefetch);
-                // a launch of many packets per wave has its neighbours for that and would only pay for the extra loads (C5's primary launch: +4 %)
-                PA.prefetch = s->cfg.packetPrefetch >= 0 ? s->cfg.packetPrefetch : ((nHost >= 0 && nHost / 64 < (long long)s->cfg.packetPrefetchBelow * grid * 4) ? 1 : 0);
                 if (useStamps && grid * 4 <= STAMP_SLOTS && F.stampRows < s->cfg.maxStampRows) { PA.stamps = W.stamps.p + (size_t)F.stampRows++ * STAMP_STRIDE; a0 = a1 = nullptr; }
                 else if (!s->cfg.launchTiming) a0 = a1 = nullptr;
                 else { pairs.push_back({ev, ev + 1}); ev += 2; }
@@ -1672,7 +1669,7 @@ int run_intersect(xrt_scene *s, const xrt_ray *d_rays, int64_t n, xrt_hit *d_hit
     const bool meshOk = mode != MODE_MESH || (meshId >= 0 && meshId < (int)s->host->meshTrees.size() && !s->host->meshTrees[(size_t)meshId].rootIsLeaf);
     if (n > 0 && s->cfg.packetMask >= 0 && (s->cfg.packetMask & 8) && packet_supported(mode, s->host->arrays.meshDepth, s->host->arrays.sceneDepth) && meshOk) {   // (testing aid: arbitrary batches through the packet kernel)
         PacketArgs PA;
-        PA.rays = d_rays; PA.hits = d_hits; PA.n = (int)n; PA.queue = queue + 1; PA.mode = mode; PA.meshId = meshId; PA.bundle = s->cfg.packetBundle ? 1 : 0;
+        PA.rays = d_rays; PA.hits = d_hits; PA.n = (int)n; PA.queue = queue + 1; PA.mode = mode; PA.meshId = meshId;
         if (s->cfg.packetSplit && mode != MODE_SCENE) {
             auto &ar = s->apiSplit[(int)((queue - s->queues.p) / (1 + PACKET_QUEUE_WORDS))];
             if ((rc = split_arena(s, ar.first, ar.second, PA, st))) return rc;
@@ -1761,7 +1758,7 @@ int scene_derive(xrt_scene *scene) {
     const SceneArrays &A = scene->host->arrays;
     SceneView &S = scene->view;
     S.blocks = scene->blocks.p; S.childDfs = scene->childDfs.p; S.leafNB = scene->leafNB.p; S.leafTB = scene->leafTB.p; S.refT = scene->refT.p; S.pblocks = scene->pblocks.p; S.lrec = scene->lrec.p; S.refN = scene->refN.p; S.refG = scene->refG.p;
-    S.meshes = scene->meshes.p; S.snodes = scene->snodes.p; S.srefs = scene->srefs.p; S.scull = scene->scull.p; S.runTB = scene->runTB.p; S.triTB = scene->triTB.p; S.runBase = scene->runBase.p;
+    S.meshes = scene->meshes.p; S.snodes = scene->snodes.p; S.srefs = scene->srefs.p; S.scull = scene->scull.p; S.runTB = scene->runTB.p; S.runBase = scene->runBase.p;
     S.objects = scene->objects.p; S.objMesh = scene->objMesh.p;
     S.nMeshes = (int)scene->host->meshes.size(); S.nObjects = (int)scene->host->objects.size();
     S.sceneDepth = A.sceneDepth + 1; S.meshDepth = A.meshDepth + 1;
@@ -1814,7 +1811,7 @@ int scene_upload(xrt_scene *scene) {
     int rc;
     if ((rc = upload(scene->blocks, A.blocks)) || (rc = upload(scene->leafNB, A.leafNB)) || (rc = upload(scene->leafTB, A.leafTB)) || (rc = upload(scene->refT, A.refT)) || (rc = upload(scene->pblocks, A.pblocks)) || (rc = upload(scene->lrec, A.lrec)) || (rc = upload(scene->refN, A.refN)) || (rc = upload(scene->refG, A.refG)) ||
         (rc = upload(scene->snodes, A.snodes)) || (rc = upload(scene->shade, A.shade)) || (rc = upload(scene->childDfs, A.childDfs)) ||
-        (rc = upload(scene->srefs, A.srefs)) || (rc = upload(scene->scull, A.scull)) || (rc = upload(scene->runTB, A.runTB)) || (rc = upload(scene->triTB, A.triTB)) || (rc = upload(scene->runBase, A.runBase)) || (rc = upload(scene->objMesh, A.objMesh)) ||
+        (rc = upload(scene->srefs, A.srefs)) || (rc = upload(scene->scull, A.scull)) || (rc = upload(scene->runTB, A.runTB)) || (rc = upload(scene->runBase, A.runBase)) || (rc = upload(scene->objMesh, A.objMesh)) ||
         (rc = upload(scene->meshes, A.meshes)) || (rc = upload(scene->objects, A.objects)) || (rc = upload(scene->materials, A.materials)) ||
         (rc = upload(scene->texels, A.texels)) || (rc = pose_upload(scene)))
         return rc;

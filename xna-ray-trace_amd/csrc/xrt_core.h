@@ -334,50 +334,6 @@ XRT_HD bool leaf_certainly_missed(const RayPre &r, const RayCull &rc, const f4 &
     return tn > tf;
 }
 
-// The same decision for a whole BUNDLE of rays at once (packet.hip: 64 lanes test 64 triangles' records against the packet's rays): true only if
-// leaf_certainly_missed is true for EVERY ray of the bundle.  The bundle is given by component-wise bounds of its rays' origins, directions and inverse
-// directions (every axis: one sign for all rays, no zero), the largest |D|_2 (RayCull::d2) and slack; the same expressions are evaluated on interval end
-// points.  Every binary32 operation involved is monotone in each argument, so the COMPUTED end points bound the values each ray computes for itself: the
-// far-corner distance from above, the lower bound of |D . n| from below, hence rho from above (the hardware reciprocal is within an ulp of a monotone
-// function: a factor 1.00001 pays for that), the entry parameters of the grown box from below and the exit parameters from above.  `tn > tf` for the bounds
-// therefore implies `tn > tf` for every ray's own test.  (Interval arithmetic loses where the rays of a bundle diverge; for the 64 rays of a 2 x 2-pixel
-// patch it loses next to nothing.)
-struct RayBundle {
-    v3 omin, omax, dmin, dmax, imin, imax;
-    float d2, slack;   // largest RayCull::d2 / slack of the bundle's rays (d2 == 0: some ray takes no part -- no bundle)
-};
-XRT_HD float min4(float a, float b, float c, float d) { return fminf(fminf(a, b), fminf(c, d)); }
-XRT_HD float max4(float a, float b, float c, float d) { return fmaxf(fmaxf(a, b), fmaxf(c, d)); }
-XRT_HD bool bundle_certainly_missed(const RayBundle &q, const f4 &a, const f4 &b, const f4 &nl, const f4 &nh) {
-    auto far1 = [](float o0, float o1, float lo, float hi) { return fmaxf(fmaxf(fabsf(o0 - lo), fabsf(o1 - lo)), fmaxf(fabsf(o0 - hi), fabsf(o1 - hi))); };
-    const float fx = far1(q.omin.x, q.omax.x, a.x, b.x), fy = far1(q.omin.y, q.omax.y, a.y, b.y), fz = far1(q.omin.z, q.omax.z, a.z, b.z);
-    const float tmax = sqrtf((fx * fx + fy * fy) + fz * fz) * 1.000001f;
-    const float x0 = q.dmin.x * nl.x, x1 = q.dmin.x * nh.x, x2 = q.dmax.x * nl.x, x3 = q.dmax.x * nh.x;
-    const float y0 = q.dmin.y * nl.y, y1 = q.dmin.y * nh.y, y2 = q.dmax.y * nl.y, y3 = q.dmax.y * nh.y;
-    const float z0 = q.dmin.z * nl.z, z1 = q.dmin.z * nh.z, z2 = q.dmax.z * nl.z, z3 = q.dmax.z * nh.z;
-    const float lo = (min4(x0, x1, x2, x3) + min4(y0, y1, y2, y3)) + min4(z0, z1, z2, z3), hi = (max4(x0, x1, x2, x3) + max4(y0, y1, y2, y3)) + max4(z0, z1, z2, z3);
-    const float cmin = fmaxf(lo, -hi) - q.slack;
-#if defined(__HIP_DEVICE_COMPILE__)
-    const float rho = (((a.w * (b.w + tmax)) * q.d2) * (__builtin_amdgcn_rcpf(cmin) * 1.000001f)) * 1.00001f;
-#else
-    const float rho = (((a.w * (b.w + tmax)) * q.d2) * ((1.0f / cmin) * 1.000001f)) * 1.00001f;
-#endif
-    if (!(nl.w > 0.0f && q.d2 > 0.0f && cmin > 0.0f && rho < 1.0e15f)) return false;
-    // per axis: the two plane parameters of every ray lie in [t1lo, t1hi], [t2lo, t2hi]; its entry parameter is >= the smaller lower end, its exit <= the larger upper end
-    auto axis = [&](float alo, float bhi, float o0, float o1, float i0, float i1, float &nearLo, float &farHi) {
-        const float v1lo = (alo - rho) - o1, v1hi = alo - o0, v2lo = bhi - o1, v2hi = (bhi + rho) - o0;
-        const float t1lo = min4(v1lo * i0, v1lo * i1, v1hi * i0, v1hi * i1), t1hi = max4(v1lo * i0, v1lo * i1, v1hi * i0, v1hi * i1);
-        const float t2lo = min4(v2lo * i0, v2lo * i1, v2hi * i0, v2hi * i1), t2hi = max4(v2lo * i0, v2lo * i1, v2hi * i0, v2hi * i1);
-        nearLo = fminf(t1lo, t2lo); farHi = fmaxf(t1hi, t2hi);
-    };
-    float nx, fxh, ny, fyh, nz, fzh;
-    axis(a.x, b.x, q.omin.x, q.omax.x, q.imin.x, q.imax.x, nx, fxh);
-    axis(a.y, b.y, q.omin.y, q.omax.y, q.imin.y, q.imax.y, ny, fyh);
-    axis(a.z, b.z, q.omin.z, q.omax.z, q.imin.z, q.imax.z, nz, fzh);
-    const float tn = fmaxf(fmaxf(fmaxf(nx, 0.0f), ny), nz), tf = fminf(fminf(fxh, fyh), fzh);
-    return tn > tf;
-}
-
 // ---- Color (RT:584,705,726,732) ---------------------------------------------------------------------------
 XRT_HD uint32_t pack_unorm255(float v) {
     v = v * 255.0f;
