@@ -55,6 +55,10 @@ struct Material {
 
     static constexpr float BYTE_RECIPROCAL = 1.0f / 255.0f;   // MAT:27
 
+    // (int)(float) of MAT:115-119, 147-148, 176-181 as the reference's platform performs it (x64 .NET, cvttss2si): truncation toward zero, 0x80000000
+    // for NaN and for anything outside [-2^31, 2^31).  A C++ cast is undefined there; this is what the lookup is DEFINED with beyond its valid range.
+    static int ToInt32(float x) { return (x >= -2147483648.0f && x < 2147483648.0f) ? (int)x : (int)0x80000000u; }
+
     static void WrapUV(Vector2 &uv) {   // MAT:125-136; C# float % == fmodf
         if (uv.X > 1.0f) uv.X = std::fmod(uv.X, 1.0f);
         if (uv.Y > 1.0f) uv.Y = std::fmod(uv.Y, 1.0f);
@@ -67,8 +71,8 @@ struct Material {
         if (uv.Y > 1.0f) uv.Y = std::fmod(uv.Y, 1.0f);
         if (uv.X < 0.0f) uv.X = 1 + std::fmod(uv.X, 1.0f);
         if (uv.Y < 0.0f) uv.Y = 1 + std::fmod(uv.Y, 1.0f);
-        if ((int)(o.X - uv.X) % 2 == 0) uv.X = 1.0f - uv.X;
-        if ((int)(o.Y - uv.Y) % 2 == 0) uv.Y = 1.0f - uv.Y;
+        if (ToInt32(o.X - uv.X) % 2 == 0) uv.X = 1.0f - uv.X;
+        if (ToInt32(o.Y - uv.Y) % 2 == 0) uv.Y = 1.0f - uv.Y;
     }
     static void ClampUV(Vector2 &uv) {   // MAT:138-143, Vector2.Clamp
         float x = uv.X; x = (x > 1.0f) ? 1.0f : x; x = (x < 0.0f) ? 0.0f : x;
@@ -76,8 +80,8 @@ struct Material {
         uv.X = x; uv.Y = y;
     }
     void GetColorPoint(const Vector2 &uv, Vector3 &color) const {   // MAT:145-160
-        int x = (int)(uv.X * (float)(Width - 1));
-        int y = (int)(uv.Y * (float)(Height - 1));
+        int x = ToInt32(uv.X * (float)(Width - 1));
+        int y = ToInt32(uv.Y * (float)(Height - 1));
         // The C# reads through a raw pointer (no bounds check); indices are in range for finite uv in
         // [0,1].  Guard so a NaN uv cannot fault the test process (reference behaviour: undefined).
         int64_t idx = (int64_t)Width * y + x;
@@ -90,15 +94,18 @@ struct Material {
     // MAT:162-232.  Texture.ColorData is the Format32bppPArgb copy (TEX:24-33); for opaque textures (every
     // fixture; a 24-bpp BMP has no alpha) it equals the Format32bppArgb words, which is what is stored here.
     void GetColorBilinear(Vector2 uv, Vector3 &color) const {
+        // A coordinate that is not a number: the C# throws (index 0x80000000); every weight below would be NaN, with a sign and payload that depend on
+        // the libm and the instruction set.  Stated instead: the canonical quiet NaN 0x7FC00000 in every channel (texture lookup).
+        if (uv.X != uv.X || uv.Y != uv.Y) { const uint32_t q = 0x7FC00000u; float qnan; std::memcpy(&qnan, &q, 4); color = V3(qnan, qnan, qnan); return; }
         const float tdx = 1.0f / (float)Width, tdy = 1.0f / (float)Height;   // texelDensity (MAT:67)
         double remainderX = std::remainder((double)uv.X, (double)tdx);         // Math.IEEERemainder (MAT:168-169)
         double remainderY = std::remainder((double)uv.Y, (double)tdy);
         uv.X -= (float)remainderX;
         uv.Y -= (float)remainderY;
-        int x = (int)(uv.X * (float)(Width - 1));
-        int y = (int)(uv.Y * (float)(Height - 1));
-        int x2 = (int)((uv.X + tdx) * (float)(Width - 1));
-        int y2 = (int)((uv.Y + tdy) * (float)(Height - 1));
+        int x = ToInt32(uv.X * (float)(Width - 1));
+        int y = ToInt32(uv.Y * (float)(Height - 1));
+        int x2 = ToInt32((uv.X + tdx) * (float)(Width - 1));
+        int y2 = ToInt32((uv.Y + tdy) * (float)(Height - 1));
         auto texel = [&](int xx, int yy) {   // the C# indexes a managed int[] (IndexOutOfRangeException when outside); guarded here
             int64_t idx = (int64_t)Width * yy + xx;
             if (idx < 0 || idx >= (int64_t)colorData.size()) idx = 0;
@@ -1051,6 +1058,7 @@ void orc_kat_spot_light(const xrt_light *l, const float pos[3], const float norm
     Vector3 r = L.GetLightForFragment(V3(pos[0], pos[1], pos[2]), V3(normal[0], normal[1], normal[2]));
     out[0] = r.X; out[1] = r.Y; out[2] = r.Z;
 }
+int32_t orc_kat_to_int32(float x) { return Material::ToInt32(x); }
 int orc_kat_lookup_uv(const xrt_material *m, const float uv[2], int address, int filtering, float out[3]) {
     Material mm; mm.UseTexture = true; mm.Width = m->tex_width; mm.Height = m->tex_height;
     mm.argb.assign(m->tex_argb, m->tex_argb + (size_t)m->tex_width * m->tex_height);

@@ -55,6 +55,8 @@ def lib():
         l.orc_kat_multiply.argtypes = [_F, _F, _F]
         l.orc_kat_build_world.argtypes = [_F, _F, _F, _F, _F, _F, _F]
         l.orc_kat_spot_light.argtypes = [C.POINTER(abi.xrt_light), _F, _F, _F]
+        l.orc_kat_to_int32.argtypes = [C.c_float]
+        l.orc_kat_to_int32.restype = C.c_int32
         l.orc_kat_lookup_uv.argtypes = [C.POINTER(abi.xrt_material), _F, C.c_int, C.c_int, _F]
         _lib = l
     return _lib

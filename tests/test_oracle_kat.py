@@ -266,6 +266,31 @@ def test_texture_lookup_wrap_point(xrt, orc):
     assert tuple(out) == (0.0, 0.0, 1.0)
 
 
+def test_float_to_int_conversion(xrt, orc):
+    """(int)(float) of the texture lookup (Material::ToInt32): cvttss2si's results, stated -- truncation toward zero inside [-2^31, 2^31), 0x80000000 for
+    NaN and everything else -- and what the lookup returns with it beyond its valid range: the guarded texel 0 for a NaN coordinate, and the Mirror
+    parity of 0x80000000 (even: the coordinate is flipped) for |uv| >= 2^31."""
+    cv = orc.lib().orc_kat_to_int32
+    assert [cv(x) for x in (0.0, -0.0, 0.999, -0.999, 1.5, -1.5, 254.99998, 2147483520.0, -2147483648.0)] == [0, 0, 0, 0, 1, -1, 254, 2147483520, -2 ** 31]
+    nan, inf = float("nan"), float("inf")
+    assert [cv(x) for x in (2147483648.0, 4294967808.0, -2147483904.0, 3e38, -3e38, inf, -inf, nan, -nan)] == [-2 ** 31] * 9
+    tex = (np.arange(16, dtype=np.uint32).reshape(4, 4) * 0x010203 + 0xFF000000).astype(np.uint32)
+    m = xrt.abi.xrt_material()
+    m.use_texture, m.tex_width, m.tex_height = 1, 4, 4
+    m.tex_argb = tex.ctypes.data_as(C.POINTER(C.c_uint32))
+    out = np.zeros(3, dtype=np.float32)
+
+    def look(u, v, mode):
+        assert orc.lib().orc_kat_lookup_uv(C.byref(m), _p(fa(u, v)), mode, xrt.abi.FILTER_POINT, _p(out)) == 0
+        return tuple(out)
+    texel0 = look(0, 0, xrt.abi.ADDRESS_CLAMP)
+    for mode in (xrt.abi.ADDRESS_WRAP, xrt.abi.ADDRESS_CLAMP, xrt.abi.ADDRESS_MIRROR):
+        assert look(nan, 0.5, mode) == texel0 and look(0.5, nan, mode) == texel0          # 4 * y + 0x80000000 < 0 / 4 * 0x80000000 + x < 0: the guard
+    # Mirror, u = 2^31 and v = 0: fmod is 0 and (int)(2^31 - 0) = 0x80000000 is even, as (int)(0 - 0) is: both are flipped to 1 -> texel (3, 3)
+    assert look(2.0 ** 31, 0.0, xrt.abi.ADDRESS_MIRROR) == look(1.0, 1.0, xrt.abi.ADDRESS_CLAMP)
+    assert look(-2.0 ** 33, 0.0, xrt.abi.ADDRESS_MIRROR) == look(0.0, 1.0, xrt.abi.ADDRESS_CLAMP)     # 1 + fmod = 1, parity even -> 1 - 1 = 0
+
+
 def test_k10_golden_c1_frame(xrt, orc):
     """The committed C1 frame (256x256, R=0) is reproduced exactly by the oracle."""
     spec = xrt.configs.config("C1")

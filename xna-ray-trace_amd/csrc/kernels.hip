@@ -885,15 +885,19 @@ __device__ __forceinline__ v3 lookup_uv(const ShadeView &V, const MaterialRec &M
         if (uy > 1.0f) uy = fmod1(uy);
         if (ux < 0.0f) ux = 1.0f + fmod1(ux);
         if (uy < 0.0f) uy = 1.0f + fmod1(uy);
-        if (((int)(ox - ux)) % 2 == 0) ux = 1.0f - ux;
-        if (((int)(oy - uy)) % 2 == 0) uy = 1.0f - uy;
+        if (cvt_i32(ox - ux) % 2 == 0) ux = 1.0f - ux;
+        if (cvt_i32(oy - uy) % 2 == 0) uy = 1.0f - uy;
     }
     if (V.filtering == XRT_FILTER_BILINEAR) {   // MAT:162-232
+        // A coordinate that is not a number (the reference throws: its texel index is 0x80000000) makes every weight below NaN.  Which NaN is no property
+        // of the arithmetic: ocml's remainder() returns the canonical one where glibc's hands its argument's on, and a subtraction here flips the sign
+        // of a NaN subtrahend where SSE keeps it.  So the answer is stated: the canonical quiet NaN in every channel (texture lookup).
+        if (is_nan(ux) || is_nan(uy)) { const float qnan = i2f(0x7fc00000); return mk(qnan, qnan, qnan); }
         const float tdx = 1.0f / (float)M.texWidth, tdy = 1.0f / (float)M.texHeight;   // MAT:67
         const double remX = remainder((double)ux, (double)tdx), remY = remainder((double)uy, (double)tdy);   // Math.IEEERemainder, exact
         ux -= (float)remX;
         uy -= (float)remY;
-        const int bx = (int)(ux * (float)(M.texWidth - 1)), by = (int)(uy * (float)(M.texHeight - 1));
+        const int bx = (int)(ux * (float)(M.texWidth - 1)), by = (int)(uy * (float)(M.texHeight - 1));   // (numbers in [0, W] by now: no cvt_i32)
         const int bx2 = (int)((ux + tdx) * (float)(M.texWidth - 1)), by2 = (int)((uy + tdy) * (float)(M.texHeight - 1));
         auto texel = [&](int xx, int yy) {
             long long idx = (long long)M.texWidth * yy + xx;
@@ -907,10 +911,10 @@ __device__ __forceinline__ v3 lookup_uv(const ShadeView &V, const MaterialRec &M
         v3 sum = add(add(add(scale(scale(c00, ix), iy), scale(scale(c01, ix), dy)), scale(scale(c10, dx), iy)), scale(scale(c11, dx), dy));
         return scale(sum, 1.0f / 255.0f);
     }
-    int x = (int)(ux * (float)(M.texWidth - 1));    // MAT:147
-    int y = (int)(uy * (float)(M.texHeight - 1));   // MAT:148
+    int x = cvt_i32(ux * (float)(M.texWidth - 1));    // MAT:147
+    int y = cvt_i32(uy * (float)(M.texHeight - 1));   // MAT:148
     long long idx = (long long)M.texWidth * y + x;
-    if (idx < 0 || idx >= (long long)M.texWidth * M.texHeight) idx = 0;   // the C# reads through a raw pointer; guard NaN uv
+    if (idx < 0 || idx >= (long long)M.texWidth * M.texHeight) idx = 0;   // the C# reads through a raw pointer; a NaN uv (x or y = 0x80000000) reads texel 0
     uint32_t argb = V.texels[M.texOffset + idx];
     const float BYTE_RECIPROCAL = 1.0f / 255.0f;   // MAT:27
     return mk((float)((argb >> 16) & 0xffu) * BYTE_RECIPROCAL, (float)((argb >> 8) & 0xffu) * BYTE_RECIPROCAL, (float)(argb & 0xffu) * BYTE_RECIPROCAL);
@@ -971,7 +975,8 @@ __device__ __forceinline__ v3 shade_light_sum(const ShadeView &V, const ShadeArg
 // miss below it returns, its colour out -- no lvlA, no lvlB, no miss record of generation 1.  Every other hit leaves its records as always and its path in
 // the compose list.
 template <bool FIN, bool END = false>
-__global__ __launch_bounds__(APPEND_BLOCK) void k_shade(SceneView S, ShadeView V, ShadeArgs X) {
+// (six waves per SIMD, 80 VGPRs: what <true, true> had before lookup_uv's conversions went through cvt_i32 -- left alone the allocator takes 81 with them, five waves)
+__global__ __launch_bounds__(APPEND_BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void k_shade(SceneView S, ShadeView V, ShadeArgs X) {
     static_assert(FIN || !END, "a frame that ends paths early finishes hits in part A");
     __shared__ int ldsCounts[END ? 34 : 17];
     const int stride = (int)(gridDim.x * blockDim.x);

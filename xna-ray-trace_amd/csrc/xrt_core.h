@@ -484,4 +484,16 @@ XRT_HD v3 light_for_fragment(const LightRec &L, v3 position, v3 normal) {
 // float % 1.0f of C# (fmod, exact) for MAT:125-136.
 XRT_HD float fmod1(float x) { return x - truncf(x); }
 
+// (int)(float) of C# as the reference's platform performs it (x64 .NET, cvttss2si): truncation toward zero, and 0x80000000 for NaN and for anything
+// outside [-2^31, 2^31) -- where C++ leaves the conversion undefined and gfx950's v_cvt_i32_f32 saturates (NaN -> 0, large -> INT_MAX).  The texture
+// lookup's conversions that can meet such a value (the Mirror parity MAT:115-119, the point filter's texel MAT:147-148; the bilinear filter answers a
+// NaN coordinate before it converts) go through it, so that what the lookup returns beyond its valid range is one thing.
+XRT_HD int cvt_i32(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return fabsf(x) < 2147483648.0f ? (int)x : (int)0x80000000u;   // one compare: -2^31 itself saturates to 0x80000000 in v_cvt_i32_f32
+#else
+    return (x >= -2147483648.0f && x < 2147483648.0f) ? (int)x : (int)0x80000000u;
+#endif
+}
+
 }  // namespace xrt
