@@ -25,51 +25,44 @@ namespace RayTraceProject.Spatial
         }
         static float[] B(BoundingBox b) { return new float[] { b.Min.X, b.Min.Y, b.Min.Z, b.Max.X, b.Max.Y, b.Max.Z }; }
 
-        // OctreeSpatialManager.Build (OctreeSpatialManager.cs:64-99) + Mesh.Init of every distinct mesh (SceneObject.cs:132)
+        // OctreeSpatialManager.Build (OctreeSpatialManager.cs:64-99) + Mesh.Init of every distinct mesh (SceneObject.cs:132).  The first Build
+        // makes the scene; a later one on the scene of this manager's own Build only replaces the body list (xrt_scene_set_bodies): meshes the
+        // library has keep their ids and octrees, meshes it has not seen are added and built by the call.  LastBuildMeshes: mesh octrees built.
+        public int LastBuildMeshes { get; private set; }
+        bool ownBuild;   // the scene was made by Build(), not by Load(): meshIds knows its meshes
+
         public void Build()
         {
+            if (this.scene != IntPtr.Zero && this.ownBuild)
+            {
+                PushMaterials();
+                foreach (SceneObject so in this.objects)
+                    foreach (Mesh mesh in so.Meshes)
+                        if (!this.meshIds.ContainsKey(mesh)) AddMesh(mesh);
+                int n = this.objects.Count, k = 0;
+                int[] start = new int[n + 1];
+                for (int i = 0; i < n; i++) start[i + 1] = start[i] + ((SceneObject)this.objects[i]).Meshes.Count;
+                int[] all = new int[Math.Max(start[n], 1)];
+                float[] world = new float[16 * n], inv = new float[16 * n], bbox = new float[6 * n], wbb = new float[6 * n];
+                for (int i = 0; i < n; i++)
+                {
+                    SceneObject so = (SceneObject)this.objects[i];
+                    foreach (Mesh mesh in so.Meshes) all[k++] = this.meshIds[mesh];
+                    M(so.World).CopyTo(world, 16 * i); M(so.InverseWorld).CopyTo(inv, 16 * i);
+                    B(so.BoundingBox).CopyTo(bbox, 6 * i); B(so.WorldBoundingBox).CopyTo(wbb, 6 * i);
+                }
+                int built;
+                Xrt.Check(Xrt.xrt_scene_set_bodies(this.scene, n, start, all, world, inv, bbox, wbb, 0, out built));
+                this.LastBuildMeshes = built;
+                return;
+            }
             if (this.scene != IntPtr.Zero) Xrt.Check(Xrt.xrt_scene_destroy(this.scene));
             Xrt.Check(Xrt.xrt_scene_create(0, out this.scene));
+            this.ownBuild = false;
             this.meshIds.Clear(); this.meshesById.Clear();
             foreach (SceneObject so in this.objects)
                 foreach (Mesh mesh in so.Meshes)
-                {
-                    if (this.meshIds.ContainsKey(mesh)) continue;          // meshes are shared by reference (SceneObject.cs:126-127)
-                    Triangle[] t = mesh.Triangles;
-                    float[] v = new float[t.Length * 9], n = new float[t.Length * 9], uv = new float[t.Length * 6],
-                            sn = new float[t.Length * 3], col = new float[t.Length * 4];
-                    for (int i = 0; i < t.Length; i++)
-                    {
-                        Put3(v, i * 9, t[i].v1); Put3(v, i * 9 + 3, t[i].v2); Put3(v, i * 9 + 6, t[i].v3);
-                        Put3(n, i * 9, t[i].n1); Put3(n, i * 9 + 3, t[i].n2); Put3(n, i * 9 + 6, t[i].n3);
-                        uv[i * 6] = t[i].uv1.X; uv[i * 6 + 1] = t[i].uv1.Y; uv[i * 6 + 2] = t[i].uv2.X; uv[i * 6 + 3] = t[i].uv2.Y;
-                        uv[i * 6 + 4] = t[i].uv3.X; uv[i * 6 + 5] = t[i].uv3.Y;
-                        Put3(sn, i * 3, t[i].surfaceNormal);
-                        col[i * 4] = t[i].color.X; col[i * 4 + 1] = t[i].color.Y; col[i * 4 + 2] = t[i].color.Z; col[i * 4 + 3] = t[i].color.W;
-                    }
-                    Material mat = mesh.MeshMaterial;
-                    XrtMaterial xm = new XrtMaterial
-                    {
-                        reflectiveness = mat.Reflectiveness, transparent = mat.Transparent ? 1 : 0, refractionIndex = mat.RefractionIndex,
-                        interpolateNormals = mat.InterpolateNormals ? 1 : 0, useTexture = mat.UseTexture ? 1 : 0,
-                        // Material.Init (Material.cs:59-69) keeps the locked bitmap in private fields; expose Scan0 / Width / Height
-                        // through three internal getters on Material (one-line additions) and pass them here:
-                        texWidth = mat.UseTexture ? mat.TextureWidth : 0, texHeight = mat.UseTexture ? mat.TextureHeight : 0,
-                        texArgb = mat.UseTexture ? mat.TextureScan0 : IntPtr.Zero
-                    };
-                    // the bilinear filter reads Material.Texture.ColorData, the premultiplied Format32bppPArgb copy (RayTracerTexture.cs:24-33,
-                    // Material.cs:186-189): pinned for the call (the library copies it)
-                    System.Runtime.InteropServices.GCHandle pin = default(System.Runtime.InteropServices.GCHandle);
-                    if (mat.UseTexture && mat.Texture != null && mat.Texture.ColorData != null)
-                    {
-                        pin = System.Runtime.InteropServices.GCHandle.Alloc(mat.Texture.ColorData, System.Runtime.InteropServices.GCHandleType.Pinned);
-                        xm.texPArgb = pin.AddrOfPinnedObject();
-                    }
-                    int id;
-                    try { Xrt.Check(Xrt.xrt_scene_add_mesh(this.scene, v, n, uv, sn, col, t.Length, ref xm, B(mesh.MeshBoundingBox), out id)); }
-                    finally { if (pin.IsAllocated) pin.Free(); }
-                    this.meshIds[mesh] = id; this.meshesById.Add(mesh);
-                }
+                    if (!this.meshIds.ContainsKey(mesh)) AddMesh(mesh);          // meshes are shared by reference (SceneObject.cs:126-127)
             foreach (SceneObject so in this.objects)
             {
                 int[] ids = new int[so.Meshes.Count];
@@ -79,6 +72,47 @@ namespace RayTraceProject.Spatial
                                                    B(so.WorldBoundingBox), out oid));
             }
             Xrt.Check(Xrt.xrt_scene_build(this.scene, 0, 0));   // thresholds 50 / 20 (MeshOctree.cs:42, OctreeSpatialManager.cs:50)
+            this.ownBuild = true;
+            this.LastBuildMeshes = this.meshesById.Count;
+        }
+
+        // xrt_scene_add_mesh for a mesh the library has not seen
+        void AddMesh(Mesh mesh)
+        {
+            Triangle[] t = mesh.Triangles;
+            float[] v = new float[t.Length * 9], n = new float[t.Length * 9], uv = new float[t.Length * 6],
+                    sn = new float[t.Length * 3], col = new float[t.Length * 4];
+            for (int i = 0; i < t.Length; i++)
+            {
+                Put3(v, i * 9, t[i].v1); Put3(v, i * 9 + 3, t[i].v2); Put3(v, i * 9 + 6, t[i].v3);
+                Put3(n, i * 9, t[i].n1); Put3(n, i * 9 + 3, t[i].n2); Put3(n, i * 9 + 6, t[i].n3);
+                uv[i * 6] = t[i].uv1.X; uv[i * 6 + 1] = t[i].uv1.Y; uv[i * 6 + 2] = t[i].uv2.X; uv[i * 6 + 3] = t[i].uv2.Y;
+                uv[i * 6 + 4] = t[i].uv3.X; uv[i * 6 + 5] = t[i].uv3.Y;
+                Put3(sn, i * 3, t[i].surfaceNormal);
+                col[i * 4] = t[i].color.X; col[i * 4 + 1] = t[i].color.Y; col[i * 4 + 2] = t[i].color.Z; col[i * 4 + 3] = t[i].color.W;
+            }
+            Material mat = mesh.MeshMaterial;
+            XrtMaterial xm = new XrtMaterial
+            {
+                reflectiveness = mat.Reflectiveness, transparent = mat.Transparent ? 1 : 0, refractionIndex = mat.RefractionIndex,
+                interpolateNormals = mat.InterpolateNormals ? 1 : 0, useTexture = mat.UseTexture ? 1 : 0,
+                // Material.Init (Material.cs:59-69) keeps the locked bitmap in private fields; expose Scan0 / Width / Height
+                // through three internal getters on Material (one-line additions) and pass them here:
+                texWidth = mat.UseTexture ? mat.TextureWidth : 0, texHeight = mat.UseTexture ? mat.TextureHeight : 0,
+                texArgb = mat.UseTexture ? mat.TextureScan0 : IntPtr.Zero
+            };
+            // the bilinear filter reads Material.Texture.ColorData, the premultiplied Format32bppPArgb copy (RayTracerTexture.cs:24-33,
+            // Material.cs:186-189): pinned for the call (the library copies it)
+            System.Runtime.InteropServices.GCHandle pin = default(System.Runtime.InteropServices.GCHandle);
+            if (mat.UseTexture && mat.Texture != null && mat.Texture.ColorData != null)
+            {
+                pin = System.Runtime.InteropServices.GCHandle.Alloc(mat.Texture.ColorData, System.Runtime.InteropServices.GCHandleType.Pinned);
+                xm.texPArgb = pin.AddrOfPinnedObject();
+            }
+            int id;
+            try { Xrt.Check(Xrt.xrt_scene_add_mesh(this.scene, v, n, uv, sn, col, t.Length, ref xm, B(mesh.MeshBoundingBox), out id)); }
+            finally { if (pin.IsAllocated) pin.Free(); }
+            this.meshIds[mesh] = id; this.meshesById.Add(mesh);
         }
 
         // Scene file (what the content pipeline would write instead of .xnb reflection data, TracerModelProcessor.cs:113-117):
@@ -88,6 +122,7 @@ namespace RayTraceProject.Spatial
         {
             if (this.scene != IntPtr.Zero) Xrt.Check(Xrt.xrt_scene_destroy(this.scene));
             Xrt.Check(Xrt.xrt_scene_load(0, path, out this.scene));
+            this.ownBuild = false;
             Xrt.Check(Xrt.xrt_scene_build(this.scene, 0, 0));
         }
 

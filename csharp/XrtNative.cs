@@ -149,6 +149,12 @@ namespace RayTraceProject.Native
         // meshIds[i] takes materials[i], also while RenderAsync tickets are open; texArgb == IntPtr.Zero keeps the texels the mesh has; nothing is rebuilt
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_materials(IntPtr scene, [In] int[] meshIds, int n,
                                                                      [In] XrtMaterial[] materials);
+        // OctreeSpatialManager.Bodies replaced and Build() run on a built scene (OctreeSpatialManager.cs:54-57, 64-99): body i has the meshes
+        // meshIds[meshStart[i] .. meshStart[i + 1]) and 16 + 16 + 6 + 6 floats; meshes added since the last build get their octrees (their number
+        // comes back in meshesBuilt), no other mesh octree is built again
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_bodies(IntPtr scene, int nBodies, [In] int[] meshStart,
+                                                                     [In] int[] meshIds, [In] float[] world, [In] float[] invWorld, [In] float[] bbox,
+                                                                     [In] float[] worldBbox, int sceneThreshold, out int meshesBuilt);
         // can n_gpus > 1 load RCCL?  OK or E_RCCL (-6) with the loader's message; no device is touched
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_rccl_probe();
         // diagnostics of the split walks of long packets (results never depend on them): subtrees handed over, taken, packets split, packets written by a taker

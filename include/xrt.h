@@ -529,6 +529,42 @@ int xrt_scene_build_tree(xrt_scene *scene, int32_t scene_threshold);
  * call on the scene. */
 int xrt_scene_set_materials(xrt_scene *scene, const int32_t *mesh_ids, int32_t n, const xrt_material *materials);
 
+/* ---- changing which bodies exist: OctreeSpatialManager.Bodies (OSM:54-57) and Build (OSM:64-99) ---------------------------------
+ * Added within ABI 203: this export is additive; no existing struct, field or entry point changed.
+ * The reference's host fills the public list Bodies and calls Build() (G1:95-109); that only files the bodies into the scene octree,
+ * because every Model got its MeshOctree when its SceneObject was constructed (SO:126-132, MESH:27-32).  xrt_scene_set_bodies is that
+ * for a built scene: the body list is replaced and the scene octree built, and no mesh octree is built that exists already.
+ *   - list replacement: the body list becomes exactly the n_bodies bodies given.  Body i has the meshes
+ *     mesh_ids[mesh_start[i] .. mesh_start[i + 1]) and world[16i..], inv_world[16i..], bbox[6i..], world_bbox[6i..] (the arguments
+ *     xrt_scene_add_object takes).  Body ids (xrt_hit.object, the ids of xrt_scene_set_poses) are positions in the new list.
+ *   - OctreeSpatialManager.Build (OSM:64-99, 218-248) then runs over the new list; scene_threshold 0 = the reference default (20, OSM:50).
+ *   - equivalence: the scene equals one made from scratch with the same meshes in the same id order, these bodies, and xrt_scene_build:
+ *     frames, hits and xrt_scene_get_tree output are the same.
+ *   - mesh ids never change, and (ignore_mesh, ignore_tri) pairs stay valid.  A mesh that no body names any more stays in the scene and
+ *     in HBM, as a loaded Model stays in the reference's ContentManager; there is no mesh removal.
+ *   - meshes added with xrt_scene_add_mesh since the last build get their MeshOctree.Build now, with the mesh_threshold of the last
+ *     xrt_scene_build; no other mesh is built again.  *meshes_built_out (may be NULL) receives the number of mesh octrees the call built:
+ *     0 when it only re-lists bodies of known meshes.  The count is this call's own and is written whenever the list was applied, also
+ *     when the call then returns XRT_E_UNSUPPORTED (the octrees it built stay built: the repairing call reports 0); a call rejected with
+ *     XRT_E_INVALID_ARG, XRT_E_NOT_BUILT or XRT_E_BUSY leaves it untouched.  The new meshes' materials and texels enter as at a build; materials changed with
+ *     xrt_scene_set_materials stay, texels kept while use_texture is 0 included.
+ *   - poses: the call supplies every pose; poses last set through xrt_scene_set_poses_device are discarded, not read back.
+ *   - the pose and material versions start again from 0, as after xrt_scene_build_tree and xrt_scene_build.
+ *   - n_bodies == 0 is legal and gives an empty scene (every ray misses); a body without meshes is legal, as in xrt_scene_add_object.
+ *   - a NULL array that is needed, n_bodies < 0, mesh_start[0] != 0, a decreasing mesh_start or an unknown mesh id: XRT_E_INVALID_ARG, and
+ *     nothing is applied.  Before the first xrt_scene_build: XRT_E_NOT_BUILT.  While a begin/end ticket is open or another thread
+ *     renders on the scene: XRT_E_BUSY, as for xrt_scene_build_tree; the frame in flight is not disturbed.  An octree too deep for the
+ *     LDS stack, or a scene octree the reference's Build would not finish (OSM:101-113: more bodies than the threshold share a point):
+ *     XRT_E_UNSUPPORTED; the scene is then as xrt_scene_build_tree leaves it in that case (the host copy holds the new list,
+ *     nothing can be traced), and a later successful call repairs it.
+ *   - on a host-only scene (device -1) the host copy is edited and the call returns XRT_OK.
+ *   - xrt_scene_save writes the new list (the file format is unchanged).
+ * xrt_scene_add_object after a build, and xrt_scene_build, behave as before. */
+int xrt_scene_set_bodies(xrt_scene *scene, int32_t n_bodies, const int32_t *mesh_start /* n_bodies + 1 */,
+                         const int32_t *mesh_ids /* mesh_start[n_bodies] */, const float *world /* 16 n */, const float *inv_world /* 16 n */,
+                         const float *bbox /* 6 n */, const float *world_bbox /* 6 n */, int32_t scene_threshold,
+                         int32_t *meshes_built_out /* nullable */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -319,6 +319,7 @@ class OctreeSpatialManager(ISpatialManager):
         self._pushed = []        # per body: the pose serial the library has
         self._pushed_mats = []   # per mesh: (its Material, the material's serial) the library has
         self._pushed_tex = []    # per mesh: (Material, texel serial) of the texels the library has, or None
+        self.last_build_meshes = 0   # mesh octrees the last Build() built (xrt_scene_set_bodies' meshes_built_out; a full build: all)
 
     def _key(self):
         return (self.meshItemTreshold, tuple((id(b), tuple(id(m) for m in b.Meshes)) for b in self.Bodies))
@@ -329,6 +330,24 @@ class OctreeSpatialManager(ISpatialManager):
             self._push_poses()
             self._push_materials()
             abi.check(abi.lib().xrt_scene_build_tree(self._scene.handle, self.itemTreshold))
+            return
+        if self._scene is not None and self._built_key is not None and self._built_key[0] == self.meshItemTreshold:
+            # a scene of this manager's own Build, the mesh threshold unchanged: the list alone changes (xrt_scene_set_bodies).  Meshes the
+            # library has keep their ids and their octrees; only those it has not seen are added (and built by the call).
+            self._push_materials()
+            for body in self.Bodies:
+                for m in body.Meshes:
+                    if id(m) not in self._mesh_ids:
+                        self._mesh_ids[id(m)] = self._scene.add_mesh(m)
+                        self.meshes.append(m)
+                        self._pushed_mats.append((m.MeshMaterial, m.MeshMaterial._serial))
+                        self._pushed_tex.append((m.MeshMaterial, m.MeshMaterial._tex_serial) if m.MeshMaterial.UseTexture else None)
+            poses = [b._build_world() for b in self.Bodies]
+            self.last_build_meshes = self.SetBodies([[self._mesh_ids[id(m)] for m in b.Meshes] for b in self.Bodies],
+                                                    [p[0] for p in poses], [p[1] for p in poses], [b.BoundingBox for b in self.Bodies],
+                                                    [p[2] for p in poses], self.itemTreshold)
+            self._built_key = self._key()
+            self._pushed = [b._pose_serial for b in self.Bodies]
             return
         self._scene = _Scene(self.device)
         self._mesh_ids = {}
@@ -346,10 +365,32 @@ class OctreeSpatialManager(ISpatialManager):
             abi.check(abi.lib().xrt_scene_add_object(self._scene.handle, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids),
                                                      _fp(world), _fp(inv), _fp(bb), _fp(wbb), C.byref(oid)))
         abi.check(abi.lib().xrt_scene_build(self._scene.handle, self.meshItemTreshold, self.itemTreshold))
+        self.last_build_meshes = len(self.meshes)
         self._built_key = self._key()
         self._pushed = [b._pose_serial for b in self.Bodies]
         self._pushed_mats = [(m.MeshMaterial, m.MeshMaterial._serial) for m in self.meshes]
         self._pushed_tex = [(m.MeshMaterial, m.MeshMaterial._tex_serial) if m.MeshMaterial.UseTexture else None for m in self.meshes]
+
+    def SetBodies(self, body_meshes, world, inv, bbox, wbb, scene_threshold=0):
+        """xrt_scene_set_bodies: the body list becomes len(body_meshes) bodies; body i has the mesh ids body_meshes[i] and world[i] (16
+        floats), inv[i] (16), bbox[i] (6), wbb[i] (6).  The scene octree is built over the new list; meshes added since the last build get
+        their octrees.  Returns the number of mesh octrees the call built (last_build_meshes holds it also when the call raises)."""
+        n = len(body_meshes)
+        start = np.zeros(n + 1, dtype=np.int32)
+        start[1:] = np.cumsum([len(m) for m in body_meshes], dtype=np.int64)
+        ids = np.ascontiguousarray([i for m in body_meshes for i in m] or [0], dtype=np.int32)
+        w = np.ascontiguousarray(world, dtype=np.float32).reshape(-1)
+        iw = np.ascontiguousarray(inv, dtype=np.float32).reshape(-1)
+        bb = np.ascontiguousarray(bbox, dtype=np.float32).reshape(-1)
+        wb = np.ascontiguousarray(wbb, dtype=np.float32).reshape(-1)
+        if w.size != 16 * n or iw.size != 16 * n or bb.size != 6 * n or wb.size != 6 * n:
+            raise ValueError("SetBodies: 16 + 16 + 6 + 6 floats per body")
+        built = C.c_int32(0)
+        rc = abi.lib().xrt_scene_set_bodies(self.handle, n, start.ctypes.data_as(C.POINTER(C.c_int32)), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            _fp(w), _fp(iw), _fp(bb), _fp(wb), int(scene_threshold), C.byref(built))
+        self.last_build_meshes = built.value   # (this call's own count, also when the scene octree could not be built: those octrees stay built)
+        abi.check(rc)
+        return built.value
 
     def _push_poses(self):
         """The poses of the bodies moved since the last push, in one xrt_scene_set_poses (before every query and frame)."""

@@ -186,11 +186,29 @@ bool HostScene::build(int meshThreshold, int sceneThreshold, std::string &err) {
     if (meshThreshold <= 0) meshThreshold = 50;    // MO:42
     if (sceneThreshold <= 0) sceneThreshold = 20;  // OSM:50
     built = false;
+    builtMeshes = -1;
     arrays = SceneArrays();
-    meshTrees.assign(meshes.size(), FlatTree());
+    meshTrees.clear();
+    raw = RawSizes();
+    this->meshThreshold = meshThreshold;
+    if (!mesh_part(err)) return false;
+    if (!body_part(sceneThreshold, err)) { builtMeshes = -1; return false; }   // (the arrays stay without their padding: nothing may append to them)
+    material_part();
+    assemble();
+    built = true;
+    return true;
+}
+
+// Meshes [raw.meshes, meshes.size()): Mesh.Init and their part of every per-mesh array, appended.  On failure `arrays` is of no use (builtMeshes -1).
+bool HostScene::mesh_part(std::string &err) {
     SceneArrays &A = arrays;
-    int triBase = 0;
-    for (size_t mi = 0; mi < meshes.size(); mi++) {
+    // what assemble() put behind the last mesh's part (padding, the dummies of empty arrays) comes off
+    A.blocks.resize(raw.blocks); A.refN.resize(raw.refN); A.refG.resize(3 * raw.refN); A.shade.resize(raw.shade); A.leafNB.resize(raw.leafNB); A.leafTB.resize(raw.leafTB);
+    A.runBase.resize(raw.runBase); A.runTB.resize(raw.runTB); A.childDfs.resize(raw.childDfs); A.pblocks.resize(raw.pblocks); A.meshes.resize(raw.meshes);
+    builtMeshes = -1;
+    meshTrees.resize(meshes.size());
+    int triBase = raw.meshes ? A.totalTris : 0;
+    for (size_t mi = raw.meshes; mi < meshes.size(); mi++) {
         const HostMesh &m = meshes[mi];
         FlatTree &t = meshTrees[mi];
         if (!build_mesh_tree(m, meshThreshold, t, err)) return false;   // Mesh.Init (MESH:27-32)
@@ -360,7 +378,6 @@ bool HostScene::build(int meshThreshold, int sceneThreshold, std::string &err) {
             A.refG.push_back(g3{p[3] - p[0], p[4] - p[1], p[5] - p[2]});   // Edge1 = v2 - v1 (RE:54)
             A.refG.push_back(g3{p[6] - p[0], p[7] - p[1], p[8] - p[2]});   // Edge2 = v3 - v1 (RE:55)
         }
-        append_material(A, m);
         for (int i = 0; i < m.ntri; i++) {
             const float *n = &m.n[(size_t)i * 9], *uv = &m.uv[(size_t)i * 6], *c = &m.color[(size_t)i * 4], *sn = &m.sn[(size_t)i * 3];
             A.shade.push_back(f4{n[0], n[1], n[2], uv[0]});
@@ -384,6 +401,17 @@ bool HostScene::build(int meshThreshold, int sceneThreshold, std::string &err) {
         triBase += m.ntri;
     }
     A.totalTris = triBase;
+    raw.blocks = A.blocks.size(); raw.refN = A.refN.size(); raw.shade = A.shade.size(); raw.leafNB = A.leafNB.size(); raw.leafTB = A.leafTB.size();
+    raw.runBase = A.runBase.size(); raw.runTB = A.runTB.size(); raw.childDfs = A.childDfs.size(); raw.pblocks = A.pblocks.size(); raw.meshes = A.meshes.size();
+    builtMeshes = (int)meshes.size();
+    return true;
+}
+
+// The bodies' records (one ObjRec per body, its mesh ids in objMesh) and OctreeSpatialManager.Build over them.
+bool HostScene::body_part(int sceneThreshold, std::string &err) {
+    SceneArrays &A = arrays;
+    A.objects.clear();
+    A.objMesh.clear();
     for (const HostObject &o : objects) {
         ObjRec r;
         std::memset(&r, 0, sizeof(r));
@@ -394,21 +422,36 @@ bool HostScene::build(int meshThreshold, int sceneThreshold, std::string &err) {
         A.objects.push_back(r);
     }
     if (!scene_part(sceneThreshold, err)) return false;
+    if (A.objMesh.empty()) A.objMesh.assign(1, -1);
+    if (A.objects.empty()) { ObjRec z; std::memset(&z, 0, sizeof(z)); A.objects.push_back(z); }
+    return true;
+}
+
+// The material table and the texel arena of ALL meshes as they are now (xrt_scene_set_materials may have changed them since they were added).
+void HostScene::material_part() {
+    SceneArrays &A = arrays;
+    A.materials.clear();
+    A.texels.clear();
+    A.anyTransparent = A.anyTexture = false;
+    for (const HostMesh &m : meshes) append_material(A, m);
+    if (A.texels.empty()) A.texels.assign(1, 0u);
+    if (A.materials.empty()) { MaterialRec z; std::memset(&z, 0, sizeof(z)); A.materials.push_back(z); }
+}
+
+// Behind mesh_part (all meshes built): the padding the kernels rely on, refT and lrec.
+void HostScene::assemble() {
+    SceneArrays &A = arrays;
     // never hand out empty arrays (a zero-size allocation has no address)
     // two dummy references at the end: the wave-packet kernel requests the next triangle's record before it knows the leaf has ended
     for (int k = 0; k < 2; k++) { A.refN.push_back(f4{0, 0, 0, i2f(-1)}); for (int j = 0; j < 3; j++) A.refG.push_back(g3{0, 0, 0}); }
-    A.refT.resize(A.refN.size() * TRI_REC_WORDS + 16, 0.0f);
+    A.refT.assign(A.refN.size() * TRI_REC_WORDS + 16, 0.0f);
     for (size_t r = 0; r < A.refN.size(); r++) {
         float *q = &A.refT[r * TRI_REC_WORDS];
         q[0] = A.refN[r].x; q[1] = A.refN[r].y; q[2] = A.refN[r].z; q[3] = A.refN[r].w;
         for (int j = 0; j < 3; j++) { q[4 + 3 * j] = A.refG[3 * r + j].x; q[5 + 3 * j] = A.refG[3 * r + j].y; q[6 + 3 * j] = A.refG[3 * r + j].z; }
     }
-    if (A.objMesh.empty()) A.objMesh.assign(1, -1);
     if (A.shade.empty()) A.shade.assign(SHADE_F4, f4{0, 0, 0, 0});
-    if (A.texels.empty()) A.texels.assign(1, 0u);
     if (A.meshes.empty()) { MeshRec z; std::memset(&z, 0, sizeof(z)); A.meshes.push_back(z); }
-    if (A.objects.empty()) { ObjRec z; std::memset(&z, 0, sizeof(z)); A.objects.push_back(z); }
-    if (A.materials.empty()) { MaterialRec z; std::memset(&z, 0, sizeof(z)); A.materials.push_back(z); }
     if (A.blocks.empty()) A.blocks.assign(2, f4{0, 0, 0, 0});
     if (A.leafNB.empty()) A.leafNB.assign(16, f4{0, 0, 0, 0});
     if (A.leafTB.empty()) A.leafTB.assign(32, f4{0, 0, 0, 0});
@@ -427,8 +470,39 @@ bool HostScene::build(int meshThreshold, int sceneThreshold, std::string &err) {
         }
         if (nRuns) std::memcpy(&A.lrec[nNodes * LREC_WORDS], A.runTB.data(), nRuns * RUN_WORDS * sizeof(float));
     }
+}
+
+int HostScene::set_bodies(int n, const int *meshStart, const int *meshIds, const float *world, const float *invWorld, const float *bbox,
+                          const float *worldBbox, int sceneThreshold, int &meshesBuilt, std::string &err) {
+    meshesBuilt = 0;
+    if (builtMeshes < 0) { err = "xrt_scene_set_bodies: call xrt_scene_build first"; return XRT_E_NOT_BUILT; }
+    if (n < 0 || !meshStart || (n > 0 && (!world || !invWorld || !bbox || !worldBbox))) { err = "xrt_scene_set_bodies: null argument"; return XRT_E_INVALID_ARG; }
+    if (meshStart[0] != 0) { err = "xrt_scene_set_bodies: mesh_start[0] is not 0"; return XRT_E_INVALID_ARG; }
+    for (int i = 0; i < n; i++)
+        if (meshStart[i + 1] < meshStart[i]) { err = "xrt_scene_set_bodies: mesh_start decreases at body " + std::to_string(i); return XRT_E_INVALID_ARG; }
+    if (meshStart[n] > 0 && !meshIds) { err = "xrt_scene_set_bodies: null argument"; return XRT_E_INVALID_ARG; }
+    for (int k = 0; k < meshStart[n]; k++)
+        if (meshIds[k] < 0 || meshIds[k] >= (int)meshes.size()) { err = "xrt_scene_set_bodies: unknown mesh id " + std::to_string(meshIds[k]); return XRT_E_INVALID_ARG; }
+    if (sceneThreshold <= 0) sceneThreshold = 20;  // OSM:50
+    std::vector<HostObject> list((size_t)n);
+    for (int i = 0; i < n; i++) {
+        HostObject &o = list[(size_t)i];
+        o.meshes.assign(meshIds + meshStart[i], meshIds + meshStart[i + 1]);
+        std::memcpy(o.world, world + 16 * (size_t)i, 64); std::memcpy(o.invWorld, invWorld + 16 * (size_t)i, 64);
+        std::memcpy(o.bbox, bbox + 6 * (size_t)i, 24); std::memcpy(o.worldBbox, worldBbox + 6 * (size_t)i, 24);
+    }
+    objects = std::move(list);
+    built = false;
+    const int firstNew = builtMeshes;
+    if ((int)meshes.size() > firstNew) {
+        if (!mesh_part(err)) return XRT_E_UNSUPPORTED;
+        meshesBuilt = (int)meshes.size() - firstNew;
+        assemble();
+    }
+    material_part();   // (also where no mesh is new: materials set while the scene waited for a build are in the meshes alone)
+    if (!body_part(sceneThreshold, err)) return XRT_E_UNSUPPORTED;
     built = true;
-    return true;
+    return XRT_OK;
 }
 
 // OctreeSpatialManager.Build (OSM:64-99) over the current poses and what is made from the scene octree: snodes, srefs, the pre-cull records
@@ -654,6 +728,7 @@ bool HostScene::load(const char *path, std::string &err) {
     if (!r.ok) { err = "xrt_scene_load: truncated or corrupt scene file" + (why.empty() ? std::string() : " (" + why + ")"); return false; }
     meshes = std::move(tmp.meshes); objects = std::move(tmp.objects);
     built = false;
+    builtMeshes = -1;
     return true;
 }
 

@@ -44,6 +44,8 @@ struct HostScene {
     FlatTree sceneTree;
     SceneArrays arrays;
     bool built = false;
+    int builtMeshes = -1;          // meshes [0, builtMeshes) have their octrees and their part of `arrays` (-1: no build yet; set_bodies builds the others)
+    int meshThreshold = 50;        // MeshOctree's threshold of the last build(): what set_bodies builds later meshes with
     bool spatialRuns = true;       // the references of a big leaf are stored in runs of neighbouring triangles (scene_host.cpp spatial_runs; XRT_LEAF_ORDER=0: in list order)
     double leafCullSafety = 1.0;   // factor on the tight-leaf-box margin (xrt_core.h LEAF_CULL_C): 0 switches the skip off, below 1 the bound is no longer proven (tests)
     double cullSafety = 2.0;   // factor S of the object pre-cull margin (scene_host.cpp); tests lower it to see the bound bite
@@ -64,12 +66,28 @@ struct HostScene {
     // every offset may have moved).
     struct MaterialEdit { bool texels = false, texFull = false; size_t texLo = 0, texHi = 0; };
     bool set_materials(const int *ids, int n, const xrt_material *mats, MaterialEdit &edit, std::string &err);
+    // OctreeSpatialManager.Bodies replaced and Build() run (xrt.h xrt_scene_set_bodies): the body list becomes the n bodies given, meshes added since
+    // the last build get their MeshOctree.Build (meshesBuilt: how many), no other mesh is built again, and `arrays`, sceneTree and meshTrees end byte for
+    // byte as build() leaves them for the same meshes and bodies.  Returns XRT_OK, XRT_E_NOT_BUILT (no build yet), XRT_E_INVALID_ARG (nothing was
+    // applied) or XRT_E_UNSUPPORTED: the list was applied and a tree could not be built.  When it was the scene tree, meshesBuilt holds what the call
+    // built, the arrays of the meshes are whole and another set_bodies (or build()) repairs the scene; when it was a mesh tree (internal errors only),
+    // `arrays` is of no use, later calls return XRT_E_NOT_BUILT and only build() repairs it.
+    int set_bodies(int n, const int *meshStart, const int *meshIds, const float *world, const float *invWorld, const float *bbox,
+                   const float *worldBbox, int sceneThreshold, int &meshesBuilt, std::string &err);
     // Scene file (xrt_scene_save / xrt_scene_load): the meshes, materials, texels and bodies exactly as they were added --
     // what the reference keeps in .xnb files (Model.Tag, TMP:113-117) -- little-endian, no pointers.  The trees are rebuilt on load.
     bool save(const char *path, std::string &err) const;
     bool load(const char *path, std::string &err);
     SceneView host_view() const;
   private:
+    // build() in its four parts.  mesh_part appends what meshes [builtMeshes, meshes.size()) add to `arrays` (behind what the others left there,
+    // the padding of assemble() taken off first); body_part makes objects / objMesh and the scene octree from `objects`; material_part the material
+    // table and the texel arena; assemble() the padding at the arrays' ends and the arrays derived from the whole (refT, lrec).
+    struct RawSizes { size_t blocks = 0, refN = 0, shade = 0, leafNB = 0, leafTB = 0, runBase = 0, runTB = 0, childDfs = 0, pblocks = 0, meshes = 0; } raw;   // sizes without the padding
+    bool mesh_part(std::string &err);
+    bool body_part(int sceneThreshold, std::string &err);
+    void material_part();
+    void assemble();
     bool scene_part(int sceneThreshold, std::string &err);
   public:   // pointers into `arrays` (CPU single-stepping in tests/emul only)
 };

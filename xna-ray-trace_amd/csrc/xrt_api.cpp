@@ -1799,6 +1799,14 @@ int scene_derive(xrt_scene *scene) {
     return XRT_OK;
 }
 
+// The material versions start again from version 0, which holds the host's materials (scene->materials / texels were just uploaded).
+void material_restart(xrt_scene *scene) {
+    const SceneArrays &A = scene->host->arrays;
+    for (auto &v : scene->mat) { v.ready.reset(); v.owner = nullptr; v.pending = false; v.serial = 0; v.texFull = true; v.texLo = v.texHi = 0; v.texCount = 0; v.anyTransparent = A.anyTransparent; }
+    scene->mat[0].texFull = false; scene->mat[0].texCount = A.texels.size();
+    scene->matCur = 0; scene->matSerial = 0;
+}
+
 // Host arrays of scene->host -> HBM of scene->device, launch geometry and scheduling defaults (second half of
 // xrt_scene_build; also what puts a replica of the scene on another device).
 int scene_upload(xrt_scene *scene) {
@@ -1815,10 +1823,7 @@ int scene_upload(xrt_scene *scene) {
         (rc = upload(scene->meshes, A.meshes)) || (rc = upload(scene->objects, A.objects)) || (rc = upload(scene->materials, A.materials)) ||
         (rc = upload(scene->texels, A.texels)) || (rc = pose_upload(scene)))
         return rc;
-    // the material versions start again from version 0, which holds the host's materials
-    for (auto &v : scene->mat) { v.ready.reset(); v.owner = nullptr; v.pending = false; v.serial = 0; v.texFull = true; v.texLo = v.texHi = 0; v.texCount = 0; v.anyTransparent = A.anyTransparent; }
-    scene->mat[0].texFull = false; scene->mat[0].texCount = A.texels.size();
-    scene->matCur = 0; scene->matSerial = 0;
+    material_restart(scene);
     return scene_derive(scene);
 }
 
@@ -2150,6 +2155,59 @@ int xrt_scene_build_tree(xrt_scene *scene, int32_t scene_threshold) {
     });
 }
 
+int xrt_scene_set_bodies(xrt_scene *scene, int32_t n_bodies, const int32_t *mesh_start, const int32_t *mesh_ids, const float *world,
+                         const float *inv_world, const float *bbox, const float *world_bbox, int32_t scene_threshold, int32_t *meshes_built_out) {
+    if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_scene_set_bodies: null scene");
+    if (in_flight(scene)) return fail(XRT_E_BUSY, "xrt_scene_set_bodies: a frame is in flight");
+    if (scene->hs.builtMeshes < 0) return fail(XRT_E_NOT_BUILT, "xrt_scene_set_bodies: call xrt_scene_build first");
+    std::lock_guard<std::mutex> lock(scene->apiMutex);
+    BusyGuard guard(scene);
+    if (!guard.owned) return fail(XRT_E_BUSY, "xrt_scene_set_bodies: a frame is in flight");
+    return guarded("xrt_scene_set_bodies", [&]() -> int {
+        // Only a scene whose device copy is whole and current (built, resident, no mesh waiting) takes the short upload below.
+        const bool current = scene->hs.built && scene->resident;
+        std::string err;
+        int built = 0;
+        const int hrc = scene->hs.set_bodies(n_bodies, mesh_start, mesh_ids, world, inv_world, bbox, world_bbox, scene_threshold, built, err);
+        if (hrc == XRT_E_INVALID_ARG || hrc == XRT_E_NOT_BUILT) return fail(hrc, "%s", err.c_str());   // (nothing was applied)
+        scene->resident = false;
+        // The call supplies every pose: what xrt_scene_set_poses_device left on the device belongs to the old list and is not read back.
+        scene->posesOnDevice = false;
+        scene->workers.clear();
+        scene->replicas.clear();   // (copies of the previous list: made again on the next n_gpus > 1 frame)
+        // What earlier frames left behind, one by one.  No buffer is sized from any of it: every frame sizes its work buffers from its own
+        // geometry and options and from the arrays as they are now (ensure() at its begin).
+        //  - genKey / genRays / genShade / genCompose: grid sizes of the next frame's launches, learned from the old list.  Scheduling only
+        //    (persistent grids, any size is correct), but worthless for another list: forgotten.
+        scene->genKey = -1; scene->genCompose = -1;
+        //  - costMap / costT / epoch ("long ray first"): the order rays are started in.  Scheduling only; costT is set again by scene_derive.
+        //  - tileCost / costTiles / balanceCost and an installed tile table: which rank renders which tile; every table is a permutation of
+        //    the frame's tiles whatever the scene holds.  Scheduling only, and the table is the caller's: kept.
+        //  - lvlCheckedTilesX / lvlCheckedTiles: arithmetic of a frame geometry, independent of the scene: kept.
+        //  - heavyPath / heavyShift / refillMin / firstBatch / deepMeshes / blocksPerCU* / packetOk / sceneMode: follow the list; scene_derive
+        //    sets every one of them again below.
+        //  - adaptiveFastOk / heapFastOk: "the optimistic way overflowed once"; the other way is always right, and a frame that overflows
+        //    is rendered again.  Kept.
+        //  - splitCost of the frame contexts: packet costs of the last frame, keyed by the frame's size; scheduling only.  Kept.
+        if (meshes_built_out) *meshes_built_out = built;   // (this call's own count, on every path that applied the list: also when the scene octree or the stack check fails below)
+        if (hrc != XRT_OK) return fail(hrc, "%s", err.c_str());
+        const SceneArrays &A = scene->hs.arrays;
+        const int stackNeeded = (A.sceneDepth + 1) + (A.meshDepth + 1);
+        if (intersect_stack_capacity(stackNeeded) < 0) return fail(XRT_E_UNSUPPORTED, "octree too deep for the LDS stack (%d levels)", stackNeeded);
+        scene->stackNeeded = stackNeeded;
+        if (scene->device < 0) return XRT_OK;
+        HIPCHECK(hipSetDevice(scene->device));
+        if (scene->poseStream) HIPCHECK(hipStreamSynchronize(scene->poseStream));
+        if (built > 0 || !current) return scene_upload(scene);   // no frame is in flight: everything again
+        int rc;
+        if ((rc = upload(scene->objMesh, A.objMesh)) || (rc = tree_upload(scene))) return rc;
+        // the host's materials are the newest; version 0 takes them and the versions start again, as after a build
+        if ((rc = upload(scene->materials, A.materials)) || (rc = upload(scene->texels, A.texels))) return rc;
+        material_restart(scene);
+        return scene_derive(scene);
+    });
+}
+
 int xrt_scene_save(const xrt_scene *scene, const char *path) {
     if (!scene || !path) return fail(XRT_E_INVALID_ARG, "xrt_scene_save: null argument");
     return guarded("xrt_scene_save", [&]() -> int {
@@ -2186,11 +2244,11 @@ int xrt_scene_get_tree(const xrt_scene *scene, int32_t mesh_id, xrt_node_info *n
     const FlatTree &t = mesh_id < 0 ? scene->hs.sceneTree : scene->hs.meshTrees[mesh_id];
     if (nodes) {
         if (*n_nodes_inout < (int64_t)t.info.size()) return fail(XRT_E_INVALID_ARG, "node array too small");
-        std::memcpy(nodes, t.info.data(), t.info.size() * sizeof(xrt_node_info));
+        if (!t.info.empty()) std::memcpy(nodes, t.info.data(), t.info.size() * sizeof(xrt_node_info));
     }
     if (refs) {
         if (*n_refs_inout < (int64_t)t.infoRefs.size()) return fail(XRT_E_INVALID_ARG, "ref array too small");
-        std::memcpy(refs, t.infoRefs.data(), t.infoRefs.size() * sizeof(int32_t));
+        if (!t.infoRefs.empty()) std::memcpy(refs, t.infoRefs.data(), t.infoRefs.size() * sizeof(int32_t));   // (an empty tree has no array to copy from)
     }
     *n_nodes_inout = (int64_t)t.info.size();
     *n_refs_inout = (int64_t)t.infoRefs.size();
