@@ -274,7 +274,10 @@ struct PkKernarg {
 // sets the packet's rays up again, seeds level 0 of its stack with the item and starts by "coming back" to it (`resume`); it may split again.  Every participant
 // leaves its lanes' answers in the arena; the one that finishes last (PacketArgs::splitRecs [0], a count of units outstanding: nobody ever waits for anybody)
 // merges them with the rule of DESIGN.md §3 and writes the packet's results.
-template <bool SPLIT>
+// LEAF_RHO: the runs of a big leaf are tested under the leaf's margin (the one-body variants).  The two-level variant keeps the run's own test in its one-piece
+// form (xrt_core.h leaf_certainly_missed_fused) and so its code of before: there the lane's kept margin costs two more dwords of scratch per lane and crates have
+// few big leaves -- C3 / C4 measured slower with it (profiles/run_margin).
+template <bool SPLIT, bool LEAF_RHO>
 __device__ __forceinline__ void pk_walk(const float *__restrict__ pblocks, const float *__restrict__ refT, const float *__restrict__ lrec,
                                         const SceneView &S, int cullMin, unsigned *stk, int lane, Lane &L,
                                         const RayCull &RC, bool fastL, int rootBlock, unsigned long long lanes0, bool nodeCull,
@@ -436,8 +439,21 @@ __device__ __forceinline__ void pk_walk(const float *__restrict__ pblocks, const
             const unsigned long long offHi = (unsigned long long)(unsigned)f2i(B.w[6]) | ((unsigned long long)(unsigned)f2i(B.w[7]) << 32);
             const int r0 = d1 + child_ref_offset(offLo, offHi, c);
             const int r1 = d1 + ((c == 7) ? d3 : child_ref_offset(offLo, offHi, c + 1));
-            if (r1 - r0 >= cullMin) {   // lanes whose ray cannot reach any triangle of the leaf (xrt_core.h leaf_certainly_missed) stay out of it
-                go = go && !leaf_certainly_missed(L.r, RC, nr[2], nr[3], nr[4], nr[5]);
+            // lanes whose ray cannot reach any triangle of the leaf (xrt_core.h leaf_certainly_missed = leaf_margin + grown_box_missed) stay out of it;
+            // a leaf that has runs keeps each lane's margin for them, whether or not it is tested itself
+            const bool big = r1 - r0 >= LEAF_RUN_MIN;
+            float rho = 0.0f;
+            bool usable = false;
+            if constexpr (LEAF_RHO) {
+                if (big || r1 - r0 >= cullMin) {
+                    usable = leaf_margin(L.r, RC, nr[2], nr[3], nr[4], nr[5], rho);
+                    if (r1 - r0 >= cullMin) {
+                        go = go && !(usable && grown_box_missed(L.r, nr[2], nr[3], rho));
+                        if (!__any(go)) continue;
+                    }
+                }
+            } else if (r1 - r0 >= cullMin) {
+                go = go && !leaf_certainly_missed_fused(L.r, RC, nr[2], nr[3], nr[4], nr[5]);
                 if (!__any(go)) continue;
             }
             PKC(5);
@@ -445,7 +461,11 @@ __device__ __forceinline__ void pk_walk(const float *__restrict__ pblocks, const
             // tight box of its own and a run no lane can reach is passed over -- the octree stops splitting at 50 triangles (MO:42) and a
             // coherent packet comes near only a few of them.  Smaller leaves are one run.
             int nRuns = 1, rb = -1;
-            if (r1 - r0 >= LEAF_RUN_MIN) { rb = f2i(lrec[(size_t)node * LREC_WORDS + 24]); if (rb >= 0) nRuns = (r1 - r0 + LEAF_RUN - 1) / LEAF_RUN; }
+            if (big) { rb = f2i(lrec[(size_t)node * LREC_WORDS + 24]); if (rb >= 0) nRuns = (r1 - r0 + LEAF_RUN - 1) / LEAF_RUN; }
+            // The leaf's margin bounds every triangle of the leaf (kappa, Tmax and Emax of a run are at most the leaf's), so a run's vertex box grown by the LEAF's
+            // rho is a proven test of the run at a third of the cost.  Wave-uniform per leaf: a lane without a usable leaf margin (a ray in a
+            // triangle's plane, axis-parallel, ..) can still be culled by a run's narrower normal box, and then all lanes take the run's own full test.
+            const bool cheap = LEAF_RHO && !__any(go && !usable);
             for (int jr = 0; jr < nRuns; jr++) {
                 int ra = r0, rz = r1;
                 bool goR = go;
@@ -453,7 +473,9 @@ __device__ __forceinline__ void pk_walk(const float *__restrict__ pblocks, const
                     ra = r0 + LEAF_RUN * jr; rz = min(ra + LEAF_RUN, r1);
                     const f4 *tb = reinterpret_cast<const f4 *>(lrec + (size_t)rb + (size_t)jr * RUN_WORDS);
                     PKC(6);
-                    goR = go && !leaf_certainly_missed(L.r, RC, tb[0], tb[1], tb[2], tb[3]);
+                    if (cheap) goR = go && !grown_box_missed(L.r, tb[0], tb[1], rho);
+                    else if constexpr (LEAF_RHO) goR = go && !leaf_certainly_missed(L.r, RC, tb[0], tb[1], tb[2], tb[3]);
+                    else goR = go && !leaf_certainly_missed_fused(L.r, RC, tb[0], tb[1], tb[2], tb[3]);
                     if (!__any(goR)) continue;
                 }
                 PKC(7);
@@ -745,7 +767,7 @@ __global__ __launch_bounds__(256, (M == MODE_SCENE) ? PK_SCENE_WAVES : (PK_SINGL
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 }
             }
-            pk_walk<splitOn>(pblocks, refT, lrec, S, A.cullMin, stk, lane, L, RC, fastL, mr.rootBlock, lanes0, nodeCull, splitOn && item >= 0);
+            pk_walk<splitOn, true>(pblocks, refT, lrec, S, A.cullMin, stk, lane, L, RC, fastL, mr.rootBlock, lanes0, nodeCull, splitOn && item >= 0);
             L.mesh = mesh;
             KA.fresh();
             bool mine = true;   // this wave writes the packet's results
@@ -913,7 +935,7 @@ __global__ __launch_bounds__(256, (M == MODE_SCENE) ? PK_SCENE_WAVES : (PK_SINGL
                                 const bool meshAway = nodeCull && all_back_facing(f4{mr.nbMin[0], mr.nbMin[1], mr.nbMin[2], mr.nbMin[3]}, f4{mr.nbMax[0], mr.nbMax[1], mr.nbMax[2], mr.nbMax[3]}, L.r.d);
                                 const unsigned long long lanes0 = __ballot(inRoot && !meshAway);
                                 if (lanes0 != 0ull)
-                                    pk_walk<false>(pblocks, refT, lrec, S, A.cullMin, stk, lane, L, RC, fastL, rootBlock, lanes0, nodeCull, false);
+                                    pk_walk<false, false>(pblocks, refT, lrec, S, A.cullMin, stk, lane, L, RC, fastL, rootBlock, lanes0, nodeCull, false);
                             }
                             if (L.mfound) {   // OSM:370-378
                                 L.mesh = m; C.obj = o;

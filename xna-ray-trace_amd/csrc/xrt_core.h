@@ -310,7 +310,43 @@ XRT_HD RayCull make_ray_cull(v3 o, v3 d) {
     c.slack = d1 * 4.7683716e-7f;              // 2^-21
     return c;
 }
+// The margin rho of a record for a ray; false when the record allows no skip for this ray (record not ok, a ray that takes no part,
+// a normal box that straddles the ray's perpendicular, rho out of range): rho is then not to be used.
+XRT_HD bool leaf_margin(const RayPre &r, const RayCull &rc, const f4 &a, const f4 &b, const f4 &nl, const f4 &nh, float &rho) {
+    // the farthest corner of the vertex box from the origin: >= |O - v1| for every triangle of the leaf
+    const float fx = fmaxf(fabsf(r.o.x - a.x), fabsf(r.o.x - b.x)), fy = fmaxf(fabsf(r.o.y - a.y), fabsf(r.o.y - b.y)),
+                fz = fmaxf(fabsf(r.o.z - a.z), fabsf(r.o.z - b.z));
+    const float tmax = sqrtf((fx * fx + fy * fy) + fz * fz) * 1.000001f;
+    // a lower bound of |D . n| over the box of the leaf's unit normals
+    const float px = r.d.x * nl.x, qx = r.d.x * nh.x, py = r.d.y * nl.y, qy = r.d.y * nh.y, pz = r.d.z * nl.z, qz = r.d.z * nh.z;
+    const float lo = (fminf(px, qx) + fminf(py, qy)) + fminf(pz, qz), hi = (fmaxf(px, qx) + fmaxf(py, qy)) + fmaxf(pz, qz);
+    const float cmin = fmaxf(lo, -hi) - rc.slack;
+#if defined(__HIP_DEVICE_COMPILE__)
+    rho = ((a.w * (b.w + tmax)) * rc.d2) * (__builtin_amdgcn_rcpf(cmin) * 1.000001f);   // (v_rcp_f32: 1 ulp)
+#else
+    rho = ((a.w * (b.w + tmax)) * rc.d2) * ((1.0f / cmin) * 1.000001f);
+#endif
+    // (every comparison below is false when something is not a finite positive number: no skip)
+    return nl.w > 0.0f && rc.d2 > 0.0f && cmin > 0.0f && rho < 1.0e15f;
+}
+// Does the ray certainly miss the box (a.xyz, b.xyz) grown by rho?  (false when a NaN is involved: no skip)
+XRT_HD bool grown_box_missed(const RayPre &r, const f4 &a, const f4 &b, float rho) {
+    const float t1x = ((a.x - rho) - r.o.x) * r.inv.x, t2x = ((b.x + rho) - r.o.x) * r.inv.x;
+    const float t1y = ((a.y - rho) - r.o.y) * r.inv.y, t2y = ((b.y + rho) - r.o.y) * r.inv.y;
+    const float t1z = ((a.z - rho) - r.o.z) * r.inv.z, t2z = ((b.z + rho) - r.o.z) * r.inv.z;
+    const float tn = fmaxf(fmaxf(fmaxf(fminf(t1x, t2x), 0.0f), fminf(t1y, t2y)), fminf(t1z, t2z));
+    const float tf = fminf(fminf(fmaxf(t1x, t2x), fmaxf(t1y, t2y)), fmaxf(t1z, t2z));
+    return tn > tf;
+}
 XRT_HD bool leaf_certainly_missed(const RayPre &r, const RayCull &rc, const f4 &a, const f4 &b, const f4 &nl, const f4 &nh) {
+    float rho;
+    if (!leaf_margin(r, rc, a, b, nl, nh, rho)) return false;
+    return grown_box_missed(r, a, b, rho);
+}
+// The same test in one piece, operation for operation (tests/run_margin compares the two on every ray it makes).  The two-level variant of the packet
+// kernel calls this form: it sits at its register budget with a few dwords of scratch, and hipcc lays its walk out 17 instructions longer around the
+// composed form above (0.9 % more vector instructions per C3 frame, C4 0.8 % slower: profiles/run_margin) -- a matter of code generation, not of arithmetic.
+XRT_HD bool leaf_certainly_missed_fused(const RayPre &r, const RayCull &rc, const f4 &a, const f4 &b, const f4 &nl, const f4 &nh) {
     // the farthest corner of the vertex box from the origin: >= |O - v1| for every triangle of the leaf
     const float fx = fmaxf(fabsf(r.o.x - a.x), fabsf(r.o.x - b.x)), fy = fmaxf(fabsf(r.o.y - a.y), fabsf(r.o.y - b.y)),
                 fz = fmaxf(fabsf(r.o.z - a.z), fabsf(r.o.z - b.z));
