@@ -10,6 +10,7 @@
 #include <thread>
 
 #include "device_res.h"   // (and <atomic>, <mutex>, <string>, <unordered_map>, <vector>)
+#include "frame_plan.h"
 #include "kernels.h"
 #include "paths.h"
 #include "rccl_gather.h"
@@ -210,25 +211,16 @@ struct xrt_scene {
         int pose = 0;                // the pose version the frame reads (xrt_scene::pose)
         int mat = 0;                 // the material version the frame reads (xrt_scene::mat)
         bool pending = false;
-        bool fast = false;           // no copy / fill / event-record commands: k_compose hands the counters over, events ride on kernels
-        long long framePaths = 0;    // paths of the frame (part) this context holds: key of the grid hints
-        int frameW = 0, frameH = 0;  // the frame's size in pixels
-        bool heap = false, redone = false;   // a ray-tree frame; ... that overflowed on the optimistic way and was rendered again
-        bool adaptiveFast = false;           // an adaptive frame enqueued without host round trips (level sizes stay on the device)
-        int cntBase = 0, levelCap = 0, quality = 0;   // words in front of the per-pass counters in `pinned`; quadrant capacity of a deeper level
-        xrt_camera redoCam; xrt_render_opts redoOpts; std::vector<xrt_light> redoLights;
+        FramePlan plan;              // what frame_begin decided about the frame in flight (frame_plan.h): frame_finish and the ticket code read it
+        bool redone = false;         // a frame that overflowed on the optimistic way and was rendered again
+        xrt_camera redoCam; xrt_render_opts redoOpts; std::vector<xrt_light> redoLights;   // what a redo needs
         uint32_t *redoOut = nullptr; float *redoOutF32 = nullptr; hipStream_t redoSt = nullptr;
         int stampRows = 0;           // traversal launches of the frame that timed themselves (device_util.h)
         Pinned<unsigned long long> stampHost;   // their (start, end) clock pairs: mapped pinned memory and its device view
         // deferred accounting
-        int tallyChunks = 0, cntStride = 0, R = 0, nL = 0;
-        bool ae = false;             // ShadeArgs::ae: rays answered at emission are not in the ray lists
-        bool endEarly = false;       // kernels.h EndArgs: generation-0 paths were coloured where they ended; its END_WORDS counts are pinned[cntStride ..]
-        unsigned long long endSkipped = 0;   // ... EndArgs::skipTiles: the paths of the tiles k_raygen never walked (they count as coloured by k_raygen)
-        unsigned long long answered = 0;   // ... their number (frame_finish)
-        bool collect = false;
+        int tallyChunks = 0;         // chunks whose counters frame_finish tallies from `pinned` (plan.cntBase words in, plan.cntStride apart)
+        unsigned long long answered = 0;   // rays answered at emission (plan.ae): they are not in the ray lists
         unsigned long long shaded = 0, closestDeep = 0, livePaths = 0, live0 = 0, validPixels = 0;
-        size_t liveCap = 0;   // room of the generation-0 ray arrays (k_raygen writes no live ray past it: a count above it is a wrong bound, reported)
         unsigned long long hcnt[2 * C_COUNT] = {0};
         WorkBufs w;
     } frames[8];   // context of ticket `slot`, part j of its frame: frames[slot + 2 * j] (a frame may be split into up to four bands on as many streams)

@@ -267,61 +267,49 @@ int make_raygen(const xrt_camera *cam, const xrt_render_opts *o, RayGenParams &g
     return XRT_OK;
 }
 
+// Tile of slot `sl` of the plan's rank: the installed table's, or the round-robin layout's.
+long long tile_of_slot(const xrt_scene &s, const FramePlan &P, long long sl) {
+    return P.tabled ? (long long)s.tileTable[(size_t)P.g.shardRank * s.tableTpr + (size_t)sl] : shard_tile(sl, P.g.shardRank, P.g.shardCount, P.g.tilesX);
+}
+
+}  // namespace
+
 // The frame: for every chunk of paths  raygen -> [intersect(closest k + shadow k-1) -> shade(A: k, B: k-1)] x (R+2) -> compose,
 // then resolve (pixel grid, fixed 16 sub-rays) or the quadrant levels of adaptive supersampling (RT:170-311).
-int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats);
-int split_arena(xrt_scene *s, DevBuf<unsigned> &items, DevBuf<unsigned> &recs, PacketArgs &PA, hipStream_t st);
-
-// A caller's ray list as the ray source of a pass (xrt_cast_rays): n rays in HBM, 16-byte aligned, and generation 0's curRef.
-struct BatchSrc {
-    const xrt_ray *rays = nullptr;
-    long long n = 0;
-    float refIndex = 1.0f;
-    // xrt_cast_rays_paths: where the ray paths go (HBM; kernels.h PathsEmitArgs), or null
-    struct Paths {
-        xrt_path_vertex *vertices = nullptr;
-        long long capacity = 0;
-        long long *vertexStart = nullptr;   // [n + 1], never null
-        xrt_ray *raysBack = nullptr;
-    };
-    const Paths *paths = nullptr;
-};
-
-// Hits of generation k in a chunk's counter block hc (frame_begin cntStride): the slots part A took plus the hits it finished itself (ShadeArgs::finish)
-static inline long long gen_hits(const int *hc, int R, int k) { return (long long)hc[(R + 2) + k] + (long long)hc[4 * (R + 2) + k]; }
-
-// Enqueues one frame on `st`.  On return the frame's kernels and its counter read-back are in flight (F.pending);
-// frame_finish waits for them.  Adaptive supersampling and ray-tree frames need host decisions between their passes and
-// are complete when this returns.
+// plan_frame decides all of it -- which pipeline, which shortcuts, every size -- from the scene's host state and the call's arguments (frame_plan.h).
 // batch != null: the paths are the batch's rays instead of the camera's pixels (cam is not read): one sample each, path p = ray p, no tiles,
-// no screen rectangle, no level map; d_out[p] / d_outF32[3p..] receive ray p's colour.  Such a pass takes the careful way (!fast): its
-// counters are read back per chunk, a ray tree is checked for overflow and retried chunk by chunk.
-int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, const xrt_light *lights, int nLights, const xrt_render_opts *opts,
-                uint32_t *d_out, float *d_outF32, hipStream_t st, int part = 0, int nParts = 1, bool heapFastAllowed = true, const BatchSrc *batch = nullptr) {
-    const bool stats = true;   // the read-back is two small pinned copies; always taken
-    xrt_scene::WorkBufs &W = F.w;
+// no screen rectangle, no level map.  Such a pass takes the careful way (!fast): its counters are read back per chunk, a ray tree is checked
+// for overflow and retried chunk by chunk.
+int plan_frame(const xrt_scene &s, int matVersion, const xrt_camera *cam, const xrt_light *lights, int nLights, const xrt_render_opts *opts, bool wantsF32,
+               bool hasStream, int part, int nParts, bool heapFastAllowed, const BatchSrc *batch, FramePlan &plan) {
     if ((!cam && !batch) || !opts || (!lights && nLights > 0) || nLights < 0) return fail(XRT_E_INVALID_ARG, "xrt_render: null argument");
     if (opts->max_reflections < 0 || opts->max_reflections > 64) return fail(XRT_E_INVALID_ARG, "max_reflections out of range");
     if (opts->address_mode < XRT_ADDRESS_CLAMP || opts->address_mode > XRT_ADDRESS_MIRROR)
         return fail(XRT_E_INVALID_ARG, "Value does not fall within the expected range: addressMode (MAT:85)");
     if (opts->filtering != XRT_FILTER_POINT && opts->filtering != XRT_FILTER_BILINEAR)
         return fail(XRT_E_INVALID_ARG, "Value does not fall within the expected range: filtering (MAT:97)");
-    const bool heap = s->mat[F.mat].anyTransparent && opts->max_reflections > 0;   // RT:586-702: binary ray tree (by the materials of the frame's version)
+    FramePlan p;
+    RayGenParams &g = p.g;
+    p.addressMode = opts->address_mode; p.filtering = opts->filtering;
+    p.heap = s.mat[matVersion].anyTransparent && opts->max_reflections > 0;   // RT:586-702: binary ray tree (by the materials of the frame's version)
+    const bool heap = p.heap;
     if (heap && opts->max_reflections > 12)
         return fail(XRT_E_UNSUPPORTED, "Transparent materials with MaxReflections > 12 (a ray tree of more than 8191 nodes per pixel)");
     const int msMode = opts->use_multisampling;
     if (msMode != XRT_MS_OFF && msMode != XRT_MS_FIXED16 && msMode != XRT_MS_ADAPTIVE) return fail(XRT_E_INVALID_ARG, "use_multisampling");
-    const bool adaptive = msMode == XRT_MS_ADAPTIVE;
-    const int quality = adaptive ? opts->multisample_quality : 0;
-    if (adaptive && (quality < 0 || quality > 6)) return fail(XRT_E_UNSUPPORTED, "MultisampleQuality above 6 (4^7 sub-quadrants per pixel)");
-    RayGenParams g;
+    p.adaptive = msMode == XRT_MS_ADAPTIVE;
+    const bool adaptive = p.adaptive;
+    p.quality = adaptive ? opts->multisample_quality : 0;
+    if (adaptive && (p.quality < 0 || p.quality > 6)) return fail(XRT_E_UNSUPPORTED, "MultisampleQuality above 6 (4^7 sub-quadrants per pixel)");
+    p.batch = batch != nullptr;
+    p.capturePaths = batch && batch->paths;   // the pass also records its ray paths (paths.hip)
+    p.collect = opts->collect_stats != 0;
     float rootBox[6] = {0, 0, 0, 0, 0, 0};
-    const bool haveRoot = s->host->arrays.snodes.size() >= 2;
+    const bool haveRoot = s.host->arrays.snodes.size() >= 2;
     if (haveRoot) {
-        const f4 lo = s->host->arrays.snodes[0], hi = s->host->arrays.snodes[1];
+        const f4 lo = s.host->arrays.snodes[0], hi = s.host->arrays.snodes[1];
         rootBox[0] = lo.x; rootBox[1] = lo.y; rootBox[2] = lo.z; rootBox[3] = hi.x; rootBox[4] = hi.y; rootBox[5] = hi.z;
     }
-    int rc = XRT_OK;
     if (batch) {   // a ray list: one row of n "pixels", every path has its record (nothing is culled by a screen rectangle)
         if (adaptive || msMode != XRT_MS_OFF || opts->shard_count > 1 || nParts > 1 || batch->n <= 0 || batch->n > 0x7fffffff / 2)
             return fail(XRT_E_INTERNAL, "a ray batch is a plain pass of 1 .. 2^30 rays");
@@ -331,33 +319,32 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         g.cullX1 = g.width - 1;
         g.batch = reinterpret_cast<const f4 *>(batch->rays); g.batchRefIndex = batch->refIndex;
     } else {
-        rc = make_raygen(cam, opts, g, (haveRoot && !s->cfg.noRectCull) ? rootBox : nullptr);
-        if (rc != XRT_OK) return rc;
+        if (int rc = make_raygen(cam, opts, g, (haveRoot && !s.cfg.noRectCull) ? rootBox : nullptr)) return rc;
         if (adaptive) g.samples = 4;
         g.cullSkipsRecord = heap ? 0 : 1;   // (k_compose_tree reads every root record)
     }
-    const int R = opts->max_reflections;
-    const int nL = nLights;
-    const long long totalTiles = (long long)g.tilesX * g.tilesY;
+    const int R = p.R = opts->max_reflections;
+    const int nL = p.nL = nLights;
+    p.totalTiles = (long long)g.tilesX * g.tilesY;
     // an installed tile table for this frame geometry replaces the round-robin layout (xrt.h xrt_scene_set_tile_table)
-    const bool tabled = !batch && !s->tileTable.empty() && s->tableW == g.width && s->tableH == g.height && s->tableCount == g.shardCount;
-    const int *const tableRow = tabled ? s->tileTable.data() + (size_t)g.shardRank * s->tableTpr : nullptr;
-    g.tileOfSlot = tabled ? s->tileTableDev.p + (size_t)g.shardRank * s->tableTpr : nullptr;
-    const long long myTiles = tabled ? s->tableTpr : shard_tiles_per_rank(totalTiles, g.shardCount, g.tilesX);   // tiles_per_rank (slots, some may be past the end)
-    auto tile_of_slot = [&](long long sl) -> long long { return tabled ? (long long)tableRow[sl] : shard_tile(sl, g.shardRank, g.shardCount, g.tilesX); };
-    const long long totalPixels = myTiles * 512;
-    if (adaptive && totalPixels * 4 > 0x7fffffffLL) return fail(XRT_E_UNSUPPORTED, "frame too large for adaptive supersampling");
-    const long long framePaths = batch ? batch->n : totalPixels * g.samples;   // the whole frame (this shard)
+    p.tabled = !batch && !s.tileTable.empty() && s.tableW == g.width && s.tableH == g.height && s.tableCount == g.shardCount;
+    g.tileOfSlot = p.tabled ? s.tileTableDev.p + (size_t)g.shardRank * s.tableTpr : nullptr;
+    p.myTiles = p.tabled ? s.tableTpr : shard_tiles_per_rank(p.totalTiles, g.shardCount, g.tilesX);   // tiles_per_rank (slots, some may be past the end)
+    p.totalPixels = p.myTiles * 512;
+    if (adaptive && p.totalPixels * 4 > 0x7fffffffLL) return fail(XRT_E_UNSUPPORTED, "frame too large for adaptive supersampling");
+    p.framePaths = batch ? batch->n : p.totalPixels * g.samples;   // the whole frame (this shard)
     // part `part` of `nParts`: a contiguous range of the frame's paths (whole tiles), rendered by its own frame context
-    const long long partStride = nParts > 1 ? ((framePaths / nParts + 8191) / 8192) * 8192 : framePaths;
-    const long long partStart = (long long)part * partStride;
-    const long long firstPaths = nParts > 1 ? std::max(0LL, std::min(partStride, framePaths - partStart)) : framePaths;
+    const long long partStride = nParts > 1 ? ((p.framePaths / nParts + 8191) / 8192) * 8192 : p.framePaths;
+    p.partStart = (long long)part * partStride;
+    p.firstPaths = nParts > 1 ? std::max(0LL, std::min(partStride, p.framePaths - p.partStart)) : p.framePaths;
+    const long long firstPaths = p.firstPaths;
     if (nParts > 1 && (adaptive || firstPaths <= 0)) return fail(XRT_E_INTERNAL, "frame parts need a plain frame");
+    p.hintPaths = (nParts == 1 && !adaptive) ? firstPaths : -1;
     // Chunking.  Without refraction a path owns one ray per generation.  With Transparent materials it may own up to
     // 2^k in generation k, but few paths do: chunks are sized optimistically (ray buffers of HEAP_RAY_CAP rays,
     // level records bounded by 8 GB) and a chunk whose generation overflows is retried with a quarter of the paths.
-    const size_t nodes = heap ? (((size_t)1 << (R + 1)) - 1) : (size_t)(R + 1);
-    long long maxPaths = s->cfg.maxChunkPaths;
+    p.nodes = heap ? (((size_t)1 << (R + 1)) - 1) : (size_t)(R + 1);
+    long long maxPaths = s.cfg.maxChunkPaths;
     // The reference iterates a List<ILight> of any length (RT:534-542).  The shadow rays of one generation are counted in an int
     // (at most 2^30): many lights shrink the chunk, they are not refused -- until not even 8192 paths fit a generation.
     const long long lightBound = (1LL << 30) / (nL > 0 ? nL : 1);
@@ -366,237 +353,814 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     // the chunk to what XRT_SHADOW_BYTES (default 8 GB per context) holds -- the frame then takes the multi-chunk path -- instead of
     // failing with XRT_E_OOM (a 1080p frame with 100 lights would want 17 GB).
     if (nL > 0) {
-        const long long byBytes = ((long long)s->cfg.shadowBytes / (84LL * nL)) & ~8191LL;
+        const long long byBytes = ((long long)s.cfg.shadowBytes / (84LL * nL)) & ~8191LL;
         if (byBytes < maxPaths) maxPaths = byBytes < 8192 ? 8192 : byBytes;
     }
     if (maxPaths < 8192) return fail(XRT_E_UNSUPPORTED, "%d lights: the shadow rays of 8192 paths do not fit one generation (2^30 rays)", nL);
     if (heap) {
         if (maxPaths > (1 << 21)) maxPaths = 1 << 21;   // (a 1080p frame is one chunk when the level records fit 8 GB: MaxReflections <= 6)
-        const long long byRecords = (long long)((8ull << 30) / (nodes * 36ull));
+        const long long byRecords = (long long)((8ull << 30) / (p.nodes * 36ull));
         if (byRecords < maxPaths) maxPaths = byRecords;
         maxPaths &= ~63LL;
         if (maxPaths < 64) maxPaths = 64;
     }
-    const long long chunkPaths = firstPaths < maxPaths ? firstPaths : maxPaths;
-    const int P = (int)chunkPaths;
-    size_t rayCap = (size_t)P;
-    F.liveCap = (size_t)P;
+    p.chunkPaths = firstPaths < maxPaths ? firstPaths : maxPaths;
+    const bool oneChunk = firstPaths <= p.chunkPaths;
+    p.P = (int)p.chunkPaths;
+    p.rayCap = (size_t)p.P;
+    p.liveCap = (size_t)p.P;
     // The per-ray arrays hold LIVE rays only (k_raygen compacts them): a live primary ray belongs to a pixel inside the screen rectangle
     // of the scene's root box, so a plain or 16-sub-ray frame of one chunk needs room for the rectangle's paths, not for every path
     // (C5: 52 % of the image); later generations have fewer rays than the one before.  (Adaptive frames: the deeper quadrant levels are
     // lists of up to a quadrant per pixel; ray trees: sized below.)
-    if (!heap && !adaptive && !batch && firstPaths <= chunkPaths) {
+    if (!heap && !adaptive && !batch && oneChunk) {
         const long long rectPaths = (long long)std::max(0, g.cullX1 - g.cullX0 + 1) * (long long)std::max(0, g.cullY1 - g.cullY0 + 1) * g.samples + 64;
-        if (rectPaths < (long long)rayCap) { rayCap = (size_t)rectPaths; F.liveCap = rayCap; }
+        if (rectPaths < (long long)p.rayCap) { p.rayCap = (size_t)rectPaths; p.liveCap = p.rayCap; }
     }
     // ... and the two per-level records (16 bytes each per path and level: the largest arrays of a frame) exist only for the TILES that overlap the rectangle (xrt_core.h
     // LvlMap): plain unsharded frames of one chunk and one part, whose tiles are numbered row by row.  (C5: 3.2 -> 1.7 GB per frame context.)
-    size_t lvlStride = (size_t)P;
+    p.lvlStride = (size_t)p.P;
     std::memset(&g.lvl, 0, sizeof(g.lvl));
-    if (!heap && !adaptive && firstPaths <= chunkPaths && nParts == 1 && partStart == 0 && g.shardCount == 1 && !tabled && g.cullSkipsRecord && s->cfg.levelMap &&
+    if (!heap && !adaptive && oneChunk && nParts == 1 && p.partStart == 0 && g.shardCount == 1 && !p.tabled && g.cullSkipsRecord && s.cfg.levelMap &&
         g.cullX1 >= g.cullX0 && g.cullY1 >= g.cullY0) {
         const int shift = 9 + (g.samples == 16 ? 4 : (g.samples == 4 ? 2 : 0));
         const int tx0 = g.cullX0 / XRT_TILE_W, tx1 = g.cullX1 / XRT_TILE_W, ty0 = g.cullY0 / XRT_TILE_H, ty1 = g.cullY1 / XRT_TILE_H;
         const long long kept = (long long)(tx1 - tx0 + 1) * (ty1 - ty0 + 1);
-        if (kept < totalTiles && (kept << shift) < (long long)P) {
-            g.lvl.on = 1; g.lvl.tilesX = g.tilesX; g.lvl.tx0 = tx0; g.lvl.ty0 = ty0; g.lvl.rw = tx1 - tx0 + 1; g.lvl.shift = shift;
-            g.lvl.inv = (unsigned)(((1ULL << 32) + (unsigned)g.tilesX - 1) / (unsigned)g.tilesX);
-            bool exact = totalTiles < (1LL << 24);
-            if (exact && !(s->lvlCheckedTilesX == g.tilesX && s->lvlCheckedTiles >= totalTiles)) {   // (checked once per frame geometry)
-                for (long long t = 0; exact && t < totalTiles; t++) exact = (unsigned)(((unsigned long long)t * g.lvl.inv) >> 32) == (unsigned)(t / g.tilesX);
-                if (exact) { s->lvlCheckedTilesX = g.tilesX; s->lvlCheckedTiles = totalTiles; }
+        if (kept < p.totalTiles && (kept << shift) < (long long)p.P) {
+            const unsigned inv = (unsigned)(((1ULL << 32) + (unsigned)g.tilesX - 1) / (unsigned)g.tilesX);
+            bool exact = p.totalTiles < (1LL << 24);
+            if (exact && !(s.lvlCheckedTilesX == g.tilesX && s.lvlCheckedTiles >= p.totalTiles)) {   // (checked once per frame geometry: the caller keeps the memo)
+                for (long long t = 0; exact && t < p.totalTiles; t++) exact = (unsigned)(((unsigned long long)t * inv) >> 32) == (unsigned)(t / g.tilesX);
+                p.lvlVerified = exact;
             }
-            if (exact) lvlStride = (size_t)(kept << shift);
-            else std::memset(&g.lvl, 0, sizeof(g.lvl));
+            if (exact) {
+                g.lvl.on = 1; g.lvl.tilesX = g.tilesX; g.lvl.tx0 = tx0; g.lvl.ty0 = ty0; g.lvl.rw = tx1 - tx0 + 1; g.lvl.shift = shift; g.lvl.inv = inv;
+                p.lvlStride = (size_t)(kept << shift);
+            }
         }
     }
     if (heap) {
-        const size_t capL = (size_t)std::min<long long>(s->cfg.heapRayCap, lightBound);   // (>= 8192 >= ... see above; P <= lightBound as well)
-        rayCap = (R < 20 && ((size_t)P << R) < capL) ? ((size_t)P << R) : capL;
-        if (rayCap < (size_t)P) rayCap = (size_t)P;
+        const size_t capL = (size_t)std::min<long long>(s.cfg.heapRayCap, lightBound);   // (>= 8192 >= ... see above; P <= lightBound as well)
+        p.rayCap = (R < 20 && ((size_t)p.P << R) < capL) ? ((size_t)p.P << R) : capL;
+        if (p.rayCap < (size_t)p.P) p.rayCap = (size_t)p.P;
     }
-    if ((unsigned long long)rayCap * (unsigned long long)(nL > 0 ? nL : 1) > (1ull << 30)) return fail(XRT_E_UNSUPPORTED, "frame too large: %zu rays x %d lights per generation", rayCap, nL);
-    const size_t shadowCap = rayCap;   // hits of one generation (each emits nL shadow rays)
-    const bool wantF32 = d_outF32 != nullptr && !adaptive && g.samples == 1;
-    bool fuseResolve = !adaptive && !heap && !batch && g.samples == 1;   // k_compose writes the framebuffer itself (not where paths end early, below)
-    // buffers
-    if ((rc = W.rays0.ensure(rayCap)) || (rc = W.rays1.ensure(rayCap)) || (rc = W.hits.ensure(rayCap)) || (rc = W.path0.ensure(rayCap)) ||
-        (rc = W.path1.ensure(rayCap)) || (rc = W.hitFlags0.ensure(rayCap)) ||
-        (rc = W.shadowFlags.ensure(rayCap * (nL > 0 ? nL : 1))) || (rc = W.slot0.ensure(rayCap)) ||
-        (rc = W.slot1.ensure(rayCap)) || (rc = W.index0.ensure(rayCap)) || (rc = W.heavyList.ensure(rayCap)) || (rc = W.shadowRays.ensure(rayCap * (nL > 0 ? nL : 1))) ||
-        (rc = W.shadowHits.ensure(rayCap * (nL > 0 ? nL : 1))) || (rc = W.lvlA.ensure(lvlStride * nodes)) ||
-        (rc = W.lvlB.ensure(lvlStride * nodes)) || (rc = W.sampleColor.ensure(P)) || (rc = W.lights.ensure(nL > 0 ? nL : 1)) ||
-        (rc = s->counters.ensure(2 * C_COUNT + 8)))
-        return rc;
-    if (!s->cfg.waveTimesPath.empty() && !s->waveTimes.p) {
-        if ((rc = s->waveTimes.ensure((size_t)16 * 3 * 8192))) return rc;
-        HIPCHECK(hipMemset(s->waveTimes.p, 0, (size_t)16 * 3 * 8192 * sizeof(unsigned long long)));
-    }
-    if (heap && ((rc = W.node0.ensure(rayCap)) || (rc = W.node1.ensure(rayCap)) || (rc = W.ref0.ensure(rayCap)) || (rc = W.ref1.ensure(rayCap)) ||
-                 (rc = W.slotNode0.ensure(rayCap)) || (rc = W.slotNode1.ensure(rayCap)) ||
-                 (rc = W.lvlAlpha.ensure((size_t)P * nodes))))
-        return rc;
-    if (wantF32 && !batch && (rc = W.sampleF32.ensure((size_t)P * 3))) return rc;   // (a batch's compose writes the caller's arrays)
-    const BatchSrc::Paths *const pout = batch ? batch->paths : nullptr;   // the pass also records its ray paths (paths.hip)
-    unsigned pathEpoch = 0;                                               // ... the tag of the chunk attempt being enqueued
-    const int cntStride = 5 * (R + 2);          // per chunk: cnt[R+2], scnt[R+2], the long-ray list lengths [R+2], the shadow rays really emitted [R+2] (ShadeArgs::ae),
-                                                // the hits that took no slot [R+2] (ShadeArgs::finish; hits of generation k = scnt[k] + fcnt[k])
-    constexpr int QW = 1 + 2 * PACKET_QUEUE_WORDS;   // per launch step k: the lane kernel's queue word and the heads of each packet launch (closest, shadow)
-    const int qStride = QW * (R + 2);
+    if ((unsigned long long)p.rayCap * (unsigned long long)(nL > 0 ? nL : 1) > (1ull << 30)) return fail(XRT_E_UNSUPPORTED, "frame too large: %zu rays x %d lights per generation", p.rayCap, nL);
+    p.shadowCap = p.rayCap;   // hits of one generation (each emits nL shadow rays)
+    p.wantF32 = wantsF32 && !adaptive && g.samples == 1;
+    p.cntStride = 5 * (R + 2);   // per chunk: cnt[R+2], scnt[R+2], the long-ray list lengths [R+2], the shadow rays really emitted [R+2] (ShadeArgs::ae),
+                                 // the hits that took no slot [R+2] (ShadeArgs::finish; hits of generation k = scnt[k] + fcnt[k])
+    p.qStride = (1 + 2 * PACKET_QUEUE_WORDS) * (R + 2);   // per launch step k: the lane kernel's queue word and the heads of each packet launch (closest, shadow)
     // The common frame (one chunk, no supersampling levels, no ray tree, no counting pass) puts nothing but its kernels
     // on the stream: counters come back through k_compose's epilogue and the frame's events ride on raygen / compose.
     // ... and so does a ray-tree frame of one chunk: its buffers are sized optimistically, so the frame carries a word that says
     // "a generation did not fit"; frame_finish then renders it again the careful way (chunks, checks, retries) and the scene's later
     // ray-tree frames take that way from the start.  Not where something is enqueued behind the frame that a redo cannot recall
     // (the in-library gather of n_gpus > 1).
-    const bool heapFast = heap && heapFastAllowed && s->cfg.heapFast && s->heapFastOk && nParts == 1;
+    const bool heapOptimistic = heap && heapFastAllowed && s.cfg.heapFast && s.heapFastOk && nParts == 1;
     // ... and an adaptive frame (RT:170-311) whose passes are one chunk each: the sizes of the deeper quadrant levels stay on the device
     // (k_ms_decide counts, the next level's kernels read the count), the level buffers are sized optimistically -- one quadrant per
     // pixel and level -- and a level that does not fit sets the same kind of word.
-    const bool adaptiveFast = adaptive && !heap && heapFastAllowed && s->cfg.adaptiveFast && s->adaptiveFastOk && nParts == 1 && !opts->collect_stats && totalPixels * 4 <= chunkPaths &&
-                              (quality + 2) * (R + 2) * 2 + 2 <= MAX_STAMP_ROWS;
-    const bool fast = (adaptive ? adaptiveFast : (!heap || heapFast)) && firstPaths <= chunkPaths && !opts->collect_stats && !batch;
+    const bool adaptiveOptimistic = adaptive && !heap && heapFastAllowed && s.cfg.adaptiveFast && s.adaptiveFastOk && nParts == 1 && !p.collect && p.totalPixels * 4 <= p.chunkPaths &&
+                                    (p.quality + 2) * (R + 2) * 2 + 2 <= MAX_STAMP_ROWS;
+    p.fast = (adaptive ? adaptiveOptimistic : (!heap || heapOptimistic)) && oneChunk && !p.collect && !batch;
+    p.heapFast = heapOptimistic && p.fast;
+    p.adaptiveFast = adaptiveOptimistic && p.fast;
+    if (p.adaptiveFast) {
+        p.cntBase = ADAPTIVE_LEVEL_WORDS;
+        p.levelCap = (int)(s.cfg.adaptiveCap > 0 ? std::min(s.cfg.adaptiveCap, p.totalPixels) : p.totalPixels);   // (XRT_ADAPTIVE_CAP; deeper levels: one quadrant per pixel)
+    }
     // Answered at emission (kernels.h ShadeArgs::ae): plain one-chunk frames of one-body scenes whose mesh CAN face away from a ray as a whole (its normal
     // box does not hold the origin).  Not with the counting pass -- it counts the reference's work for every query from the ray lists --, not for ray trees.
     // (a batch of one chunk too: what part A answers depends on the hits alone, not on where generation 0 came from)
-    bool ae = (fast || (batch && firstPaths <= chunkPaths && !opts->collect_stats)) && !heap && !adaptive && nParts == 1 && s->sceneMode == MODE_SINGLE &&
-              s->view.nodeCull != 0 && s->cfg.answerAtEmission;
-    if (ae) {
-        const MeshRec &m0 = s->host->arrays.meshes[0];
-        ae = m0.nbMin[3] == 0.0f && (m0.nbMin[0] > 0.0f || m0.nbMax[0] < 0.0f || m0.nbMin[1] > 0.0f || m0.nbMax[1] < 0.0f || m0.nbMin[2] > 0.0f || m0.nbMax[2] < 0.0f);
+    if ((p.fast || (batch && oneChunk && !p.collect)) && !heap && !adaptive && nParts == 1 && s.sceneMode == MODE_SINGLE && s.view.nodeCull != 0 && s.cfg.answerAtEmission) {
+        const MeshRec &m0 = s.host->arrays.meshes[0];
+        p.ae = m0.nbMin[3] == 0.0f && (m0.nbMin[0] > 0.0f || m0.nbMax[0] < 0.0f || m0.nbMin[1] > 0.0f || m0.nbMax[1] < 0.0f || m0.nbMin[2] > 0.0f || m0.nbMax[2] < 0.0f);
     }
-    F.ae = ae;
     // Finished in part A (kernels.h ShadeArgs::finish): such a frame's hits whose shadow rays are all answered at emission take no slot.  Not with path capture --
     // k_paths_capture reads every hit's position from its slot record --, and the lights have to fit part A's bit mask.
-    const bool finishA = ae && !heap && !(batch && batch->paths) && nL <= 32 && s->cfg.finishInPartA;
-    if (ae && ((rc = W.shadowOut.ensure(rayCap * (nL > 0 ? nL : 1))) || (rc = W.shadowFlags1.ensure(rayCap * (nL > 0 ? nL : 1))))) return rc;
+    p.finishA = p.ae && !p.capturePaths && nL <= 32 && s.cfg.finishInPartA;
     // End early (kernels.h EndArgs): the frames that finish hits in part A, when they put nothing but kernels on the stream (their counters come back with
     // k_compose) and want no float colours -- every path that ends at generation 0 is coloured where it ends, k_compose walks a list of the others.
-    const bool endEarly = finishA && fast && !batch && !d_outF32 && s->cfg.endEarly;
-    if (endEarly) {
-        // The early writers go through the context's sample buffer and k_resolve copies it out: d_out stays what it was until the frame's last kernel,
-        // as in every other frame (a caller may have queued work of its own on it that is still running when k_raygen starts).
-        fuseResolve = false;
-        const int *before = W.composeList.p;
-        if ((rc = W.composeList.ensure(rayCap + 16))) return rc;
-        if (W.composeList.p != before) {   // the count words (kernels.h EndArgs::cnt) start at zero; a new allocation is rare, and the frame's stream is not chosen yet
-            HIPCHECK(hipMemsetAsync(W.composeList.p, 0, 16 * sizeof(int), s->stream));
-            HIPCHECK(hipStreamSynchronize(s->stream));
-        }
-    }
-    F.endEarly = endEarly;
+    p.endEarly = p.finishA && p.fast && !wantsF32 && s.cfg.endEarly;
     // ... and where such a frame has a level map, the tiles outside it take no part (kernels.h EndArgs::skipTiles).  Not with one sample per pixel: a group of the walk
     // would cover eight kept tiles, and C5 at one sample measured 0.740 -> 0.752 ms per step with it (profiles/gen0_latency) -- such frames keep the old walk.
-    const bool skipTiles = endEarly && g.lvl.on != 0 && g.samples > 1;
-    F.endSkipped = skipTiles ? (unsigned long long)(totalTiles - lvl_kept_tiles(g)) << g.lvl.shift : 0;
-    F.fast = fast;
-    F.heap = heap;
-    F.redone = false;
-    F.adaptiveFast = adaptiveFast && fast;
-    F.cntBase = 0;
-    if ((heapFast || adaptiveFast) && fast) {   // what a redo needs
-        F.redoCam = *cam; F.redoOpts = *opts; F.redoLights.assign(lights, lights + nLights);
-        F.redoOut = d_out; F.redoOutF32 = d_outF32; F.redoSt = st;
-    }
-    F.framePaths = (nParts == 1 && !adaptive) ? firstPaths : -1;
-    F.frameW = g.width; F.frameH = g.height;
+    p.skipTiles = p.endEarly && g.lvl.on != 0 && g.samples > 1;
+    p.endSkipped = p.skipTiles ? (unsigned long long)(p.totalTiles - lvl_kept_tiles(g)) << g.lvl.shift : 0;
+    // k_compose writes the framebuffer itself.  Not where paths end early: the early writers go through the context's sample buffer and k_resolve copies it
+    // out -- d_out stays what it was until the frame's last kernel, as in every other frame (a caller may have queued work of its own on it that is still
+    // running when k_raygen starts).
+    p.fuseResolve = !adaptive && !heap && !batch && g.samples == 1 && !p.endEarly;
     // the traversal launches time themselves on the device clock instead of carrying events (device_util.h); a frame of more
     // than MAX_STAMP_ROWS launches (many chunks or supersampling levels) goes on with events
-    const bool useStamps = !s->cfg.launchEvents && s->cfg.launchTiming && s->wallClockKHz > 0;
-    F.stampRows = 0;
-    if (useStamps) {
-        if ((rc = W.stamps.ensure((size_t)MAX_STAMP_ROWS * STAMP_STRIDE))) return rc;
-        if ((rc = F.stampHost.ensure((size_t)MAX_STAMP_ROWS * 2 * sizeof(unsigned long long), hipHostMallocMapped))) return rc;
-    }
-    if (!st) {
-        // No stream given.  Single-chunk frames get a stream per context, so that two frames in flight overlap on the GPU
-        // (C2: 0.139 -> 0.115 ms per frame, C3 2.7 -> 2.3); everything else, and frames of a few microseconds, stay on the
-        // scene's one stream.  (While every traversal launch carried two events, enqueueing on a stream that had gone idle cost
-        // ~15 us a launch and alternating streams made the host the bottleneck of 0.2 ms frames; the launches time themselves
-        // now, device_util.h.)
-        if (fast && s->lastFrameMs >= s->cfg.overlapMinMs && !s->cfg.oneStream) {
-            if ((rc = W.stream.create())) return rc;
-            st = W.stream;
-        } else st = s->stream;
-    }
-    if ((rc = pose_wait(s, F.pose, st)) || (rc = mat_acquire(s, F.mat, st))) return rc;   // (the poses and materials set before the frame's begin)
-    if (pout) {   // staging records like the level records: one per node and path of a chunk; cleared when allocated, told apart by tag afterwards
-        auto ensure_cleared = [&](DevBuf<f4> &b, size_t n) -> int {
-            const f4 *before = b.p; const size_t capBefore = b.cap;
-            int rc2 = b.ensure(n);
-            if (rc2 != XRT_OK) return rc2;
-            if (b.p != before || b.cap != capBefore) HIPCHECK(hipMemsetAsync(b.p, 0, b.cap * sizeof(f4), st));
-            return XRT_OK;
-        };
-        const size_t pathBlocks = ((size_t)P + PATHS_BLOCK - 1) / PATHS_BLOCK;
-        if ((rc = ensure_cleared(s->pathHit, lvlStride * nodes)) || (heap && (rc = ensure_cleared(s->pathDir, lvlStride * nodes))) || (rc = s->pathLocal.ensure((size_t)P)) ||
-            (rc = s->pathBlockSum.ensure(pathBlocks)) || (rc = s->pathBlockBase.ensure(pathBlocks)))
-            return rc;
-        if ((rc = s->pathPinned.ensure(64, hipHostMallocDefault))) return rc;
-    }
-    // Tile costs (xrt.h xrt_scene_tile_costs): the packets of plain one-chunk frames add their device-clock ticks to the tile of their first
-    // ray.  The words belong to the scene (both frame contexts add to them); a frame of another geometry or tile table starts them afresh.
-    unsigned *tileCostDev = nullptr;
-    if (fast && !adaptive && !heap && s->packetOk && framePaths < (1LL << 31)) {
-        if ((rc = s->tileCost.ensure((size_t)myTiles))) return rc;
-        bool same = s->costW == g.width && s->costH == g.height && (long long)s->costTiles.size() == myTiles;
-        for (long long sl = 0; same && sl < myTiles; sl++) { const long long t = tile_of_slot(sl); same = s->costTiles[(size_t)sl] == (t < totalTiles ? (int)t : -1); }
-        if (!same) {
-            s->costTiles.resize((size_t)myTiles);
-            for (long long sl = 0; sl < myTiles; sl++) { const long long t = tile_of_slot(sl); s->costTiles[(size_t)sl] = t < totalTiles ? (int)t : -1; }
-            s->costW = g.width; s->costH = g.height;
-            HIPCHECK(hipMemsetAsync(s->tileCost.p, 0, (size_t)myTiles * sizeof(unsigned), st));
-            if (s->frames[0].pending || s->frames[1].pending) HIPCHECK(hipStreamSynchronize(st));   // (the other context's frame may be adding to them: start clean)
-        }
-        tileCostDev = s->tileCost.p;
-    }
+    p.useStamps = !s.cfg.launchEvents && s.cfg.launchTiming && s.wallClockKHz > 0;
+    // No stream given.  Single-chunk frames get a stream per context, so that two frames in flight overlap on the GPU
+    // (C2: 0.139 -> 0.115 ms per frame, C3 2.7 -> 2.3); everything else, and frames of a few microseconds, stay on the
+    // scene's one stream.  (While every traversal launch carried two events, enqueueing on a stream that had gone idle cost
+    // ~15 us a launch and alternating streams made the host the bottleneck of 0.2 ms frames; the launches time themselves
+    // now, device_util.h.)
+    p.ownStream = !hasStream && p.fast && s.lastFrameMs >= s.cfg.overlapMinMs && !s.cfg.oneStream;
+    // Tile costs (xrt.h xrt_scene_tile_costs): the packets of plain one-chunk frames add their device-clock ticks to the tile of their first ray.
+    p.tileCosts = p.fast && !adaptive && !heap && s.packetOk && p.framePaths < (1LL << 31);
     // which ray populations the wave-packet kernel traces this frame (packet.hip): bit 0 primary rays, 1 shadow rays, 2 closest-hit
     // rays of later generations
     // (two-level scenes: at any sample count and in every generation -- what a packet shares there is the scene walk, the bodies'
     // records and the mesh walk of a body, and an 8x8-pixel block of a 1-sample frame sees one or two bodies: C3 2.28 -> 1.57 ms,
     // C4 6.64 -> 4.37 ms per pipelined frame (packets for the first two generations only: 1.78 / 5.0, profiles/r03/packet_masks.txt);
     // one-body scenes: only with 16 sub-rays, and only the first two generations, see above)
-    const int pkAuto = s->sceneMode == MODE_SCENE ? 23 : (g.samples >= 16 ? 7 : 0);
+    const int pkAuto = s.sceneMode == MODE_SCENE ? 23 : (g.samples >= 16 ? 7 : 0);
     // (ray-tree frames -- Transparent materials -- of two-level scenes: the first two generations and the first shadow rays, where the image
     // is big enough for a launch to be more than its floor: G2 at 720p 1.12 -> 0.97 ms, the reference's default scene at 512x512 0.31 ->
     // 0.40 with packets, so not there; packets in every generation of a ray tree are 1.5-3 x slower (profiles/r03/packet_masks_ray_trees.txt))
-    const int pkHeap = s->cfg.packetMaskHeap >= 0 ? s->cfg.packetMaskHeap : ((s->sceneMode == MODE_SCENE && (long long)g.width * g.height * g.samples >= 600000LL) ? 7 : 0);
-    int pkMask = !s->packetOk ? 0 : (heap ? pkHeap : (s->cfg.packetMask >= 0 ? s->cfg.packetMask : pkAuto));
+    const int pkHeap = s.cfg.packetMaskHeap >= 0 ? s.cfg.packetMaskHeap : ((s.sceneMode == MODE_SCENE && (long long)g.width * g.height * g.samples >= 600000LL) ? 7 : 0);
+    const int pkScene = !s.packetOk ? 0 : (heap ? pkHeap : (s.cfg.packetMask >= 0 ? s.cfg.packetMask : pkAuto));
     // A batch's generation 0 is in the caller's order, which nothing says is coherent: 64 consecutive rays need not be a patch of the same
     // surface, and a packet of scattered rays walks the union of their paths.  It goes to the per-lane kernel unless XRT_PACKET / XRT_PACKET_HEAP
     // name the packet kernel for it (bit 0; both kernels give the same answers).  Its later generations follow the hits as a frame's do.
-    if (batch && (heap ? s->cfg.packetMaskHeap : s->cfg.packetMask) < 0) pkMask &= ~1;
-    const bool laneClosest = (pkMask & 5) != 5;   // some closest-hit generation is traced ray by ray: the long-ray feedback has a reader
-    const bool wantFeedback = fast && !heap && !adaptive && s->deepMeshes && !s->cfg.noFeedback && laneClosest;   // (the paths of a deeper quadrant level are a list: no stable key)
+    p.pkMask = (batch && (heap ? s.cfg.packetMaskHeap : s.cfg.packetMask) < 0) ? (pkScene & ~1) : pkScene;
+    const bool laneClosest = (p.pkMask & 5) != 5;   // some closest-hit generation is traced ray by ray: the long-ray feedback has a reader
+    p.wantFeedback = p.fast && !heap && !adaptive && s.deepMeshes && !s.cfg.noFeedback && laneClosest;   // (the paths of a deeper quadrant level are a list: no stable key)
+    // "long ray first" (kernels.hip): the producer of generation k lists its long rays, launch #k takes them first
+    p.listLong = s.heavyPath > 0.0f || p.wantFeedback;
+    p.hinted = p.fast && nParts == 1 && s.genKey == firstPaths * 64 + nL && s.genHeap == heap && s.cfg.gridHints;
+    // valid pixels of this part
+    if (batch) p.validPixels = (unsigned long long)batch->n;
+    else {
+        const long long slot0 = p.partStart / (512LL * g.samples), slot1 = (p.partStart + firstPaths + 512LL * g.samples - 1) / (512LL * g.samples);   // tile slots of this part
+        for (long long sl = slot0; sl < slot1; sl++) {
+            const long long t = tile_of_slot(s, p, sl);
+            if (t >= p.totalTiles) break;
+            if (t < 0) continue;   // (an unused slot of a tile table)
+            const int tx = (int)(t % g.tilesX), ty = (int)(t / g.tilesX);
+            const int w = std::min(g.width - tx * XRT_TILE_W, (int)XRT_TILE_W), h = std::min(g.height - ty * XRT_TILE_H, (int)XRT_TILE_H);
+            p.validPixels += (unsigned long long)w * h;
+        }
+    }
+    for (int i = 0; i < nL; i++)
+        if (lights[i].kind != XRT_LIGHT_SPOT && lights[i].kind != XRT_LIGHT_DIRECTIONAL) return fail(XRT_E_INVALID_ARG, "unknown light kind");
+    plan = p;
+    return XRT_OK;
+}
+
+namespace {
+
+int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats);
+int split_arena(xrt_scene *s, DevBuf<unsigned> &items, DevBuf<unsigned> &recs, PacketArgs &PA, hipStream_t st);
+
+// Hits of generation k in a chunk's counter block hc (FramePlan::cntStride): the slots part A took plus the hits it finished itself (ShadeArgs::finish)
+static inline long long gen_hits(const int *hc, int R, int k) { return (long long)hc[(R + 2) + k] + (long long)hc[4 * (R + 2) + k]; }
+
+// One chunk's counters hc into the frame's tallies.  The `answered` part runs only in frames answered at emission: queries part A answered itself -- the
+// hits' shadow rays that were not emitted, and (not in the last generation) their reflections.
+void tally_chunk(xrt_scene::FrameCtx &F, const int *hc) {
+    const FramePlan &P = F.plan;
+    const int R = P.R;
+    for (int k = 0; k <= R; k++) {
+        F.shaded += (unsigned long long)gen_hits(hc, R, k);
+        if (k > 0) F.closestDeep += (unsigned long long)(P.heap ? hc[k] : gen_hits(hc, R, k - 1));   // reflection chain: one ray per parent hit
+        else F.live0 += (unsigned long long)hc[0];
+        if (P.ae) {
+            F.answered += (unsigned long long)gen_hits(hc, R, k) * (unsigned long long)P.nL - (unsigned long long)hc[3 * (R + 2) + k];
+            if (k < R) F.answered += (unsigned long long)(gen_hits(hc, R, k) - hc[k + 1]);
+        }
+    }
+}
+
+// Every work buffer of the frame context (and the scene's shared ones) at the size the plan names.  What is new and must start at zero is cleared here on
+// the SCENE's stream (the compose list's count words: the frame's stream is not chosen yet, and a new allocation is rare); the path staging records are
+// cleared on the frame's stream by the caller, who is told which of them are new (freshPathRecs: bit 0 pathHit, bit 1 pathDir).
+int ensure_frame_buffers(xrt_scene *s, xrt_scene::FrameCtx &F, const FramePlan &P, unsigned &freshPathRecs) {
+    xrt_scene::WorkBufs &W = F.w;
+    const size_t rayCap = P.rayCap, perLight = rayCap * (size_t)(P.nL > 0 ? P.nL : 1);
+    int rc;
+    if ((rc = W.rays0.ensure(rayCap)) || (rc = W.rays1.ensure(rayCap)) || (rc = W.hits.ensure(rayCap)) || (rc = W.path0.ensure(rayCap)) ||
+        (rc = W.path1.ensure(rayCap)) || (rc = W.hitFlags0.ensure(rayCap)) ||
+        (rc = W.shadowFlags.ensure(perLight)) || (rc = W.slot0.ensure(rayCap)) ||
+        (rc = W.slot1.ensure(rayCap)) || (rc = W.index0.ensure(rayCap)) || (rc = W.heavyList.ensure(rayCap)) || (rc = W.shadowRays.ensure(perLight)) ||
+        (rc = W.shadowHits.ensure(perLight)) || (rc = W.lvlA.ensure(P.lvlStride * P.nodes)) ||
+        (rc = W.lvlB.ensure(P.lvlStride * P.nodes)) || (rc = W.sampleColor.ensure(P.P)) || (rc = W.lights.ensure(P.nL > 0 ? P.nL : 1)) ||
+        (rc = s->counters.ensure(2 * C_COUNT + 8)))
+        return rc;
+    if (!s->cfg.waveTimesPath.empty() && !s->waveTimes.p) {
+        if ((rc = s->waveTimes.ensure((size_t)16 * 3 * 8192))) return rc;
+        HIPCHECK(hipMemset(s->waveTimes.p, 0, (size_t)16 * 3 * 8192 * sizeof(unsigned long long)));
+    }
+    if (P.heap && ((rc = W.node0.ensure(rayCap)) || (rc = W.node1.ensure(rayCap)) || (rc = W.ref0.ensure(rayCap)) || (rc = W.ref1.ensure(rayCap)) ||
+                   (rc = W.slotNode0.ensure(rayCap)) || (rc = W.slotNode1.ensure(rayCap)) ||
+                   (rc = W.lvlAlpha.ensure((size_t)P.P * P.nodes))))
+        return rc;
+    if (P.wantF32 && !P.batch && (rc = W.sampleF32.ensure((size_t)P.P * 3))) return rc;   // (a batch's compose writes the caller's arrays)
+    if (P.ae && ((rc = W.shadowOut.ensure(perLight)) || (rc = W.shadowFlags1.ensure(perLight)))) return rc;
+    if (P.endEarly) {
+        const int *before = W.composeList.p;
+        if ((rc = W.composeList.ensure(rayCap + 16))) return rc;
+        if (W.composeList.p != before) {   // the count words (kernels.h EndArgs::cnt) start at zero
+            HIPCHECK(hipMemsetAsync(W.composeList.p, 0, 16 * sizeof(int), s->stream));
+            HIPCHECK(hipStreamSynchronize(s->stream));
+        }
+    }
+    if (P.useStamps) {
+        if ((rc = W.stamps.ensure((size_t)MAX_STAMP_ROWS * STAMP_STRIDE))) return rc;
+        if ((rc = F.stampHost.ensure((size_t)MAX_STAMP_ROWS * 2 * sizeof(unsigned long long), hipHostMallocMapped))) return rc;
+    }
+    freshPathRecs = 0;
+    if (P.capturePaths) {   // staging records like the level records: one per node and path of a chunk; cleared when allocated, told apart by tag afterwards
+        auto ensure_fresh = [&](DevBuf<f4> &b, size_t n, unsigned bit) -> int {
+            const f4 *before = b.p; const size_t capBefore = b.cap;
+            const int rc2 = b.ensure(n);
+            if (rc2 == XRT_OK && (b.p != before || b.cap != capBefore)) freshPathRecs |= bit;
+            return rc2;
+        };
+        const size_t pathBlocks = ((size_t)P.P + PATHS_BLOCK - 1) / PATHS_BLOCK;
+        if ((rc = ensure_fresh(s->pathHit, P.lvlStride * P.nodes, 1u)) || (P.heap && (rc = ensure_fresh(s->pathDir, P.lvlStride * P.nodes, 2u))) || (rc = s->pathLocal.ensure((size_t)P.P)) ||
+            (rc = s->pathBlockSum.ensure(pathBlocks)) || (rc = s->pathBlockBase.ensure(pathBlocks)))
+            return rc;
+        if ((rc = s->pathPinned.ensure(64, hipHostMallocDefault))) return rc;
+    }
+    return XRT_OK;
+}
+
+// What a pass does with a chunk's samples once the chunk is enqueued.
+struct ChunkPost {
+    enum Kind { NOTHING, EMIT_PATHS, RESOLVE, COPY_LEVEL } kind = NOTHING;
+    uint32_t *levelColor = nullptr;   // COPY_LEVEL: the quadrant level's colour array
+};
+
+// The enqueue of one frame on its stream: what frame_begin has gathered (scene, context, plan, views, stream, the two frame events, the caller's
+// arrays) and the little that changes while the frame's launches are made.
+struct FrameJob {
+    xrt_scene *s;
+    xrt_scene::FrameCtx &F;
+    const FramePlan &P;
+    xrt_scene::WorkBufs &W;
+    SceneView S;          // every kernel of the frame reads one pose version
+    ShadeView V;          // ... and one material version
+    hipStream_t st;
+    hipEvent_t e0, e1;    // the frame's start and end
+    const BatchSrc *batch;
+    uint32_t *d_out;
+    float *d_outF32;
+    unsigned *tileCostDev;   // the scene's tile cost words, or null
+    int *overflowFlag;       // "a generation did not fit its buffers"
+    bool startEvent;         // the frame's first raygen launch carries its start event (fast frames put nothing but kernels on the stream)
+    unsigned pathEpoch = 0;  // path capture: the tag of the chunk attempt being enqueued
+
+    static constexpr int QW = 1 + 2 * PACKET_QUEUE_WORDS;   // queue words of a launch step (FramePlan::qStride)
+
+    // One launch step of a chunk: what its traversal launches share.
+    struct Step {
+        const RayGenParams &gp;
+        unsigned *q;              // the chunk's queue words
+        long long pathBase;
+        int k;
+        const int *pathOfClosest; // path of every closest-hit ray of the step
+        const SlotRec *slotPrev;  // slot records of the generation whose shadow rays the step traces
+    };
+
+    bool packet_closest(int k) const { const int m = P.pkMask; return (k == 0 ? (m & 1) : (k == 1 ? (m & 4) : ((m & 4) && (m & 16)))) != 0; }
+    bool packet_shadow(int k) const { return (P.pkMask & 2) != 0 && (k <= 1 || (P.pkMask & 16) != 0); }   // shadow rays of generation k-1
+    long long hint(const long long *v, int k) const { return (P.hinted && k < 68 && v[k] >= 0) ? 4 * v[k] + 4096 : -1; }
+    int ensure_pinned(size_t bytes) { return F.pinned.bytes < bytes ? F.pinned.ensure(bytes + 4096, hipHostMallocMapped) : XRT_OK; }
+    HeavyArgs heavy_for(int k, int *hcnt) const;
+    int pick_timing(int grid, unsigned long long *&stamps, hipEvent_t &a0, hipEvent_t &a1);
+    int launch_packets(const Step &T, const IntersectArgs &I, bool shadow, long long nHost, const IntersectArgs *I2 = nullptr);
+    int launch_lanes(const Step &T, const IntersectArgs *C, const IntersectArgs *B, int Pc);
+    int enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int Pc, long long pathBase, uint32_t *sampleOut = nullptr, const FrameEpilogue *epi = nullptr,
+                      int *listCnt = nullptr);
+    int post_chunk(const ChunkPost &post, int Pc, long long pathBase);
+    int run_pass_tree(const RayGenParams &gp, long long total, const ChunkPost &post, float progress0, float progress1, bool finalPass);
+    int run_pass(const RayGenParams &gp, long long total, const ChunkPost &post, float progress0, float progress1, bool finalPass);
+    int batch_frame();
+    int plain_frame();
+    int adaptive_in_flight();
+    int adaptive_careful();
+};
+
+// The long-ray list of launch #k, if it has one (hcnt: the chunk's list lengths).
+HeavyArgs FrameJob::heavy_for(int k, int *hcnt) const {
+    HeavyArgs H;
+    if (P.listLong && (k == 0 || !P.heap) && !packet_closest(k)) {   // (packets are not scheduled ray by ray)
+        H.list = W.heavyList.p; H.count = hcnt + k; H.path = s->heavyPath;
+        if (P.wantFeedback) { H.costMap = s->costMap.p + (size_t)k * (size_t)P.framePaths + (size_t)P.partStart; H.epoch = s->epoch & 0xffffu; H.costThreshold = s->costT[k]; }
+    }
+    return H;
+}
+
+// How a traversal launch of `grid` blocks is timed: by a row of device-clock stamps (stamps), by a pair of events (a0, a1), or not at all.
+int FrameJob::pick_timing(int grid, unsigned long long *&stamps, hipEvent_t &a0, hipEvent_t &a1) {
+    a0 = get_event(F.events, F.ev); a1 = get_event(F.events, F.ev + 1);
+    if (!a0 || !a1) return fail(XRT_E_HIP, "hipEventCreate failed");
+    if (P.useStamps && grid * 4 <= STAMP_SLOTS && F.stampRows < s->cfg.maxStampRows) { stamps = W.stamps.p + (size_t)F.stampRows++ * STAMP_STRIDE; a0 = a1 = nullptr; }
+    else if (!s->cfg.launchTiming) a0 = a1 = nullptr;
+    else { F.pairs.push_back({F.ev, F.ev + 1}); F.ev += 2; }
+    return XRT_OK;
+}
+
+// A segment of coherent rays to the wave-packet kernel (I2: a second ray population for the same launch -- the shadow rays beside the closest-hit rays -- or null).
+int FrameJob::launch_packets(const Step &T, const IntersectArgs &I, bool shadow, long long nHost, const IntersectArgs *I2) {
+    const int k = T.k, word = shadow ? 1 : 0, R = P.R, nL = P.nL;
+    int rc;
+    PacketArgs PA;
+    PA.rays = I.rays; PA.hits = I.hits; PA.flags = I.flags; PA.index = I.index; PA.nDev = I.nDev; PA.nMul = I.nMul; PA.n = I.n; PA.nCap = I.nCap;
+    PA.scatter = I.scatter;
+    if (I2) { PA.rays2 = I2->rays; PA.hits2 = I2->hits; PA.flags2 = I2->flags; PA.nDev2 = I2->nDev; PA.nMul2 = I2->nMul; PA.nCap2 = I2->nCap; PA.scatter2 = I2->scatter; }
+    if (tileCostDev) {   // which tile pays for a packet: the path of its first ray (closest-hit rays: the path list; shadow rays: their hit's slot record)
+        PA.tileCost = tileCostDev; PA.tileBase = (int)T.pathBase; PA.tileShift = 9 + (T.gp.samples == 16 ? 4 : (T.gp.samples == 4 ? 2 : 0));
+        if (shadow) { PA.slotOf1 = T.slotPrev; PA.nL1 = nL; }
+        else PA.pathOf1 = T.pathOfClosest;
+        if (I2) { PA.slotOf2 = T.slotPrev; PA.nL2 = nL; }
+    }
+    PA.queue = T.q + QW * k + 1 + PACKET_QUEUE_WORDS * word; PA.mode = s->sceneMode; PA.meshId = 0; PA.unmark = 0; PA.staticDiv = s->cfg.packetStaticDiv; PA.grabMax = s->cfg.packetGrabMax; PA.cullMin = s->cfg.packetCullMin;
+    if (s->cfg.packetSplit && s->sceneMode != MODE_SCENE) {
+        if ((rc = split_arena(s, W.splitItems, W.splitRecs, PA, st))) return rc;
+        if (P.fast && !P.adaptive && !P.heap && s->cfg.packetLongUs > 0) {   // plain frames: the packets of launch #k are the same from frame to frame while the camera stands still, and nearly so while it moves
+            const size_t stride = (P.rayCap + 63) / 64 + ((size_t)P.shadowCap * (size_t)(nL > 0 ? nL : 1) + 63) / 64 + 2;
+            if (W.splitCostStride != stride || !W.splitCost.p) {
+                if ((rc = W.splitCost.ensure(stride * 2 * (size_t)(R + 2)))) return rc;
+                HIPCHECK(hipMemsetAsync(W.splitCost.p, 0, stride * 2 * (size_t)(R + 2) * sizeof(unsigned), st));
+                W.splitCostStride = stride;
+            }
+            PA.splitCost = W.splitCost.p + stride * (size_t)(2 * k + word);
+            PA.splitLong = s->cfg.packetLongUs; PA.splitBudgetLong = std::max(1, s->cfg.packetBudgetLongUs);
+        }
+    }
+    int grid = s->numCUs * s->blocksPerCUPacket;
+    if (nHost >= 0) { const long long want = (nHost + 255) / 256; if (want < grid) grid = (int)(want < 1 ? 1 : want); }
+    hipEvent_t a0, a1;
+    if ((rc = pick_timing(grid, PA.stamps, a0, a1))) return rc;
+    launch_packet(S, PA, grid, st, a0, a1);
+    return XRT_OK;
+}
+
+// The segments that are traced ray by ray (C: closest-hit rays, B: shadow rays; either may be null), together in one launch of the per-lane kernel.
+int FrameJob::launch_lanes(const Step &T, const IntersectArgs *C, const IntersectArgs *B, int Pc) {
+    const int k = T.k;
+    IntersectArgs A = C ? *C : *B;
+    if (C && B) { A.rays2 = B->rays; A.hits2 = B->hits; A.flags2 = B->flags; A.nDev2 = B->nDev; A.nMul2 = B->nMul; A.nCap2 = B->nCap; A.scatter2 = B->scatter; }
+    const int grid = k == 0 ? persistent_grid(s, Pc) : persistent_grid(s, hint(s->genRays, k), 16);
+    hipEvent_t a0, a1;
+    if (int rc = pick_timing(grid, A.stamps, a0, a1)) return rc;
+    if (s->waveTimes.p && k < 16) A.debugTimes = s->waveTimes.p + (size_t)k * 3 * 8192;
+    launch_intersect(S, A, s->stackNeeded, grid, st, a0, a1);
+    return XRT_OK;
+}
+
+// Enqueue one chunk of `Pc` paths starting at `pathBase`: raygen, R+2 rounds of (intersect, shade), compose.
+// Intersect launch #k traces the closest-hit rays of generation k together with the shadow rays of generation k-1
+// (both exist once k_shade has looked at the hits of generation k-1); k_shade #k then shades generation k-1 with the
+// shadow answers and turns the hits of generation k into shadow rays and the rays of generation k+1.
+// (sampleOut: where the chunk's quantised colours go -- the context's sample buffer, or a quadrant level's colour array; epi: the
+// frame epilogue this chunk's compose kernel carries, if any)
+// (listCnt: the chunk ends generation-0 paths early, kernels.h EndArgs -- the count word of its compose list)
+int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int Pc, long long pathBase, uint32_t *sampleOut, const FrameEpilogue *epi, int *listCnt) {
+    const int R = P.R, nL = P.nL;
+    const bool heap = P.heap, ae = P.ae, fast = P.fast, feedback = P.wantFeedback;
+    const size_t rayCap = P.rayCap, shadowCap = P.shadowCap;
+    int rc;
+    int *scnt = cnt + (R + 2), *hcnt = cnt + 2 * (R + 2), *acnt = cnt + 3 * (R + 2);   // (acnt[k]: shadow rays of generation k that were really emitted, ShadeArgs::ae)
+    int *fcnt = cnt + 4 * (R + 2);                                                      // (fcnt[k]: hits of generation k finished in part A, ShadeArgs::finish)
+    const int chunkRow0 = F.stampRows;
+    if (P.capturePaths) {   // this attempt's records carry a number no earlier attempt had
+        if (++s->pathEpoch == 0) {
+            HIPCHECK(hipMemsetAsync(s->pathHit.p, 0, s->pathHit.cap * sizeof(f4), st));
+            if (s->pathDir.p) HIPCHECK(hipMemsetAsync(s->pathDir.p, 0, s->pathDir.cap * sizeof(f4), st));
+            s->pathEpoch = 1;
+        }
+        pathEpoch = s->pathEpoch;
+    }
+    xrt_ray *rays[2] = {W.rays0.p, W.rays1.p};
+    int *paths[2] = {W.path0.p, W.path1.p};
+    int *nodesOf[2] = {W.node0.p, W.node1.p};
+    float *refOf[2] = {W.ref0.p, W.ref1.p};
+    // cnt[0] counts the primary rays that reach the scene's root box; index0 lists them
+    RayGenParams gb = gp;
+    if (gp.batch && heap) gb.batchRef = refOf[0];
+    EndArgs endArgs;
+    if (listCnt) {
+        endArgs.on = 1; endArgs.sampleColor = sampleOut ? sampleOut : W.sampleColor.p;
+        endArgs.list = W.composeList.p + 16; endArgs.cnt = listCnt; endArgs.listCap = (int)rayCap;
+        endArgs.skipTiles = P.skipTiles ? 1 : 0;
+    }
+    { Range r("xrt raygen"); launch_raygen(gb, S, rays[0], W.lvlB.p, W.index0.p, cnt, Pc, pathBase, heavy_for(0, hcnt), st, startEvent ? e0 : nullptr, (int)rayCap, &endArgs); startEvent = false; }
+    // (one buffer serves every generation: the closest-hit answers of launch #k are read by part A of k_shade #k alone -- part B works from the
+    // slot records -- and launch #k+1 starts after it on the frame's stream)
+    xrt_hit *hitsOf[2] = {W.hits.p, W.hits.p};
+    int *flagsOf[2] = {W.hitFlags0.p, W.hitFlags0.p};
+    SlotRec *slotOf[2] = {W.slot0.p, W.slot1.p};
+    int *slotNodeOf[2] = {W.slotNode0.p, W.slotNode1.p};
+    int *const shadowFlagsOf[2] = {W.shadowFlags.p, ae ? W.shadowFlags1.p : W.shadowFlags.p};   // (the words of generation g: [g & 1])
+    for (int k = 0; k <= R + 1; k++) {
+        const int cur = k & 1, prv = cur ^ 1;
+        const bool hasClosest = k <= R, hasShadow = k >= 1 && nL > 0;
+        // a reflection chain keeps the ray of generation k at its parent's slot: their number is scnt[k-1]
+        const int *nClosest = (k == 0 || heap || ae) ? cnt + k : scnt + (k - 1);   // (ae: the reflections that were emitted are a compact list, counted by part A)
+        IntersectArgs C, B;   // closest-hit segment, shadow segment
+        C.rays = rays[cur]; C.hits = hitsOf[cur]; C.index = nullptr; C.nDev = nClosest; C.nMul = 1; C.n = Pc;   // (generation 0: cnt[0] live rays, compact)
+        C.nCap = (int)rayCap;
+        C.flags = flagsOf[cur]; B.flags = shadowFlagsOf[(k + 1) & 1];   // launch #k traces the shadow rays of generation k - 1
+        C.missRecords = (feedback && !packet_closest(k)) ? 1 : 0;   // k_shade #k reads the cost word of every ray of the generation
+        { const HeavyArgs H = heavy_for(k, hcnt); C.heavyIdx = H.list; C.nHeavy = H.count; }
+        B.rays = W.shadowRays.p; B.hits = W.shadowHits.p; B.index = nullptr; B.nDev = hasShadow ? scnt + (k - 1) : nullptr; B.nMul = nL; B.n = 0;
+        if (ae && hasShadow) { B.nDev = acnt + (k - 1); B.nMul = 1; B.scatter = W.shadowOut.p; }   // the emitted shadow rays, compact; answers go back to (slot, light)
+        B.nCap = (int)((long long)shadowCap * nL);
+        for (IntersectArgs *a : {&C, &B}) {
+            a->queue = q + QW * k; a->mode = s->sceneMode; a->meshId = 0;
+            set_knobs(*a, s);
+        }
+        // segments of coherent rays go to the wave-packet kernel, the others (together, one launch) to the per-lane kernel
+        const bool pkC = hasClosest && packet_closest(k), pkB = hasShadow && packet_shadow(k);
+        const Step T{gp, q, pathBase, k, k == 0 ? W.index0.p : paths[cur], slotOf[prv]};
+        Range ri("xrt intersect #%d", k);
+        // both populations of a step in ONE packet launch where both go to the packet kernel: one launch's tail instead of two
+        if (pkC && pkB && s->cfg.packetMerge) { if ((rc = launch_packets(T, C, false, hint(s->genRays, k), &B))) return rc; }
+        else {
+            if (pkC && (rc = launch_packets(T, C, false, k == 0 ? Pc : hint(s->genRays, k)))) return rc;
+            if (pkB && (rc = launch_packets(T, B, true, hint(s->genRays, k)))) return rc;
+        }
+        const bool laneC = hasClosest && !pkC, laneB = hasShadow && !pkB;
+        if ((laneC || laneB) && (rc = launch_lanes(T, laneC ? &C : nullptr, laneB ? &B : nullptr, Pc))) return rc;
+        if ((hasClosest || hasShadow) && P.collect) {   // generation 0: the live list; culled rays are added in frame_finish
+            if (hasClosest) launch_count(S, C, s->counters.p, st);
+            if (hasShadow) launch_count(S, B, s->counters.p + C_COUNT, st);
+        }
+        if (ri.on) { roctx().pop(); ri.on = false; }
+        Range rs("xrt shade #%d", k);
+        ShadeArgs X;
+        std::memset(&X, 0, sizeof(X));
+        X.level = k; X.doA = hasClosest ? 1 : 0; X.doB = k >= 1 ? 1 : 0;
+        X.maxReflections = R; X.P = (int)P.lvlStride; X.lvl = gp.lvl; X.heap = heap ? 1 : 0; X.overflow = overflowFlag;
+        X.rays = rays[cur]; X.hits = hitsOf[cur]; X.hitFlags = flagsOf[cur]; X.shadowFlags = shadowFlagsOf[(k + 1) & 1]; X.nDev = nClosest; X.nHost = Pc; X.cap = (int)rayCap;
+        X.index = nullptr; X.rayPath = k == 0 ? W.index0.p : paths[cur];   // (generation 0: the j-th live ray belongs to path index0[j])
+        X.rayNode = (heap && k > 0) ? nodesOf[cur] : nullptr;
+        X.rayRef = (heap && (k > 0 || gp.batch)) ? refOf[cur] : nullptr;   // (a batch's generation 0 carries the caller's currentRefIndex, k_ingest)
+        X.slotOut = slotOf[cur]; X.slotNodeOut = heap ? slotNodeOf[cur] : nullptr; X.scnt = scnt + k; X.shadowCap = (int)shadowCap; X.shadowRays = W.shadowRays.p;
+        X.nextRays = rays[prv]; X.nextPath = paths[prv]; X.nextNode = heap ? nodesOf[prv] : nullptr; X.nextRef = heap ? refOf[prv] : nullptr;
+        X.nextCnt = cnt + k + 1; X.nextCap = (int)rayCap;
+        if (ae) { X.ae = 1; X.shadowCnt = acnt + k; X.shadowOut = W.shadowOut.p; X.shadowFlagsOut = shadowFlagsOf[k & 1]; }
+        if (P.finishA) { X.finish = 1; X.finishCnt = fcnt + k; }
+        if (listCnt && k == 0) X.end = endArgs;
+        X.slotPrev = slotOf[prv]; X.slotNodePrev = heap ? slotNodeOf[prv] : nullptr; X.scntPrev = k >= 1 ? scnt + (k - 1) : nullptr; X.shadowHits = W.shadowHits.p;
+        X.lvlA = W.lvlA.p; X.lvlB = W.lvlB.p; X.lvlAlpha = heap ? W.lvlAlpha.p : nullptr;
+        if (k < R) X.heavy = heavy_for(k + 1, hcnt);
+        if (feedback && hasClosest && !packet_closest(k)) { X.costOut = s->costMap.p + (size_t)k * (size_t)P.framePaths + (size_t)P.partStart; X.epoch = s->epoch & 0xffffu; }
+        {   // (a small generation: 256-thread blocks, so that its work items land on many CUs instead of on the first few)
+            const long long h = hint(s->genShade, k);
+            if (h >= 0 && h < 4 * 131072 + 4096) launch_shade(S, V, X, st, (int)((h + 255) / 256), 256);
+            else launch_shade(S, V, X, st, h < 0 ? 1024 : (int)((h + 1023) / 1024 < 1024 ? (h + 1023) / 1024 : 1024));
+        }
+        if (P.capturePaths && hasClosest) {   // the generation's hits and the refraction rays it cast, before slots and ray buffers are reused
+            PathsCaptureArgs Cp;
+            Cp.slots = slotOf[cur]; Cp.slotNode = heap ? slotNodeOf[cur] : nullptr; Cp.scnt = scnt + k; Cp.slotCap = (int)shadowCap; Cp.level = k;
+            if (heap && k < R) { Cp.nextRays = rays[prv]; Cp.nextNode = nodesOf[prv]; Cp.nextPath = paths[prv]; Cp.nextCnt = cnt + k + 1; Cp.nextCap = (int)rayCap; }
+            Cp.hitRec = s->pathHit.p; Cp.dirRec = s->pathDir.p; Cp.P = (int)P.lvlStride; Cp.epoch = pathEpoch;
+            launch_paths_capture(Cp, (int)((rayCap + 255) / 256), st);
+        }
+    }
+    Range rc_("xrt compose");
+    // a batch: path p of the chunk is ray pathBase + p, and the compose kernel writes its colour straight into the caller's arrays (a ray-tree chunk
+    // that overflowed is retried over the same range: the retry overwrites what the discarded attempt wrote)
+    uint32_t *const colorOut = gp.batch ? d_out + pathBase : (sampleOut ? sampleOut : W.sampleColor.p);
+    float *const f32Out = gp.batch ? (d_outF32 ? d_outF32 + 3 * (size_t)pathBase : nullptr) : (P.wantF32 ? W.sampleF32.p : nullptr);
+    StampFold fold;
+    fold.src = W.stamps.p; fold.host = F.stampHost.dev; fold.row0 = chunkRow0; fold.row1 = F.stampRows;
+    if (heap) {
+        FrameEpilogue E;
+        if (fast) { E.cntSrc = cnt; E.hostCnt = F.pinned.dev; E.cntWords = P.cntStride; E.zeroWords = P.cntStride + P.qStride; E.flagSrc = overflowFlag; }
+        launch_compose_tree(W.lvlA.p, W.lvlB.p, W.lvlAlpha.p, Pc, P.P, R, colorOut, f32Out, fold, E, st);
+    }
+    else {
+        ResolveArgs RA;
+        RA.fused = P.fuseResolve ? 1 : 0; RA.g = gp; RA.pixelBase = pathBase; RA.out = d_out; RA.outF32 = d_outF32;
+        RA.stamps = fold;
+        if (epi) { RA.cntSrc = epi->cntSrc; RA.hostCnt = epi->hostCnt; RA.cntWords = epi->cntWords; RA.zeroWords = epi->zeroWords; RA.zeroFrom = epi->zeroFrom; }
+        else if (fast && !P.adaptive) { RA.cntSrc = cnt; RA.hostCnt = F.pinned.dev; RA.cntWords = P.cntStride; RA.zeroWords = P.cntStride + P.qStride; }
+        int blocks = 0;
+        if (listCnt) {
+            RA.list = W.composeList.p + 16; RA.endCnt = listCnt; RA.listCap = (int)rayCap;
+            if (P.hinted && s->genCompose >= 0) blocks = (int)((4 * s->genCompose + 4096 + 255) / 256);
+        }
+        launch_compose(W.lvlA.p, W.lvlB.p, Pc, (int)P.lvlStride, R, colorOut, P.fuseResolve ? nullptr : f32Out, RA, st,
+                       (fast && P.fuseResolve) ? e1 : nullptr, blocks);
+    }
+    return XRT_OK;
+}
+
+int FrameJob::post_chunk(const ChunkPost &post, int Pc, long long pathBase) {
+    switch (post.kind) {
+    case ChunkPost::NOTHING: break;
+    case ChunkPost::EMIT_PATHS: {   // the chunk's segments in the recursion's order, behind those of the rays before it
+        const BatchSrc::Paths *pout = batch->paths;
+        PathsEmitArgs E;
+        E.batch = batch->rays; E.pathBase = pathBase; E.Pc = Pc; E.P = (int)P.lvlStride; E.depth = P.R; E.tree = P.heap ? 1 : 0; E.epoch = pathEpoch;
+        E.hitRec = s->pathHit.p; E.dirRec = s->pathDir.p; E.local = s->pathLocal.p; E.blockSum = s->pathBlockSum.p; E.blockBase = s->pathBlockBase.p;
+        E.vertexStart = pout->vertexStart; E.vertices = pout->vertices; E.capacity = pout->capacity; E.raysBack = pout->raysBack;
+        launch_paths_emit(E, st);
+        break;
+    }
+    case ChunkPost::RESOLVE:
+        launch_resolve(P.g, W.sampleColor.p, P.wantF32 ? W.sampleF32.p : nullptr, Pc / P.g.samples, pathBase / P.g.samples, d_out, d_outF32, st, nullptr, 0, P.skipTiles ? 1 : 0);
+        break;
+    case ChunkPost::COPY_LEVEL:
+        HIPCHECK(hipMemcpyAsync(post.levelColor + pathBase, W.sampleColor.p, (size_t)Pc * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        break;
+    }
+    return XRT_OK;
+}
+
+// A pass of a ray-tree frame the careful way: one chunk at a time, checked for overflow, retried with fewer paths when a generation did not fit.
+int FrameJob::run_pass_tree(const RayGenParams &gp, long long total, const ChunkPost &post, float progress0, float progress1, bool finalPass) {
+    int rc;
+    const int cntStride = P.cntStride;
+    const size_t nb2 = 2 * C_COUNT * sizeof(unsigned long long);
+    const size_t words = (size_t)cntStride + (size_t)P.qStride;
+    if ((rc = W.cnts.ensure(words)) || (rc = ensure_pinned(words * sizeof(int) + nb2 + 64 + 8 + 64))) return rc;
+    W.cntsClean = false;
+    unsigned *q = reinterpret_cast<unsigned *>(W.cnts.p + cntStride);
+    long long pathBase = 0, curChunk = P.chunkPaths;   // (ray-tree frames are never split: partStart == 0)
+    while (pathBase < total) {
+        const int Pc = (int)((total - pathBase) < curChunk ? (total - pathBase) : curChunk);
+        HIPCHECK(hipMemsetAsync(W.cnts.p, 0, words * sizeof(int), st));
+        const size_t pairsMark = F.pairs.size(), evMark = F.ev;
+        const int rowsMark = F.stampRows;
+        if ((rc = enqueue_chunk(gp, W.cnts.p, q, Pc, pathBase))) return rc;
+        // the chunk's samples are consumed before the host has looked at the overflow flag: a retry overwrites them
+        if ((rc = post_chunk(post, Pc, pathBase))) return rc;
+        char *pin = (char *)F.pinned.p;
+        const size_t cAt = ((size_t)cntStride * sizeof(int) + 7) & ~(size_t)7;   // counters + spare words (overflow flag) in one copy
+        HIPCHECK(hipMemcpyAsync(pin, W.cnts.p, (size_t)cntStride * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(pin + cAt, s->counters.p, nb2, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(pin + cAt + nb2 + 64, overflowFlag, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        const int over = *(const int *)(pin + cAt + nb2 + 64);
+        if (over) {
+            if (curChunk <= 64) return fail(XRT_E_UNSUPPORTED, "the ray tree of 64 paths does not fit the ray buffers (MaxReflections too high for this scene)");
+            curChunk = (curChunk / 4) & ~63LL;
+            if (curChunk < 64) curChunk = 64;
+            HIPCHECK(hipMemsetAsync(overflowFlag, 0, sizeof(int), st));
+            HIPCHECK(hipMemcpyAsync(s->counters.p, F.hcnt, nb2, hipMemcpyHostToDevice, st));   // undo this attempt's counting
+            HIPCHECK(hipStreamSynchronize(st));
+            F.pairs.resize(pairsMark); F.ev = evMark; F.stampRows = rowsMark;   // its launches are not part of the frame's timing
+            continue;
+        }
+        tally_chunk(F, (const int *)pin);
+        std::memcpy(F.hcnt, pin + cAt, nb2);
+        pathBase += Pc;
+        s->progress.store(progress0 + (progress1 - progress0) * (float)pathBase / (float)total);
+    }
+    if (finalPass) HIPCHECK(hipEventRecord(e1, st));
+    return XRT_OK;
+}
+
+// One pass = trace `total` paths produced by generator `gp`; after every chunk `post` consumes sampleColor.
+int FrameJob::run_pass(const RayGenParams &gp, long long total, const ChunkPost &post, float progress0, float progress1, bool finalPass) {
+    if (P.heap && !P.fast) return run_pass_tree(gp, total, post, progress0, progress1, finalPass);
+    int rc;
+    const int cntStride = P.cntStride, qStride = P.qStride;
+    const long long chunkPaths = P.chunkPaths;
+    const bool fast = P.fast;
+    const size_t nb2 = 2 * C_COUNT * sizeof(unsigned long long);
+    const int nChunks = (int)((total + chunkPaths - 1) / chunkPaths);
+    // ray counts and queue heads of all chunks live in one allocation: one memset per pass
+    const size_t cntWords = (size_t)nChunks * cntStride, qWords = (size_t)nChunks * qStride;
+    const int *cntsBefore = W.cnts.p;
+    if ((rc = W.cnts.ensure(cntWords + qWords))) return rc;
+    unsigned *queuesBase = reinterpret_cast<unsigned *>(W.cnts.p + cntWords);
+    if (fast && (rc = ensure_pinned(cntWords * sizeof(int) + 64))) return rc;   // (+ the overflow word of a ray-tree frame)
+    if (!fast || !W.cntsClean || W.cnts.p != cntsBefore) HIPCHECK(hipMemsetAsync(W.cnts.p, 0, W.cnts.cap * sizeof(int), st));
+    W.cntsClean = false;
+    for (int c = 0; c < nChunks; c++) {
+        const long long localBase = (long long)c * chunkPaths, pathBase = P.partStart + localBase;
+        const int Pc = (int)((total - localBase) < chunkPaths ? (total - localBase) : chunkPaths);
+        if ((rc = enqueue_chunk(gp, W.cnts.p + (size_t)c * cntStride, queuesBase + (size_t)c * qStride, Pc, pathBase, nullptr, nullptr,
+                                P.endEarly ? W.composeList.p : nullptr))) return rc;
+        if (!P.fuseResolve && (rc = post_chunk(post, Pc, pathBase))) return rc;
+        if (nChunks > 1) {   // frames of more than MAX_CHUNK_PATHS rays: xrt_progress follows the chunks
+            HIPCHECK(hipStreamSynchronize(st));
+            s->progress.store(progress0 + (progress1 - progress0) * (float)(c + 1) / (float)nChunks);
+        }
+    }
+    if (fast) {   // counters arrive with k_compose; frame_finish tallies them
+        if (!P.fuseResolve) HIPCHECK(hipEventRecord(e1, st));   // fixed 16 sub-rays: k_resolve is the last kernel
+        W.cntsClean = true;
+        F.tallyChunks = 1;
+        return XRT_OK;
+    }
+    if (finalPass) HIPCHECK(hipEventRecord(e1, st));
+    // per-pass ray accounting (the counter block is reused by the next pass): one pinned read-back -- two small copies, always taken
+    const size_t nb = (size_t)nChunks * cntStride * sizeof(int);
+    if ((rc = ensure_pinned(nb + nb2))) return rc;
+    HIPCHECK(hipMemcpyAsync(F.pinned.p, W.cnts.p, nb, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync((char *)F.pinned.p + nb, s->counters.p, nb2, hipMemcpyDeviceToHost, st));
+    if (finalPass) { F.tallyChunks = nChunks; return XRT_OK; }   // frame_finish tallies after the frame's done event
+    HIPCHECK(hipStreamSynchronize(st));
+    for (int c = 0; c < nChunks; c++) tally_chunk(F, F.pinned.p + (size_t)c * cntStride);
+    std::memcpy(F.hcnt, (char *)F.pinned.p + nb, nb2);
+    return XRT_OK;
+}
+
+// A pass over a caller's rays: path p is ray p, the compose kernels write the caller's arrays themselves (enqueue_chunk).
+int FrameJob::batch_frame() {
+    F.livePaths = F.validPixels;
+    ChunkPost post;
+    if (P.capturePaths) post.kind = ChunkPost::EMIT_PATHS;
+    if (int rc = run_pass(P.g, P.firstPaths, post, 0.0f, 1.0f, true)) return rc;
+    if (P.capturePaths) HIPCHECK(hipMemcpyAsync(s->pathPinned.p, batch->paths->vertexStart + batch->n, sizeof(long long), hipMemcpyDeviceToHost, st));
+    return XRT_OK;
+}
+
+// One sample or sixteen per pixel: one pass, resolved chunk by chunk (or by k_compose itself, FramePlan::fuseResolve).
+int FrameJob::plain_frame() {
+    F.livePaths = F.validPixels * (unsigned long long)P.g.samples;
+    ChunkPost post;
+    post.kind = ChunkPost::RESOLVE;
+    return run_pass(P.g, P.firstPaths, post, 0.0f, 1.0f, true);
+}
+
+// RenderFirstPass / GetColorForQuadrant (RT:170-311) without a host round trip: every level's pass is enqueued now.  Level 0 has
+// one quadrant per pixel; how many quadrants a deeper level has only the device knows (k_ms_decide counts them into lvlCnt[l],
+// the level's ray generation, compose and fold kernels read that word; the traversal and shading kernels follow the ray
+// counts as always).  Deeper levels get room for one quadrant per pixel (XRT_ADAPTIVE_CAP); a level that needs more sets the
+// overflow word and frame_finish renders the frame again the careful way.
+int FrameJob::adaptive_in_flight() {
+    const RayGenParams &g = P.g;
+    const int quality = P.quality, cntStride = P.cntStride, qStride = P.qStride;
+    const long long totalPixels = P.totalPixels;
+    const int nPass = quality + 1;
+    constexpr int LW = ADAPTIVE_LEVEL_WORDS;
+    int rc;
+    auto cap_of = [&](int l) { return l == 0 ? totalPixels : (long long)P.levelCap; };
+    const size_t words = (size_t)LW + (size_t)nPass * cntStride + (size_t)nPass * qStride;
+    const int *cntsBefore = W.cnts.p;
+    if ((rc = W.cnts.ensure(words)) || (rc = ensure_pinned(((size_t)LW + (size_t)nPass * cntStride) * sizeof(int) + 64))) return rc;
+    if (!W.cntsClean || W.cnts.p != cntsBefore) HIPCHECK(hipMemsetAsync(W.cnts.p, 0, W.cnts.cap * sizeof(int), st));
+    W.cntsClean = false;
+    for (int l = 0; l <= quality; l++) {
+        auto &Lv = W.levels[l];
+        const size_t c = (size_t)cap_of(l);
+        if ((rc = Lv.color.ensure(c * 4))) return rc;
+        if (l < quality && ((rc = Lv.childBase.ensure(c)) || (rc = Lv.childMask.ensure(c)))) return rc;
+        if (l > 0 && ((rc = Lv.cx.ensure(c)) || (rc = Lv.cy.ensure(c)))) return rc;
+    }
+    int *const lvlCnt = W.cnts.p, *const ovf = W.cnts.p + LW - 1;
+    int *const cnt0 = W.cnts.p + LW;
+    unsigned *const q0 = reinterpret_cast<unsigned *>(cnt0 + (size_t)nPass * cntStride);
+    float size = 1.0f;
+    for (int l = 0; l <= quality; l++) {
+        auto &Lv = W.levels[l];
+        RayGenParams gl = g;
+        gl.quadLevel = l; gl.quadSize = size; gl.quadCx = Lv.cx.p; gl.quadCy = Lv.cy.p;
+        if (l > 0) { gl.pathsDev = lvlCnt + l; gl.pathsMul = 4; gl.pathsCap = (int)cap_of(l); }
+        FrameEpilogue E;
+        const bool last = l == quality;
+        if (last) { E.cntSrc = W.cnts.p; E.hostCnt = F.pinned.dev; E.cntWords = LW + nPass * cntStride; E.zeroWords = (int)words; E.zeroFrom = LW; }
+        if ((rc = enqueue_chunk(gl, cnt0 + (size_t)l * cntStride, q0 + (size_t)l * qStride, (int)(cap_of(l) * 4), 0, Lv.color.p, last ? &E : nullptr))) return rc;
+        if (l < quality) {   // RT:279-306
+            auto &Nx = W.levels[l + 1];
+            launch_ms_decide(gl, Lv.color.p, l > 0 ? lvlCnt + l : nullptr, (int)cap_of(l), 0, Lv.childBase.p, Lv.childMask.p, Nx.cx.p, Nx.cy.p, lvlCnt + l + 1, st,
+                             (int)cap_of(l + 1), ovf);
+            size = size / 2.0f;   // RT:290
+        }
+    }
+    for (int l = quality - 1; l >= 0; l--)
+        launch_ms_fold(W.levels[l].color.p, W.levels[l + 1].color.p, W.levels[l].childBase.p, W.levels[l].childMask.p, (int)cap_of(l), st, l > 0 ? lvlCnt + l : nullptr);
+    RayGenParams g0 = g;
+    g0.quadLevel = 0; g0.quadSize = 1.0f;
+    launch_resolve(g0, W.levels[0].color.p, nullptr, (int)totalPixels, 0, d_out, d_outF32, st, lvlCnt, LW);   // ... and clears the level words for the next frame
+    HIPCHECK(hipEventRecord(e1, st));
+    W.cntsClean = true;
+    F.tallyChunks = nPass;
+    return XRT_OK;
+}
+
+// RenderFirstPass / GetColorForQuadrant (RT:170-311), the careful way (a host read-back of every level's size): level 0
+// quadrants are the pixels (size 1); a level's quadrants each cast four rays; corners that deviate are subdivided into the next
+// level, down to MultisampleQuality; results fold back up.  The frame is complete when this returns.
+int FrameJob::adaptive_careful() {
+    const RayGenParams &g = P.g;
+    const int quality = P.quality;
+    int rc = XRT_OK;
+    struct Level : xrt_scene::WorkBufs::Level { long long n = 0; };   // (the frame's own: freed when it is done, however it ends)
+    std::vector<Level> lv((size_t)quality + 1);
+    int *levelCount = reinterpret_cast<int *>(s->counters.p + 2 * C_COUNT);   // [quality+1] ints in the spare counter words
+    lv[0].n = P.totalPixels;
+    float size = 1.0f;
+    for (int l = 0; l <= quality && rc == XRT_OK; l++) {
+        Level &L = lv[l];
+        if (L.n == 0) break;
+        if ((rc = L.color.ensure((size_t)L.n * 4))) break;
+        RayGenParams gl = g;
+        gl.quadLevel = l; gl.quadSize = size; gl.quadCx = L.cx.p; gl.quadCy = L.cy.p;
+        F.livePaths += (l == 0 ? F.validPixels : (unsigned long long)L.n) * 4ull;
+        ChunkPost post;
+        post.kind = ChunkPost::COPY_LEVEL; post.levelColor = L.color.p;
+        rc = run_pass(gl, L.n * 4, post, (float)l / (float)(quality + 1), (float)(l + 1) / (float)(quality + 1), false);
+        if (rc != XRT_OK) break;
+        if (l < quality) {   // RT:279-306
+            Level &N = lv[l + 1];
+            if ((rc = L.childBase.ensure((size_t)L.n)) || (rc = L.childMask.ensure((size_t)L.n)) || (rc = N.cx.ensure((size_t)L.n * 4)) ||
+                (rc = N.cy.ensure((size_t)L.n * 4)))
+                break;
+            launch_ms_decide(gl, L.color.p, nullptr, (int)L.n, 0, L.childBase.p, L.childMask.p, N.cx.p, N.cy.p, levelCount + l + 1, st);
+            int hn = 0;
+            hipError_t e = hipMemcpyAsync(&hn, levelCount + l + 1, sizeof(int), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) { rc = fail(XRT_E_HIP, "adaptive level readback: %s", hipGetErrorString(e)); break; }
+            N.n = hn;
+            size = size / 2.0f;   // RT:290
+        }
+    }
+    if (rc != XRT_OK) return rc;
+    for (int l = quality - 1; l >= 0; l--)
+        if (lv[l + 1].n > 0) launch_ms_fold(lv[l].color.p, lv[l + 1].color.p, lv[l].childBase.p, lv[l].childMask.p, (int)lv[l].n, st);
+    RayGenParams g0 = g;
+    g0.quadLevel = 0; g0.quadSize = 1.0f;
+    launch_resolve(g0, lv[0].color.p, nullptr, (int)P.totalPixels, 0, d_out, d_outF32, st);
+    hipError_t e = hipEventRecord(e1, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(F.hcnt, s->counters.p, sizeof(F.hcnt), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(XRT_E_HIP, "adaptive resolve: %s", hipGetErrorString(e));
+    return XRT_OK;
+}
+
+// The scene's tile cost words for this frame (xrt.h xrt_scene_tile_costs).  They belong to the scene (both frame contexts add to them); a frame of
+// another geometry or tile table starts them afresh.
+int tile_cost_words(xrt_scene *s, const FramePlan &P, hipStream_t st, unsigned *&words) {
+    const RayGenParams &g = P.g;
+    const long long myTiles = P.myTiles;
+    if (int rc = s->tileCost.ensure((size_t)myTiles)) return rc;
+    auto slot_tile = [&](long long sl) { const long long t = tile_of_slot(*s, P, sl); return t < P.totalTiles ? (int)t : -1; };
+    bool same = s->costW == g.width && s->costH == g.height && (long long)s->costTiles.size() == myTiles;
+    for (long long sl = 0; same && sl < myTiles; sl++) same = s->costTiles[(size_t)sl] == slot_tile(sl);
+    if (!same) {
+        s->costTiles.resize((size_t)myTiles);
+        for (long long sl = 0; sl < myTiles; sl++) s->costTiles[(size_t)sl] = slot_tile(sl);
+        s->costW = g.width; s->costH = g.height;
+        HIPCHECK(hipMemsetAsync(s->tileCost.p, 0, (size_t)myTiles * sizeof(unsigned), st));
+        if (s->frames[0].pending || s->frames[1].pending) HIPCHECK(hipStreamSynchronize(st));   // (the other context's frame may be adding to them: start clean)
+    }
+    words = s->tileCost.p;
+    return XRT_OK;
+}
+
+// Enqueues one frame on `st`.  On return the frame's kernels and its counter read-back are in flight (F.pending);
+// frame_finish waits for them.  Adaptive supersampling and ray-tree frames the careful way need host decisions between their passes and
+// are complete when this returns.  d_out[p] / d_outF32[3p..] receive pixel p's colour (a batch: ray p's).
+int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, const xrt_light *lights, int nLights, const xrt_render_opts *opts,
+                uint32_t *d_out, float *d_outF32, hipStream_t st, int part = 0, int nParts = 1, bool heapFastAllowed = true, const BatchSrc *batch = nullptr) {
+    xrt_scene::WorkBufs &W = F.w;
+    int rc;
+    // the plan
+    if ((rc = plan_frame(*s, F.mat, cam, lights, nLights, opts, d_outF32 != nullptr, st != nullptr, part, nParts, heapFastAllowed, batch, F.plan))) return rc;
+    const FramePlan &P = F.plan;
+    const int R = P.R, nL = P.nL;
+    if (P.lvlVerified) { s->lvlCheckedTilesX = P.g.tilesX; s->lvlCheckedTiles = P.totalTiles; }
+    // the buffers
+    unsigned freshPathRecs = 0;
+    if ((rc = ensure_frame_buffers(s, F, P, freshPathRecs))) return rc;
+    F.redone = false;
+    if (P.heapFast || P.adaptiveFast) {   // what a redo needs
+        F.redoCam = *cam; F.redoOpts = *opts; F.redoLights.assign(lights, lights + nLights);
+        F.redoOut = d_out; F.redoOutF32 = d_outF32; F.redoSt = st;
+    }
+    F.stampRows = 0;
+    // the stream, and what the frame waits for
+    if (!st) {
+        if (P.ownStream) {
+            if ((rc = W.stream.create())) return rc;
+            st = W.stream;
+        } else st = s->stream;
+    }
+    if ((rc = pose_wait(s, F.pose, st)) || (rc = mat_acquire(s, F.mat, st))) return rc;   // (the poses and materials set before the frame's begin)
+    if (freshPathRecs & 1u) HIPCHECK(hipMemsetAsync(s->pathHit.p, 0, s->pathHit.cap * sizeof(f4), st));
+    if (freshPathRecs & 2u) HIPCHECK(hipMemsetAsync(s->pathDir.p, 0, s->pathDir.cap * sizeof(f4), st));
+    unsigned *tileCostDev = nullptr;
+    if (P.tileCosts && (rc = tile_cost_words(s, P, st, tileCostDev))) return rc;
     {   // The other context's frame may still be running on another stream.  Two single-chunk frames share nothing they
         // write except scheduling hints; anything else (counting pass, supersampling levels, ray tree, a cost map
         // about to be reallocated or released) runs alone.
-        const bool remap = wantFeedback ? (s->costMapPaths != (size_t)framePaths || s->costMap.cap < (size_t)(R + 1) * (size_t)framePaths) : (s->costMap.p != nullptr);
+        const bool remap = P.wantFeedback ? (s->costMapPaths != (size_t)P.framePaths || s->costMap.cap < (size_t)(R + 1) * (size_t)P.framePaths) : (s->costMap.p != nullptr);
         for (xrt_scene::FrameCtx &O : s->frames)
-            if (&O != &F && O.pending && O.w.lastStream != st && (!fast || !O.fast || remap)) HIPCHECK(hipEventSynchronize(O.fast ? O.events[1] : O.done));
+            if (&O != &F && O.pending && O.w.lastStream != st && (!P.fast || !O.plan.fast || remap)) HIPCHECK(hipEventSynchronize(O.plan.fast ? O.events[1] : O.done));
         W.lastStream = st;
     }
-    if (wantFeedback) {
-        const size_t need = (size_t)(R + 1) * (size_t)framePaths;
-        if (s->costMapPaths != (size_t)framePaths || s->costMap.cap < need) {   // new frame geometry: forget
+    if (P.wantFeedback) {
+        const size_t need = (size_t)(R + 1) * (size_t)P.framePaths;
+        if (s->costMapPaths != (size_t)P.framePaths || s->costMap.cap < need) {   // new frame geometry: forget
             if ((rc = s->costMap.ensure(need))) return rc;
             HIPCHECK(hipMemsetAsync(s->costMap.p, 0, s->costMap.cap * sizeof(unsigned), st));
-            s->costMapPaths = (size_t)framePaths;
+            s->costMapPaths = (size_t)P.framePaths;
         }
         if (part == 0) s->epoch++;
     } else if (s->costMap.p) {
         s->costMap.release(); s->costMapPaths = 0;   // (freed early on purpose: a map of (R + 1) words per path that no frame of this kind reads)
     }
-    if (!fast) {
+    // the uploads and clears
+    if (!P.fast) {
         W.cntsClean = false;
         HIPCHECK(hipMemsetAsync(s->counters.p, 0, (2 * C_COUNT + 8) * sizeof(unsigned long long), st));
     }
     std::vector<LightRec> &hl = F.hostLights;   // must outlive the asynchronous upload
     hl.assign(nL > 0 ? nL : 1, LightRec());
-    for (int i = 0; i < nL; i++) {
-        if (lights[i].kind != XRT_LIGHT_SPOT && lights[i].kind != XRT_LIGHT_DIRECTIONAL) return fail(XRT_E_INVALID_ARG, "unknown light kind");
-        hl[i] = make_light(lights[i]);
-    }
+    for (int i = 0; i < nL; i++) hl[i] = make_light(lights[i]);
     const bool sameLights = W.lightsOnDevice.size() == (size_t)nL && W.lightsDevPtr == W.lights.p &&
                             (nL == 0 || std::memcmp(W.lightsOnDevice.data(), hl.data(), nL * sizeof(LightRec)) == 0);
     if (nL > 0 && !sameLights) {
@@ -606,476 +1170,89 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
     }
     ShadeView V;
     V.shade = s->shade.p; V.materials = mat_records(s, F.mat).p; V.texels = mat_texels(s, F.mat).p; V.meshes = s->meshes.p;
-    V.lights = W.lights.p; V.nLights = nL; V.addressMode = opts->address_mode; V.filtering = opts->filtering;
-    const SceneView S = pose_view(s, F.pose);   // every kernel of the frame reads one pose version (and, above, one material version)
-    xrt_ray *rays[2] = {W.rays0.p, W.rays1.p};
-    int *paths[2] = {W.path0.p, W.path1.p};
-    int *nodesOf[2] = {W.node0.p, W.node1.p};
-    float *refOf[2] = {W.ref0.p, W.ref1.p};
-    size_t &ev = F.ev;
-    ev = 0;
-    std::vector<std::pair<size_t, size_t>> &pairs = F.pairs;
-    pairs.clear();
-    hipEvent_t e0 = get_event(F.events, ev++), e1 = get_event(F.events, ev++);
+    V.lights = W.lights.p; V.nLights = nL; V.addressMode = P.addressMode; V.filtering = P.filtering;
+    F.ev = 0;
+    F.pairs.clear();
+    hipEvent_t e0 = get_event(F.events, F.ev++), e1 = get_event(F.events, F.ev++);
     if (!e0 || !e1 || F.done.create() != XRT_OK) return fail(XRT_E_HIP, "hipEventCreate failed");
-    if (!fast) HIPCHECK(hipEventRecord(e0, st));
+    if (!P.fast) HIPCHECK(hipEventRecord(e0, st));
     s->progress.store(0.0f);
-    unsigned long long &shaded = F.shaded, &closestDeep = F.closestDeep, &livePaths = F.livePaths, &live0 = F.live0;
-    shaded = closestDeep = livePaths = live0 = 0;
+    F.shaded = F.closestDeep = F.livePaths = F.live0 = 0;
     F.answered = 0;
-    unsigned long long *hcntHost = F.hcnt;
-    std::memset(hcntHost, 0, sizeof(F.hcnt));
-    F.tallyChunks = 0; F.cntStride = cntStride; F.R = R; F.nL = nL; F.collect = opts->collect_stats != 0;
-
-    // One pass = trace `total` paths produced by generator `gp`; after every chunk `post(Pc, pathBase)` consumes sampleColor.
+    F.validPixels = P.validPixels;
+    std::memset(F.hcnt, 0, sizeof(F.hcnt));
+    F.tallyChunks = 0;
     // "a generation did not fit its buffers": ray-tree frames have the word to themselves (two of them may be in flight)
-    if (heap) {
+    if (P.heap) {
         const bool fresh = W.heapFlag.p == nullptr;
         if ((rc = W.heapFlag.ensure(16))) return rc;
-        if (fresh || !fast || !W.heapFlagClean) HIPCHECK(hipMemsetAsync(W.heapFlag.p, 0, 16 * sizeof(int), st));
-        W.heapFlagClean = fast;   // (the frame epilogue clears it again)
+        if (fresh || !P.fast || !W.heapFlagClean) HIPCHECK(hipMemsetAsync(W.heapFlag.p, 0, 16 * sizeof(int), st));
+        W.heapFlagClean = P.fast;   // (the frame epilogue clears it again)
     }
-    int *overflowFlag = heap ? W.heapFlag.p : reinterpret_cast<int *>(s->counters.p + 2 * C_COUNT) + 12;   // (else: a spare counter word, never set)
-
-    // Enqueue one chunk of `Pc` paths starting at `pathBase`: raygen, R+2 rounds of (intersect, shade), compose.
-    // Intersect launch #k traces the closest-hit rays of generation k together with the shadow rays of generation k-1
-    // (both exist once k_shade has looked at the hits of generation k-1); k_shade #k then shades generation k-1 with the
-    // shadow answers and turns the hits of generation k into shadow rays and the rays of generation k+1.
-    bool startEvent = fast;   // the frame's first raygen launch carries its start event (fast frames put nothing but kernels on the stream)
-    // (sampleOut: where the chunk's quantised colours go -- the context's sample buffer, or a quadrant level's colour array; epi: the
-    // frame epilogue this chunk's compose kernel carries, if any)
-    // (listCnt: the chunk ends generation-0 paths early, kernels.h EndArgs -- the count word of its compose list)
-    auto enqueue_chunk = [&](const RayGenParams &gp, int *cnt, unsigned *q, int Pc, long long pathBase, uint32_t *sampleOut = nullptr,
-                             const FrameEpilogue *epi = nullptr, int *listCnt = nullptr) -> int {
-        int *scnt = cnt + (R + 2), *hcnt = cnt + 2 * (R + 2), *acnt = cnt + 3 * (R + 2);   // (acnt[k]: shadow rays of generation k that were really emitted, ShadeArgs::ae)
-        int *fcnt = cnt + 4 * (R + 2);                                                      // (fcnt[k]: hits of generation k finished in part A, ShadeArgs::finish)
-        const int chunkRow0 = F.stampRows;
-        if (pout) {   // this attempt's records carry a number no earlier attempt had
-            if (++s->pathEpoch == 0) {
-                HIPCHECK(hipMemsetAsync(s->pathHit.p, 0, s->pathHit.cap * sizeof(f4), st));
-                if (s->pathDir.p) HIPCHECK(hipMemsetAsync(s->pathDir.p, 0, s->pathDir.cap * sizeof(f4), st));
-                s->pathEpoch = 1;
-            }
-            pathEpoch = s->pathEpoch;
-        }
-        // "long ray first" (kernels.hip): the producer of generation k lists its long rays, launch #k takes them first
-        const bool feedback = fast && s->deepMeshes && s->costMap.p != nullptr;
-        const bool listLong = s->heavyPath > 0.0f || feedback;
-        // (generation 0 and 1 and the shadow rays of generation 0 are the big coherent populations; after two bounces the 64 rays
-        // of a packet have little in common and a few packets take three times as long as the rest of their launch: bit 4)
-        auto packet_closest = [&](int k) { return (k == 0 ? (pkMask & 1) : (k == 1 ? (pkMask & 4) : ((pkMask & 4) && (pkMask & 16)))) != 0; };
-        const bool hinted = fast && nParts == 1 && s->genKey == firstPaths * 64 + nL && s->genHeap == heap && s->cfg.gridHints;
-        auto hint = [&](const long long *v, int k) -> long long { return (hinted && k < 68 && v[k] >= 0) ? 4 * v[k] + 4096 : -1; };
-        auto packet_shadow = [&](int k) { return (pkMask & 2) != 0 && (k <= 1 || (pkMask & 16) != 0); };   // shadow rays of generation k-1
-        auto heavy_for = [&](int k) {
-            HeavyArgs H;
-            if (listLong && (k == 0 || !heap) && !packet_closest(k)) {   // (packets are not scheduled ray by ray)
-                H.list = W.heavyList.p; H.count = hcnt + k; H.path = s->heavyPath;
-                if (feedback) { H.costMap = s->costMap.p + (size_t)k * (size_t)framePaths + (size_t)partStart; H.epoch = s->epoch & 0xffffu; H.costThreshold = s->costT[k]; }
-            }
-            return H;
-        };
-        // cnt[0] counts the primary rays that reach the scene's root box; index0 lists them
-        RayGenParams gb = gp;
-        if (gp.batch && heap) gb.batchRef = refOf[0];
-        EndArgs endArgs;
-        if (listCnt) {
-            endArgs.on = 1; endArgs.sampleColor = sampleOut ? sampleOut : W.sampleColor.p;
-            endArgs.list = W.composeList.p + 16; endArgs.cnt = listCnt; endArgs.listCap = (int)rayCap;
-            endArgs.skipTiles = skipTiles ? 1 : 0;
-        }
-        { Range r("xrt raygen"); launch_raygen(gb, S, rays[0], W.lvlB.p, W.index0.p, cnt, Pc, pathBase, heavy_for(0), st, startEvent ? e0 : nullptr, (int)rayCap, &endArgs); startEvent = false; }
-        // (one buffer serves every generation: the closest-hit answers of launch #k are read by part A of k_shade #k alone -- part B works from the
-        // slot records -- and launch #k+1 starts after it on the frame's stream)
-        xrt_hit *hitsOf[2] = {W.hits.p, W.hits.p};
-        int *flagsOf[2] = {W.hitFlags0.p, W.hitFlags0.p};
-        SlotRec *slotOf[2] = {W.slot0.p, W.slot1.p};
-        int *slotNodeOf[2] = {W.slotNode0.p, W.slotNode1.p};
-        for (int k = 0; k <= R + 1; k++) {
-            const int cur = k & 1, prv = cur ^ 1;
-            const bool hasClosest = k <= R, hasShadow = k >= 1 && nL > 0;
-            // a reflection chain keeps the ray of generation k at its parent's slot: their number is scnt[k-1]
-            const int *nClosest = (k == 0 || heap || ae) ? cnt + k : scnt + (k - 1);   // (ae: the reflections that were emitted are a compact list, counted by part A)
-            IntersectArgs C, B;   // closest-hit segment, shadow segment
-            C.rays = rays[cur]; C.hits = hitsOf[cur]; C.index = nullptr; C.nDev = nClosest; C.nMul = 1; C.n = Pc;   // (generation 0: cnt[0] live rays, compact)
-            C.nCap = (int)rayCap;
-            int *const shadowFlagsOf[2] = {W.shadowFlags.p, ae ? W.shadowFlags1.p : W.shadowFlags.p};   // (the words of generation g: [g & 1])
-            C.flags = flagsOf[cur]; B.flags = shadowFlagsOf[(k + 1) & 1];   // launch #k traces the shadow rays of generation k - 1
-            C.missRecords = (feedback && !packet_closest(k)) ? 1 : 0;   // k_shade #k reads the cost word of every ray of the generation
-            { const HeavyArgs H = heavy_for(k); C.heavyIdx = H.list; C.nHeavy = H.count; }
-            B.rays = W.shadowRays.p; B.hits = W.shadowHits.p; B.index = nullptr; B.nDev = hasShadow ? scnt + (k - 1) : nullptr; B.nMul = nL; B.n = 0;
-            if (ae && hasShadow) { B.nDev = acnt + (k - 1); B.nMul = 1; B.scatter = W.shadowOut.p; }   // the emitted shadow rays, compact; answers go back to (slot, light)
-            B.nCap = (int)((long long)shadowCap * nL);
-            for (IntersectArgs *a : {&C, &B}) {
-                a->queue = q + QW * k; a->mode = s->sceneMode; a->meshId = 0;
-                set_knobs(*a, s);
-            }
-            // segments of coherent rays go to the wave-packet kernel, the others (together, one launch) to the per-lane kernel
-            const bool pkC = hasClosest && packet_closest(k), pkB = hasShadow && packet_shadow(k);
-            // (I2: a second ray population for the same launch -- the shadow rays beside the closest-hit rays -- or null)
-            auto launch_pk = [&](const IntersectArgs &I, int word, long long nHost, const IntersectArgs *I2 = nullptr) -> int {
-                PacketArgs PA;
-                PA.rays = I.rays; PA.hits = I.hits; PA.flags = I.flags; PA.index = I.index; PA.nDev = I.nDev; PA.nMul = I.nMul; PA.n = I.n; PA.nCap = I.nCap;
-                PA.scatter = I.scatter;
-                if (I2) { PA.rays2 = I2->rays; PA.hits2 = I2->hits; PA.flags2 = I2->flags; PA.nDev2 = I2->nDev; PA.nMul2 = I2->nMul; PA.nCap2 = I2->nCap; PA.scatter2 = I2->scatter; }
-                if (tileCostDev) {   // which tile pays for a packet: the path of its first ray (closest-hit rays: the path list; shadow rays: their hit's slot record)
-                    PA.tileCost = tileCostDev; PA.tileBase = (int)pathBase; PA.tileShift = 9 + (gp.samples == 16 ? 4 : (gp.samples == 4 ? 2 : 0));
-                    if (&I == &B) { PA.slotOf1 = slotOf[prv]; PA.nL1 = nL; }
-                    else PA.pathOf1 = k == 0 ? W.index0.p : paths[cur];
-                    if (I2) { PA.slotOf2 = slotOf[prv]; PA.nL2 = nL; }
-                }
-                PA.queue = q + QW * k + 1 + PACKET_QUEUE_WORDS * word; PA.mode = s->sceneMode; PA.meshId = 0; PA.unmark = 0; PA.staticDiv = s->cfg.packetStaticDiv; PA.grabMax = s->cfg.packetGrabMax; PA.cullMin = s->cfg.packetCullMin;
-                if (s->cfg.packetSplit && s->sceneMode != MODE_SCENE) {
-                    if ((rc = split_arena(s, W.splitItems, W.splitRecs, PA, st))) return rc;
-                    if (fast && !adaptive && !heap && s->cfg.packetLongUs > 0) {   // plain frames: the packets of launch #k are the same from frame to frame while the camera stands still, and nearly so while it moves
-                        const size_t stride = (rayCap + 63) / 64 + ((size_t)shadowCap * (size_t)(nL > 0 ? nL : 1) + 63) / 64 + 2;
-                        if (W.splitCostStride != stride || !W.splitCost.p) {
-                            if ((rc = W.splitCost.ensure(stride * 2 * (size_t)(R + 2)))) return rc;
-                            HIPCHECK(hipMemsetAsync(W.splitCost.p, 0, stride * 2 * (size_t)(R + 2) * sizeof(unsigned), st));
-                            W.splitCostStride = stride;
-                        }
-                        PA.splitCost = W.splitCost.p + stride * (size_t)(2 * k + word);
-                        PA.splitLong = s->cfg.packetLongUs; PA.splitBudgetLong = std::max(1, s->cfg.packetBudgetLongUs);
-                    }
-                }
-                hipEvent_t a0 = get_event(F.events, ev), a1 = get_event(F.events, ev + 1);
-                if (!a0 || !a1) return fail(XRT_E_HIP, "hipEventCreate failed");
-                int grid = s->numCUs * s->blocksPerCUPacket;
-                if (nHost >= 0) { const long long want = (nHost + 255) / 256; if (want < grid) grid = (int)(want < 1 ? 1 : want); }
-                if (useStamps && grid * 4 <= STAMP_SLOTS && F.stampRows < s->cfg.maxStampRows) { PA.stamps = W.stamps.p + (size_t)F.stampRows++ * STAMP_STRIDE; a0 = a1 = nullptr; }
-                else if (!s->cfg.launchTiming) a0 = a1 = nullptr;
-                else { pairs.push_back({ev, ev + 1}); ev += 2; }
-                launch_packet(S, PA, grid, st, a0, a1);
-                return XRT_OK;
-            };
-            Range ri("xrt intersect #%d", k);
-            // both populations of a step in ONE packet launch where both go to the packet kernel: one launch's tail instead of two
-            if (pkC && pkB && s->cfg.packetMerge) { if ((rc = launch_pk(C, 0, hint(s->genRays, k), &B))) return rc; }
-            else {
-                if (pkC && (rc = launch_pk(C, 0, k == 0 ? Pc : hint(s->genRays, k)))) return rc;
-                if (pkB && (rc = launch_pk(B, 1, hint(s->genRays, k)))) return rc;
-            }
-            const bool laneC = hasClosest && !pkC, laneB = hasShadow && !pkB;
-            if (laneC || laneB) {
-                IntersectArgs A = laneC ? C : B;
-                if (laneC && laneB) { A.rays2 = B.rays; A.hits2 = B.hits; A.flags2 = B.flags; A.nDev2 = B.nDev; A.nMul2 = B.nMul; A.nCap2 = B.nCap; A.scatter2 = B.scatter; }
-                hipEvent_t a0 = get_event(F.events, ev), a1 = get_event(F.events, ev + 1);
-                if (!a0 || !a1) return fail(XRT_E_HIP, "hipEventCreate failed");
-                const int grid = k == 0 ? persistent_grid(s, Pc) : persistent_grid(s, hint(s->genRays, k), 16);
-                if (useStamps && grid * 4 <= STAMP_SLOTS && F.stampRows < s->cfg.maxStampRows) { A.stamps = W.stamps.p + (size_t)F.stampRows++ * STAMP_STRIDE; a0 = a1 = nullptr; }
-                else if (!s->cfg.launchTiming) a0 = a1 = nullptr;
-                else { pairs.push_back({ev, ev + 1}); ev += 2; }
-                if (s->waveTimes.p && k < 16) A.debugTimes = s->waveTimes.p + (size_t)k * 3 * 8192;
-                launch_intersect(S, A, s->stackNeeded, grid, st, a0, a1);
-            }
-            if ((hasClosest || hasShadow) && opts->collect_stats) {   // generation 0: the live list; culled rays are added in frame_finish
-                if (hasClosest) launch_count(S, C, s->counters.p, st);
-                if (hasShadow) launch_count(S, B, s->counters.p + C_COUNT, st);
-            }
-            if (ri.on) { roctx().pop(); ri.on = false; }
-            Range rs("xrt shade #%d", k);
-            ShadeArgs X;
-            std::memset(&X, 0, sizeof(X));
-            X.level = k; X.doA = hasClosest ? 1 : 0; X.doB = k >= 1 ? 1 : 0;
-            X.maxReflections = R; X.P = (int)lvlStride; X.lvl = gp.lvl; X.heap = heap ? 1 : 0; X.overflow = overflowFlag;
-            X.rays = rays[cur]; X.hits = hitsOf[cur]; X.hitFlags = flagsOf[cur]; X.shadowFlags = shadowFlagsOf[(k + 1) & 1]; X.nDev = nClosest; X.nHost = Pc; X.cap = (int)rayCap;
-            X.index = nullptr; X.rayPath = k == 0 ? W.index0.p : paths[cur];   // (generation 0: the j-th live ray belongs to path index0[j])
-            X.rayNode = (heap && k > 0) ? nodesOf[cur] : nullptr;
-            X.rayRef = (heap && (k > 0 || gp.batch)) ? refOf[cur] : nullptr;   // (a batch's generation 0 carries the caller's currentRefIndex, k_ingest)
-            X.slotOut = slotOf[cur]; X.slotNodeOut = heap ? slotNodeOf[cur] : nullptr; X.scnt = scnt + k; X.shadowCap = (int)shadowCap; X.shadowRays = W.shadowRays.p;
-            X.nextRays = rays[prv]; X.nextPath = paths[prv]; X.nextNode = heap ? nodesOf[prv] : nullptr; X.nextRef = heap ? refOf[prv] : nullptr;
-            X.nextCnt = cnt + k + 1; X.nextCap = (int)rayCap;
-            if (ae) { X.ae = 1; X.shadowCnt = acnt + k; X.shadowOut = W.shadowOut.p; X.shadowFlagsOut = shadowFlagsOf[k & 1]; }
-            if (finishA) { X.finish = 1; X.finishCnt = fcnt + k; }
-            if (listCnt && k == 0) X.end = endArgs;
-            X.slotPrev = slotOf[prv]; X.slotNodePrev = heap ? slotNodeOf[prv] : nullptr; X.scntPrev = k >= 1 ? scnt + (k - 1) : nullptr; X.shadowHits = W.shadowHits.p;
-            X.lvlA = W.lvlA.p; X.lvlB = W.lvlB.p; X.lvlAlpha = heap ? W.lvlAlpha.p : nullptr;
-            if (k < R) X.heavy = heavy_for(k + 1);
-            if (feedback && hasClosest && !packet_closest(k)) { X.costOut = s->costMap.p + (size_t)k * (size_t)framePaths + (size_t)partStart; X.epoch = s->epoch & 0xffffu; }
-            {   // (a small generation: 256-thread blocks, so that its work items land on many CUs instead of on the first few)
-                const long long h = hint(s->genShade, k);
-                if (h >= 0 && h < 4 * 131072 + 4096) launch_shade(S, V, X, st, (int)((h + 255) / 256), 256);
-                else launch_shade(S, V, X, st, h < 0 ? 1024 : (int)((h + 1023) / 1024 < 1024 ? (h + 1023) / 1024 : 1024));
-            }
-            if (pout && hasClosest) {   // the generation's hits and the refraction rays it cast, before slots and ray buffers are reused
-                PathsCaptureArgs Cp;
-                Cp.slots = slotOf[cur]; Cp.slotNode = heap ? slotNodeOf[cur] : nullptr; Cp.scnt = scnt + k; Cp.slotCap = (int)shadowCap; Cp.level = k;
-                if (heap && k < R) { Cp.nextRays = rays[prv]; Cp.nextNode = nodesOf[prv]; Cp.nextPath = paths[prv]; Cp.nextCnt = cnt + k + 1; Cp.nextCap = (int)rayCap; }
-                Cp.hitRec = s->pathHit.p; Cp.dirRec = s->pathDir.p; Cp.P = (int)lvlStride; Cp.epoch = pathEpoch;
-                launch_paths_capture(Cp, (int)((rayCap + 255) / 256), st);
-            }
-        }
-        Range rc_("xrt compose");
-        // a batch: path p of the chunk is ray pathBase + p, and the compose kernel writes its colour straight into the caller's arrays (a ray-tree chunk
-        // that overflowed is retried over the same range: the retry overwrites what the discarded attempt wrote)
-        uint32_t *const colorOut = gp.batch ? d_out + pathBase : (sampleOut ? sampleOut : W.sampleColor.p);
-        float *const f32Out = gp.batch ? (d_outF32 ? d_outF32 + 3 * (size_t)pathBase : nullptr) : (wantF32 ? W.sampleF32.p : nullptr);
-        StampFold fold;
-        fold.src = W.stamps.p; fold.host = F.stampHost.dev; fold.row0 = chunkRow0; fold.row1 = F.stampRows;
-        if (heap) {
-            FrameEpilogue E;
-            if (fast) { E.cntSrc = cnt; E.hostCnt = F.pinned.dev; E.cntWords = cntStride; E.zeroWords = cntStride + qStride; E.flagSrc = overflowFlag; }
-            launch_compose_tree(W.lvlA.p, W.lvlB.p, W.lvlAlpha.p, Pc, P, R, colorOut, f32Out, fold, E, st);
-        }
-        else {
-            ResolveArgs RA;
-            RA.fused = fuseResolve ? 1 : 0; RA.g = gp; RA.pixelBase = pathBase; RA.out = d_out; RA.outF32 = d_outF32;
-            RA.stamps = fold;
-            if (epi) { RA.cntSrc = epi->cntSrc; RA.hostCnt = epi->hostCnt; RA.cntWords = epi->cntWords; RA.zeroWords = epi->zeroWords; RA.zeroFrom = epi->zeroFrom; }
-            else if (fast && !adaptive) { RA.cntSrc = cnt; RA.hostCnt = F.pinned.dev; RA.cntWords = cntStride; RA.zeroWords = cntStride + qStride; }
-            int blocks = 0;
-            if (listCnt) {
-                RA.list = W.composeList.p + 16; RA.endCnt = listCnt; RA.listCap = (int)rayCap;
-                if (hinted && s->genCompose >= 0) blocks = (int)((4 * s->genCompose + 4096 + 255) / 256);
-            }
-            launch_compose(W.lvlA.p, W.lvlB.p, Pc, (int)lvlStride, R, colorOut, fuseResolve ? nullptr : f32Out, RA, st,
-                           (fast && fuseResolve) ? e1 : nullptr, blocks);
-        }
-        return XRT_OK;
-    };
-    auto ensure_pinned = [&](size_t bytes) -> int { return F.pinned.bytes < bytes ? F.pinned.ensure(bytes + 4096, hipHostMallocMapped) : XRT_OK; };
-    auto tally = [&](const int *hc) {
-        for (int k = 0; k <= R; k++) {
-            shaded += (unsigned long long)gen_hits(hc, R, k);
-            if (k > 0) closestDeep += (unsigned long long)(heap ? hc[k] : gen_hits(hc, R, k - 1));   // reflection chain: one ray per parent hit
-            else live0 += (unsigned long long)hc[0];
-        }
-    };
-
-    // One pass = trace `total` paths produced by generator `gp`; after every chunk `post(Pc, pathBase)` consumes sampleColor.
-    auto run_pass = [&](const RayGenParams &gp, long long total, auto &&post, float progress0, float progress1, bool finalPass) -> int {
-        int rc2;
-        const size_t nb2 = 2 * C_COUNT * sizeof(unsigned long long);
-        if (heap && !fast) {
-            // ray-tree mode, the careful way: one chunk at a time, checked for overflow, retried with fewer paths when a generation did not fit
-            const size_t words = (size_t)cntStride + (size_t)qStride;
-            if ((rc2 = W.cnts.ensure(words)) || (rc2 = ensure_pinned(words * sizeof(int) + nb2 + 64 + 8 + 64))) return rc2;
-            W.cntsClean = false;
-            unsigned *q = reinterpret_cast<unsigned *>(W.cnts.p + cntStride);
-            long long pathBase = 0, curChunk = chunkPaths;   // (ray-tree frames are never split: partStart == 0)
-            while (pathBase < total) {
-                const int Pc = (int)((total - pathBase) < curChunk ? (total - pathBase) : curChunk);
-                HIPCHECK(hipMemsetAsync(W.cnts.p, 0, words * sizeof(int), st));
-                const size_t pairsMark = pairs.size(), evMark = ev;
-                const int rowsMark = F.stampRows;
-                if ((rc2 = enqueue_chunk(gp, W.cnts.p, q, Pc, pathBase))) return rc2;
-                // the chunk's samples are consumed before the host has looked at the overflow flag: a retry overwrites them
-                if ((rc2 = post(Pc, pathBase))) return rc2;
-                char *pin = (char *)F.pinned.p;
-                const size_t cAt = ((size_t)cntStride * sizeof(int) + 7) & ~(size_t)7;   // counters + spare words (overflow flag) in one copy
-                HIPCHECK(hipMemcpyAsync(pin, W.cnts.p, (size_t)cntStride * sizeof(int), hipMemcpyDeviceToHost, st));
-                HIPCHECK(hipMemcpyAsync(pin + cAt, s->counters.p, nb2, hipMemcpyDeviceToHost, st));
-                HIPCHECK(hipMemcpyAsync(pin + cAt + nb2 + 64, overflowFlag, sizeof(int), hipMemcpyDeviceToHost, st));
-                HIPCHECK(hipStreamSynchronize(st));
-                const int over = *(const int *)(pin + cAt + nb2 + 64);
-                if (over) {
-                    if (curChunk <= 64) return fail(XRT_E_UNSUPPORTED, "the ray tree of 64 paths does not fit the ray buffers (MaxReflections too high for this scene)");
-                    curChunk = (curChunk / 4) & ~63LL;
-                    if (curChunk < 64) curChunk = 64;
-                    HIPCHECK(hipMemsetAsync(overflowFlag, 0, sizeof(int), st));
-                    HIPCHECK(hipMemcpyAsync(s->counters.p, hcntHost, nb2, hipMemcpyHostToDevice, st));   // undo this attempt's counting
-                    HIPCHECK(hipStreamSynchronize(st));
-                    pairs.resize(pairsMark); ev = evMark; F.stampRows = rowsMark;   // its launches are not part of the frame's timing
-                    continue;
-                }
-                tally((const int *)pin);
-                std::memcpy(hcntHost, pin + cAt, nb2);
-                pathBase += Pc;
-                s->progress.store(progress0 + (progress1 - progress0) * (float)pathBase / (float)total);
-            }
-            if (finalPass) HIPCHECK(hipEventRecord(e1, st));
-            return XRT_OK;
-        }
-        const int nChunks = (int)((total + chunkPaths - 1) / chunkPaths);
-        // ray counts and queue heads of all chunks live in one allocation: one memset per pass
-        const size_t cntWords = (size_t)nChunks * cntStride, qWords = (size_t)nChunks * qStride;
-        const int *cntsBefore = W.cnts.p;
-        if ((rc2 = W.cnts.ensure(cntWords + qWords))) return rc2;
-        unsigned *queuesBase = reinterpret_cast<unsigned *>(W.cnts.p + cntWords);
-        if (fast && (rc2 = ensure_pinned(cntWords * sizeof(int) + 64))) return rc2;   // (+ the overflow word of a ray-tree frame)
-        if (!fast || !W.cntsClean || W.cnts.p != cntsBefore) HIPCHECK(hipMemsetAsync(W.cnts.p, 0, W.cnts.cap * sizeof(int), st));
-        W.cntsClean = false;
-        for (int c = 0; c < nChunks; c++) {
-            const long long localBase = (long long)c * chunkPaths, pathBase = partStart + localBase;
-            const int Pc = (int)((total - localBase) < chunkPaths ? (total - localBase) : chunkPaths);
-            if ((rc2 = enqueue_chunk(gp, W.cnts.p + (size_t)c * cntStride, queuesBase + (size_t)c * qStride, Pc, pathBase, nullptr, nullptr,
-                                     endEarly ? W.composeList.p : nullptr))) return rc2;
-            if (!fuseResolve && (rc2 = post(Pc, pathBase))) return rc2;
-            if (nChunks > 1) {   // frames of more than MAX_CHUNK_PATHS rays: xrt_progress follows the chunks
-                HIPCHECK(hipStreamSynchronize(st));
-                s->progress.store(progress0 + (progress1 - progress0) * (float)(c + 1) / (float)nChunks);
-            }
-        }
-        if (fast) {   // counters arrive with k_compose; frame_finish tallies them
-            if (!fuseResolve) HIPCHECK(hipEventRecord(e1, st));   // fixed 16 sub-rays: k_resolve is the last kernel
-            W.cntsClean = true;
-            F.tallyChunks = 1;
-            return XRT_OK;
-        }
-        if (finalPass) HIPCHECK(hipEventRecord(e1, st));
-        if (stats) {   // per-pass ray accounting (the counter block is reused by the next pass): one pinned read-back
-            const size_t nb = (size_t)nChunks * cntStride * sizeof(int);
-            if ((rc2 = ensure_pinned(nb + nb2))) return rc2;
-            HIPCHECK(hipMemcpyAsync(F.pinned.p, W.cnts.p, nb, hipMemcpyDeviceToHost, st));
-            HIPCHECK(hipMemcpyAsync((char *)F.pinned.p + nb, s->counters.p, nb2, hipMemcpyDeviceToHost, st));
-            if (finalPass) { F.tallyChunks = nChunks; return XRT_OK; }   // frame_finish tallies after the frame's done event
-            HIPCHECK(hipStreamSynchronize(st));
-            for (int c = 0; c < nChunks; c++) tally(F.pinned.p + (size_t)c * cntStride);
-            std::memcpy(hcntHost, (char *)F.pinned.p + nb, nb2);
-        }
-        return XRT_OK;
-    };
-
-    // valid pixels of this shard
-    unsigned long long &validPixels = F.validPixels;
-    validPixels = 0;
-    if (batch) {   // path p is ray p: the compose kernels write the caller's arrays themselves (enqueue_chunk), nothing to do after a chunk
-        validPixels = (unsigned long long)batch->n;
-        livePaths = validPixels;
-        rc = run_pass(g, firstPaths, [&](int Pc, long long pathBase) -> int {
-            if (!pout) return XRT_OK;
-            PathsEmitArgs E;   // the chunk's segments in the recursion's order, behind those of the rays before it
-            E.batch = batch->rays; E.pathBase = pathBase; E.Pc = Pc; E.P = (int)lvlStride; E.depth = R; E.tree = heap ? 1 : 0; E.epoch = pathEpoch;
-            E.hitRec = s->pathHit.p; E.dirRec = s->pathDir.p; E.local = s->pathLocal.p; E.blockSum = s->pathBlockSum.p; E.blockBase = s->pathBlockBase.p;
-            E.vertexStart = pout->vertexStart; E.vertices = pout->vertices; E.capacity = pout->capacity; E.raysBack = pout->raysBack;
-            launch_paths_emit(E, st);
-            return XRT_OK;
-        }, 0.0f, 1.0f, true);
-        if (rc != XRT_OK) return rc;
-        if (pout) HIPCHECK(hipMemcpyAsync(s->pathPinned.p, pout->vertexStart + batch->n, sizeof(long long), hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipEventRecord(F.done, st));
-        HIPCHECK(hipGetLastError());
-        F.pending = true;
-        return XRT_OK;
-    }
-    const long long slot0 = partStart / (512LL * g.samples), slot1 = (partStart + firstPaths + 512LL * g.samples - 1) / (512LL * g.samples);   // tile slots of this part
-    for (long long sl = slot0; sl < slot1; sl++) {
-        const long long t = tile_of_slot(sl);
-        if (t >= totalTiles) break;
-        if (t < 0) continue;   // (an unused slot of a tile table)
-        int tx = (int)(t % g.tilesX), ty = (int)(t / g.tilesX);
-        int w = g.width - tx * XRT_TILE_W; if (w > XRT_TILE_W) w = XRT_TILE_W;
-        int h = g.height - ty * XRT_TILE_H; if (h > XRT_TILE_H) h = XRT_TILE_H;
-        validPixels += (unsigned long long)w * h;
-    }
-
-    if (!adaptive) {
-        livePaths = validPixels * (unsigned long long)g.samples;
-        rc = run_pass(g, firstPaths, [&](int Pc, long long pathBase) -> int {
-            launch_resolve(g, W.sampleColor.p, wantF32 ? W.sampleF32.p : nullptr, Pc / g.samples, pathBase / g.samples, d_out, d_outF32, st, nullptr, 0, skipTiles ? 1 : 0);
-            return XRT_OK;
-        }, 0.0f, 1.0f, true);
-        if (rc != XRT_OK) return rc;
-    } else if (F.adaptiveFast) {
-        // RenderFirstPass / GetColorForQuadrant (RT:170-311) without a host round trip: every level's pass is enqueued now.  Level 0 has
-        // one quadrant per pixel; how many quadrants a deeper level has only the device knows (k_ms_decide counts them into lvlCnt[l],
-        // the level's ray generation, compose and fold kernels read that word; the traversal and shading kernels follow the ray
-        // counts as always).  Deeper levels get room for one quadrant per pixel (XRT_ADAPTIVE_CAP); a level that needs more sets the
-        // overflow word and frame_finish renders the frame again the careful way below.
-        const int nPass = quality + 1;
-        constexpr int LW = 16;   // words in front of the per-pass counters: lvlCnt[0 .. quality], overflow word at LW - 1
-        const long long capDeep = s->cfg.adaptiveCap > 0 ? std::min(s->cfg.adaptiveCap, totalPixels) : totalPixels;
-        auto cap_of = [&](int l) { return l == 0 ? totalPixels : capDeep; };
-        const size_t words = (size_t)LW + (size_t)nPass * cntStride + (size_t)nPass * qStride;
-        const int *cntsBefore = W.cnts.p;
-        if ((rc = W.cnts.ensure(words)) || (rc = ensure_pinned(((size_t)LW + (size_t)nPass * cntStride) * sizeof(int) + 64))) return rc;
-        if (!W.cntsClean || W.cnts.p != cntsBefore) HIPCHECK(hipMemsetAsync(W.cnts.p, 0, W.cnts.cap * sizeof(int), st));
-        W.cntsClean = false;
-        for (int l = 0; l <= quality; l++) {
-            auto &Lv = W.levels[l];
-            const size_t c = (size_t)cap_of(l);
-            if ((rc = Lv.color.ensure(c * 4))) return rc;
-            if (l < quality && ((rc = Lv.childBase.ensure(c)) || (rc = Lv.childMask.ensure(c)))) return rc;
-            if (l > 0 && ((rc = Lv.cx.ensure(c)) || (rc = Lv.cy.ensure(c)))) return rc;
-        }
-        int *const lvlCnt = W.cnts.p, *const ovf = W.cnts.p + LW - 1;
-        int *const cnt0 = W.cnts.p + LW;
-        unsigned *const q0 = reinterpret_cast<unsigned *>(cnt0 + (size_t)nPass * cntStride);
-        float size = 1.0f;
-        for (int l = 0; l <= quality; l++) {
-            auto &Lv = W.levels[l];
-            RayGenParams gl = g;
-            gl.quadLevel = l; gl.quadSize = size; gl.quadCx = Lv.cx.p; gl.quadCy = Lv.cy.p;
-            if (l > 0) { gl.pathsDev = lvlCnt + l; gl.pathsMul = 4; gl.pathsCap = (int)cap_of(l); }
-            FrameEpilogue E;
-            const bool last = l == quality;
-            if (last) { E.cntSrc = W.cnts.p; E.hostCnt = F.pinned.dev; E.cntWords = LW + nPass * cntStride; E.zeroWords = (int)words; E.zeroFrom = LW; }
-            if ((rc = enqueue_chunk(gl, cnt0 + (size_t)l * cntStride, q0 + (size_t)l * qStride, (int)(cap_of(l) * 4), 0, Lv.color.p, last ? &E : nullptr))) return rc;
-            if (l < quality) {   // RT:279-306
-                auto &Nx = W.levels[l + 1];
-                launch_ms_decide(gl, Lv.color.p, l > 0 ? lvlCnt + l : nullptr, (int)cap_of(l), 0, Lv.childBase.p, Lv.childMask.p, Nx.cx.p, Nx.cy.p, lvlCnt + l + 1, st,
-                                 (int)cap_of(l + 1), ovf);
-                size = size / 2.0f;   // RT:290
-            }
-        }
-        for (int l = quality - 1; l >= 0; l--)
-            launch_ms_fold(W.levels[l].color.p, W.levels[l + 1].color.p, W.levels[l].childBase.p, W.levels[l].childMask.p, (int)cap_of(l), st, l > 0 ? lvlCnt + l : nullptr);
-        RayGenParams g0 = g;
-        g0.quadLevel = 0; g0.quadSize = 1.0f;
-        launch_resolve(g0, W.levels[0].color.p, nullptr, (int)totalPixels, 0, d_out, d_outF32, st, lvlCnt, LW);   // ... and clears the level words for the next frame
-        HIPCHECK(hipEventRecord(e1, st));
-        W.cntsClean = true;
-        F.tallyChunks = nPass; F.cntBase = LW; F.levelCap = (int)capDeep; F.quality = quality;
-    } else {
-        // RenderFirstPass / GetColorForQuadrant (RT:170-311), the careful way (a host read-back of every level's size): level 0
-        // quadrants are the pixels (size 1); a level's
-        // quadrants each cast four rays; corners that deviate are subdivided into the next level, down to
-        // MultisampleQuality; results fold back up.
-        struct Level : xrt_scene::WorkBufs::Level { long long n = 0; };   // (the frame's own: freed when it is done, however it ends)
-        std::vector<Level> lv((size_t)quality + 1);
-        int *levelCount = reinterpret_cast<int *>(s->counters.p + 2 * C_COUNT);   // [quality+1] ints in the spare counter words
-        lv[0].n = totalPixels;
-        float size = 1.0f;
-        for (int l = 0; l <= quality && rc == XRT_OK; l++) {
-            Level &L = lv[l];
-            if (L.n == 0) break;
-            if ((rc = L.color.ensure((size_t)L.n * 4))) break;
-            RayGenParams gl = g;
-            gl.quadLevel = l; gl.quadSize = size; gl.quadCx = L.cx.p; gl.quadCy = L.cy.p;
-            livePaths += (l == 0 ? validPixels : (unsigned long long)L.n) * 4ull;
-            rc = run_pass(gl, L.n * 4, [&](int Pc, long long pathBase) -> int {
-                HIPCHECK(hipMemcpyAsync(L.color.p + pathBase, W.sampleColor.p, (size_t)Pc * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-                return XRT_OK;
-            }, (float)l / (float)(quality + 1), (float)(l + 1) / (float)(quality + 1), false);
-            if (rc != XRT_OK) break;
-            if (l < quality) {   // RT:279-306
-                Level &N = lv[l + 1];
-                if ((rc = L.childBase.ensure((size_t)L.n)) || (rc = L.childMask.ensure((size_t)L.n)) || (rc = N.cx.ensure((size_t)L.n * 4)) ||
-                    (rc = N.cy.ensure((size_t)L.n * 4)))
-                    break;
-                launch_ms_decide(gl, L.color.p, nullptr, (int)L.n, 0, L.childBase.p, L.childMask.p, N.cx.p, N.cy.p, levelCount + l + 1, st);
-                int hn = 0;
-                hipError_t e = hipMemcpyAsync(&hn, levelCount + l + 1, sizeof(int), hipMemcpyDeviceToHost, st);
-                if (e == hipSuccess) e = hipStreamSynchronize(st);
-                if (e != hipSuccess) { rc = fail(XRT_E_HIP, "adaptive level readback: %s", hipGetErrorString(e)); break; }
-                N.n = hn;
-                size = size / 2.0f;   // RT:290
-            }
-        }
-        if (rc == XRT_OK) {
-            for (int l = quality - 1; l >= 0; l--)
-                if (lv[l + 1].n > 0) launch_ms_fold(lv[l].color.p, lv[l + 1].color.p, lv[l].childBase.p, lv[l].childMask.p, (int)lv[l].n, st);
-            RayGenParams g0 = g;
-            g0.quadLevel = 0; g0.quadSize = 1.0f;
-            launch_resolve(g0, lv[0].color.p, nullptr, (int)totalPixels, 0, d_out, d_outF32, st);
-            hipError_t e = hipEventRecord(e1, st);
-            if (e == hipSuccess && stats) e = hipMemcpyAsync(hcntHost, s->counters.p, sizeof(F.hcnt), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) rc = fail(XRT_E_HIP, "adaptive resolve: %s", hipGetErrorString(e));
-        }
-        if (rc != XRT_OK) return rc;
-    }
-    if (!fast) HIPCHECK(hipEventRecord(F.done, st));
+    int *overflowFlag = P.heap ? W.heapFlag.p : reinterpret_cast<int *>(s->counters.p + 2 * C_COUNT) + 12;   // (else: a spare counter word, never set)
+    // the enqueue, by the frame's shape
+    FrameJob J{s, F, P, W, pose_view(s, F.pose), V, st, e0, e1, batch, d_out, d_outF32, tileCostDev, overflowFlag, P.fast};
+    if ((rc = P.batch ? J.batch_frame() : (!P.adaptive ? J.plain_frame() : (P.adaptiveFast ? J.adaptive_in_flight() : J.adaptive_careful())))) return rc;
+    if (!P.fast) HIPCHECK(hipEventRecord(F.done, st));
     HIPCHECK(hipGetLastError());
     F.pending = true;
     return XRT_OK;
+}
+
+// A frame in flight did not fit its optimistically sized buffers: it is rendered again the careful way, and frame_finish runs on the new attempt.
+int redo_careful(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
+    F.tallyChunks = 0;
+    const std::vector<xrt_light> lights = F.redoLights;
+    const xrt_camera cam = F.redoCam;
+    const xrt_render_opts opts = F.redoOpts;
+    int rc = frame_begin(s, F, &cam, lights.data(), (int)lights.size(), &opts, F.redoOut, F.redoOutF32, F.redoSt);
+    if (rc != XRT_OK) return rc;
+    rc = frame_finish(s, F, stats);
+    F.redone = true;
+    return rc;
+}
+
+// Sizes of a finished single-chunk frame's generations (hc: its counters): grid hints for the next one (sizing only).
+void update_grid_hints(xrt_scene *s, const FramePlan &P, const int *hc) {
+    const int R = P.R;
+    const bool same0 = s->genKey == P.hintPaths * 64 + P.nL && s->genHeap == P.heap;
+    for (int k = 0; k <= R + 1 && k < 68; k++) {
+        const long long closest = (k == 0 || ((P.heap || P.ae) && k <= R)) ? hc[k] : (k <= R ? gen_hits(hc, R, k - 1) : 0), shaded = k >= 1 ? gen_hits(hc, R, k - 1) : 0;
+        // (a hint shrinks by an eighth per frame at most: a camera that looks away for a frame, or alternates between two views,
+        // must not leave the next full view with a grid of sixteen blocks)
+        const long long rays = closest + shaded * P.nL, work = closest > shaded ? closest : shaded;
+        const long long keepR = same0 && s->genRays[k] > 0 ? s->genRays[k] - s->genRays[k] / 8 : 0, keepS = same0 && s->genShade[k] > 0 ? s->genShade[k] - s->genShade[k] / 8 : 0;
+        s->genRays[k] = rays > keepR ? rays : keepR;
+        s->genShade[k] = work > keepS ? work : keepS;
+    }
+    for (int k = R + 2; k < 68; k++) s->genRays[k] = s->genShade[k] = -1;
+    {
+        const long long listed = P.endEarly ? hc[P.cntStride] : -1, keep = same0 && s->genCompose > 0 ? s->genCompose - s->genCompose / 8 : 0;
+        s->genCompose = listed < 0 ? -1 : (listed > keep ? listed : keep);
+    }
+    s->genKey = P.hintPaths * 64 + P.nL;
+    s->genHeap = P.heap;
+}
+
+// Steer the "long ray" thresholds towards 2-6 % of each generation's rays (hc: a finished single-chunk frame's counters).
+void steer_long_ray_thresholds(xrt_scene *s, const FramePlan &P, const int *hc) {
+    const int R = P.R;
+    for (int k = 0; k <= R && k < 66; k++) {
+        const long long rays = k == 0 ? hc[0] : gen_hits(hc, R, k - 1), listed = hc[2 * (R + 2) + k];
+        if (rays < 4096) continue;
+        if (listed * 100 > rays * s->cfg.longFracHi) s->costT[k] = s->costT[k] + s->costT[k] / 4 + 1;
+        else if (listed * 100 < rays * s->cfg.longFracLo && s->costT[k] > 1) s->costT[k] = s->costT[k] - s->costT[k] / 5 - (s->costT[k] < 5 ? 1 : 0);
+        if (s->costT[k] < 1) s->costT[k] = 1;
+        if (s->costT[k] > 60000) s->costT[k] = 60000;
+    }
 }
 
 // Waits for a frame enqueued by frame_begin and turns its counters / events into xrt_stats.
 int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
     if (!F.pending) return fail(XRT_E_INVALID_ARG, "no frame in flight for this ticket");
     F.pending = false;
-    HIPCHECK(hipEventSynchronize(F.fast ? F.events[1] : F.done));
+    const FramePlan &P = F.plan;
+    HIPCHECK(hipEventSynchronize(P.fast ? F.events[1] : F.done));
     s->progress.store(1.0f);
     if (s->waveTimes.p) {   // development aid: launch k of the frame occupies rows [k*8192, (k+1)*8192) x 3 clocks
         std::vector<unsigned long long> h((size_t)16 * 3 * 8192);
@@ -1087,106 +1264,48 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
         HIPCHECK(hipMemcpy(h.data(), F.w.stamps.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         if (FILE *f = fopen(s->cfg.stampDumpPath.c_str(), "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
     }
-    const int R = F.R;
-    if (F.fast && F.adaptiveFast && F.pinned.p[F.cntBase - 1] != 0) {
+    if (P.adaptiveFast && F.pinned.p[P.cntBase - 1] != 0) {
         // A quadrant level of the adaptive frame did not fit its optimistically sized buffers: the frame is rendered again the careful
         // way (a host read-back per level, exact sizes), and so are this scene's later adaptive frames from the start.
         s->adaptiveFastOk = false;
-        F.tallyChunks = 0;
-        F.adaptiveFast = false;
-        const std::vector<xrt_light> lights = F.redoLights;
-        const xrt_camera cam = F.redoCam;
-        const xrt_render_opts opts = F.redoOpts;
-        int rc = frame_begin(s, F, &cam, lights.data(), (int)lights.size(), &opts, F.redoOut, F.redoOutF32, F.redoSt);
-        if (rc != XRT_OK) return rc;
-        rc = frame_finish(s, F, stats);
-        F.redone = true;
-        return rc;
+        return redo_careful(s, F, stats);
     }
-    if (F.fast && F.adaptiveFast) {   // rays of the frame: four per level-0 pixel and four per quadrant of every deeper level
+    if (P.adaptiveFast) {   // rays of the frame: four per level-0 pixel and four per quadrant of every deeper level
         const int *lw = F.pinned.p;
         F.livePaths = F.validPixels * 4ull;
-        for (int l = 1; l <= F.quality; l++) F.livePaths += 4ull * (unsigned long long)std::min(lw[l], F.levelCap);
+        for (int l = 1; l <= P.quality; l++) F.livePaths += 4ull * (unsigned long long)std::min(lw[l], P.levelCap);
     }
-    if (F.fast && F.heap && F.tallyChunks == 1 && F.pinned.p[F.cntStride] != 0) {
+    if (P.heapFast && F.tallyChunks == 1 && F.pinned.p[P.cntStride] != 0) {
         // A generation of the ray tree did not fit the optimistically sized buffers: the frame is rendered again the careful way
         // (chunks, overflow checks, retries with fewer paths), and so are this scene's later ray-tree frames from the start.
         s->heapFastOk = false;
-        F.tallyChunks = 0;
-        const std::vector<xrt_light> lights = F.redoLights;
-        const xrt_camera cam = F.redoCam;
-        const xrt_render_opts opts = F.redoOpts;
-        int rc = frame_begin(s, F, &cam, lights.data(), (int)lights.size(), &opts, F.redoOut, F.redoOutF32, F.redoSt);
-        if (rc != XRT_OK) return rc;
-        rc = frame_finish(s, F, stats);
-        F.redone = true;
-        return rc;
+        return redo_careful(s, F, stats);
     }
+    const int *const hc0 = F.pinned.p + P.cntBase;   // the first chunk's counters
     if (F.tallyChunks > 0) {   // single-pass frame: the read-back was left in flight
-        const size_t nb = (size_t)F.tallyChunks * F.cntStride * sizeof(int);
+        const size_t nb = (size_t)F.tallyChunks * P.cntStride * sizeof(int);
         for (int c = 0; c < F.tallyChunks; c++) {
-            const int *hc = F.pinned.p + F.cntBase + (size_t)c * F.cntStride;
-            if (hc[0] < 0 || (size_t)hc[0] > F.liveCap)
-                return fail(XRT_E_INTERNAL, "%d primary rays reach the scene but the frame's ray arrays were sized for %zu (screen rectangle of the root box)", hc[0], F.liveCap);
-            if (F.endEarly && (hc[F.cntStride] < 0 || hc[F.cntStride] > hc[0]))
-                return fail(XRT_E_INTERNAL, "%d paths on the compose list of a frame with %d live primary rays", hc[F.cntStride], hc[0]);
-            for (int k = 0; k <= R; k++) {
-                F.shaded += (unsigned long long)gen_hits(hc, R, k);
-                if (k > 0) F.closestDeep += (unsigned long long)(F.heap ? hc[k] : gen_hits(hc, R, k - 1));   // reflection chain: one ray per parent hit
-                else F.live0 += (unsigned long long)hc[0];
-                if (F.ae) {   // queries part A answered itself: the hits' shadow rays that were not emitted, and (not in the last generation) their reflections
-                    F.answered += (unsigned long long)gen_hits(hc, R, k) * (unsigned long long)F.nL - (unsigned long long)hc[3 * (R + 2) + k];
-                    if (k < R) F.answered += (unsigned long long)(gen_hits(hc, R, k) - hc[k + 1]);
-                }
-            }
+            const int *hc = hc0 + (size_t)c * P.cntStride;
+            if (hc[0] < 0 || (size_t)hc[0] > P.liveCap)
+                return fail(XRT_E_INTERNAL, "%d primary rays reach the scene but the frame's ray arrays were sized for %zu (screen rectangle of the root box)", hc[0], P.liveCap);
+            if (P.endEarly && (hc[P.cntStride] < 0 || hc[P.cntStride] > hc[0]))
+                return fail(XRT_E_INTERNAL, "%d paths on the compose list of a frame with %d live primary rays", hc[P.cntStride], hc[0]);
+            tally_chunk(F, hc);
         }
 #ifdef XRT_DEV
         if (s->cfg.finishCounts)   // (profiles/shade_finish: which share of a generation's hits part A finished; a frame not answered at emission emits every shadow ray)
-            for (int k = 0; k <= R; k++) {
-                const int *hc = F.pinned.p + F.cntBase;
-                fprintf(stderr, "xrt finish: %s generation %d hits %lld finished %d shadow rays emitted %lld\n", F.ae ? "answered at emission," : "not answered at emission,", k,
-                        gen_hits(hc, R, k), hc[4 * (R + 2) + k], F.ae ? (long long)hc[3 * (R + 2) + k] : gen_hits(hc, R, k) * (long long)F.nL);
-            }
+            for (int k = 0, R = P.R; k <= R; k++)
+                fprintf(stderr, "xrt finish: %s generation %d hits %lld finished %d shadow rays emitted %lld\n", P.ae ? "answered at emission," : "not answered at emission,", k,
+                        gen_hits(hc0, R, k), hc0[4 * (R + 2) + k], P.ae ? (long long)hc0[3 * (R + 2) + k] : gen_hits(hc0, R, k) * (long long)P.nL);
 #endif
-        if (!F.fast) std::memcpy(F.hcnt, (char *)F.pinned.p + nb, sizeof(F.hcnt));
-        // (adaptive frames in flight put the level-count words in front of the per-pass counters and have no framePaths key: no hints from them)
-        if (F.fast && F.tallyChunks == 1 && !F.adaptiveFast) {   // sizes of this frame's generations: grid hints for the next one (sizing only)
-            const int *hc = F.pinned.p + F.cntBase;
-            const bool same0 = s->genKey == F.framePaths * 64 + F.nL && s->genHeap == F.heap;
-            for (int k = 0; k <= R + 1 && k < 68; k++) {
-                const long long closest = (k == 0 || ((F.heap || F.ae) && k <= R)) ? hc[k] : (k <= R ? gen_hits(hc, R, k - 1) : 0), shaded = k >= 1 ? gen_hits(hc, R, k - 1) : 0;
-                // (a hint shrinks by an eighth per frame at most: a camera that looks away for a frame, or alternates between two views,
-                // must not leave the next full view with a grid of sixteen blocks)
-                const bool same = same0;
-                const long long rays = closest + shaded * F.nL, work = closest > shaded ? closest : shaded;
-                const long long keepR = same && s->genRays[k] > 0 ? s->genRays[k] - s->genRays[k] / 8 : 0, keepS = same && s->genShade[k] > 0 ? s->genShade[k] - s->genShade[k] / 8 : 0;
-                s->genRays[k] = rays > keepR ? rays : keepR;
-                s->genShade[k] = work > keepS ? work : keepS;
-            }
-            for (int k = R + 2; k < 68; k++) s->genRays[k] = s->genShade[k] = -1;
-            {
-                const long long listed = F.endEarly ? hc[F.cntStride] : -1, keep = same0 && s->genCompose > 0 ? s->genCompose - s->genCompose / 8 : 0;
-                s->genCompose = listed < 0 ? -1 : (listed > keep ? listed : keep);
-            }
-            s->genKey = F.framePaths * 64 + F.nL;
-            s->genHeap = F.heap;
-        }
-        if (F.fast && s->costMap.p && !F.adaptiveFast) {   // steer the "long ray" thresholds towards 2-6 % of each generation's rays
-            const int *hc = F.pinned.p + F.cntBase;
-            for (int k = 0; k <= R && k < 66; k++) {
-                const long long rays = k == 0 ? hc[0] : gen_hits(hc, R, k - 1), listed = hc[2 * (R + 2) + k];
-                if (rays < 4096) continue;
-                if (listed * 100 > rays * s->cfg.longFracHi) s->costT[k] = s->costT[k] + s->costT[k] / 4 + 1;
-                else if (listed * 100 < rays * s->cfg.longFracLo && s->costT[k] > 1) s->costT[k] = s->costT[k] - s->costT[k] / 5 - (s->costT[k] < 5 ? 1 : 0);
-                if (s->costT[k] < 1) s->costT[k] = 1;
-                if (s->costT[k] > 60000) s->costT[k] = 60000;
-            }
-        }
+        if (!P.fast) std::memcpy(F.hcnt, (char *)F.pinned.p + nb, sizeof(F.hcnt));
+        // (adaptive frames in flight put the level-count words in front of the per-pass counters and have no hintPaths key: no hints from them)
+        if (P.fast && F.tallyChunks == 1 && !P.adaptiveFast) update_grid_hints(s, P, hc0);
+        if (P.fast && s->costMap.p && !P.adaptiveFast) steer_long_ray_thresholds(s, P, hc0);
         F.tallyChunks = 0;
     }
-    if (F.endEarly) {   // (xrt_debug_end_counts: a frame that engaged has one chunk and its counters in `pinned`)
-        const int *hc = F.pinned.p + F.cntBase;
-        s->endCounts[0] = (unsigned long long)hc[F.cntStride + END_BY_RAYGEN] + F.endSkipped; s->endCounts[1] = (unsigned long long)hc[F.cntStride + END_BY_SHADE]; s->endCounts[2] = (unsigned long long)hc[F.cntStride + END_LISTED];
+    if (P.endEarly) {   // (xrt_debug_end_counts: a frame that engaged has one chunk and its counters in `pinned`)
+        s->endCounts[0] = (unsigned long long)hc0[P.cntStride + END_BY_RAYGEN] + P.endSkipped; s->endCounts[1] = (unsigned long long)hc0[P.cntStride + END_BY_SHADE]; s->endCounts[2] = (unsigned long long)hc0[P.cntStride + END_LISTED];
     } else s->endCounts[0] = s->endCounts[1] = s->endCounts[2] = 0;
     {
         float frameMs = 0;
@@ -1197,7 +1316,7 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
         std::memset(stats, 0, sizeof(*stats));
         unsigned long long hcnt[2 * C_COUNT];
         std::memcpy(hcnt, F.hcnt, sizeof(hcnt));
-        if (F.collect) {
+        if (P.collect) {
             // primary rays answered by k_raygen (they miss the scene root box): one query and one OSM:460 test each
             const unsigned long long culled = F.livePaths - F.live0;
             hcnt[C_RAYS] += culled;
@@ -1206,11 +1325,11 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
             std::memset(hcnt, 0, sizeof(hcnt));
             hcnt[C_RAYS] = F.livePaths + F.closestDeep;
             hcnt[C_HITS] = F.shaded;
-            hcnt[C_COUNT + C_RAYS] = F.shaded * (unsigned long long)F.nL;
+            hcnt[C_COUNT + C_RAYS] = F.shaded * (unsigned long long)P.nL;
         }
         fill_stats(stats, hcnt, F.shaded, F.validPixels);
         stats->rays_traversed = stats->rays_closest + stats->rays_shadow - (F.livePaths - F.live0) - F.answered;   // all but the primary rays k_raygen answered and the rays k_shade answered at emission
-        if (!F.collect) stats->algorithmic_bytes = 0;   // needs the counting pass
+        if (!P.collect) stats->algorithmic_bytes = 0;   // needs the counting pass
         float ms = 0;
         HIPCHECK(hipEventElapsedTime(&ms, F.events[0], F.events[1]));
         stats->ms_total = ms;
@@ -1502,7 +1621,7 @@ int multi_end(xrt_scene *s, int slot, int n, xrt_stats *stats, bool balance) {
     }
     if (rc == XRT_OK && balance && !s->frames[slot ^ 1].pending) {   // this frame's tile costs, all ranks: what the next frame's table is made from
         const xrt_scene::FrameCtx &F0 = s->frames[slot];
-        const int w = F0.frameW, h = F0.frameH;
+        const int w = F0.plan.g.width, h = F0.plan.g.height;
         const int tiles = ((w + XRT_TILE_W - 1) / XRT_TILE_W) * ((h + XRT_TILE_H - 1) / XRT_TILE_H);
         std::vector<float> cost((size_t)tiles, 0.0f);
         bool ok = w > 0 && h > 0;
@@ -1567,7 +1686,7 @@ int open_frame_impl(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_lig
     if (O.tail) {   // work enqueued behind the frame's own kernels: its end is an event of its own
         for (int j = 1; j < nParts; j++) {   // (the other half ends with an event on its last kernel)
             xrt_scene::FrameCtx &Fj = s->frames[slot + 2 * j];
-            HIPCHECK(hipStreamWaitEvent(st0, Fj.fast ? Fj.events[1] : Fj.done, 0));
+            HIPCHECK(hipStreamWaitEvent(st0, Fj.plan.fast ? Fj.events[1] : Fj.done, 0));
         }
         if (host_out && px) HIPCHECK(hipMemcpyAsync(host_out, d_out, px * sizeof(uint32_t), hipMemcpyDeviceToHost, st0));   // CurrentTarget.SetData (RT:123)
         if ((rc = s->tailDone[slot].create())) return rc;
