@@ -148,6 +148,27 @@ namespace RayTraceProject.Spatial
             Xrt.Check(Xrt.xrt_scene_set_materials(this.scene, ids, ids.Length, mats));
         }
 
+        // Triangle.n1..n3 / uv1..uv3 / color (Triangle.cs:17-23) between frames: a host that wrote these fields of mesh.Triangles[first .. first + count)
+        // -- scrolled UVs, painted colours, the highlight of the triangle a click hit (Game1.cs:296-325), a faded alpha -- calls this before the next
+        // RenderAsync (tickets may be open; nothing is rebuilt).  There is no change detection on public fields: nothing is pushed unless the host asks.
+        // surfaceNormal and the vertices are not settable this way: a mesh whose geometry changed is added again and built.
+        public void PushTriangleShading(Mesh mesh, int first, int count)
+        {
+            if (this.scene == IntPtr.Zero || count <= 0) return;
+            Triangle[] t = mesh.Triangles;
+            float[] n = new float[count * 9], uv = new float[count * 6], col = new float[count * 4];
+            for (int k = 0; k < count; k++)
+            {
+                int i = first + k;
+                Put3(n, k * 9, t[i].n1); Put3(n, k * 9 + 3, t[i].n2); Put3(n, k * 9 + 6, t[i].n3);
+                uv[k * 6] = t[i].uv1.X; uv[k * 6 + 1] = t[i].uv1.Y; uv[k * 6 + 2] = t[i].uv2.X; uv[k * 6 + 3] = t[i].uv2.Y;
+                uv[k * 6 + 4] = t[i].uv3.X; uv[k * 6 + 5] = t[i].uv3.Y;
+                col[k * 4] = t[i].color.X; col[k * 4 + 1] = t[i].color.Y; col[k * 4 + 2] = t[i].color.Z; col[k * 4 + 3] = t[i].color.W;
+            }
+            Xrt.Check(Xrt.xrt_scene_set_triangle_shading(this.scene, this.meshIds[mesh], null, first, count, n, uv, col));
+        }
+        public void PushTriangleShading(Mesh mesh) { PushTriangleShading(mesh, 0, mesh.Triangles.Length); }
+
         static void Put3(float[] a, int o, Vector3 p) { a[o] = p.X; a[o + 1] = p.Y; a[o + 2] = p.Z; }
 
         // Batched form used by a wavefront renderer.

@@ -155,6 +155,12 @@ namespace RayTraceProject.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_bodies(IntPtr scene, int nBodies, [In] int[] meshStart,
                                                                      [In] int[] meshIds, [In] float[] world, [In] float[] invWorld, [In] float[] bbox,
                                                                      [In] float[] worldBbox, int sceneThreshold, out int meshesBuilt);
+        // Triangle.n1..n3 / uv1..uv3 / color (Triangle.cs:17-23) between frames: entry i edits triangle triIds[i] of the mesh (triIds null: firstTri + i)
+        // with 9 + 6 + 4 floats; a null array leaves that field; also while RenderAsync tickets are open; surfaceNormal and vertices are not settable
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_triangle_shading(IntPtr scene, int meshId, [In] int[] triIds,
+                                                                     int firstTri, int n, [In] float[] normals, [In] float[] uv, [In] float[] color);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_triangle_shading_device(IntPtr scene, int meshId, IntPtr dTriIds,
+                                                                     int firstTri, int n, IntPtr dNormals, IntPtr dUv, IntPtr dColor, IntPtr stream);
         // can n_gpus > 1 load RCCL?  OK or E_RCCL (-6) with the loader's message; no device is touched
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_rccl_probe();
         // diagnostics of the split walks of long packets (results never depend on them): subtrees handed over, taken, packets split, packets written by a taker

@@ -565,6 +565,46 @@ int xrt_scene_set_bodies(xrt_scene *scene, int32_t n_bodies, const int32_t *mesh
                          const float *bbox /* 6 n */, const float *world_bbox /* 6 n */, int32_t scene_threshold,
                          int32_t *meshes_built_out /* nullable */);
 
+/* ---- changing triangle normals, texture coordinates and colours between frames: Triangle.n1..n3 / uv1..uv3 / color (TRI:17-23) ------
+ * Added within ABI 203: these two exports are additive; no existing struct, field or entry point changed.
+ * The reference's Triangle has public fields that CastRay reads at every hit: n1 / n2 / n3 for the fragment normal of an
+ * InterpolateNormals material (RT:520-524), uv1 / uv2 / uv3 for the texture lookup (RT:570-572, 713-715), color.XYZ for the surface
+ * colour of an untextured material (RT:578-580, 721-723) and color.W for the light a Transparent occluder lets through (RT:491) and the
+ * refraction blend (RT:699).  A host that scrolls a texture's coordinates, paints vertex colours, highlights the triangle a click hit
+ * (G1:296-325) or fades a glass body's alpha sees it in the next frame; no octree depends on these fields, so nothing is rebuilt.
+ * xrt_scene_set_triangle_shading is that, batched, for the triangles of one mesh:
+ *   - which triangles: entry i edits triangle tri_ids[i] of mesh mesh_id; indices are positions in Mesh.Triangles[], as in xrt_hit.tri.
+ *     With tri_ids == NULL entry i edits triangle first_tri + i; with tri_ids != NULL first_tri must be 0.
+ *   - which fields: an entry takes normals[9i..] (n1, n2, n3), uv[6i..] (uv1, uv2, uv3) and color[4i..], the layout of xrt_scene_add_mesh.
+ *     A NULL array leaves that field of every listed triangle as it is; all three NULL with n > 0 is XRT_E_INVALID_ARG.  Values are taken
+ *     bit for bit: NaN payloads, infinities and -0.0 are stored as given.
+ *   - never touched: Triangle.surfaceNormal and the vertices are NOT settable.  The culling test (RE:49) and every conservative
+ *     rejection of this library (normal boxes, tight boxes, runs, pre-cull records, answers at emission) are built on them; a host that
+ *     changes them adds the mesh again (xrt_scene_add_mesh) and builds.  Mesh octrees, runs, normal and tight boxes, poses, the scene
+ *     octree, materials, texels and tile tables are not touched either.
+ *   - errors: mesh_id out of range, n < 0, first_tri < 0, a range or an id outside [0, ntri), tri_ids != NULL with first_tri != 0:
+ *     XRT_E_INVALID_ARG.  A failing call applies nothing.  n == 0 does nothing and returns XRT_OK.  A triangle listed twice takes its
+ *     last entry.
+ *   - before the first xrt_scene_build the call edits what the build will use; on a host-only scene (device -1) the host copy is
+ *     edited and the call returns XRT_OK.
+ *   - xrt_scene_save writes the current values (the file format is unchanged), those set through the device variant included: they are
+ *     read back first.  Unlike device poses under xrt_scene_set_bodies, triangle values set on the device are never discarded: they
+ *     survive xrt_scene_build_tree and xrt_scene_set_bodies (also the call that builds new meshes), are present in the replicas of an
+ *     n_gpus > 1 render, and xrt_scene_build starts again from the host copy, which then holds them.
+ * xrt_scene_set_triangle_shading_device: the same with the arrays in HBM (each 16-byte aligned, else XRT_E_INVALID_ARG; each nullable as
+ * above).  They are read in order after the work already enqueued on `stream` (NULL: the scene's stream), and work enqueued on `stream`
+ * afterwards follows the update.  The ids are not inspected on the host: ids outside [0, ntri) are skipped, and the ids of one call
+ * must be distinct.  A host-only scene: XRT_E_NO_DEVICE; before xrt_scene_build: XRT_E_NOT_BUILT.
+ * Pipelining, exactly as xrt_scene_set_materials: the calls may be made while one or two begin/end tickets are open, and neither
+ * synchronise the device nor wait for the frames in flight.  A frame renders with the values set before its _begin, never with later
+ * ones; xrt_cast_rays* use the latest values; xrt_scene_intersect* and xrt_mesh_intersect are unaffected.  XRT_E_BUSY only while another
+ * thread is inside a render call on the scene. */
+int xrt_scene_set_triangle_shading(xrt_scene *scene, int32_t mesh_id, const int32_t *tri_ids /* nullable */, int32_t first_tri, int32_t n,
+                                   const float *normals /* nullable, 9 n */, const float *uv /* nullable, 6 n */,
+                                   const float *color /* nullable, 4 n */);
+int xrt_scene_set_triangle_shading_device(xrt_scene *scene, int32_t mesh_id, const void *d_tri_ids /* nullable */, int32_t first_tri, int32_t n,
+                                          const void *d_normals, const void *d_uv, const void *d_color /* each nullable */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

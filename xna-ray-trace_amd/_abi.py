@@ -151,6 +151,9 @@ SYMBOLS = {
     "xrt_scene_set_materials": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int32, _P(xrt_material)]),
     "xrt_scene_set_bodies": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_int32), _P(C.c_int32), _P(C.c_float), _P(C.c_float), _P(C.c_float),
                                        _P(C.c_float), C.c_int32, _P(C.c_int32)]),
+    "xrt_scene_set_triangle_shading": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_int32), C.c_int32, C.c_int32, _F, _F, _F]),
+    "xrt_scene_set_triangle_shading_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p]),
 }
 
 _lib = None

@@ -461,6 +461,74 @@ class OctreeSpatialManager(ISpatialManager):
         abi.check(abi.lib().xrt_scene_set_poses_device(self.handle, C.c_void_p(ids.data_ptr()), n, C.c_void_p(world.data_ptr()),
                                                        C.c_void_p(inv.data_ptr()), C.c_void_p(wbb.data_ptr()), C.c_void_p(s.cuda_stream)))
 
+    @staticmethod
+    def _tri_selection(tri_ids_or_range):
+        """(ids array or None, first, n) of a `range` with step 1 (triangles first .. first + n - 1) or a list of triangle ids."""
+        if isinstance(tri_ids_or_range, range):
+            r = tri_ids_or_range
+            if r.step != 1:
+                raise ValueError("SetTriangleShading: a range of triangles has step 1")
+            return None, int(r.start), len(r)
+        ids = np.ascontiguousarray(tri_ids_or_range, dtype=np.int32).reshape(-1)
+        return ids, 0, int(ids.shape[0])
+
+    def _mirror_triangle_shading(self, mesh_id, ids, first, n, normals, uv, color):
+        if not (0 <= mesh_id < len(self.meshes)):
+            return   # (a loaded scene: its geometry lives in the library alone)
+        d = self.meshes[mesh_id].data
+        sel = slice(first, first + n) if ids is None else np.asarray(ids, dtype=np.int64)
+        if ids is not None and np.unique(sel).size != sel.size:   # of a triangle listed twice the last entry counts
+            last = {int(t): i for i, t in enumerate(sel)}
+            keep = np.array(sorted(last.values()), dtype=np.int64)
+            sel = sel[keep]
+            normals, uv, color = (None if a is None else a[keep] for a in (normals, uv, color))
+        for have, new in ((d.n, normals), (d.uv, uv), (d.color, color)):
+            if new is not None:
+                have[sel] = new
+
+    def SetTriangleShading(self, mesh_id, tri_ids_or_range, normals=None, uv=None, color=None):
+        """xrt_scene_set_triangle_shading: Triangle.n1..n3 / uv1..uv3 / color (TRI:17-23) of the listed triangles of mesh `mesh_id` --
+        a `range` with step 1 or a list of triangle ids -- take normals[i] (3 x 3 floats), uv[i] (3 x 2) and color[i] (4); None leaves
+        a field as it is.  Nothing is rebuilt; surface normals and vertices are not settable.  The mirror's MeshData.n / uv / color are
+        updated too, so that a later from-scratch Build() and Save() agree.  There is NO implicit push: the mirror cannot see writes
+        into the numpy arrays of a MeshData, so a host that edits them calls this with the new values."""
+        ids, first, n = self._tri_selection(tri_ids_or_range)
+        arrs = []
+        for a, per, shape in ((normals, 9, (n, 3, 3)), (uv, 6, (n, 3, 2)), (color, 4, (n, 4))):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.size != per * n:
+                    raise ValueError("SetTriangleShading: 9 / 6 / 4 floats per triangle")
+                a = a.reshape(shape)
+            arrs.append(a)
+        abi.check(abi.lib().xrt_scene_set_triangle_shading(self.handle, int(mesh_id), None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                           first, n, *(None if a is None else _fp(a) for a in arrs)))
+        self._mirror_triangle_shading(int(mesh_id), ids, first, n, *arrs)
+
+    def SetTriangleShadingDevice(self, mesh_id, tri_ids_or_range, normals=None, uv=None, color=None, stream=None):
+        """xrt_scene_set_triangle_shading_device on CUDA tensors (a `range` with step 1 or an int32 tensor of DISTINCT ids; float32 normals
+        / uv / color with 9 / 6 / 4 values per entry, contiguous, None to leave a field), ordered after `stream` (a torch stream; default:
+        the current one).  Ids out of range are skipped.  The mirror's MeshData follows (one copy to the host)."""
+        import torch
+        if isinstance(tri_ids_or_range, range):
+            ids, (_, first, n) = None, self._tri_selection(tri_ids_or_range)
+        else:
+            ids, first, n = tri_ids_or_range, 0, tri_ids_or_range.numel()
+        for t, k, dt in ((ids, 1, torch.int32), (normals, 9, torch.float32), (uv, 6, torch.float32), (color, 4, torch.float32)):
+            if t is not None and (not t.is_cuda or not t.is_contiguous() or t.dtype != dt or t.numel() != k * n):
+                raise ValueError("SetTriangleShadingDevice: contiguous CUDA tensors, int32 ids and float32 values (9 + 6 + 4 per entry)")
+        some = next((t for t in (ids, normals, uv, color) if t is not None), None)
+        s = stream if stream is not None else torch.cuda.current_stream(some.device if some is not None else None)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        abi.check(abi.lib().xrt_scene_set_triangle_shading_device(self.handle, int(mesh_id), ptr(ids), first, n, ptr(normals), ptr(uv), ptr(color),
+                                                                  C.c_void_p(s.cuda_stream)))
+        if 0 <= mesh_id < len(self.meshes):
+            hids = np.arange(first, first + n, dtype=np.int64) if ids is None else ids.detach().cpu().numpy()
+            keep = (hids >= 0) & (hids < self.meshes[mesh_id].data.ntri)   # (the others are the entries the kernel skips)
+            host = lambda t, shape: None if t is None else t.detach().cpu().numpy().reshape(shape)[keep]
+            self._mirror_triangle_shading(int(mesh_id), hids[keep], 0, int(keep.sum()), host(normals, (n, 3, 3)), host(uv, (n, 3, 2)),
+                                          host(color, (n, 4)))
+
     def Save(self, path):
         """xrt_scene_save: the built scene's meshes, materials, texels and bodies as one file (the reference's .xnb content)."""
         self._push_materials()

@@ -281,6 +281,19 @@ struct PoseArgs {
 };
 void launch_pose(const PoseArgs &P, hipStream_t st);
 
+// xrt_scene_set_triangle_shading[_device]: entry i gives triangle ids[i] (ids null: first + i) of mesh `mesh` the normals normals[9i..], the
+// texture coordinates uv[6i..] and the colour color[4i..] (TRI:17-23), each as raw 32-bit words and each nullable: k_tri_shading writes only
+// the words of records 0..4 of `shade` (scene_host.h SHADE_F4) that the call gives; record 5 (the surface normal) and the material word of
+// record 4 are never written.  Ids outside [0, meshes[mesh].ntri) are skipped; the ids of one call must be distinct.
+struct TriShadingArgs {
+    const int *ids = nullptr;
+    int first = 0, n = 0, mesh = 0;
+    const uint32_t *normals = nullptr, *uv = nullptr, *color = nullptr;
+    const MeshRec *meshes = nullptr;
+    f4 *shade = nullptr;
+};
+void launch_tri_shading(const TriShadingArgs &T, hipStream_t st);
+
 // ---- RayTracer.points: the ray paths of xrt_cast_rays_paths (paths.hip; the order of the segments is paths.h's) --------------------------
 // Staging records of one chunk, addressed like the level records (node * P + path): hitRec = (world position of the node's hit, tag),
 // dirRec = (direction a refraction child was cast with, tag) -- ray trees only.  A record belongs to this attempt of the chunk when its

@@ -1601,4 +1601,37 @@ void launch_pose(const PoseArgs &P, hipStream_t st) {
     hipLaunchKernelGGL(k_pose, dim3(P.copyObjects ? 1 : (P.n + 255) / 256), dim3(256), 0, st, P);
 }
 
+// ---- triangle shading (xrt_scene_set_triangle_shading): one thread per (entry, f4 record 0..4) ------------------------------
+// Consecutive lanes write consecutive 16-byte records of `shade` when the ids are a range (five of a triangle's six: record 5 is never
+// written).  Every word is moved as 32 bits, so NaN payloads, infinities and -0.0 arrive as given.  Plain stores; no entry reads `shade`.
+__global__ __launch_bounds__(256) void k_tri_shading(TriShadingArgs T) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 5LL * T.n) return;   // (the tail block)
+    const long long i = t / 5;
+    const int r = (int)(t - 5 * i);
+    const MeshRec &m = T.meshes[T.mesh];
+    const long long id = T.ids ? (long long)T.ids[i] : (long long)T.first + i;
+    if (id < 0 || id >= (long long)m.ntri) return;
+    uint32_t *rec = reinterpret_cast<uint32_t *>(T.shade + (size_t)(m.triBase + id) * 6 + r);
+    if (r < 3) {          // (n_{r+1}.xyz, one word of uv1 / uv2.x)
+        if (T.normals && T.uv) {
+            const uint32_t *n = T.normals + 9 * i + 3 * r;
+            *reinterpret_cast<uint4 *>(rec) = make_uint4(n[0], n[1], n[2], T.uv[6 * i + r]);
+        } else if (T.normals) {
+            const uint32_t *n = T.normals + 9 * i + 3 * r;
+            rec[0] = n[0]; rec[1] = n[1]; rec[2] = n[2];
+        } else if (T.uv) rec[3] = T.uv[6 * i + r];
+    } else if (r == 3) {  // color.xyzw
+        if (T.color) *reinterpret_cast<uint4 *>(rec) = *reinterpret_cast<const uint4 *>(T.color + 4 * i);
+    } else if (T.uv) {    // (uv2.y, uv3.x, uv3.y); .w is the material
+        const uint32_t *u = T.uv + 6 * i + 3;
+        rec[0] = u[0]; rec[1] = u[1]; rec[2] = u[2];
+    }
+}
+void launch_tri_shading(const TriShadingArgs &T, hipStream_t st) {
+    if (T.n <= 0) return;
+    const long long blocks = (5LL * T.n + 255) / 256;
+    hipLaunchKernelGGL(k_tri_shading, dim3((unsigned)blocks), dim3(256), 0, st, T);
+}
+
 }  // namespace xrt

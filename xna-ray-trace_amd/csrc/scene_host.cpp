@@ -616,6 +616,47 @@ bool HostScene::set_materials(const int *ids, int n, const xrt_material *mats, M
     return true;
 }
 
+bool HostScene::set_triangle_shading(int mesh, const int *ids, int first, int n, const float *normals, const float *uv, const float *color, std::string &err) {
+    const std::string fn = "xrt_scene_set_triangle_shading: ";
+    if (mesh < 0 || mesh >= (int)meshes.size()) { err = fn + "mesh id " + std::to_string(mesh) + " out of range (" + std::to_string(meshes.size()) + " meshes)"; return false; }
+    if (n < 0 || first < 0) { err = fn + "negative count or first triangle"; return false; }
+    if (ids && first != 0) { err = fn + "first_tri must be 0 with a list of triangle ids"; return false; }
+    if (n > 0 && !normals && !uv && !color) { err = fn + "no field given"; return false; }
+    HostMesh &hm = meshes[(size_t)mesh];
+    if (!ids && (long long)first + n > (long long)hm.ntri) { err = fn + "triangles " + std::to_string(first) + " .. " + std::to_string((long long)first + n) + " outside the mesh's " + std::to_string(hm.ntri); return false; }
+    for (int i = 0; ids && i < n; i++)
+        if (ids[i] < 0 || ids[i] >= hm.ntri) { err = fn + "triangle id " + std::to_string(ids[i]) + " outside the mesh's " + std::to_string(hm.ntri); return false; }
+    // entries in the order given: a later entry of a triangle overwrites an earlier one
+    f4 *recs = mesh < builtMeshes ? arrays.shade.data() + (size_t)SHADE_F4 * (size_t)arrays.meshes[(size_t)mesh].triBase : nullptr;
+    for (int i = 0; i < n; i++) {
+        const size_t t = (size_t)(ids ? ids[i] : first + i);
+        if (normals) std::memcpy(&hm.n[9 * t], normals + 9 * (size_t)i, 36);
+        if (uv) std::memcpy(&hm.uv[6 * t], uv + 6 * (size_t)i, 24);
+        if (color) std::memcpy(&hm.color[4 * t], color + 4 * (size_t)i, 16);
+        if (!recs) continue;   // (the next build reads the mesh)
+        f4 *s = recs + SHADE_F4 * t;
+        if (normals) for (int k = 0; k < 3; k++) std::memcpy(&s[k], normals + 9 * (size_t)i + 3 * k, 12);
+        if (uv) {
+            for (int k = 0; k < 3; k++) std::memcpy(&s[k].w, uv + 6 * (size_t)i + k, 4);
+            std::memcpy(&s[4], uv + 6 * (size_t)i + 3, 12);
+        }
+        if (color) std::memcpy(&s[3], color + 4 * (size_t)i, 16);
+    }
+    return true;
+}
+
+void HostScene::take_triangle_shading(int mesh, const f4 *recs) {
+    HostMesh &hm = meshes[(size_t)mesh];
+    f4 *own = mesh < builtMeshes ? arrays.shade.data() + (size_t)SHADE_F4 * (size_t)arrays.meshes[(size_t)mesh].triBase : nullptr;
+    for (size_t t = 0; t < (size_t)hm.ntri; t++) {
+        const f4 *s = recs + SHADE_F4 * t;
+        for (int k = 0; k < 3; k++) { std::memcpy(&hm.n[9 * t + 3 * k], &s[k], 12); std::memcpy(&hm.uv[6 * t + k], &s[k].w, 4); }
+        std::memcpy(&hm.uv[6 * t + 3], &s[4], 12);
+        std::memcpy(&hm.color[4 * t], &s[3], 16);
+        if (own) { std::memcpy(own + SHADE_F4 * t, s, 4 * sizeof(f4)); std::memcpy(own + SHADE_F4 * t + 4, &s[4], 12); }
+    }
+}
+
 bool HostScene::build_tree(int sceneThreshold, std::string &err) {
     if (!built) { err = "xrt_scene_build_tree: call xrt_scene_build first"; return false; }
     if (sceneThreshold <= 0) sceneThreshold = 20;  // OSM:50

@@ -66,6 +66,15 @@ struct HostScene {
     // every offset may have moved).
     struct MaterialEdit { bool texels = false, texFull = false; size_t texLo = 0, texHi = 0; };
     bool set_materials(const int *ids, int n, const xrt_material *mats, MaterialEdit &edit, std::string &err);
+    // Triangle's public fields n1..n3, uv1..uv3 and color (TRI:17-23), batched (xrt.h xrt_scene_set_triangle_shading): entry i edits triangle
+    // ids[i] (ids null: first + i) of mesh `mesh`; a null array leaves its field alone.  Everything is checked before anything is applied; of
+    // a triangle listed twice the last entry counts.  The words are copied as bits.  Where `arrays` holds the mesh (it is among the built
+    // ones) the words of records 0..4 of arrays.shade that the call gives are written too, and nothing else of `arrays` is touched: no tree,
+    // box or run depends on these fields.
+    bool set_triangle_shading(int mesh, const int *ids, int first, int n, const float *normals, const float *uv, const float *color, std::string &err);
+    // ... and the reverse for a whole mesh out of `recs`, the mesh's SHADE_F4 * ntri records as a device version holds them (the values
+    // xrt_scene_set_triangle_shading_device left there): the mesh's n / uv / color and records 0..4 of arrays.shade.
+    void take_triangle_shading(int mesh, const f4 *recs);
     // OctreeSpatialManager.Bodies replaced and Build() run (xrt.h xrt_scene_set_bodies): the body list becomes the n bodies given, meshes added since
     // the last build get their MeshOctree.Build (meshesBuilt: how many), no other mesh is built again, and `arrays`, sceneTree and meshTrees end byte for
     // byte as build() leaves them for the same meshes and bodies.  Returns XRT_OK, XRT_E_NOT_BUILT (no build yet), XRT_E_INVALID_ARG (nothing was

@@ -117,6 +117,25 @@ struct xrt_scene {
     unsigned long long matSerial = 0;      // writes since the build
     Stream matStream;                      // (n_gpus > 1: the primary's copies run here when its replicas need the version before its own frame is enqueued)
     std::vector<DevBuf<uint32_t>> matRetired;   // arenas that were outgrown while a ticket was open: freed when none is (hipFree waits for the device)
+    // Triangle-shading versions (xrt_scene_set_triangle_shading), as the pose versions: a frame reads the `shade` array of ONE version, the one
+    // that was current at its begin (FrameCtx::shade).  Version 0 is `shade`; versions 1 and 2 are allocated when an update must not
+    // overwrite what an open ticket reads, and are brought up to date from the current version by a device-to-device copy first.  Every
+    // write runs on shadeStream, so the writes of all versions are ordered among themselves; readers wait for the version's event.
+    struct ShadeVer {
+        DevBuf<f4> shade;                  // (version 0: the scene's own `shade`)
+        Event ready;                       // recorded behind the version's last write; null while it holds the upload's records
+        unsigned long long serial = 0;     // which write it holds (a replica copies the primary's version when the serials differ)
+    } shadeVer[3];
+    int shadeCur = 0;                      // the version new frames and ray batches read
+    int slotShade[2] = {-1, -1};           // the version of the open ticket `slot`
+    unsigned long long shadeSerial = 0;    // writes since `shade` was uploaded
+    size_t shadeCount = 0;                 // records of every version: the size `shade` was uploaded with
+    bool shadeOnDevice = false;            // hs's n / uv / color are behind: an update came from device arrays (xrt_scene_set_triangle_shading_device)
+    Stream shadeStream;                    // the updates run here
+    Event shadeInput;                      // the caller's stream -> shadeStream
+    DevBuf<uint32_t> shadeIn;              // the host form's arrays on the device: ids | normals | uv | color, each part 16-byte aligned
+    Pinned<void> shadePinned;              // ... and their page-locked staging
+    Event shadeStaged;                     // the staging copy is done (the staging may be refilled)
     bool resident = false;
     int numCUs = 256;
     int stackNeeded = 2;
@@ -210,6 +229,7 @@ struct xrt_scene {
         std::vector<LightRec> hostLights;
         int pose = 0;                // the pose version the frame reads (xrt_scene::pose)
         int mat = 0;                 // the material version the frame reads (xrt_scene::mat)
+        int shade = 0;               // the triangle-shading version the frame reads (xrt_scene::shadeVer)
         bool pending = false;
         FramePlan plan;              // what frame_begin decided about the frame in flight (frame_plan.h): frame_finish and the ticket code read it
         bool redone = false;         // a frame that overflowed on the optimistic way and was rendered again

@@ -105,6 +105,21 @@ int mat_texel_room(xrt_scene *s, DevBuf<uint32_t> &b, size_t n) {
     return XRT_OK;
 }
 
+// ---- triangle-shading versions (xrt_scene_set_triangle_shading) ------------------------------------------------------------
+DevBuf<f4> &shade_records(xrt_scene *s, int v) { return v == 0 ? s->shade : s->shadeVer[v].shade; }
+// Work on `st` that reads version v starts after the version's last write (no event: the version holds what the upload left).
+int shade_wait(xrt_scene *s, int v, hipStream_t st) {
+    if (s->shadeVer[v].ready) HIPCHECK(hipStreamWaitEvent(st, s->shadeVer[v].ready, 0));
+    return XRT_OK;
+}
+bool shade_referenced(const xrt_scene *s, int v) { return s->slotShade[0] == v || s->slotShade[1] == v; }
+// The versions start again from version 0, which holds the host's records (scene->shade was just uploaded).
+void shade_restart(xrt_scene *scene) {
+    for (auto &v : scene->shadeVer) { v.ready.reset(); v.serial = 0; }
+    scene->shadeCur = 0; scene->shadeSerial = 0; scene->shadeOnDevice = false;
+    scene->shadeCount = scene->host->arrays.shade.size();
+}
+
 int persistent_grid(xrt_scene *s, long long nHost, int raysPerBlock = 256) {
     int full = s->numCUs * s->blocksPerCU;
     if (nHost >= 0) {
@@ -1129,7 +1144,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
             st = W.stream;
         } else st = s->stream;
     }
-    if ((rc = pose_wait(s, F.pose, st)) || (rc = mat_acquire(s, F.mat, st))) return rc;   // (the poses and materials set before the frame's begin)
+    if ((rc = pose_wait(s, F.pose, st)) || (rc = mat_acquire(s, F.mat, st)) || (rc = shade_wait(s, F.shade, st))) return rc;   // (the poses, materials and triangle values set before the frame's begin)
     if (freshPathRecs & 1u) HIPCHECK(hipMemsetAsync(s->pathHit.p, 0, s->pathHit.cap * sizeof(f4), st));
     if (freshPathRecs & 2u) HIPCHECK(hipMemsetAsync(s->pathDir.p, 0, s->pathDir.cap * sizeof(f4), st));
     unsigned *tileCostDev = nullptr;
@@ -1169,7 +1184,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         W.lightsDevPtr = W.lights.p;
     }
     ShadeView V;
-    V.shade = s->shade.p; V.materials = mat_records(s, F.mat).p; V.texels = mat_texels(s, F.mat).p; V.meshes = s->meshes.p;
+    V.shade = shade_records(s, F.shade).p; V.materials = mat_records(s, F.mat).p; V.texels = mat_texels(s, F.mat).p; V.meshes = s->meshes.p;
     V.lights = W.lights.p; V.nLights = nL; V.addressMode = P.addressMode; V.filtering = P.filtering;
     F.ev = 0;
     F.pairs.clear();
@@ -1382,6 +1397,9 @@ int ensure_replicas(xrt_scene *s, int n) {
         // ... and the host's materials: the primary's CURRENT version (scene_upload read the host arrays); every frame's version arrives by replica_material
         for (auto &v : r->mat) v.serial = ~0ull;
         if (s->matCur == 0) r->mat[0].serial = s->mat[0].serial;
+        // ... and the host's triangle values: the primary's version 0 only while none was set since `shade` was uploaded
+        for (auto &v : r->shadeVer) v.serial = ~0ull;
+        if (s->shadeSerial == 0) r->shadeVer[0].serial = 0;
         s->workers.emplace_back(new RankWorker(r->device));
         s->replicas.push_back(std::move(r));
     }
@@ -1461,6 +1479,24 @@ int replica_material(xrt_scene *s, xrt_scene *r, int v) {
     return XRT_OK;
 }
 
+// Replica r renders version v of the primary's triangle values: its `shade` array, copied when r's copy is of another write -- the route
+// replica_pose takes.
+int replica_triangle_shading(xrt_scene *s, xrt_scene *r, int v) {
+    xrt_scene::ShadeVer &P = s->shadeVer[v], &R = r->shadeVer[v];
+    if (R.serial == P.serial) return XRT_OK;
+    const size_t n = s->shadeCount;
+    int rc;
+    HIPCHECK(hipSetDevice(r->device));
+    if ((rc = shade_records(r, v).ensure(n))) return rc;
+    if (P.ready) HIPCHECK(hipStreamWaitEvent(r->stream, P.ready, 0));
+    if (r->device == s->device) HIPCHECK(hipMemcpyAsync(shade_records(r, v).p, shade_records(s, v).p, n * sizeof(f4), hipMemcpyDeviceToDevice, r->stream));
+    else HIPCHECK(hipMemcpyPeerAsync(shade_records(r, v).p, r->device, shade_records(s, v).p, s->device, n * sizeof(f4), r->stream));
+    if ((rc = R.ready.create())) return rc;
+    HIPCHECK(hipEventRecord(R.ready, r->stream));
+    R.serial = P.serial;
+    return XRT_OK;
+}
+
 // Frame `slot` on n devices: rank i renders the tiles t with t % n == i (its own frame context `slot`, its own stream, one
 // host thread per device so that frames which need host decisions between passes still run side by side), then ONE
 // grouped RCCL exchange moves the tile buffers to rank 0 -- the path's only exchange step -- and k_detile writes the
@@ -1515,7 +1551,8 @@ int multi_begin(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_light *
         if (s->cfg.fakeGpus && (rc = r->tilesReady[slot].create())) return rc;
     }
     for (int i = 1; i < n; i++)
-        if ((rc = replica_pose(s, rank_scene(s, i), s->slotPose[slot])) || (rc = replica_material(s, rank_scene(s, i), s->slotMat[slot]))) { (void)hipSetDevice(s->device); return rc; }
+        if ((rc = replica_pose(s, rank_scene(s, i), s->slotPose[slot])) || (rc = replica_material(s, rank_scene(s, i), s->slotMat[slot])) ||
+            (rc = replica_triangle_shading(s, rank_scene(s, i), s->slotShade[slot]))) { (void)hipSetDevice(s->device); return rc; }
     HIPCHECK(hipSetDevice(s->device));
     // every device's share is enqueued by its own (persistent) host thread
     std::vector<int> rcs((size_t)n, XRT_OK);
@@ -1528,6 +1565,7 @@ int multi_begin(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_light *
         uint32_t *dst = i == 0 ? s->gathered[slot].p : r->tileOut[slot].p;
         r->frames[slot].pose = s->slotPose[slot];   // (every rank renders the primary's versions)
         r->frames[slot].mat = s->slotMat[slot];
+        r->frames[slot].shade = s->slotShade[slot];
         rcs[(size_t)i] = frame_begin(r, r->frames[slot], cam, lights, nLights, &o, dst, nullptr, nullptr, 0, 1, false);   // (the gather is enqueued behind the frame: no redo)
         if (rcs[(size_t)i] != XRT_OK) errs[(size_t)i] = g_err;
     };
@@ -1657,11 +1695,12 @@ int open_frame_impl(xrt_scene *s, int slot, const xrt_camera *cam, const xrt_lig
     int nParts = 1;
     s->slotPose[slot] = s->poseCur;   // the frame renders the poses and materials set before its begin, whatever is set while it is open
     s->slotMat[slot] = s->matCur;
+    s->slotShade[slot] = s->shadeCur;
     struct PoseRelease {   // (an open that fails leaves no ticket)
         xrt_scene *s; int slot; bool keep = false;
-        ~PoseRelease() { if (!keep) s->slotPose[slot] = s->slotMat[slot] = -1; }
+        ~PoseRelease() { if (!keep) s->slotPose[slot] = s->slotMat[slot] = s->slotShade[slot] = -1; }
     } poseRelease{s, slot};
-    for (int j = 0; j < 4; j++) { s->frames[slot + 2 * j].pose = s->poseCur; s->frames[slot + 2 * j].mat = s->matCur; }
+    for (int j = 0; j < 4; j++) { s->frames[slot + 2 * j].pose = s->poseCur; s->frames[slot + 2 * j].mat = s->matCur; s->frames[slot + 2 * j].shade = s->shadeCur; }
     if (n == 1) {
         // Two halves on two streams?  Only plain single-pass frames that run long enough for the drain of their launches to
         // matter, on streams of the library's choosing; by default only when no other frame is in flight to fill the gaps.
@@ -1726,7 +1765,7 @@ int close_frame_impl(xrt_scene *s, int slot, xrt_stats *stats) {
         if (e != hipSuccess && rc == XRT_OK) rc = fail(XRT_E_HIP, "hipEventSynchronize: %s", hipGetErrorString(e));
     }
     O = xrt_scene::OpenFrame();
-    s->slotPose[slot] = s->slotMat[slot] = -1;
+    s->slotPose[slot] = s->slotMat[slot] = s->slotShade[slot] = -1;
     if (rc == XRT_OK) rc = guards_check("end of frame");
     return rc;
 }
@@ -1838,6 +1877,7 @@ int cast_rays_impl(xrt_scene *s, const xrt_ray *d_rays, int64_t n, int32_t itera
     xrt_scene::FrameCtx &F = s->frames[0];
     F.pose = s->poseCur;
     F.mat = s->matCur;   // (a ray batch reads the latest materials)
+    F.shade = s->shadeCur;   // (... and the latest triangle values)
     Range rf("xrt cast rays (%lld)", (long long)n);
     int rc = frame_begin(s, F, nullptr, lights, nLights, &o, d_out, d_outF32, st, 0, 1, false, &b);
     if (rc != XRT_OK) {
@@ -1943,6 +1983,7 @@ int scene_upload(xrt_scene *scene) {
         (rc = upload(scene->texels, A.texels)) || (rc = pose_upload(scene)))
         return rc;
     material_restart(scene);
+    shade_restart(scene);
     return scene_derive(scene);
 }
 
@@ -2058,6 +2099,64 @@ int pull_poses(xrt_scene *s) {
     return XRT_OK;
 }
 
+// Enqueue one update of triangle values: entries [0, n) of the device arrays (kernels.h TriShadingArgs; T.shade is set here), ready on `st`,
+// are written into the newest version.  The version written is the current one unless an open ticket reads it; then a free one, brought up
+// to date from the current one first by a device-to-device copy.  Nothing here waits for the device: copy and kernel run on shadeStream
+// behind `st` -- every write of every version runs there, so the copy follows the current version's last write --, and `st` continues
+// behind the update (the caller may refill its arrays there).  A version no open ticket reads has no reader left: a ticket's frame is
+// finished when it is closed, a ray batch before its call returns.  Caller holds apiMutex and the scene (BusyGuard).
+int shading_enqueue(xrt_scene *s, TriShadingArgs T, hipStream_t st) {
+    const int cur = s->shadeCur;
+    int v = cur;
+    if (shade_referenced(s, v))
+        for (int x = 0; x < 3; x++) if (x != cur && !shade_referenced(s, x)) { v = x; break; }
+    if (shade_referenced(s, v)) return fail(XRT_E_INTERNAL, "xrt_scene_set_triangle_shading: no free version");
+    xrt_scene::ShadeVer &P = s->shadeVer[v];
+    const size_t count = s->shadeCount;
+    int rc;
+    if ((rc = s->shadeStream.create()) || (rc = s->shadeInput.create())) return rc;
+    hipStream_t ps = s->shadeStream;
+    if (st != ps) {
+        HIPCHECK(hipEventRecord(s->shadeInput, st));
+        HIPCHECK(hipStreamWaitEvent(ps, s->shadeInput, 0));
+    }
+    if (v != cur) {
+        if ((rc = shade_records(s, v).ensure(count))) return rc;   // (versions 1 and 2 are allocated here, when they are first written; version 0 is the scene's own array)
+        HIPCHECK(hipMemcpyAsync(shade_records(s, v).p, shade_records(s, cur).p, count * sizeof(f4), hipMemcpyDeviceToDevice, ps));
+    }
+    T.shade = shade_records(s, v).p;
+    T.meshes = s->meshes.p;
+    launch_tri_shading(T, ps);
+    HIPCHECK(hipGetLastError());
+    if ((rc = P.ready.create())) return rc;
+    HIPCHECK(hipEventRecord(P.ready, ps));
+    if (st != ps) HIPCHECK(hipStreamWaitEvent(st, P.ready, 0));
+    P.serial = ++s->shadeSerial;
+    s->shadeCur = v;
+    return XRT_OK;
+}
+
+// hs's triangle values <- the device's current version (after xrt_scene_set_triangle_shading_device): what xrt_scene_save, xrt_scene_build and
+// the uploads of xrt_scene_set_bodies read.  The device holds the meshes `shade` was uploaded with; the host has had none removed since.
+int pull_shading(xrt_scene *s) {
+    if (!s->shadeOnDevice) return XRT_OK;
+    HIPCHECK(hipSetDevice(s->device));
+    if (s->shadeStream) HIPCHECK(hipStreamSynchronize(s->shadeStream));
+    const SceneArrays &A = s->hs.arrays;
+    const f4 *dev = shade_records(s, s->shadeCur).p;
+    std::vector<f4> recs;
+    for (int m = 0; m < s->hs.builtMeshes && m < (int)A.meshes.size(); m++) {
+        const size_t base = (size_t)SHADE_F4 * (size_t)A.meshes[(size_t)m].triBase, n = (size_t)SHADE_F4 * (size_t)A.meshes[(size_t)m].ntri;
+        if (base + n > s->shadeCount) break;   // (a mesh built after the upload: the device never held it)
+        if (n == 0) continue;
+        recs.resize(n);
+        HIPCHECK(hipMemcpy(recs.data(), dev + base, n * sizeof(f4), hipMemcpyDeviceToHost));
+        s->hs.take_triangle_shading(m, recs.data());
+    }
+    s->shadeOnDevice = false;
+    return XRT_OK;
+}
+
 }  // namespace
 
 // Every render entry point funnels through these two: no C++ exception (std::bad_alloc from a host-side vector, ...) crosses the C boundary.
@@ -2155,6 +2254,8 @@ int xrt_scene_build(xrt_scene *scene, int32_t mesh_threshold, int32_t scene_thre
     if (in_flight(scene)) return fail(XRT_E_BUSY, "scene is rendering");
     return guarded("xrt_scene_build", [&]() -> int {
         std::string err;
+        int rc;
+        if (scene->device >= 0 && (rc = pull_shading(scene))) return rc;   // (the build starts from the host copy: it holds the values set on the device)
         scene->resident = false;
         if (!scene->hs.build(mesh_threshold, scene_threshold, err)) return fail(XRT_E_UNSUPPORTED, "%s", err.c_str());
         scene->workers.clear();
@@ -2247,6 +2348,81 @@ int xrt_scene_set_materials(xrt_scene *scene, const int32_t *mesh_ids, int32_t n
     });
 }
 
+int xrt_scene_set_triangle_shading(xrt_scene *scene, int32_t mesh_id, const int32_t *tri_ids, int32_t first_tri, int32_t n, const float *normals,
+                                   const float *uv, const float *color) {
+    if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_scene_set_triangle_shading: null scene");
+    std::lock_guard<std::mutex> lock(scene->apiMutex);
+    BusyGuard guard(scene);
+    if (!guard.owned) return fail(XRT_E_BUSY, "xrt_scene_set_triangle_shading: another call is rendering on the scene");
+    return guarded("xrt_scene_set_triangle_shading", [&]() -> int {
+        // the host copy first (checked as a whole before anything is applied): save and the next build read it
+        std::string err;
+        if (!scene->hs.set_triangle_shading(mesh_id, tri_ids, first_tri, n, normals, uv, color, err)) return fail(XRT_E_INVALID_ARG, "%s", err.c_str());
+        if (n == 0 || !(scene->device >= 0 && scene->hs.built && scene->resident)) return XRT_OK;
+        HIPCHECK(hipSetDevice(scene->device));
+        // of a triangle listed twice the last entry counts: the kernel's ids must be distinct, so only that entry is staged
+        std::vector<int> order;
+        if (tri_ids) {
+            std::vector<int> last((size_t)scene->hs.meshes[(size_t)mesh_id].ntri, -1);
+            for (int i = 0; i < n; i++) last[(size_t)tri_ids[i]] = i;
+            for (int i = 0; i < n; i++) if (last[(size_t)tri_ids[i]] == i) order.push_back(i);
+        }
+        const size_t m = tri_ids ? order.size() : (size_t)n;
+        const bool whole = !tri_ids || m == (size_t)n;   // (no entry dropped: the arrays are staged as they are)
+        // staging: ids | normals | uv | color in page-locked memory, every part 16-byte aligned, one asynchronous copy to the device
+        auto pad = [](size_t w) { return (w + 3) / 4 * 4; };
+        const size_t wIds = tri_ids ? pad(m) : 0, wN = normals ? pad(9 * m) : 0, wUv = uv ? pad(6 * m) : 0, wC = color ? 4 * m : 0;
+        const size_t words = wIds + wN + wUv + wC;
+        if (scene->shadeStaged) HIPCHECK(hipEventSynchronize(scene->shadeStaged));   // (the previous update's copy)
+        int rc;
+        if ((rc = scene->shadePinned.ensure(words * 4, hipHostMallocDefault)) || (rc = scene->shadeIn.ensure(words))) return rc;
+        uint32_t *h = (uint32_t *)scene->shadePinned.p;
+        auto stage = [&](uint32_t *dst, const void *src, size_t per) {
+            if (whole) { std::memcpy(dst, src, m * per * 4); return; }
+            for (size_t k = 0; k < m; k++) std::memcpy(dst + per * k, (const uint32_t *)src + per * (size_t)order[k], per * 4);
+        };
+        if (tri_ids) stage(h, tri_ids, 1);
+        if (normals) stage(h + wIds, normals, 9);
+        if (uv) stage(h + wIds + wN, uv, 6);
+        if (color) stage(h + wIds + wN + wUv, color, 4);
+        if ((rc = scene->shadeStream.create()) || (rc = scene->shadeStaged.create())) return rc;
+        HIPCHECK(hipMemcpyAsync(scene->shadeIn.p, h, words * 4, hipMemcpyHostToDevice, scene->shadeStream));
+        HIPCHECK(hipEventRecord(scene->shadeStaged, scene->shadeStream));
+        const uint32_t *d = scene->shadeIn.p;
+        TriShadingArgs T;
+        T.ids = tri_ids ? (const int *)d : nullptr; T.first = first_tri; T.n = (int)m; T.mesh = mesh_id;
+        T.normals = normals ? d + wIds : nullptr; T.uv = uv ? d + wIds + wN : nullptr; T.color = color ? d + wIds + wN + wUv : nullptr;
+        return shading_enqueue(scene, T, scene->shadeStream);
+    });
+}
+
+int xrt_scene_set_triangle_shading_device(xrt_scene *scene, int32_t mesh_id, const void *d_tri_ids, int32_t first_tri, int32_t n, const void *d_normals,
+                                          const void *d_uv, const void *d_color, void *stream) {
+    const char *fn = "xrt_scene_set_triangle_shading_device";
+    if (!scene) return fail(XRT_E_INVALID_ARG, "%s: null scene", fn);
+    int rc = need_device(scene, fn);
+    if (rc != XRT_OK) return rc;
+    if (mesh_id < 0 || mesh_id >= (int)scene->hs.arrays.meshes.size() || mesh_id >= scene->hs.builtMeshes)
+        return fail(XRT_E_INVALID_ARG, "%s: mesh id %d out of range", fn, mesh_id);
+    if (n < 0 || first_tri < 0) return fail(XRT_E_INVALID_ARG, "%s: negative count or first triangle", fn);
+    if (d_tri_ids && first_tri != 0) return fail(XRT_E_INVALID_ARG, "%s: first_tri must be 0 with a list of triangle ids", fn);
+    if (n > 0 && !d_normals && !d_uv && !d_color) return fail(XRT_E_INVALID_ARG, "%s: no field given", fn);
+    if (((uintptr_t)d_tri_ids & 15) || ((uintptr_t)d_normals & 15) || ((uintptr_t)d_uv & 15) || ((uintptr_t)d_color & 15))
+        return fail(XRT_E_INVALID_ARG, "%s: device arrays must be 16-byte aligned", fn);
+    if (n == 0) return XRT_OK;
+    std::lock_guard<std::mutex> lock(scene->apiMutex);
+    BusyGuard guard(scene);
+    if (!guard.owned) return fail(XRT_E_BUSY, "%s: another call is rendering on the scene", fn);
+    return guarded(fn, [&]() -> int {
+        TriShadingArgs T;
+        T.ids = (const int *)d_tri_ids; T.first = first_tri; T.n = n; T.mesh = mesh_id;
+        T.normals = (const uint32_t *)d_normals; T.uv = (const uint32_t *)d_uv; T.color = (const uint32_t *)d_color;
+        if ((rc = shading_enqueue(scene, T, stream ? (hipStream_t)stream : scene->stream))) return rc;
+        scene->shadeOnDevice = true;
+        return XRT_OK;
+    });
+}
+
 int xrt_scene_build_tree(xrt_scene *scene, int32_t scene_threshold) {
     if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_scene_build_tree: null scene");
     if (in_flight(scene)) return fail(XRT_E_BUSY, "xrt_scene_build_tree: a frame is in flight");
@@ -2287,6 +2463,8 @@ int xrt_scene_set_bodies(xrt_scene *scene, int32_t n_bodies, const int32_t *mesh
         const bool current = scene->hs.built && scene->resident;
         std::string err;
         int built = 0;
+        // Triangle values set on the device are the scene's, not the old list's: read back before `shade` may be sent again.
+        if (scene->device >= 0) if (int prc = pull_shading(scene)) return prc;
         const int hrc = scene->hs.set_bodies(n_bodies, mesh_start, mesh_ids, world, inv_world, bbox, world_bbox, scene_threshold, built, err);
         if (hrc == XRT_E_INVALID_ARG || hrc == XRT_E_NOT_BUILT) return fail(hrc, "%s", err.c_str());   // (nothing was applied)
         scene->resident = false;
@@ -2335,6 +2513,11 @@ int xrt_scene_save(const xrt_scene *scene, const char *path) {
         if (s->device >= 0 && s->resident) {
             std::lock_guard<std::mutex> lock(s->apiMutex);
             int rc = pull_poses(s);
+            if (rc != XRT_OK) return rc;
+        }
+        if (s->device >= 0 && s->shadeOnDevice) {   // (... and the triangle values; they outlive `resident`)
+            std::lock_guard<std::mutex> lock(s->apiMutex);
+            int rc = pull_shading(s);
             if (rc != XRT_OK) return rc;
         }
         if (!scene->hs.save(path, err)) return fail(XRT_E_INVALID_ARG, "%s (%s)", err.c_str(), path);
