@@ -187,7 +187,7 @@ struct ShadeArgs {
     // hit / miss words of `hits` and `shadowHits` (IntersectArgs::flags): the 48-byte record of a miss does not exist
     const int *hitFlags = nullptr, *shadowFlags = nullptr;
     // Answered at emission (one-body scenes, plain frames): part A asks, for every ray it is about to emit, what the traversal kernel would ask
-    // first once it has the object-space ray -- do ALL the mesh's triangles face away from it (traverse.h all_back_facing on MeshRec::nbMin/nbMax)?
+    // first once it has the object-space ray -- do ALL the mesh's triangles face away from it (traverse.h mesh_faces_away on MeshRec::nbMin/nbMax/nbDiag)?
     // RE:48-51 then rejects every triangle, the query's answer is "no intersection", and the ray is not emitted: a shadow ray's hit / miss word is
     // written here (shadowFlagsOut), a reflection's level record too (the path ends, RT:729-733).  The rays that are left form COMPACT lists: shadow
     // rays at shadowRays[0 .. *shadowCnt) with shadowOut[i] = slot * nLights + light (where their answers go), reflections at nextRays[0 .. *nextCnt).

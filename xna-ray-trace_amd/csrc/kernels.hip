@@ -463,8 +463,8 @@ __device__ void count_mesh(const SceneView &S, const RayPre &r, int mesh, int ig
         }
     };
     if (mr.rootBlock < 0) { count_leaf(mr.rootRef, mr.rootCount, key); return; }
-    // (how many of the queries the reference walks below are answered by the mesh's normal box on this library: every triangle faces away)
-    if (all_back_facing(f4{mr.nbMin[0], mr.nbMin[1], mr.nbMin[2], mr.nbMin[3]}, f4{mr.nbMax[0], mr.nbMax[1], mr.nbMax[2], mr.nbMax[3]}, r.d)) c[C_MESH_AWAY]++;
+    // (how many of the queries the reference walks below are answered by the mesh's normal bounds on this library: every triangle faces away)
+    if (mesh_faces_away(mr, r.d)) c[C_MESH_AWAY]++;
     // explicit DFS over every child of every hit interior node (the reference does not prune): stack of
     // (block, pending mask) words plus the parent box per level
     struct Frame { int blk, mask; v3 bmin, half; };
@@ -923,14 +923,14 @@ __device__ __forceinline__ v3 lookup_uv(const ShadeView &V, const MaterialRec &M
 // CastRay's shading for one step of the wavefront.  After intersect launch #k two independent pieces of work exist and
 // ShadeArgs::ae: would the one body's one mesh answer this world-space ray "no intersection" because all its triangles face away from it?  The
 // object-space direction is formed exactly as the traversal kernels form it (traverse.h lane_begin, OSM:358-364), the test is theirs
-// (all_back_facing on the mesh's normal box, with its margin; a NaN anywhere makes it false: such a ray is traced).
+// (traverse.h mesh_faces_away: the mesh's normal box and its diagonal box, each with its margin; a NaN anywhere makes it false: such a ray is traced).
 __device__ __forceinline__ bool faces_away_single(const SceneView &S, v3 o, v3 d) {
     const ObjRec &ob = S.objects[0];
     const MeshRec &mr = S.meshes[0];
     const v3 v1 = transform(o, ob.invWorld);
     const v3 v2 = transform(add(o, d), ob.invWorld);
     const v3 dir = normalize(sub(v2, v1));
-    return all_back_facing(f4{mr.nbMin[0], mr.nbMin[1], mr.nbMin[2], mr.nbMin[3]}, f4{mr.nbMax[0], mr.nbMax[1], mr.nbMax[2], mr.nbMax[3]}, dir);
+    return mesh_faces_away(mr, dir);
 }
 
 // one kernel does both:

@@ -751,7 +751,7 @@ __global__ __launch_bounds__(256, (M == MODE_SCENE) ? PK_SCENE_WAVES : (PK_SINGL
             // leaf is k_intersect's business: packet_supported)
             // (S.nodeCull: 1 = packets of rays that leave a surface -- the shadow rays and reflections of a frame --, 2 = every packet)
             const bool nodeCull = S.nodeCull == 2 || (S.nodeCull == 1 && __any(valid && L.ignoreId >= 0));
-            const bool meshAway = nodeCull && all_back_facing(f4{mr.nbMin[0], mr.nbMin[1], mr.nbMin[2], mr.nbMin[3]}, f4{mr.nbMax[0], mr.nbMax[1], mr.nbMax[2], mr.nbMax[3]}, L.r.d);
+            const bool meshAway = nodeCull && mesh_faces_away(mr, L.r.d);
             unsigned long long lanes0 = mr.rootBlock < 0 ? 0ull : __ballot(valid && L.state == ST_NODE && L.mask != 0 && !meshAway);
             if (splitOn) {
                 if (item >= 0) {   // level 0 of the stack := the item; the lanes' answers so far := what its giver had (a pruning hint, and a candidate like any other)
@@ -932,7 +932,7 @@ __global__ __launch_bounds__(256, (M == MODE_SCENE) ? PK_SCENE_WAVES : (PK_SINGL
                                     }
                                 }
                             } else {
-                                const bool meshAway = nodeCull && all_back_facing(f4{mr.nbMin[0], mr.nbMin[1], mr.nbMin[2], mr.nbMin[3]}, f4{mr.nbMax[0], mr.nbMax[1], mr.nbMax[2], mr.nbMax[3]}, L.r.d);
+                                const bool meshAway = nodeCull && mesh_faces_away(mr, L.r.d);
                                 const unsigned long long lanes0 = __ballot(inRoot && !meshAway);
                                 if (lanes0 != 0ull)
                                     pk_walk<false, false>(pblocks, refT, lrec, S, A.cullMin, stk, lane, L, RC, fastL, rootBlock, lanes0, nodeCull, false);

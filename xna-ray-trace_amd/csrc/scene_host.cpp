@@ -182,6 +182,63 @@ static void append_material(SceneArrays &A, const HostMesh &m) {
     A.anyTexture = A.anyTexture || m.useTexture;
 }
 
+// The surface normals sn[3 * tris[i]] bounded in one DIAGONAL frame (traverse.h all_back_facing_diag): for each axis c, with a and b the axes that follow it
+// cyclically, the intervals of fl(N_a + N_b) and fl(N_a - N_b), each end moved one float outwards (a sum of two floats is off by at most half an ulp, so
+// the interval holds the real sums).  ONE axis is kept.  The rule: a fixed set of 256 directions spread evenly over the sphere is put to the exact bounds
+// (in double, no margin); the axis whose diagonal box answers the most directions that the axis-aligned box [nlo, nhi] does NOT answer wins, ties go to the
+// smaller (smax - smin) + (dmax - dmin), then to the lower axis.  Widths alone mislead: for a cone of normals about +y the frames about x and z have the
+// narrower s and d intervals and answer nothing the axis-aligned box does not, the frame about y answers more than a quarter of what is left.
+// Returns 1, 2, 3 = x, y, z and fills dg = (smin, smax, dmin, dmax), or 0: no frame can answer anything (or a normal is not finite).
+static int diagonal_normal_box(const float *sn, const int *tris, size_t n, const f4 &nlo, const f4 &nhi, f4 &dg) {
+    if (n == 0) return 0;
+    const float lo3[3] = {nlo.x, nlo.y, nlo.z}, hi3[3] = {nhi.x, nhi.y, nhi.z};
+    float box[3][4];
+    bool usable[3];
+    for (int c = 0; c < 3; c++) {
+        const int a = (c + 1) % 3, b = (c + 2) % 3;
+        float smin = FLT_MAX, smax = -FLT_MAX, dmin = FLT_MAX, dmax = -FLT_MAX;
+        bool finite = true;
+        for (size_t i = 0; i < n; i++) {
+            const float *N = sn + 3 * (size_t)tris[i];
+            const float s = N[a] + N[b], d = N[a] - N[b];
+            if (!(std::fabs(s) <= FLT_MAX && std::fabs(d) <= FLT_MAX)) { finite = false; break; }
+            smin = s < smin ? s : smin; smax = s > smax ? s : smax; dmin = d < dmin ? d : dmin; dmax = d > dmax ? d : dmax;
+        }
+        box[c][0] = std::nextafterf(smin, -INFINITY); box[c][1] = std::nextafterf(smax, INFINITY);
+        box[c][2] = std::nextafterf(dmin, -INFINITY); box[c][3] = std::nextafterf(dmax, INFINITY);
+        usable[c] = finite && std::fabs(box[c][0]) <= FLT_MAX && std::fabs(box[c][1]) <= FLT_MAX && std::fabs(box[c][2]) <= FLT_MAX && std::fabs(box[c][3]) <= FLT_MAX &&
+                    std::fabs(lo3[c]) <= FLT_MAX && std::fabs(hi3[c]) <= FLT_MAX;
+        // (a box whose three intervals all hold 0 answers nothing)
+        usable[c] = usable[c] && (box[c][0] > 0.0f || box[c][1] < 0.0f || box[c][2] > 0.0f || box[c][3] < 0.0f || lo3[c] > 0.0f || hi3[c] < 0.0f);
+    }
+    int gained[3] = {0, 0, 0};
+    const int K = 256;
+    for (int k = 0; k < K; k++) {   // a Fibonacci lattice on the sphere
+        const double y = 1.0 - (2.0 * k + 1.0) / K, r = std::sqrt(1.0 - y * y), phi = 2.399963229728653 * k;
+        const double D[3] = {r * std::cos(phi), y, r * std::sin(phi)};
+        double axisBound = 0.0;
+        for (int j = 0; j < 3; j++) axisBound += std::fmin((double)lo3[j] * D[j], (double)hi3[j] * D[j]);
+        if (axisBound > 0.0) continue;
+        for (int c = 0; c < 3; c++) {
+            if (!usable[c]) continue;
+            const int a = (c + 1) % 3, b = (c + 2) % 3;
+            const double p = D[a] + D[b], q = D[a] - D[b];
+            const double bound = std::fmin((double)lo3[c] * D[c], (double)hi3[c] * D[c]) + 0.5 * (std::fmin(box[c][0] * p, box[c][1] * p) + std::fmin(box[c][2] * q, box[c][3] * q));
+            if (bound > 0.0) gained[c]++;
+        }
+    }
+    int best = -1;
+    double bestWidth = 0.0;
+    for (int c = 0; c < 3; c++) {
+        if (!usable[c]) continue;
+        const double width = ((double)box[c][1] - box[c][0]) + ((double)box[c][3] - box[c][2]);
+        if (best < 0 || gained[c] > gained[best] || (gained[c] == gained[best] && width < bestWidth)) { best = c; bestWidth = width; }
+    }
+    if (best < 0) return 0;
+    dg = f4{box[best][0], box[best][1], box[best][2], box[best][3]};
+    return best + 1;
+}
+
 bool HostScene::build(int meshThreshold, int sceneThreshold, std::string &err) {
     if (meshThreshold <= 0) meshThreshold = 50;    // MO:42
     if (sceneThreshold <= 0) sceneThreshold = 20;  // OSM:50
@@ -394,7 +451,12 @@ bool HostScene::mesh_part(std::string &err) {
         mr.rootBlock = t.rootIsLeaf ? -1 : blockBase;
         mr.rootRef = refBase; mr.rootCount = t.rootIsLeaf ? t.rootCount : 0;
         mr.nbMin[0] = meshNBlo.x; mr.nbMin[1] = meshNBlo.y; mr.nbMin[2] = meshNBlo.z; mr.nbMin[3] = meshNBlo.w;
-        mr.nbMax[0] = meshNBhi.x; mr.nbMax[1] = meshNBhi.y; mr.nbMax[2] = meshNBhi.z; mr.nbMax[3] = meshNBhi.w;
+        mr.nbMax[0] = meshNBhi.x; mr.nbMax[1] = meshNBhi.y; mr.nbMax[2] = meshNBhi.z; mr.nbMax[3] = 0.0f;
+        if (meshNBlo.w == 0.0f) {   // ... and the same normals -- those of the leaf references, lr -- bounded in one diagonal frame
+            f4 dg;
+            const int axis = diagonal_normal_box(m.sn.data(), lr.data(), lr.size(), meshNBlo, meshNBhi, dg);
+            if (axis) { mr.nbMax[3] = (float)axis; mr.nbDiag[0] = dg.x; mr.nbDiag[1] = dg.y; mr.nbDiag[2] = dg.z; mr.nbDiag[3] = dg.w; }
+        }
         mr.triBase = triBase; mr.ntri = m.ntri; mr.material = (int)mi; mr.maxDepth = t.maxDepth; mr.dfsBase = blockBase * 8;
         A.meshes.push_back(mr);
         if (t.maxDepth > A.meshDepth) A.meshDepth = t.maxDepth;
@@ -627,6 +689,8 @@ bool HostScene::set_triangle_shading(int mesh, const int *ids, int first, int n,
     for (int i = 0; ids && i < n; i++)
         if (ids[i] < 0 || ids[i] >= hm.ntri) { err = fn + "triangle id " + std::to_string(ids[i]) + " outside the mesh's " + std::to_string(hm.ntri); return false; }
     // entries in the order given: a later entry of a triangle overwrites an earlier one
+    // (hm.sn -- the surface normals of RE:49, what refN, the node normal boxes and MeshRec's nbMin / nbMax / nbDiag are built from -- is not among the fields:
+    // every bound on the normals stays valid, no record of the octree changes)
     f4 *recs = mesh < builtMeshes ? arrays.shade.data() + (size_t)SHADE_F4 * (size_t)arrays.meshes[(size_t)mesh].triBase : nullptr;
     for (int i = 0; i < n; i++) {
         const size_t t = (size_t)(ids ? ids[i] : first + i);

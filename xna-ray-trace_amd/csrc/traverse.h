@@ -106,6 +106,7 @@ XRT_HD int node_dfs(const SceneView &S, int node) { return node < 0 ? 0 : S.chil
 
 XRT_HD void finish_mesh_query(Lane &L, int mode);
 XRT_HD bool all_back_facing(f4 nmin, f4 nmax, v3 d);
+XRT_HD bool mesh_faces_away(const MeshRec &mr, v3 d);
 
 // The eight children of block `blk`: descriptor into registers, every non-empty child pending.
 XRT_HD void load_block(Lane &L, const SceneView &S, int blk) {
@@ -235,7 +236,7 @@ XRT_HD void begin_mesh_query(Lane &L, const SceneView &S, int mesh, bool enter =
     if (!enter) { L.mask = 1; return; }   // (mask 1 tells the packet "inside the root box": a ray that misses it ends here with mask 0, MO:265)
     // every triangle of the mesh faces away from the ray (RE:48-51 would reject each one): the answer of MO:259 is "no intersection"
     if (S.nodeCull && (S.nodeCull == 2 || !L.spec) &&
-        all_back_facing(f4{mr.nbMin[0], mr.nbMin[1], mr.nbMin[2], mr.nbMin[3]}, f4{mr.nbMax[0], mr.nbMax[1], mr.nbMax[2], mr.nbMax[3]}, L.r.d)) return;
+        mesh_faces_away(mr, L.r.d)) return;
     L.bmin = mk(mr.rmin[0], mr.rmin[1], mr.rmin[2]);
     L.half = half_of(L.bmin, mk(mr.rmax[0], mr.rmax[1], mr.rmax[2]));
     load_block(L, S, mr.rootBlock);
@@ -443,6 +444,44 @@ XRT_HD bool all_back_facing(f4 nmin, f4 nmax, v3 d) {
     float lower = (lx + ly) + lz, scale_ = (sx + sy) + sz;
     return nmin.w == 0.0f && lower > 1e-5f * scale_ && scale_ < 3.0e38f && lower == lower && d.x == d.x && d.y == d.y && d.z == d.z;
 }
+
+// The same question asked in a DIAGONAL frame (DESIGN.md §3 "Normals bounded in a diagonal frame").  For an axis c with the other two axes a, b and
+// s = N_a + N_b, d = N_a - N_b, p = D_a + D_b, q = D_a - D_b:  N.D = N_c D_c + (s p + d q) / 2  in real numbers, so intervals of c, s and d over a set
+// of normals bound N.D from below like the box does -- without charging the box's corners that no normal of a cone reaches.  The record: the axis in
+// nmax.w (1, 2, 3 = x, y, z; 0: no record, the answer is false), the c interval is the box's own (nmin / nmax of that axis), dg = (smin, smax, dmin, dmax)
+// rounded OUTWARDS on the host, so they hold the real s and d of every normal.  Error budget, u = 2^-24: p and q are rounded once (u |p|, u |q|), each
+// product once more, the two sums once each: the evaluated bound is off by at most 4u S;  the reference's fl(N.D) by 3u sum|N_k D_k| <= 3u S, with
+//     S = |c|max |D_c| + (|s|max + |d|max) / 2 * (|D_a| + |D_b|)      (|N_a|, |N_b| <= (|s|max + |d|max) / 2;  |p|, |q| <= |D_a| + |D_b|).
+// The margin 2.5e-5 S is 60 x 7u S.  Unlike the box's bound this one is not monotone in the roundings, so products that underflow (absolute error
+// 2^-150 each, not relative) are kept out by S > 1e-30; an overflow of p or q makes S infinite or a NaN.  NaNs make the comparisons false (no skip).
+XRT_HD bool all_back_facing_diag(f4 nmin, f4 nmax, f4 dg, v3 d) {
+    const int ax = (int)nmax.w;
+    const float dc = ax == 1 ? d.x : (ax == 2 ? d.y : d.z), da = ax == 1 ? d.y : (ax == 2 ? d.z : d.x), db = ax == 1 ? d.z : (ax == 2 ? d.x : d.y);
+    const float clo = ax == 1 ? nmin.x : (ax == 2 ? nmin.y : nmin.z), chi = ax == 1 ? nmax.x : (ax == 2 ? nmax.y : nmax.z);
+    const float p = da + db, q = da - db;
+    const float lc = fminf(clo * dc, chi * dc), ls = fminf(dg.x * p, dg.y * p), ld = fminf(dg.z * q, dg.w * q);
+    const float lower = lc + 0.5f * (ls + ld);
+    const float half_ = 0.5f * (fmaxf(fabsf(dg.x), fabsf(dg.y)) + fmaxf(fabsf(dg.z), fabsf(dg.w)));
+    const float scale_ = fmaxf(fabsf(clo), fabsf(chi)) * fabsf(dc) + half_ * (fabsf(da) + fabsf(db));
+    return ax != 0 && nmin.w == 0.0f && lower > 2.5e-5f * scale_ && scale_ > 1e-30f && scale_ < 3.0e38f && lower == lower && d.x == d.x && d.y == d.y && d.z == d.z;
+}
+// Can the record ever answer?  Each of the three terms of either bound is <= 0 for every direction when its interval holds 0.
+XRT_HD bool normal_bounds_can_pass(f4 nmin, f4 nmax, f4 dg) {
+    const bool box = nmin.x > 0.0f || nmax.x < 0.0f || nmin.y > 0.0f || nmax.y < 0.0f || nmin.z > 0.0f || nmax.z < 0.0f;
+    const bool diag = nmax.w != 0.0f && (dg.x > 0.0f || dg.y < 0.0f || dg.z > 0.0f || dg.w < 0.0f);   // (its c interval is one of the box's)
+    return nmin.w == 0.0f && (box || diag);
+}
+
+// "Does the whole mesh face away from a ray of direction d (object space)?" -- the ONE place that decides it, for the walks (begin_mesh_query, packet.hip),
+// the emission test of k_shade (kernels.hip faces_away_single), the counting pass and, through mesh_can_face_away, the frame plan: the larger of the two
+// lower bounds decides, each against its own margin.
+XRT_HD f4 mesh_nb_min(const MeshRec &mr) { return f4{mr.nbMin[0], mr.nbMin[1], mr.nbMin[2], mr.nbMin[3]}; }
+XRT_HD f4 mesh_nb_max(const MeshRec &mr) { return f4{mr.nbMax[0], mr.nbMax[1], mr.nbMax[2], mr.nbMax[3]}; }
+XRT_HD f4 mesh_nb_diag(const MeshRec &mr) { return f4{mr.nbDiag[0], mr.nbDiag[1], mr.nbDiag[2], mr.nbDiag[3]}; }
+XRT_HD bool mesh_faces_away(const MeshRec &mr, v3 d) {
+    return all_back_facing(mesh_nb_min(mr), mesh_nb_max(mr), d) || all_back_facing_diag(mesh_nb_min(mr), mesh_nb_max(mr), mesh_nb_diag(mr), d);
+}
+XRT_HD bool mesh_can_face_away(const MeshRec &mr) { return normal_bounds_can_pass(mesh_nb_min(mr), mesh_nb_max(mr), mesh_nb_diag(mr)); }
 
 // ---- mesh level: one child of the current block (MO:328-353), front to back, with key pruning ------------------
 // Memory is touched only when a block is entered (descend) or re-entered (pop): 32 bytes of descriptor.

@@ -445,11 +445,10 @@ int plan_frame(const xrt_scene &s, int matVersion, const xrt_camera *cam, const 
         p.levelCap = (int)(s.cfg.adaptiveCap > 0 ? std::min(s.cfg.adaptiveCap, p.totalPixels) : p.totalPixels);   // (XRT_ADAPTIVE_CAP; deeper levels: one quadrant per pixel)
     }
     // Answered at emission (kernels.h ShadeArgs::ae): plain one-chunk frames of one-body scenes whose mesh CAN face away from a ray as a whole (its normal
-    // box does not hold the origin).  Not with the counting pass -- it counts the reference's work for every query from the ray lists --, not for ray trees.
+    // box or its diagonal box does not hold the origin: traverse.h mesh_can_face_away).  Not with the counting pass -- it counts the reference's work for every query from the ray lists --, not for ray trees.
     // (a batch of one chunk too: what part A answers depends on the hits alone, not on where generation 0 came from)
     if ((p.fast || (batch && oneChunk && !p.collect)) && !heap && !adaptive && nParts == 1 && s.sceneMode == MODE_SINGLE && s.view.nodeCull != 0 && s.cfg.answerAtEmission) {
-        const MeshRec &m0 = s.host->arrays.meshes[0];
-        p.ae = m0.nbMin[3] == 0.0f && (m0.nbMin[0] > 0.0f || m0.nbMax[0] < 0.0f || m0.nbMin[1] > 0.0f || m0.nbMax[1] < 0.0f || m0.nbMin[2] > 0.0f || m0.nbMax[2] < 0.0f);
+        p.ae = mesh_can_face_away(s.host->arrays.meshes[0]);   // (a fan of normals 50 degrees to either side of (1, 1, 0) holds 0 in every axis interval, not in that of N_x + N_y)
     }
     // Finished in part A (kernels.h ShadeArgs::finish): such a frame's hits whose shadow rays are all answered at emission take no slot.  Not with path capture --
     // k_paths_capture reads every hit's position from its slot record --, and the lights have to fit part A's bit mask.

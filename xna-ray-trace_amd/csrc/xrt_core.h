@@ -61,7 +61,7 @@ constexpr int ROOT_NODE = -1;
 //             performs per test)
 struct g3 { float x, y, z; };
 
-struct MeshRec {        // 112 B = seven f4
+struct MeshRec {        // 128 B = eight f4
     float bmin[3];      // Mesh.MeshBoundingBox (MESH:14, TMP:244-307)
     int   rootBlock;    // block of the root's children, or -1 when the root is a leaf
     float bmax[3];
@@ -76,6 +76,9 @@ struct MeshRec {        // 112 B = seven f4
     int   dfsBase;      // offset of this mesh's entries in childDfs (= rootBlock * 8 for interior roots)
     float nbMin[4];     // component-wise min / max of ALL the mesh's surface normals (nbMin[3] != 0: a NaN normal, never cull) -- the
     float nbMax[4];     // root's record of the node normal boxes (SceneView::leafNB holds the other nodes', interior ones included)
+    // ... and their bounds in ONE diagonal frame (traverse.h all_back_facing_diag): nbMax[3] = its axis c (1, 2, 3 = x, y, z; 0: none), with a, b the two
+    // axes that follow c cyclically nbDiag = (min, max of N_a + N_b, min, max of N_a - N_b), rounded outwards; the c interval is nbMin[c] .. nbMax[c]
+    float nbDiag[4];
 };
 
 struct ObjRec {         // 176 B
