@@ -177,6 +177,15 @@ namespace RayTraceProject.Spatial
             Xrt.Check(Xrt.xrt_scene_intersect(this.scene, rays, null, rays.Length, hits, IntPtr.Zero));
         }
 
+        // The colours of caller-chosen screen positions (centers: x0 y0 x1 y1 ..) -- GetColorForQuadrant / the body of Render's inner loop
+        // (RayTracer.cs:215-311, 412-425) for each, by the camera, lights and options of a frame: the rectangle an edit touched, a progressive
+        // preview's every 16th pixel, the pixel under the mouse.  colors[i] is the packed Color of entry i (Color.PackedValue).
+        public unsafe void RenderPixels(ref XrtCamera camera, XrtLight[] lights, ref XrtRenderOpts opts, float[] centers, uint[] colors)
+        {
+            fixed (uint* c = colors)
+                Xrt.Check(Xrt.xrt_render_pixels(this.scene, ref camera, lights, lights == null ? 0 : lights.Length, ref opts, centers, colors.Length, c, null, IntPtr.Zero));
+        }
+
         // The single-ray signature of the interface, forwarded as a batch of one (correct, slow: a P/Invoke plus a kernel
         // launch per ray; RayTracer.RenderInternal should call xrt_render instead, see INTEGRATION.md).
         public bool GetRayIntersection(ref Ray ray, out IntersectionResult? result, Triangle ignoreTriangle, Mesh ignoreObject)

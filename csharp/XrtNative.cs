@@ -161,6 +161,12 @@ namespace RayTraceProject.Native
                                                                      int firstTri, int n, [In] float[] normals, [In] float[] uv, [In] float[] color);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_triangle_shading_device(IntPtr scene, int meshId, IntPtr dTriIds,
                                                                      int firstTri, int n, IntPtr dNormals, IntPtr dUv, IntPtr dColor, IntPtr stream);
+        // GetColorForQuadrant / the body of Render's inner loop (RayTracer.cs:215-311, 412-425) on a list of screen positions (centers: x0 y0 x1 y1 ..): the colour
+        // of every entry in the caller's order, all three multisampling modes; an integer centre gets the frame's pixel bit for bit
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern unsafe int xrt_render_pixels(IntPtr scene, ref XrtCamera camera, XrtLight[] lights, int nLights,
+                                                                     ref XrtRenderOpts opts, [In] float[] centers, long n, uint* rgbaOut, float* rgbF32Out, IntPtr stats);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_render_pixels_device(IntPtr scene, ref XrtCamera camera, XrtLight[] lights, int nLights,
+                                                                     ref XrtRenderOpts opts, IntPtr dCenters, long n, IntPtr dRgbaOut, IntPtr dRgbF32Out, IntPtr stream, IntPtr stats);
         // can n_gpus > 1 load RCCL?  OK or E_RCCL (-6) with the loader's message; no device is touched
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_rccl_probe();
         // diagnostics of the split walks of long packets (results never depend on them): subtrees handed over, taken, packets split, packets written by a taker

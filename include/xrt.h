@@ -605,6 +605,52 @@ int xrt_scene_set_triangle_shading(xrt_scene *scene, int32_t mesh_id, const int3
 int xrt_scene_set_triangle_shading_device(xrt_scene *scene, int32_t mesh_id, const void *d_tri_ids /* nullable */, int32_t first_tri, int32_t n,
                                           const void *d_normals, const void *d_uv, const void *d_color /* each nullable */, void *stream);
 
+/* ---- seam 2 on caller-chosen pixels: GetColorForQuadrant (RT:215-311) and the body of Render's inner loop (RT:412-425), batched ---------
+ * Added within ABI 203: these two exports are additive; no existing struct, field or entry point changed.
+ * The reference's unit of work is smaller than a frame: both functions take a screen position and produce one colour.  xrt_render_pixels is
+ * that for a list: entry i has the centre (cx, cy) = (centers[2i], centers[2i + 1]) in the screen coordinates Viewport.Unproject is given
+ * (RT:415), and rgba_out[i] is its colour -- a screen rectangle after an edit, every 16th pixel of a preview, the pixel under the mouse, a
+ * random batch of a training step, a frame too large for its work buffers in chunks of the host's choosing.
+ *   - XRT_MS_OFF: RT:412-425 with screenSpaceCoord.X = cx, .Y = cy: two Unproject, subtract, normalise,
+ *     CastRay(ref ray, out color, 0, null, null, 1.0f).
+ *   - XRT_MS_ADAPTIVE: GetColorForQuadrant(cx, cy, 1.0f, 0, out result) with opts->multisample_quality (RT:195, RT:215-311, including
+ *     RT:305 writing urColor).
+ *   - XRT_MS_FIXED16: the 16 level-1 positions around (cx, cy), as a frame takes them around a pixel: (c + (+-0.25f)) + (+-0.125f) in this
+ *     association, corner q = s / 4 in UL, UR, LL, LR order, sub-sample s % 4 in the same order; the result is the RT:309 mean of four
+ *     RT:309 means, each re-quantised.
+ *   - any float centre is legal: fractional values and positions outside [0, vp_width) x [0, vp_height) are taken as Unproject takes them.
+ *     vp_width / vp_height enter only through Unproject: there is no frame size, no tile, no cull rectangle.  Duplicates are legal, every
+ *     entry gets its own answer; the order is the caller's.
+ *   - equality with frames: an entry whose centre is the integer pixel (x, y) of the viewport receives, bit for bit, what xrt_render writes
+ *     for that pixel, in rgba_out and in rgb_f32_out (nullable, 3 n; as for xrt_render: with XRT_MS_OFF the vector before packing, in the
+ *     supersampled modes ToVector3() of the final colour), in all three modes.
+ *   - opts: max_reflections, use_multisampling, multisample_quality, address_mode, filtering and collect_stats are read as for a frame;
+ *     shard_count and n_gpus must be 0 or 1 (XRT_E_INVALID_ARG).  The limits of frames apply with their codes: MultisampleQuality above 6
+ *     and Transparent materials above 12 reflections XRT_E_UNSUPPORTED, max_reflections above 64 XRT_E_INVALID_ARG.  Transparent materials
+ *     (ray trees) are supported, as xrt_cast_rays supports them.
+ *   - poses, materials and triangle values: the latest, as for xrt_cast_rays.
+ *   - errors: n < 0, a NULL array that is needed, a non-finite centre (host form; nothing is rendered): XRT_E_INVALID_ARG.  What is wrong
+ *     with the arguments alone is said first, also on a host-only scene; then n == 0 does nothing and returns XRT_OK; then XRT_E_NO_DEVICE /
+ *     XRT_E_NOT_BUILT, then XRT_E_BUSY under the rule of xrt_render (RT:62-63): while another call renders on the scene or a begin/end
+ *     ticket is open.
+ *   - stats_out (may be NULL): pixels = n; rays_closest, rays_shadow, hits_closest, shaded_hits and rays_traversed as a frame reports them
+ *     for the same work (every quadrant level of an adaptive list included); hits_shadow and the reference work counters with
+ *     collect_stats; ms_total, ms_intersect and intersect_launches summed over the passes of the call.
+ *   - a long list is split into chunks that fit a byte budget; nothing about the answers depends on the split.
+ * Blocking.  There is no begin/end form. */
+int xrt_render_pixels(xrt_scene *scene, const xrt_camera *camera, const xrt_light *lights, int32_t n_lights,
+                      const xrt_render_opts *opts, const float *centers /* 2 n: x0 y0 x1 y1 .. */, int64_t n,
+                      uint32_t *rgba_out /* n */, float *rgb_f32_out /* nullable, 3 n */, xrt_stats *stats_out /* nullable */);
+
+/* The same on HBM buffers (d_centers: 2 n floats, d_rgba_out: n words, d_rgb_f32_out: NULL or 3 n floats; each 16-byte aligned, else
+ * XRT_E_INVALID_ARG), enqueued on `stream` (a hipStream_t; NULL = the scene's stream) and complete when the call returns, like
+ * xrt_cast_rays_device (the stream is synchronised after every pass: the level counts of an adaptive list come back to the host between
+ * the levels).  The centres must be ready on `stream`.  They are not inspected: an entry with a non-finite centre gets an unspecified colour and
+ * affects no other entry. */
+int xrt_render_pixels_device(xrt_scene *scene, const xrt_camera *camera, const xrt_light *lights, int32_t n_lights,
+                             const xrt_render_opts *opts, const void *d_centers, int64_t n,
+                             void *d_rgba_out, void *d_rgb_f32_out /* nullable */, void *stream, xrt_stats *stats_out /* nullable */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -850,6 +850,36 @@ class RayTracer:
         begin.begin, begin.end = begin, end
         return begin
 
+    # ---- GetColorForQuadrant / the body of Render's inner loop (RT:215-311, 412-425) on caller-chosen pixels: xrt_render_pixels ----
+    def RenderPixels(self, centers, want_float=False, device=False, stream=None):
+        """The colour of every screen position of a list, by the tracer's camera, lights and options as in Render (all three multisampling
+        modes; an integer centre gets the frame's pixel bit for bit).  Host form: `centers` an (n, 2) float32 array -> uint32 colours (and
+        float32 (n, 3) with want_float).  device=True: `centers` a contiguous CUDA tensor of n float32 pairs -> torch tensors on its device
+        (int32 holding the packed colours; float32 (n, 3)), enqueued on `stream` (a torch stream, default: the current one)."""
+        cam, opts, lights = self._camera_abi(), self._opts_abi(shard_count=0), self._lights_abi()
+        opts.n_gpus = 0
+        st, lib = abi.xrt_stats(), abi.lib()
+        if device:
+            import torch
+            if centers.dtype != torch.float32 or not centers.is_contiguous() or centers.numel() % 2:
+                raise ValueError("centers: a contiguous float32 tensor of (x, y) pairs")
+            n = centers.numel() // 2
+            rgba = torch.empty(n, dtype=torch.int32, device=centers.device)
+            rgbf = torch.empty((n, 3), dtype=torch.float32, device=centers.device) if want_float else None
+            s = stream if stream is not None else torch.cuda.current_stream(centers.device)
+            abi.check(lib.xrt_render_pixels_device(self._scene_handle(), C.byref(cam), lights, len(self.Lights), C.byref(opts),
+                                                   C.c_void_p(centers.data_ptr()), n, C.c_void_p(rgba.data_ptr()),
+                                                   C.c_void_p(rgbf.data_ptr()) if want_float else None, C.c_void_p(s.cuda_stream), C.byref(st)))
+        else:
+            centers = np.ascontiguousarray(centers, dtype=np.float32).reshape(-1, 2)
+            n = centers.shape[0]
+            rgba = np.zeros(n, dtype=np.uint32)
+            rgbf = np.zeros((n, 3), dtype=np.float32) if want_float else None
+            abi.check(lib.xrt_render_pixels(self._scene_handle(), C.byref(cam), lights, len(self.Lights), C.byref(opts), _fp(centers), n,
+                                            rgba.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(rgbf) if want_float else None, C.byref(st)))
+        self.last_stats = st.as_dict()
+        return (rgba, rgbf) if want_float else rgba
+
     # ---- RayTracer.CastRay (RT:506-737) on caller-given rays: xrt_cast_rays, xrt_cast_rays_paths ----
     def CastRays(self, rays, iteration=0, currentRefIndex=1.0, want_float=False, device=False, stream=None, paths=False, vertex_capacity=None):
         """CastRay(ref rays[i], out color, iteration, origin_i, null, currentRefIndex) for every ray of a batch, origin_i = the ray's

@@ -173,6 +173,11 @@ struct xrt_scene {
     DevBuf<xrt_ray> pathBack;
     unsigned pathEpoch = 0;            // number of the last attempt of a chunk (the tag of its records; 0 is "never written")
     Pinned<long long> pathPinned;      // the batch's vertex count on its way to the host
+    // xrt_render_pixels (pixels.hip): the rays and the sample colours of one chunk of the centre list, and the host form's copy of the centres
+    // (its colours come back through castRGBA / castF32); the quadrant levels of an adaptive call are the call's own and freed when it returns
+    DevBuf<xrt_ray> pixelRays;
+    DevBuf<uint32_t> pixelSamples;
+    DevBuf<float> pixelCenters;
     DevBuf<unsigned> queues;
     DevBuf<uint32_t> outRGBA;
     DevBuf<float> outF32;

@@ -63,6 +63,7 @@ struct Settings {
     long long heapRayCap = HEAP_RAY_CAP;         // XRT_HEAP_RAY_CAP=<n> forces small ray buffers (tests of the overflow / retry path)
     long long shadowBytes = 8LL << 30;   // budget of a frame context's shadow rays / hits / words (XRT_SHADOW_BYTES): many lights shrink the chunk
     long long maxChunkPaths = MAX_CHUNK_PATHS;   // XRT_CHUNK_PATHS=<n> (multiple of 8192) forces smaller chunks (tests of the multi-chunk path)
+    long long pixelBytes = 4LL << 30;   // XRT_PIXEL_BYTES=<n>: byte budget of one chunk of an xrt_render_pixels list (pixels_plan.h; tests of the split)
     float overlapMinMs = 0.05f;  // frames at least this long run on per-context streams (XRT_OVERLAP_MS=0: every single-chunk frame gets its context's stream)
     // A launch of persistent waves leaves the machine half empty while its last rays finish; a blocking single frame (what the
     // C# host's RenderInternal asks for) has no other frame to fill the gaps, so it is rendered as two halves of its tiles on
@@ -148,6 +149,7 @@ inline Settings read_settings() {
     env_int("XRT_HEAP_RAY_CAP", c.heapRayCap, 1024, HEAP_RAY_CAP);
     env_int("XRT_SHADOW_BYTES", c.shadowBytes, 1LL << 20, LLONG_MAX);
     env_int("XRT_CHUNK_PATHS", c.maxChunkPaths, 8192, MAX_CHUNK_PATHS, 8192);
+    env_int("XRT_PIXEL_BYTES", c.pixelBytes, 1, LLONG_MAX);
     env_float("XRT_OVERLAP_MS", c.overlapMinMs);
     env_int("XRT_SPLIT", c.splitMode, 0, 2);
     env_int("XRT_SPLIT_PARTS", c.splitParts, 2, 4);

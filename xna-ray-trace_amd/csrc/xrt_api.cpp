@@ -18,6 +18,8 @@
 using namespace xrt;
 
 #include "scene_state.h"   // xrt_scene and its parts (global, as include/xrt.h declares it; its members' types are xrt's)
+#include "pixels.h"        // xrt_render_pixels: the list kernels (pixels.hip) ...
+#include "pixels_plan.h"   // ... and how a list is split into chunks
 
 namespace {
 
@@ -1886,6 +1888,149 @@ int cast_rays_impl(xrt_scene *s, const xrt_ray *d_rays, int64_t n, int32_t itera
     return frame_finish(s, F, stats);
 }
 
+// ---- xrt_render_pixels: GetColorForQuadrant / the body of Render's inner loop (RT:215-311, 412-425) on a caller's list of centres ----------
+// What is wrong with the arguments alone (the scene is not looked at): the codes of a frame for the fields a frame reads.
+int pixels_check_args(const char *fn, const xrt_camera *cam, const xrt_light *lights, int32_t nLights, const xrt_render_opts *opts, int64_t n) {
+    if (n < 0) return fail(XRT_E_INVALID_ARG, "%s: n = %lld out of range", fn, (long long)n);
+    if (!cam || !opts || (!lights && nLights > 0) || nLights < 0) return fail(XRT_E_INVALID_ARG, "%s: null argument", fn);
+    const int ms = opts->use_multisampling;
+    if (ms != XRT_MS_OFF && ms != XRT_MS_FIXED16 && ms != XRT_MS_ADAPTIVE) return fail(XRT_E_INVALID_ARG, "%s: use_multisampling", fn);
+    if (opts->shard_count < 0 || opts->shard_count > 1) return fail(XRT_E_INVALID_ARG, "%s: shard_count must be 0 or 1", fn);
+    if (opts->n_gpus < 0 || opts->n_gpus > 1) return fail(XRT_E_INVALID_ARG, "%s: n_gpus must be 0 or 1", fn);
+    if (opts->max_reflections < 0 || opts->max_reflections > 64) return fail(XRT_E_INVALID_ARG, "max_reflections out of range");
+    if (opts->address_mode < XRT_ADDRESS_CLAMP || opts->address_mode > XRT_ADDRESS_MIRROR)
+        return fail(XRT_E_INVALID_ARG, "Value does not fall within the expected range: addressMode (MAT:85)");
+    if (opts->filtering != XRT_FILTER_POINT && opts->filtering != XRT_FILTER_BILINEAR)
+        return fail(XRT_E_INVALID_ARG, "Value does not fall within the expected range: filtering (MAT:97)");
+    if (ms == XRT_MS_ADAPTIVE && (opts->multisample_quality < 0 || opts->multisample_quality > 6))
+        return fail(XRT_E_UNSUPPORTED, "MultisampleQuality above 6 (4^7 sub-quadrants per pixel)");
+    if (cam->vp_width <= 0 || cam->vp_height <= 0) return fail(XRT_E_INVALID_ARG, "viewport must be positive");
+    return XRT_OK;
+}
+
+// One call on n > 0 centres in HBM (interleaved x y).  Every ray goes through cast_rays_impl -- iteration 0, currentRefIndex 1.0f (RT:424), the
+// latest poses, materials and triangle values, plain or ray tree by the materials, its own chunking -- and every cast is complete when it
+// returns, so the level counts of an adaptive list are read back between the levels as adaptive_careful reads them.  The caller holds the scene.
+struct PixelsJob {
+    xrt_scene *s;
+    const xrt_light *lights;
+    int nL;
+    xrt_render_opts o;     // the options of every cast: one ray, one colour
+    RayGenParams g;        // camera part only (make_raygen without a root box: no cull rectangle)
+    hipStream_t st;
+    uint64_t budget;
+    xrt_stats acc;
+    bool any = false;
+
+    void tally(const xrt_stats &t) {   // counters and times add up over the casts of the call
+        uint64_t *a = reinterpret_cast<uint64_t *>(&acc);
+        const uint64_t *b = reinterpret_cast<const uint64_t *>(&t);
+        for (size_t k = 0; k < offsetof(xrt_stats, ms_total) / sizeof(uint64_t); k++) a[k] += b[k];
+        acc.ms_total += t.ms_total; acc.ms_intersect += t.ms_intersect;
+        acc.ms_intersect_longest = std::max(acc.ms_intersect_longest, t.ms_intersect_longest);
+        acc.intersect_launches += t.intersect_launches;
+        acc.rays_traversed += t.rays_traversed; acc.mesh_queries_facing_away += t.mesh_queries_facing_away;
+        any = true;
+    }
+    // The colours of entries [first, first + count) of a list, `samples` rays each: d_col[0 .. count * samples), d_f32 (nullable) likewise.
+    int cast(const float *cx, const float *cy, int stride, long long first, long long count, float size, int mode, uint32_t *d_col, float *d_f32) {
+        const int ms = mode == PIXEL_FIXED16 ? XRT_MS_FIXED16 : (mode == PIXEL_QUADRANT ? XRT_MS_ADAPTIVE : XRT_MS_OFF);
+        const long long samples = pixel_samples(ms);
+        const std::vector<long long> b = pixel_chunks(count, ms, 0, nL, budget);
+        for (size_t c = 0; c + 1 < b.size(); c++) {
+            const long long m = b[c + 1] - b[c], rays = m * samples;
+            int rc;
+            if ((rc = s->pixelRays.ensure((size_t)rays))) return rc;
+            launch_pixel_rays(g, cx, cy, stride, first + b[c], (int)m, size, mode, s->pixelRays.p, st);
+            HIPCHECK(hipGetLastError());
+            xrt_stats t;
+            if ((rc = cast_rays_impl(s, s->pixelRays.p, rays, 0, 1.0f, lights, nL, &o, d_col + b[c] * samples, d_f32 ? d_f32 + 3 * b[c] * samples : nullptr, st, &t)))
+                return rc;
+            tally(t);
+        }
+        return XRT_OK;
+    }
+    // RenderFirstPass / GetColorForQuadrant(cx, cy, 1.0f, 0) (RT:195, 215-311) for entries [first, first + m): level 0's quadrants are the
+    // entries, a level's quadrants each cast four rays, corners that deviate go to the next level, results fold back up (RT:305 slot rule:
+    // k_ms_fold as it is), and the level-0 quadrants are resolved in list order.
+    int adaptive(const float *centers, long long first, long long m, int quality, uint32_t *d_out, float *d_outF32) {
+        struct Level : xrt_scene::WorkBufs::Level { long long n = 0; };
+        std::vector<Level> lv((size_t)quality + 1);
+        DevBuf<int> levelCount;
+        int rc;
+        if ((rc = levelCount.ensure((size_t)quality + 1))) return rc;
+        HIPCHECK(hipMemsetAsync(levelCount.p, 0, ((size_t)quality + 1) * sizeof(int), st));
+        lv[0].n = m;
+        float size = 1.0f;   // RT:195
+        for (int l = 0; l <= quality; l++) {
+            Level &L = lv[l];
+            if (L.n == 0) break;
+            if (L.n > PIXEL_CHUNK_MAX_RAYS) return fail(XRT_E_UNSUPPORTED, "xrt_render_pixels: %lld quadrants at level %d of one chunk", L.n, l);
+            if ((rc = L.color.ensure((size_t)L.n * 4))) return rc;
+            const float *cx = l == 0 ? centers + 2 * first : L.cx.p, *cy = l == 0 ? cx + 1 : L.cy.p;
+            const int stride = l == 0 ? 2 : 1;
+            if ((rc = cast(cx, cy, stride, 0, L.n, size, PIXEL_QUADRANT, L.color.p, nullptr))) return rc;
+            if (l < quality) {   // RT:279-306
+                Level &N = lv[l + 1];
+                if ((rc = L.childBase.ensure((size_t)L.n)) || (rc = L.childMask.ensure((size_t)L.n)) || (rc = N.cx.ensure((size_t)L.n * 4)) || (rc = N.cy.ensure((size_t)L.n * 4)))
+                    return rc;
+                launch_pixel_decide(L.color.p, cx, cy, stride, (int)L.n, size, L.childBase.p, L.childMask.p, N.cx.p, N.cy.p, levelCount.p + l + 1, st);
+                HIPCHECK(hipGetLastError());
+                int hn = 0;
+                HIPCHECK(hipMemcpyAsync(&hn, levelCount.p + l + 1, sizeof(int), hipMemcpyDeviceToHost, st));
+                HIPCHECK(hipStreamSynchronize(st));
+                N.n = hn;
+                size = size / 2.0f;   // RT:290
+            }
+        }
+        for (int l = quality - 1; l >= 0; l--)
+            if (lv[l + 1].n > 0) launch_ms_fold(lv[l].color.p, lv[l + 1].color.p, lv[l].childBase.p, lv[l].childMask.p, (int)lv[l].n, st);
+        launch_pixel_resolve(lv[0].color.p, (int)m, PIXEL_QUADRANT, d_out + first, d_outF32 ? d_outF32 + 3 * first : nullptr, st);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(st));   // (the levels are freed on return)
+        return XRT_OK;
+    }
+    int run(const float *centers, int64_t n, uint32_t *d_out, float *d_outF32) {
+        const int ms = o.use_multisampling, quality = o.multisample_quality;
+        o.use_multisampling = XRT_MS_OFF; o.multisample_quality = 0;
+        if (ms == XRT_MS_OFF) return cast(centers, centers + 1, 2, 0, n, 1.0f, PIXEL_ONE, d_out, d_outF32);   // RT:412-425: the cast writes the caller's arrays
+        const std::vector<long long> b = pixel_chunks(n, ms, quality, nL, budget);
+        for (size_t c = 0; c + 1 < b.size(); c++) {
+            const long long first = b[c], m = b[c + 1] - b[c];
+            int rc;
+            if (ms == XRT_MS_ADAPTIVE) {
+                if ((rc = adaptive(centers, first, m, quality, d_out, d_outF32))) return rc;
+                continue;
+            }
+            if ((rc = s->pixelSamples.ensure((size_t)m * 16))) return rc;
+            if ((rc = cast(centers, centers + 1, 2, first, m, 1.0f, PIXEL_FIXED16, s->pixelSamples.p, nullptr))) return rc;
+            launch_pixel_resolve(s->pixelSamples.p, (int)m, PIXEL_FIXED16, d_out + first, d_outF32 ? d_outF32 + 3 * first : nullptr, st);
+            HIPCHECK(hipGetLastError());
+        }
+        return XRT_OK;
+    }
+};
+
+int render_pixels_impl(xrt_scene *s, const xrt_camera *cam, const xrt_light *lights, int32_t nLights, const xrt_render_opts *opts, const float *d_centers,
+                       int64_t n, uint32_t *d_out, float *d_outF32, hipStream_t st, xrt_stats *stats) {
+    PixelsJob J;
+    J.s = s; J.lights = lights; J.nL = nLights; J.st = st;
+    J.o = *opts;
+    J.o.shard_count = 0; J.o.shard_rank = 0; J.o.n_gpus = 0; J.o.balance_tiles = 0;
+    J.budget = (uint64_t)s->cfg.pixelBytes;
+    std::memset(&J.acc, 0, sizeof(J.acc));
+    if (int rc = make_raygen(cam, &J.o, J.g)) return rc;
+    Range rf("xrt render pixels");
+    int rc = J.run(d_centers, n, d_out, d_outF32);
+    if (rc == XRT_OK) HIPCHECK(hipStreamSynchronize(st));   // (the resolve of the last chunk)
+    if (stats) {
+        *stats = J.acc;
+        stats->pixels = (uint64_t)n;
+        stats->pieces = 1;
+    }
+    return rc;
+}
+
 int pose_upload(xrt_scene *scene);
 
 // What is made from the scene octree and the poses (snodes, srefs, objects, scull, the positions of every body's records in scull, the
@@ -2928,6 +3073,55 @@ int xrt_cast_rays_paths_device(xrt_scene *scene, const void *d_rays, int64_t n, 
             HIPCHECK(hipStreamSynchronize(st));
         }
         return guards_check("end of a ray batch");
+    });
+}
+
+int xrt_render_pixels(xrt_scene *scene, const xrt_camera *camera, const xrt_light *lights, int32_t n_lights, const xrt_render_opts *opts, const float *centers,
+                      int64_t n, uint32_t *rgba_out, float *rgb_f32_out, xrt_stats *stats_out) {
+    return guarded("xrt_render_pixels", [&]() -> int {
+        if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_render_pixels: null scene");
+        int rc;
+        if ((rc = pixels_check_args("xrt_render_pixels", camera, lights, n_lights, opts, n))) return rc;
+        if (n > 0 && (!centers || !rgba_out)) return fail(XRT_E_INVALID_ARG, "xrt_render_pixels: null argument");
+        for (int64_t i = 0; i < 2 * n; i++)
+            if (!std::isfinite(centers[i]))
+                return fail(XRT_E_INVALID_ARG, "xrt_render_pixels: centre %lld is not finite", (long long)(i / 2));
+        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+        if (n == 0) return XRT_OK;
+        if ((rc = need_device(scene, "xrt_render_pixels"))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        if ((rc = scene->pixelCenters.ensure((size_t)n * 2)) || (rc = scene->castRGBA.ensure((size_t)n)) || (rgb_f32_out && (rc = scene->castF32.ensure((size_t)n * 3)))) return rc;
+        HIPCHECK(hipMemcpyAsync(scene->pixelCenters.p, centers, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, scene->stream));
+        if ((rc = render_pixels_impl(scene, camera, lights, n_lights, opts, scene->pixelCenters.p, n, scene->castRGBA.p, rgb_f32_out ? scene->castF32.p : nullptr,
+                                     scene->stream, stats_out)))
+            return rc;
+        HIPCHECK(hipMemcpyAsync(rgba_out, scene->castRGBA.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, scene->stream));
+        if (rgb_f32_out) HIPCHECK(hipMemcpyAsync(rgb_f32_out, scene->castF32.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, scene->stream));
+        HIPCHECK(hipStreamSynchronize(scene->stream));
+        return guards_check("end of a pixel list");
+    });
+}
+
+int xrt_render_pixels_device(xrt_scene *scene, const xrt_camera *camera, const xrt_light *lights, int32_t n_lights, const xrt_render_opts *opts,
+                             const void *d_centers, int64_t n, void *d_rgba_out, void *d_rgb_f32_out, void *stream, xrt_stats *stats_out) {
+    return guarded("xrt_render_pixels_device", [&]() -> int {
+        if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_render_pixels_device: null scene");
+        int rc;
+        if ((rc = pixels_check_args("xrt_render_pixels_device", camera, lights, n_lights, opts, n))) return rc;
+        if (n > 0 && (!d_centers || !d_rgba_out)) return fail(XRT_E_INVALID_ARG, "xrt_render_pixels_device: null argument");
+        if (((uintptr_t)d_centers & 15) || ((uintptr_t)d_rgba_out & 15) || ((uintptr_t)d_rgb_f32_out & 15))
+            return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
+        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+        if (n == 0) return XRT_OK;
+        if ((rc = need_device(scene, "xrt_render_pixels_device"))) return rc;
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        hipStream_t st = (hipStream_t)stream;
+        if (!st) st = scene->stream;
+        if ((rc = render_pixels_impl(scene, camera, lights, n_lights, opts, (const float *)d_centers, n, (uint32_t *)d_rgba_out, (float *)d_rgb_f32_out, st, stats_out)))
+            return rc;
+        return guards_check("end of a pixel list");
     });
 }
 
