@@ -138,6 +138,12 @@ namespace RayTraceProject.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_cast_rays_paths_device(IntPtr scene, IntPtr dRays, long n, int iteration, float currentRefIndex,
                                                                       XrtLight[] lights, int nLights, ref XrtRenderOpts opts, IntPtr dRgbaOut, IntPtr dRgbF32Out, IntPtr dRaysBack,
                                                                       IntPtr dVertexStart, IntPtr dVertices, long vertexCapacity, IntPtr stream, out long nVerticesOut, IntPtr stats);
+        // what CastRay does with an IntersectionResult (RT:514-737) on caller-given hits: hits[i] stands for the query of rays[i] (RT:512), nothing is traced for the
+        // first level -- relighting or re-materialing a still whose hits are known (additive within ABI 203)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern unsafe int xrt_shade_hits(IntPtr scene, [In] XrtRay[] rays, [In] XrtHit[] hits, long n, int iteration, float currentRefIndex,
+                                                                      XrtLight[] lights, int nLights, ref XrtRenderOpts opts, uint* rgbaOut, float* rgbF32Out, IntPtr stats);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_shade_hits_device(IntPtr scene, IntPtr dRays, IntPtr dHits, long n, int iteration, float currentRefIndex,
+                                                                      XrtLight[] lights, int nLights, ref XrtRenderOpts opts, IntPtr dRgbaOut, IntPtr dRgbF32Out, IntPtr stream, IntPtr stats);
         // SceneObject.Position / Rotation / Scale (SO:51-88) between frames: the dirty bodies' World / InverseWorld / WorldBoundingBox
         // (16 + 16 + 6 floats per id), also while RenderAsync tickets are open; the scene octree stays until xrt_scene_build_tree
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_poses(IntPtr scene, [In] int[] objectIds, int n,

@@ -418,6 +418,48 @@ int xrt_cast_rays_device(xrt_scene *scene, const void *d_rays, int64_t n, int32_
                          const xrt_light *lights, int32_t n_lights, const xrt_render_opts *opts,
                          void *d_rgba_out, void *d_rgb_f32_out, void *stream, xrt_stats *stats_out /* nullable */);
 
+/* ---- seam 3 without its query: the part of CastRay that follows from an IntersectionResult (RT:514-737), on caller-given hits ----------
+ * Added within ABI 203: these two exports are additive; no existing struct, field or entry point changed.
+ * CastRay is a closest-hit query (RT:512) and then everything that follows from its result: fragment normal, shadow rays, the reflection
+ * and refraction recursion, texture lookup, the RGBA8 quantisation of every level.  xrt_scene_intersect is the first half alone and
+ * xrt_cast_rays the two in a row; xrt_shade_hits is the second half alone, for a host that already knows what its rays hit -- a still whose
+ * lights, materials or triangle values change from image to image (G1:152-190), or hits taken from a raster G-buffer.
+ * For every i: CastRay(ref rays[i], out color, iteration, origin, null, current_ref_index) with RT:512 replaced by "the query returned hits[i]":
+ *   hits[i].hit == 0: the query returned false, the path ends as a miss (RT:729-733).
+ *   otherwise result.mesh, .triangle, .u, .v, .worldPosition = mesh, tri, u, v, (wx, wy, wz), taken bit for bit (NaN, infinities, -0.0 as given).
+ * Of the ray CastRay reads Direction (RT:549 and the refraction).  What it does not read is accepted and ignored: the ray's origin,
+ * ignore_mesh / ignore_tri (the origin triangle only enters the query that is skipped), and of a hit d, leaf, reserved and object.  The host
+ * form still rejects, as a caller's mistake, an entry with hit != 0 whose mesh is not in [0, n_meshes), whose tri is not in [0, ntri(mesh)),
+ * whose object is not in [0, n_bodies) or whose mesh is not one of that body's meshes: XRT_E_INVALID_ARG, the message names the first
+ * offending index, nothing is rendered.
+ * Hence xrt_shade_hits(R, xrt_scene_intersect(R)) gives the rgba_out and rgb_f32_out of xrt_cast_rays(R) bit for bit for the same iteration,
+ * current_ref_index, lights and opts, and with xrt_generate_primary_rays and XRT_MS_OFF the frame of xrt_render.  Every level below the
+ * first is traced as xrt_cast_rays traces it.
+ * iteration, current_ref_index, lights, opts, the depth limits (above 64 generations XRT_E_INVALID_ARG, Transparent materials above 12
+ * XRT_E_UNSUPPORTED), the outputs, n == 0 (XRT_OK), blocking and XRT_E_BUSY: as for xrt_cast_rays, word for word.  Ray trees are supported;
+ * poses, materials and triangle values are the latest.  What is wrong with the arguments alone is said first, also on a host-only scene;
+ * then XRT_E_NO_DEVICE, XRT_E_NOT_BUILT, XRT_E_BUSY.
+ * stats_out (may be NULL): pixels = n.  The n skipped queries are not counted: rays_closest and hits_closest count the queries of the levels
+ * below the first (xrt_cast_rays' figures minus n, and minus the entries with hit != 0); rays_shadow and shaded_hits as for xrt_cast_rays;
+ * rays_traversed what was handed to the traversal kernels; with collect_stats the reference work counters cover the queries the call made.
+ * With n_lights == 0 and max_reflections <= iteration no traversal kernel is launched at all (intersect_launches == 0).
+ * There is no form that records ray paths and no begin / end form. */
+int xrt_shade_hits(xrt_scene *scene, const xrt_ray *rays, const xrt_hit *hits, int64_t n,
+                   int32_t iteration, float current_ref_index,
+                   const xrt_light *lights, int32_t n_lights, const xrt_render_opts *opts,
+                   uint32_t *rgba_out, float *rgb_f32_out /* nullable */, xrt_stats *stats_out /* nullable */);
+
+/* The same on HBM buffers (d_rays: n xrt_ray, d_hits: n xrt_hit, d_rgba_out: n words, d_rgb_f32_out: NULL or 3n floats; each 16-byte
+ * aligned, else XRT_E_INVALID_ARG), enqueued on `stream` (a hipStream_t; NULL = the scene's stream) and synchronised before it returns, like
+ * xrt_cast_rays_device.  Rays and hits must be ready on `stream`.  Nothing is inspected on the host and `object` is not looked at: the
+ * kernel range-checks mesh and tri of every entry, and an entry out of range is shaded as a miss -- it affects no other entry and can
+ * never address outside the scene's arrays. */
+int xrt_shade_hits_device(xrt_scene *scene, const void *d_rays, const void *d_hits, int64_t n,
+                          int32_t iteration, float current_ref_index,
+                          const xrt_light *lights, int32_t n_lights, const xrt_render_opts *opts,
+                          void *d_rgba_out, void *d_rgb_f32_out /* nullable */, void *stream,
+                          xrt_stats *stats_out /* nullable */);
+
 /* ---- seam 3, second half: RayTracer.points (RT:504, 543, 701, 740-747) and CastRay's `ref Ray ray` (RT:692-694) ---------------------
  * Added within ABI 203: one struct and two exports, additive; no existing struct, field or entry point changed.
  * Every CastRay appends line segments to the public list RayTracer.points -- the reference's host draws it over its preview (G1:403-413) --

@@ -969,6 +969,44 @@ class RayTracer:
             out = out + (vertices, vstart, back)
         return out if len(out) > 1 else out[0]
 
+    # ---- what CastRay does with an IntersectionResult (RT:514-737) on caller-given hits: xrt_shade_hits ----
+    def ShadeHits(self, rays, hits, iteration=0, currentRefIndex=1.0, want_float=False, device=False, stream=None):
+        """CastRay(ref rays[i], out color, iteration, origin, null, currentRefIndex) for every ray of a batch with its closest-hit query
+        (RT:512) replaced by "the query returned hits[i]": nothing is traced for the first level, everything below it is.  Host form:
+        `rays` an xrt_ray array (RAY_DTYPE), `hits` the structured array OctreeSpatialManager.IntersectBatch returns (HIT_DTYPE) -> uint32
+        colours (and float32 (n, 3) colour vectors with want_float).  device=True: `rays` a contiguous CUDA tensor of n 32-byte records
+        and `hits` one of n x 12 32-bit words on the same device -> torch tensors on it (int32 holding the packed colours; float32 (n, 3)),
+        enqueued on `stream` (a torch stream, default: the current one)."""
+        opts, lights = self._opts_abi(shard_count=0), self._lights_abi()
+        opts.n_gpus = 0
+        st, lib = abi.xrt_stats(), abi.lib()
+        if device:
+            import torch
+            if not rays.is_contiguous() or rays.numel() * rays.element_size() % 32:
+                raise ValueError("rays: a contiguous tensor of 32-byte xrt_ray records")
+            n = rays.numel() * rays.element_size() // 32
+            if not hits.is_contiguous() or hits.element_size() != 4 or hits.numel() != 12 * n or hits.device != rays.device:
+                raise ValueError("hits: a contiguous tensor of n x 12 32-bit words (xrt_hit records) on the rays' device")
+            rgba = torch.empty(n, dtype=torch.int32, device=rays.device)
+            rgbf = torch.empty((n, 3), dtype=torch.float32, device=rays.device) if want_float else None
+            s = stream if stream is not None else torch.cuda.current_stream(rays.device)
+            abi.check(lib.xrt_shade_hits_device(self._scene_handle(), C.c_void_p(rays.data_ptr()), C.c_void_p(hits.data_ptr()), n, int(iteration),
+                                                float(currentRefIndex), lights, len(self.Lights), C.byref(opts), C.c_void_p(rgba.data_ptr()),
+                                                C.c_void_p(rgbf.data_ptr()) if want_float else None, C.c_void_p(s.cuda_stream), C.byref(st)))
+        else:
+            rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+            hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+            n = rays.shape[0]
+            if hits.shape[0] != n:
+                raise ValueError("hits: one xrt_hit per ray")
+            rgba = np.zeros(n, dtype=np.uint32)
+            rgbf = np.zeros((n, 3), dtype=np.float32) if want_float else None
+            abi.check(lib.xrt_shade_hits(self._scene_handle(), rays.ctypes.data_as(C.POINTER(abi.xrt_ray)), hits.ctypes.data_as(C.POINTER(abi.xrt_hit)), n,
+                                         int(iteration), float(currentRefIndex), lights, len(self.Lights), C.byref(opts),
+                                         rgba.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(rgbf) if want_float else None, C.byref(st)))
+        self.last_stats = st.as_dict()
+        return (rgba, rgbf) if want_float else rgba
+
     def CastRay(self, ray, iteration=0, origin=None, currentRefIndex=1.0, want_float=False):
         """RT:506: one ray = (position, direction) -> the packed Color (and its float colour vector with want_float).  origin: the
         triangle the ray leaves, (mesh, index in Mesh.Triangles[]) as GetRayIntersection's ignoreTriangle, or None.

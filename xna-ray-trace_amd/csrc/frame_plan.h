@@ -20,6 +20,8 @@ struct BatchSrc {
         xrt_ray *raysBack = nullptr;
     };
     const Paths *paths = nullptr;
+    // xrt_shade_hits: the closest hits of the rays (n xrt_hit in HBM, 16-byte aligned) -- generation 0 is ingested from them and not traced -- or null
+    const xrt_hit *hits = nullptr;
 };
 
 constexpr int ADAPTIVE_LEVEL_WORDS = 16;   // adaptive frames in flight: words in front of the per-pass counters -- lvlCnt[0 .. quality], the overflow word at the end
@@ -47,6 +49,7 @@ struct FramePlan {
     bool adaptive = false;           // XRT_MS_ADAPTIVE
     int quality = 0;
     bool batch = false, capturePaths = false;   // the paths are a caller's rays (BatchSrc); ... and their ray paths are recorded
+    bool givenHits = false;          // ... and their closest hits are the caller's too (BatchSrc::hits): closest-hit launch #0 and its counting pass do not happen
     bool collect = false;            // the counting pass (xrt_render_opts.collect_stats)
     bool fast = false;               // nothing but kernels on the stream: counters come back with k_compose, the events ride on kernels
     bool heapFast = false;           // a ray-tree frame the optimistic way (fast)

@@ -164,6 +164,7 @@ struct xrt_scene {
     DevBuf<xrt_ray> castRays;     // xrt_cast_rays: the host's rays and their colours
     DevBuf<uint32_t> castRGBA;
     DevBuf<float> castF32;
+    DevBuf<xrt_hit> castHits;     // xrt_shade_hits: the host's hits (its rays and colours go through castRays / castRGBA / castF32)
     // xrt_cast_rays_paths (paths.hip): staging records of a chunk -- (hit position, tag) and (refraction direction, tag) per (node, path), allocated
     // only when a paths call is made --, the work arrays of the ordering pass, and the host form's copies of the caller's arrays
     DevBuf<f4> pathHit, pathDir;

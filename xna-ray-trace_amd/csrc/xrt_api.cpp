@@ -20,6 +20,7 @@ using namespace xrt;
 #include "scene_state.h"   // xrt_scene and its parts (global, as include/xrt.h declares it; its members' types are xrt's)
 #include "pixels.h"        // xrt_render_pixels: the list kernels (pixels.hip) ...
 #include "pixels_plan.h"   // ... and how a list is split into chunks
+#include "hits.h"          // xrt_shade_hits: generation 0 from a caller's hits (hits.hip)
 
 namespace {
 
@@ -320,6 +321,8 @@ int plan_frame(const xrt_scene &s, int matVersion, const xrt_camera *cam, const 
     if (adaptive && (p.quality < 0 || p.quality > 6)) return fail(XRT_E_UNSUPPORTED, "MultisampleQuality above 6 (4^7 sub-quadrants per pixel)");
     p.batch = batch != nullptr;
     p.capturePaths = batch && batch->paths;   // the pass also records its ray paths (paths.hip)
+    p.givenHits = batch && batch->hits;       // generation 0 arrives answered (hits.hip)
+    if (p.givenHits && p.capturePaths) return fail(XRT_E_INTERNAL, "a batch of given hits records no ray paths");
     p.collect = opts->collect_stats != 0;
     float rootBox[6] = {0, 0, 0, 0, 0, 0};
     const bool haveRoot = s.host->arrays.snodes.size() >= 2;
@@ -756,6 +759,15 @@ int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int P
         endArgs.list = W.composeList.p + 16; endArgs.cnt = listCnt; endArgs.listCap = (int)rayCap;
         endArgs.skipTiles = P.skipTiles ? 1 : 0;
     }
+    if (P.givenHits) {   // the caller's rays AND their closest hits: the live slots get ray, hit and hit word here, launch #0 below does not happen (hits.hip)
+        Range r("xrt ingest hits");
+        IngestHitsArgs G;
+        G.rays = batch->rays; G.hits = batch->hits; G.pathBase = pathBase; G.P = Pc;
+        G.raysOut = rays[0]; G.hitsOut = W.hits.p; G.flagsOut = W.hitFlags0.p; G.index = W.index0.p; G.count = cnt; G.lvlB0 = W.lvlB.p;
+        G.refOut = heap ? refOf[0] : nullptr; G.refIndex = batch->refIndex; G.liveCap = (int)rayCap;
+        launch_ingest_hits(S, G, st, startEvent ? e0 : nullptr);
+        startEvent = false;
+    } else
     { Range r("xrt raygen"); launch_raygen(gb, S, rays[0], W.lvlB.p, W.index0.p, cnt, Pc, pathBase, heavy_for(0, hcnt), st, startEvent ? e0 : nullptr, (int)rayCap, &endArgs); startEvent = false; }
     // (one buffer serves every generation: the closest-hit answers of launch #k are read by part A of k_shade #k alone -- part B works from the
     // slot records -- and launch #k+1 starts after it on the frame's stream)
@@ -767,6 +779,7 @@ int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int P
     for (int k = 0; k <= R + 1; k++) {
         const int cur = k & 1, prv = cur ^ 1;
         const bool hasClosest = k <= R, hasShadow = k >= 1 && nL > 0;
+        const bool traceClosest = hasClosest && !(k == 0 && P.givenHits);   // (given hits: generation 0 is shaded, never traced or counted)
         // a reflection chain keeps the ray of generation k at its parent's slot: their number is scnt[k-1]
         const int *nClosest = (k == 0 || heap || ae) ? cnt + k : scnt + (k - 1);   // (ae: the reflections that were emitted are a compact list, counted by part A)
         IntersectArgs C, B;   // closest-hit segment, shadow segment
@@ -783,7 +796,7 @@ int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int P
             set_knobs(*a, s);
         }
         // segments of coherent rays go to the wave-packet kernel, the others (together, one launch) to the per-lane kernel
-        const bool pkC = hasClosest && packet_closest(k), pkB = hasShadow && packet_shadow(k);
+        const bool pkC = traceClosest && packet_closest(k), pkB = hasShadow && packet_shadow(k);
         const Step T{gp, q, pathBase, k, k == 0 ? W.index0.p : paths[cur], slotOf[prv]};
         Range ri("xrt intersect #%d", k);
         // both populations of a step in ONE packet launch where both go to the packet kernel: one launch's tail instead of two
@@ -792,10 +805,10 @@ int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int P
             if (pkC && (rc = launch_packets(T, C, false, k == 0 ? Pc : hint(s->genRays, k)))) return rc;
             if (pkB && (rc = launch_packets(T, B, true, hint(s->genRays, k)))) return rc;
         }
-        const bool laneC = hasClosest && !pkC, laneB = hasShadow && !pkB;
+        const bool laneC = traceClosest && !pkC, laneB = hasShadow && !pkB;
         if ((laneC || laneB) && (rc = launch_lanes(T, laneC ? &C : nullptr, laneB ? &B : nullptr, Pc))) return rc;
         if ((hasClosest || hasShadow) && P.collect) {   // generation 0: the live list; culled rays are added in frame_finish
-            if (hasClosest) launch_count(S, C, s->counters.p, st);
+            if (traceClosest) launch_count(S, C, s->counters.p, st);
             if (hasShadow) launch_count(S, B, s->counters.p + C_COUNT, st);
         }
         if (ri.on) { roctx().pop(); ri.on = false; }
@@ -1334,17 +1347,17 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
         std::memcpy(hcnt, F.hcnt, sizeof(hcnt));
         if (P.collect) {
             // primary rays answered by k_raygen (they miss the scene root box): one query and one OSM:460 test each
-            const unsigned long long culled = F.livePaths - F.live0;
+            const unsigned long long culled = P.givenHits ? 0 : F.livePaths - F.live0;   // (given hits: generation 0 made no query)
             hcnt[C_RAYS] += culled;
             hcnt[C_SCENE_NODES] += culled;
         } else {
             std::memset(hcnt, 0, sizeof(hcnt));
-            hcnt[C_RAYS] = F.livePaths + F.closestDeep;
-            hcnt[C_HITS] = F.shaded;
+            hcnt[C_RAYS] = P.givenHits ? F.closestDeep : F.livePaths + F.closestDeep;   // (given hits: the queries of generation >= 1)
+            hcnt[C_HITS] = P.givenHits ? F.shaded - F.live0 : F.shaded;                 // (... and their hits: live0 = the entries that were shaded)
             hcnt[C_COUNT + C_RAYS] = F.shaded * (unsigned long long)P.nL;
         }
         fill_stats(stats, hcnt, F.shaded, F.validPixels);
-        stats->rays_traversed = stats->rays_closest + stats->rays_shadow - (F.livePaths - F.live0) - F.answered;   // all but the primary rays k_raygen answered and the rays k_shade answered at emission
+        stats->rays_traversed = stats->rays_closest + stats->rays_shadow - (P.givenHits ? 0 : F.livePaths - F.live0) - F.answered;   // all but the primary rays k_raygen answered and the rays k_shade answered at emission
         if (!P.collect) stats->algorithmic_bytes = 0;   // needs the counting pass
         float ms = 0;
         HIPCHECK(hipEventElapsedTime(&ms, F.events[0], F.events[1]));
@@ -1858,28 +1871,37 @@ int run_intersect(xrt_scene *s, const xrt_ray *d_rays, int64_t n, xrt_hit *d_hit
 
 // RayTracer.CastRay (RT:506-737) on n rays already in HBM: the pass of frame_begin with the batch as its ray source, MaxReflections - iteration
 // generations deep, then the pass's counters.  The caller holds the scene (BusyGuard, no frame in flight).
-int cast_rays_impl(xrt_scene *s, const xrt_ray *d_rays, int64_t n, int32_t iteration, float refIndex, const xrt_light *lights, int32_t nLights,
-                   const xrt_render_opts *opts, uint32_t *d_out, float *d_outF32, hipStream_t st, xrt_stats *stats, const BatchSrc::Paths *paths = nullptr) {
-    if (!opts) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: null opts");
-    if (opts->use_multisampling != XRT_MS_OFF) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: use_multisampling must be XRT_MS_OFF (one ray, one colour)");
-    if (opts->shard_count < 0 || opts->shard_count > 1) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: shard_count must be 0 or 1");
-    if (opts->n_gpus < 0 || opts->n_gpus > 1) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: n_gpus must be 0 or 1");
+// What is wrong with the opts of a ray batch alone (fn: the entry point the messages name).
+int batch_check_opts(const char *fn, const xrt_render_opts *opts, int32_t iteration) {
+    if (!opts) return fail(XRT_E_INVALID_ARG, "%s: null opts", fn);
+    if (opts->use_multisampling != XRT_MS_OFF) return fail(XRT_E_INVALID_ARG, "%s: use_multisampling must be XRT_MS_OFF (one ray, one colour)", fn);
+    if (opts->shard_count < 0 || opts->shard_count > 1) return fail(XRT_E_INVALID_ARG, "%s: shard_count must be 0 or 1", fn);
+    if (opts->n_gpus < 0 || opts->n_gpus > 1) return fail(XRT_E_INVALID_ARG, "%s: n_gpus must be 0 or 1", fn);
     if (opts->max_reflections < 0) return fail(XRT_E_INVALID_ARG, "max_reflections out of range");
     // CastRay(.., iteration, ..) reflects while iteration < MaxReflections (RT:545): a frame's recursion of max(0, M - iteration) generations
     const long long depth = std::max(0LL, (long long)opts->max_reflections - (long long)iteration);
-    if (depth > 64) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: max_reflections - iteration = %lld is above 64", depth);
+    if (depth > 64) return fail(XRT_E_INVALID_ARG, "%s: max_reflections - iteration = %lld is above 64", fn, depth);
+    return XRT_OK;
+}
+
+// (d_hits, xrt_shade_hits: the closest hits of the rays, n xrt_hit in HBM -- generation 0 is not traced)
+int cast_rays_impl(xrt_scene *s, const xrt_ray *d_rays, int64_t n, int32_t iteration, float refIndex, const xrt_light *lights, int32_t nLights,
+                   const xrt_render_opts *opts, uint32_t *d_out, float *d_outF32, hipStream_t st, xrt_stats *stats, const BatchSrc::Paths *paths = nullptr,
+                   const xrt_hit *d_hits = nullptr, const char *fn = "xrt_cast_rays") {
+    if (int rc = batch_check_opts(fn, opts, iteration)) return rc;
+    const long long depth = std::max(0LL, (long long)opts->max_reflections - (long long)iteration);
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (n == 0) return XRT_OK;
     xrt_render_opts o = *opts;
     o.max_reflections = (int32_t)depth;
     o.use_multisampling = XRT_MS_OFF; o.shard_count = 0; o.shard_rank = 0; o.n_gpus = 0; o.balance_tiles = 0;
     BatchSrc b;
-    b.rays = d_rays; b.n = n; b.refIndex = refIndex; b.paths = paths;
+    b.rays = d_rays; b.n = n; b.refIndex = refIndex; b.paths = paths; b.hits = d_hits;
     xrt_scene::FrameCtx &F = s->frames[0];
     F.pose = s->poseCur;
     F.mat = s->matCur;   // (a ray batch reads the latest materials)
     F.shade = s->shadeCur;   // (... and the latest triangle values)
-    Range rf("xrt cast rays (%lld)", (long long)n);
+    Range rf(d_hits ? "xrt shade hits (%lld)" : "xrt cast rays (%lld)", (long long)n);
     int rc = frame_begin(s, F, nullptr, lights, nLights, &o, d_out, d_outF32, st, 0, 1, false, &b);
     if (rc != XRT_OK) {
         if (F.pending) (void)frame_finish(s, F, nullptr);
@@ -2980,6 +3002,85 @@ int xrt_cast_rays_device(xrt_scene *scene, const void *d_rays, int64_t n, int32_
                                  (float *)d_rgb_f32_out, st, stats_out)))
             return rc;
         return guards_check("end of a ray batch");
+    });
+}
+
+// What is wrong with the arguments of xrt_shade_hits[_device] alone, in the order the header gives (the scene's device is not looked at).
+static int shade_hits_check_args(const char *fn, const xrt_scene *scene, const void *rays, const void *hits, int64_t n, int32_t iteration, const xrt_light *lights,
+                                 int32_t n_lights, const xrt_render_opts *opts, const void *rgba_out) {
+    if (!scene) return fail(XRT_E_INVALID_ARG, "%s: null scene", fn);
+    if (n < 0 || n > 0x7fffffff / 2) return fail(XRT_E_INVALID_ARG, "%s: n = %lld out of range", fn, (long long)n);
+    if (!opts || (n > 0 && (!rays || !hits || !rgba_out)) || (!lights && n_lights > 0) || n_lights < 0) return fail(XRT_E_INVALID_ARG, "%s: null argument", fn);
+    return batch_check_opts(fn, opts, iteration);
+}
+// ... and with its lights, once there is something to shade (n > 0)
+static int shade_hits_check_lights(const xrt_light *lights, int32_t n_lights) {
+    for (int i = 0; i < n_lights; i++)
+        if (lights[i].kind != XRT_LIGHT_SPOT && lights[i].kind != XRT_LIGHT_DIRECTIONAL) return fail(XRT_E_INVALID_ARG, "unknown light kind");
+    return XRT_OK;
+}
+
+int xrt_shade_hits(xrt_scene *scene, const xrt_ray *rays, const xrt_hit *hits, int64_t n, int32_t iteration, float current_ref_index, const xrt_light *lights,
+                   int32_t n_lights, const xrt_render_opts *opts, uint32_t *rgba_out, float *rgb_f32_out, xrt_stats *stats_out) {
+    return guarded("xrt_shade_hits", [&]() -> int {
+        int rc;
+        if ((rc = shade_hits_check_args("xrt_shade_hits", scene, rays, hits, n, iteration, lights, n_lights, opts, rgba_out))) return rc;
+        // a hit names a triangle of a mesh of a body of the scene, as the query would have (the lists as they were added: known on a host-only scene too)
+        const auto &meshes = scene->host->meshes;
+        const auto &bodies = scene->host->objects;
+        for (int64_t i = 0; i < n; i++) {
+            const xrt_hit &h = hits[i];
+            if (h.hit == 0) continue;
+            if (h.mesh < 0 || h.mesh >= (int)meshes.size())
+                return fail(XRT_E_INVALID_ARG, "xrt_shade_hits: hit %lld names mesh %d, which does not exist", (long long)i, h.mesh);
+            if (h.tri < 0 || h.tri >= meshes[(size_t)h.mesh].ntri)
+                return fail(XRT_E_INVALID_ARG, "xrt_shade_hits: hit %lld names triangle %d of mesh %d, which does not exist", (long long)i, h.tri, h.mesh);
+            if (h.object < 0 || h.object >= (int)bodies.size())
+                return fail(XRT_E_INVALID_ARG, "xrt_shade_hits: hit %lld names body %d, which does not exist", (long long)i, h.object);
+            const std::vector<int> &bm = bodies[(size_t)h.object].meshes;
+            if (std::find(bm.begin(), bm.end(), h.mesh) == bm.end())
+                return fail(XRT_E_INVALID_ARG, "xrt_shade_hits: hit %lld names mesh %d, which is not a mesh of body %d", (long long)i, h.mesh, h.object);
+        }
+        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+        if (n == 0) return XRT_OK;
+        if ((rc = shade_hits_check_lights(lights, n_lights))) return rc;
+        if ((rc = need_device(scene, "xrt_shade_hits"))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        if ((rc = scene->castRays.ensure((size_t)n)) || (rc = scene->castHits.ensure((size_t)n)) || (rc = scene->castRGBA.ensure((size_t)n)) ||
+            (rgb_f32_out && (rc = scene->castF32.ensure((size_t)n * 3))))
+            return rc;
+        HIPCHECK(hipMemcpyAsync(scene->castRays.p, rays, (size_t)n * sizeof(xrt_ray), hipMemcpyHostToDevice, scene->stream));
+        HIPCHECK(hipMemcpyAsync(scene->castHits.p, hits, (size_t)n * sizeof(xrt_hit), hipMemcpyHostToDevice, scene->stream));
+        if ((rc = cast_rays_impl(scene, scene->castRays.p, n, iteration, current_ref_index, lights, n_lights, opts, scene->castRGBA.p,
+                                 rgb_f32_out ? scene->castF32.p : nullptr, scene->stream, stats_out, nullptr, scene->castHits.p, "xrt_shade_hits")))
+            return rc;
+        HIPCHECK(hipMemcpyAsync(rgba_out, scene->castRGBA.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, scene->stream));
+        if (rgb_f32_out) HIPCHECK(hipMemcpyAsync(rgb_f32_out, scene->castF32.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, scene->stream));
+        HIPCHECK(hipStreamSynchronize(scene->stream));
+        return guards_check("end of a batch of hits");
+    });
+}
+
+int xrt_shade_hits_device(xrt_scene *scene, const void *d_rays, const void *d_hits, int64_t n, int32_t iteration, float current_ref_index, const xrt_light *lights,
+                          int32_t n_lights, const xrt_render_opts *opts, void *d_rgba_out, void *d_rgb_f32_out, void *stream, xrt_stats *stats_out) {
+    return guarded("xrt_shade_hits_device", [&]() -> int {
+        int rc;
+        if ((rc = shade_hits_check_args("xrt_shade_hits_device", scene, d_rays, d_hits, n, iteration, lights, n_lights, opts, d_rgba_out))) return rc;
+        if (((uintptr_t)d_rays & 15) || ((uintptr_t)d_hits & 15) || ((uintptr_t)d_rgba_out & 15) || ((uintptr_t)d_rgb_f32_out & 15))
+            return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
+        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+        if (n == 0) return XRT_OK;
+        if ((rc = shade_hits_check_lights(lights, n_lights))) return rc;
+        if ((rc = need_device(scene, "xrt_shade_hits_device"))) return rc;
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        hipStream_t st = (hipStream_t)stream;
+        if (!st) st = scene->stream;
+        if ((rc = cast_rays_impl(scene, (const xrt_ray *)d_rays, n, iteration, current_ref_index, lights, n_lights, opts, (uint32_t *)d_rgba_out,
+                                 (float *)d_rgb_f32_out, st, stats_out, nullptr, (const xrt_hit *)d_hits, "xrt_shade_hits_device")))
+            return rc;
+        return guards_check("end of a batch of hits");
     });
 }
 
