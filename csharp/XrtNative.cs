@@ -179,6 +179,9 @@ namespace RayTraceProject.Native
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_split_stats(IntPtr scene, [Out] ulong[] out4, int reset);
         // diagnostics of "end early" (results never depend on it): the last frame's paths coloured by the ray generation kernel, by the shading kernel, left to the compose list
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_debug_end_counts(IntPtr scene, [Out] ulong[] out3);
+        // diagnostics of the primary packets (results never depend on them): the last one-chunk frame's packet table (first slot, rays per packet) and its live list
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_debug_packet_table(IntPtr scene, [Out] ulong[] counts2, [Out] uint[] entriesOut, long entriesCap,
+                                                                     [Out] int[] pathsOut, long pathsCap);
 
         // error convention of the reference: InvalidOperationException when busy (RayTracer.cs:26-27,62-63),
         // ArgumentException for bad arguments (SceneObject.cs:123-124, Material.cs:85,97)

@@ -381,6 +381,14 @@ int xrt_split_stats(xrt_scene *scene, uint64_t out[4], int32_t reset);
  * only, on this way as on every other. */
 int xrt_debug_end_counts(xrt_scene *scene, uint64_t out[3]);
 
+/* Diagnostics of the primary packets (testing aid; XRT_PK_QUADS, results never depend on it).  The ray generation kernel compacts a frame's live primary
+ * rays into slots 0 .. live-1 and, where the packet kernel traces them, writes a table beside them: one entry (first slot, rays) per aligned unit of 64
+ * places of the frame that has a live ray; a packet of the first traversal launch is one entry.  For the last finished frame of the scene, if it had
+ * one chunk: counts[0] entries of the table, counts[1] live primary rays; up to entries_cap entries go to entries_out (two words each: first slot,
+ * rays) and up to paths_cap words of the live list -- the path of the frame whose ray sits in slot j -- to paths_out (either may be null with a capacity
+ * of 0).  counts[0] == 0: the frame's first launch took no table (another kernel, a batch, an adaptive frame, XRT_PK_QUADS=0). */
+int xrt_debug_packet_table(xrt_scene *scene, uint64_t counts[2], uint32_t *entries_out, int64_t entries_cap, int32_t *paths_out, int64_t paths_cap);
+
 /* RayTracer.Progress (RT:43-46): fraction of the frame's ray generations completed; callable from
  * another thread during xrt_render. */
 float xrt_progress(const xrt_scene *scene);

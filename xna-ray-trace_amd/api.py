@@ -566,6 +566,17 @@ class OctreeSpatialManager(ISpatialManager):
         abi.check(abi.lib().xrt_debug_end_counts(self.handle, out))
         return tuple(int(x) for x in out)
 
+    def PacketTable(self):
+        """xrt_debug_packet_table: the last finished one-chunk frame's packet table, an (entries, 2) array of (first slot, rays), and its live list, the
+        path of the ray in every slot (no entries: the frame's first traversal launch took no table)."""
+        counts = (C.c_uint64 * 2)()
+        abi.check(abi.lib().xrt_debug_packet_table(self.handle, counts, None, 0, None, 0))
+        entries = np.zeros((int(counts[0]), 2), dtype=np.uint32)
+        paths = np.zeros(int(counts[1]), dtype=np.int32)
+        abi.check(abi.lib().xrt_debug_packet_table(self.handle, counts, entries.ctypes.data_as(C.POINTER(C.c_uint32)), entries.shape[0],
+                                                   paths.ctypes.data_as(C.POINTER(C.c_int32)), paths.shape[0]))
+        return entries, paths
+
     def IntersectBatch(self, rays, stats=False):
         """Batched ISpatialManager.GetRayIntersection (ISM:15): xrt_ray array -> xrt_hit array."""
         rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)

@@ -67,6 +67,7 @@ struct FramePlan {
     bool tileCosts = false;          // packets add their ticks to the scene's tile costs
     bool useStamps = false;          // traversal launches time themselves on the device clock
     int pkMask = 0;                  // which ray populations take the packet kernel
+    size_t pkEntries = 0;            // entries of the packet table of the primary rays (kernels.h QuadTable): one per 64 places of a chunk's generation-0 walk; 0: launch #0 takes no table
     bool ownStream = false;          // no stream given and the frame is worth the context's own
     int cntBase = 0, levelCap = 0;   // adaptive in flight: words in front of the per-pass counters in `pinned`; quadrant capacity of a deeper level
 };

@@ -118,7 +118,26 @@ struct PacketArgs {
     // the far siblings of a ray that is about to find a near hit would have been pruned; and a cost in TICKS is contagious: the speculative work slows every packet,
     // more of them count as long.  profiles/r04/split_walks.txt.)
     unsigned *splitCost = nullptr;   // (splitLong, splitBudgetLong: above, behind `flags`)
+    // The packets of the FIRST segment as their producer formed them (QuadTable, k_raygen): packet pk is the rays pkTable[pk].x .. + pkTable[pk].y - 1 (1 .. 64 of
+    // them) and there are min(*pkCount, pkCap) packets.  Null: packet pk is the rays 64 pk .. 64 pk + 63.  (The fields sit at the end: every other one keeps its offset.)
+    const uint2 *pkTable = nullptr;
+    const unsigned *pkCount = nullptr;
+    int pkCap = 0;
 };
+// The packet table of a frame's primary rays.  A wave of k_raygen holds 64 consecutive, 64-aligned places of the walk: one aligned unit of the screen (a 2x2
+// pixel quad x 16 samples, a 4x4 block x 4 samples, an 8x8 block at one sample -- xrt_core.h tile_slot_xy is Z-order).  The live rays are compacted densely, so 64
+// consecutive SLOTS are the tail of one unit and the head of the next as soon as one unit is partly dead; k_raygen therefore writes, for every wave and round
+// with a live ray, the entry (first slot, live rays) and launch #0 of k_packet takes its packets from the entries.  Entries are reserved like the slots (once
+// per block and group: the lane next to the one that reserves the slots, in the same atomic instruction, on a word with a 256-byte line of its own) and are in
+// ascending place order inside a group.
+// The count words alternate from chunk to chunk: k_raygen counts into `count` and clears `clear`, the word of the chunk before the last -- nobody else ever clears
+// them, so the count of the last chunk stays readable when its frame is over (xrt_debug_packet_table).
+struct QuadTable {
+    uint2 *table = nullptr;      // null: off
+    unsigned *count = nullptr, *clear = nullptr;
+    int cap = 0;                 // entries the table has room for: one per 64 places of the walk
+};
+constexpr int QUAD_HEAD_WORDS = 128;   // the two count words, 256 bytes apart, in front of the entries of a context's table
 constexpr int PACKET_QUEUE_HEADS = 8, PACKET_HEAD_STRIDE = 64;   // every head on a 256-byte line of its own: atomics on one line serialise whatever the word
 constexpr int PACKET_SPLIT_WORDS = 320;                          // ... and behind the heads the lines of the split-walk counters (PacketArgs::splitCtl: 9 x 128 bytes, aligned)
 constexpr int PACKET_QUEUE_WORDS = PACKET_QUEUE_HEADS * PACKET_HEAD_STRIDE + PACKET_SPLIT_WORDS;
@@ -209,7 +228,8 @@ void launch_intersect(const SceneView &S, const IntersectArgs &A, int stackNeede
 int  intersect_blocks_per_cu(int stackNeeded, int mode);
 void launch_count(const SceneView &S, const IntersectArgs &A, unsigned long long *counters, hipStream_t st);
 void launch_raygen(const RayGenParams &g, const SceneView &S, xrt_ray *rays, f4 *lvlB0, int *index, int *count, int P, long long pathBase,
-                   const HeavyArgs &H, hipStream_t st, hipEvent_t startEvent = nullptr, int liveCap = 0x7fffffff, const EndArgs *end = nullptr);
+                   const HeavyArgs &H, hipStream_t st, hipEvent_t startEvent = nullptr, int liveCap = 0x7fffffff, const EndArgs *end = nullptr,
+                   const QuadTable *quads = nullptr);
 void launch_shade(const SceneView &S, const ShadeView &V, const ShadeArgs &X, hipStream_t st, int blocks = 1024, int threads = 1024);   // (any grid is correct: grid-stride loops)
 // Frame epilogue of the compose kernels: the clock stamps of traversal launches row0 .. row1-1 are folded into (start, latest
 // end) pairs in host-visible memory (device_util.h)

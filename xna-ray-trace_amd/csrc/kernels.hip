@@ -640,6 +640,9 @@ __device__ __forceinline__ v3 compose_step(uint32_t below, v3 surf, float refl, 
 // One global atomic per list covers RG_ROUNDS x 1024 consecutive paths of a block (2025 atomics on one word were 20 of
 // the kernel's 21 us on a 1080p frame): the rays are written first, the list slots afterwards.
 constexpr int RG_ROUNDS = 4;
+// A wave of a walk (the plain one and the kept-tile one: path_of keeps the low bits of a place) holds 64 consecutive, 64-aligned places in every round: the unit
+// of the packet table (kernels.h QuadTable).
+static_assert(APPEND_BLOCK % 64 == 0 && (RG_ROUNDS * APPEND_BLOCK) % 64 == 0, "a wave's places are one aligned unit of 64");
 // With a live list (`index`, inside frames) the rays are COMPACT: the ray of the j-th live path sits at rays[j] and index[j] names its path
 // -- what the traversal kernels read is one contiguous run, and every per-ray array of generation 0 needs room for the live rays only
 // (at most the paths inside the root box's screen rectangle, known on the host: `liveCap`), not for every path of the frame.  Without
@@ -648,8 +651,9 @@ constexpr int RG_ROUNDS = 4;
 // black (RT:732), where k_compose would have written it, and no record.
 template <bool END>
 __global__ __launch_bounds__(APPEND_BLOCK) void k_raygen(RayGenParams g, SceneView S, xrt_ray *rays, f4 *lvlB0, int *index, int *count, int Phost,
-                                                         long long pathBase, HeavyArgs H, int liveCap, EndArgs E, int keptTiles) {
+                                                         long long pathBase, HeavyArgs H, int liveCap, EndArgs E, int keptTiles, QuadTable Q) {
     __shared__ int ldsLive[RG_ROUNDS * 16], ldsHeavy[RG_ROUNDS * 16];
+    if (Q.table && blockIdx.x == 0 && threadIdx.x == 0) *Q.clear = 0u;   // (the count word of the chunk before the last: its readers are long done, the next chunk counts into it)
     if constexpr (END) { if (blockIdx.x == 0 && threadIdx.x == 0) E.cnt[END_LISTED] = 0; }   // the frame's compose list starts empty (k_shade #0 fills it, a launch later)
     int nEnded = 0;   // END: paths of this thread that ended here
     const int P = pass_paths(g, Phost);
@@ -720,7 +724,21 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_raygen(RayGenParams g, SceneVi
         }
         if (!index) continue;   // grid-uniform: no lists
         __syncthreads();
-        if (wave < 2 && (wave == 0 || H.list)) {   // wave 0 reserves the block's range of the live list, wave 1 of the long-ray list
+        int quadLen = 0, quadAt = 0;   // wave 0 of a launch with a packet table: the live rays of this lane's cell and its entry
+        if (wave == 0 && Q.table) {
+            // Wave 0 reserves the block's range of the live list AND its entries of the packet table -- one per cell (wave and round) that has a live ray, in the
+            // order of the slots -- with ONE atomic instruction: lane 0 adds the rays to `count`, lane 1 the entries to the table's count word (a 256-byte line of
+            // its own), both requests are under way together.  The entries themselves are stored behind the barrier, with the rays: a store in front of it is a
+            // round trip the whole block waits for.
+            quadLen = ldsLive[lane];   // entry r * 16 + w: ascending path order
+            const int incl = wave_scan_add(quadLen);
+            const int total = __builtin_amdgcn_readlane(incl, 63);
+            const unsigned long long mq = __ballot(quadLen > 0);
+            int got = 0;
+            if (lane < 2 && total) got = lane == 0 ? atomicAdd(count, total) : (int)atomicAdd(Q.count, (unsigned)__popcll(mq));
+            quadAt = __builtin_amdgcn_readlane(got, 1) + lanes_below(mq);
+            ldsLive[lane] = __builtin_amdgcn_readlane(got, 0) + incl - quadLen;
+        } else if (wave < 2 && (wave == 0 || H.list)) {   // wave 0 reserves the block's range of the live list, wave 1 of the long-ray list
             int *cells = wave == 0 ? ldsLive : ldsHeavy;
             const int c = cells[lane];   // entry r * 16 + w: ascending path order
             const int incl = wave_scan_add(c);
@@ -731,6 +749,8 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_raygen(RayGenParams g, SceneVi
             cells[lane] = base + incl - c;
         }
         __syncthreads();
+        // the block's entries, one coalesced store of wave 0 (Q.cap bounds the entries by construction, as liveCap the rays)
+        if (quadLen > 0 && quadAt < Q.cap) Q.table[quadAt] = make_uint2((unsigned)ldsLive[lane], (unsigned)quadLen);
 #pragma unroll
         for (int r = 0; r < RG_ROUNDS; r++) {
             const int p = path_of(grp * span + r * APPEND_BLOCK + (int)threadIdx.x);
@@ -817,7 +837,7 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_ingest(RayGenParams g, SceneVi
     }
 }
 void launch_raygen(const RayGenParams &g, const SceneView &S, xrt_ray *rays, f4 *lvlB0, int *index, int *count, int P, long long pathBase,
-                   const HeavyArgs &H, hipStream_t st, hipEvent_t startEvent, int liveCap, const EndArgs *end) {
+                   const HeavyArgs &H, hipStream_t st, hipEvent_t startEvent, int liveCap, const EndArgs *end, const QuadTable *quads) {
     static_assert(RG_ROUNDS * 16 == 64, "one wave scans the block's cells");
     const bool ending = !g.batch && end && end->on && index;
     const int kept = (ending && end->skipTiles) ? lvl_kept_tiles(g) : 0;   // (k_resolve colours the other tiles)
@@ -825,9 +845,10 @@ void launch_raygen(const RayGenParams &g, const SceneView &S, xrt_ray *rays, f4 
     int blocks = (int)((walk + RG_ROUNDS * APPEND_BLOCK - 1) / (RG_ROUNDS * APPEND_BLOCK));
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
+    const QuadTable Q = (quads && index) ? *quads : QuadTable();   // (k_ingest writes no table)
     if (g.batch) hipExtLaunchKernelGGL(k_ingest, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap);
-    else if (ending) hipExtLaunchKernelGGL(k_raygen<true>, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap, *end, kept);
-    else hipExtLaunchKernelGGL(k_raygen<false>, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap, EndArgs(), 0);
+    else if (ending) hipExtLaunchKernelGGL(k_raygen<true>, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap, *end, kept, Q);
+    else hipExtLaunchKernelGGL(k_raygen<false>, dim3(blocks), dim3(APPEND_BLOCK), 0, st, startEvent, nullptr, 0, g, S, rays, lvlB0, index, count, P, pathBase, H, liveCap, EndArgs(), 0, Q);
 }
 
 // ---- shading ----------------------------------------------------------------------------------------------------------

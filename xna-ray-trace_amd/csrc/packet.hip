@@ -591,7 +591,11 @@ __global__ __launch_bounds__(256, (M == MODE_SCENE) ? PK_SCENE_WAVES : (PK_SINGL
     if (A.nCap > 0 && n > A.nCap) n = A.nCap;
     int n2 = A.nDev2 ? (*A.nDev2) * A.nMul2 : 0;   // second segment (PacketArgs::rays2)
     if (n2 > A.nCap2) n2 = A.nCap2;
-    const int nPk1 = (n + 63) >> 6, nPk = nPk1 + ((n2 + 63) >> 6);   // (a packet never mixes the two populations)
+    // The first segment's packets: 64 consecutive rays each, or -- the primary rays of a frame -- the entries of their producer's packet table (kernels.h
+    // QuadTable): one aligned unit of the screen per packet, whatever the live-ray compaction made of the slots.
+    int nPkT = (n + 63) >> 6;
+    if (A.pkTable) { const int t = (int)*A.pkCount; nPkT = t > A.pkCap ? A.pkCap : t; }
+    const int nPk1 = nPkT, nPk = nPk1 + ((n2 + 63) >> 6);   // (a packet never mixes the two populations)
     // Work distribution.  A quarter (PacketArgs::staticDiv) of the packets are dealt statically and strided -- wave w takes packets w, w + nWaves, .. -- so that
     // every wave sees a fair sample of the image (rays skimming the surface near the horizon cost tens of times the average) while
     // neighbouring waves work on neighbouring packets at the same time (their leaves are in cache); the rest comes from a
@@ -724,8 +728,16 @@ __global__ __launch_bounds__(256, (M == MODE_SCENE) ? PK_SCENE_WAVES : (PK_SINGL
 #endif
         const unsigned long long tPacket = costed ? wall_clock64() : 0ull;
         const bool seg2 = pk >= nPk1;   // wave-uniform
-        const int w = (seg2 ? pk - nPk1 : pk) * 64 + lane;
-        const bool valid = w < (seg2 ? n2 : n);
+        int w = (seg2 ? pk - nPk1 : pk) * 64 + lane;
+        bool valid = w < (seg2 ? n2 : n);
+        if (!seg2) {   // (the entry is read per packet like every other argument a packet needs once, not held in scalar registers across the walk)
+            const uint2 *const tab = KA.args()->pkTable;
+            if (tab) {
+                const uint2 e = tab[pk];
+                w = rfl((int)e.x) + lane;
+                valid = lane < rfl((int)e.y) && w < n;
+            }
+        }
         const xrt_ray *const raysS = seg2 ? KA.args()->rays2 : KA.args()->rays;
         Lane L;
         L.state = ST_FINISH; L.mfound = 0; L.cost = 0; L.rayIndex = 0; L.mesh = 0; L.weird = 0; L.dmask = 0; L.ignoreId = -1; L.mask = 0;
@@ -993,7 +1005,7 @@ __global__ __launch_bounds__(256, (M == MODE_SCENE) ? PK_SCENE_WAVES : (PK_SINGL
             if (lane == 0 && KA.args()->tileCost) {
 #endif
                 const PkArgsK a = KA.args();
-                const int first = (seg2 ? pk - nPk1 : pk) * 64;
+                const int first = (!seg2 && a->pkTable) ? (int)a->pkTable[pk].x : (seg2 ? pk - nPk1 : pk) * 64;
                 const SlotRec *const sl = seg2 ? a->slotOf2 : a->slotOf1;
                 const int *const po = a->pathOf1;
                 const int *const scat = seg2 ? a->scatter2 : a->scatter;

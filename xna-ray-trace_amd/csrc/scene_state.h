@@ -153,6 +153,7 @@ struct xrt_scene {
     bool genHeap = false;        // ... made by a ray-tree frame (a frame of the other pipeline takes no hints from them: the counter words mean other things)
     long long genCompose = -1;   // ... and the length of its compose list (kernels.h EndArgs; -1: the frame had none)
     unsigned long long endCounts[3] = {0, 0, 0};   // xrt_debug_end_counts: the last finished frame's paths coloured by k_raygen, by k_shade, and on the compose list
+    int quadCtx = -1; unsigned long long quadLive = 0;   // xrt_debug_packet_table: the frame context of the last finished frame if it had one chunk and a packet table (-1: none), its live primary rays
     int lvlCheckedTilesX = 0; long long lvlCheckedTiles = 0;   // (LvlMap::inv verified for this frame geometry)
     unsigned splitSerial = 0;
     std::map<int, std::pair<DevBuf<unsigned>, DevBuf<unsigned>>> apiSplit;   // seam 1 (testing aid, XRT_PACKET & 8): an arena per stream
@@ -190,6 +191,8 @@ struct xrt_scene {
         DevBuf<xrt_hit> hits, shadowHits;
         DevBuf<int> path0, path1, index0, heavyList, cnts;
         DevBuf<int> composeList;                // kernels.h EndArgs: [0 .. END_WORDS) the count words, [16 ..] the paths k_compose has to walk
+        DevBuf<unsigned> quadTable;             // kernels.h QuadTable: the two count words at [0] and [64] (QUAD_HEAD_WORDS in all), then two words per entry
+        int quadWord = 0;                       // ... the count word (0 / 1) the context's last chunk with a table counted into
         DevBuf<int> node0, node1, heapFlag;     // ray-tree frames: heap node of every ray; heapFlag[0]: a generation overflowed its buffers
         DevBuf<float> ref0, ref1, lvlAlpha;     // ... refraction index of the medium a ray travels in; alpha per level record
         DevBuf<int> hitFlags0, shadowFlags;   // hit / miss word per ray of hits, shadowHits (a miss has no record)

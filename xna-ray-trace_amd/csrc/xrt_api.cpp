@@ -496,6 +496,13 @@ int plan_frame(const xrt_scene &s, int matVersion, const xrt_camera *cam, const 
     // surface, and a packet of scattered rays walks the union of their paths.  It goes to the per-lane kernel unless XRT_PACKET / XRT_PACKET_HEAP
     // name the packet kernel for it (bit 0; both kernels give the same answers).  Its later generations follow the hits as a frame's do.
     p.pkMask = (batch && (heap ? s.cfg.packetMaskHeap : s.cfg.packetMask) < 0) ? (pkScene & ~1) : pkScene;
+    // The packet table (kernels.h QuadTable): wherever launch #0 is a packet launch of k_raygen's rays -- not a batch's (k_ingest keeps the caller's order; of an
+    // adaptive frame level 0 alone, the deeper levels are quadrant lists).  One entry per 64 places k_raygen's walk of a chunk can cover: the kept tiles where it
+    // walks those alone, else the chunk.
+    if (s.cfg.packetQuads && (p.pkMask & 1) && !batch) {
+        const long long walk = p.skipTiles ? ((long long)lvl_kept_tiles(g) << g.lvl.shift) : (long long)p.P;
+        p.pkEntries = (size_t)((walk + 63) / 64);
+    }
     const bool laneClosest = (p.pkMask & 5) != 5;   // some closest-hit generation is traced ray by ray: the long-ray feedback has a reader
     p.wantFeedback = p.fast && !heap && !adaptive && s.deepMeshes && !s.cfg.noFeedback && laneClosest;   // (the paths of a deeper quadrant level are a list: no stable key)
     // "long ray first" (kernels.hip): the producer of generation k lists its long rays, launch #k takes them first
@@ -577,6 +584,14 @@ int ensure_frame_buffers(xrt_scene *s, xrt_scene::FrameCtx &F, const FramePlan &
             HIPCHECK(hipStreamSynchronize(s->stream));
         }
     }
+    if (P.pkEntries) {
+        const unsigned *before = W.quadTable.p; const size_t capBefore = W.quadTable.cap;
+        if ((rc = W.quadTable.ensure((size_t)QUAD_HEAD_WORDS + 2 * P.pkEntries))) return rc;
+        if (W.quadTable.p != before || W.quadTable.cap != capBefore) {   // the count words (kernels.h QuadTable) start at zero; from then on k_raygen clears the one it does not count into
+            HIPCHECK(hipMemsetAsync(W.quadTable.p, 0, QUAD_HEAD_WORDS * sizeof(unsigned), s->stream));
+            HIPCHECK(hipStreamSynchronize(s->stream));
+        }
+    }
     if (P.useStamps) {
         if ((rc = W.stamps.ensure((size_t)MAX_STAMP_ROWS * STAMP_STRIDE))) return rc;
         if ((rc = F.stampHost.ensure((size_t)MAX_STAMP_ROWS * 2 * sizeof(unsigned long long), hipHostMallocMapped))) return rc;
@@ -641,7 +656,7 @@ struct FrameJob {
     int ensure_pinned(size_t bytes) { return F.pinned.bytes < bytes ? F.pinned.ensure(bytes + 4096, hipHostMallocMapped) : XRT_OK; }
     HeavyArgs heavy_for(int k, int *hcnt) const;
     int pick_timing(int grid, unsigned long long *&stamps, hipEvent_t &a0, hipEvent_t &a1);
-    int launch_packets(const Step &T, const IntersectArgs &I, bool shadow, long long nHost, const IntersectArgs *I2 = nullptr);
+    int launch_packets(const Step &T, const IntersectArgs &I, bool shadow, long long nHost, const IntersectArgs *I2 = nullptr, const QuadTable *quads = nullptr);
     int launch_lanes(const Step &T, const IntersectArgs *C, const IntersectArgs *B, int Pc);
     int enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int Pc, long long pathBase, uint32_t *sampleOut = nullptr, const FrameEpilogue *epi = nullptr,
                       int *listCnt = nullptr);
@@ -674,13 +689,15 @@ int FrameJob::pick_timing(int grid, unsigned long long *&stamps, hipEvent_t &a0,
     return XRT_OK;
 }
 
-// A segment of coherent rays to the wave-packet kernel (I2: a second ray population for the same launch -- the shadow rays beside the closest-hit rays -- or null).
-int FrameJob::launch_packets(const Step &T, const IntersectArgs &I, bool shadow, long long nHost, const IntersectArgs *I2) {
+// A segment of coherent rays to the wave-packet kernel (I2: a second ray population for the same launch -- the shadow rays beside the closest-hit rays -- or null;
+// quads: the packet table k_raygen wrote for the segment -- launch #0 of a frame -- or null).
+int FrameJob::launch_packets(const Step &T, const IntersectArgs &I, bool shadow, long long nHost, const IntersectArgs *I2, const QuadTable *quads) {
     const int k = T.k, word = shadow ? 1 : 0, R = P.R, nL = P.nL;
     int rc;
     PacketArgs PA;
     PA.rays = I.rays; PA.hits = I.hits; PA.flags = I.flags; PA.index = I.index; PA.nDev = I.nDev; PA.nMul = I.nMul; PA.n = I.n; PA.nCap = I.nCap;
     PA.scatter = I.scatter;
+    if (quads && quads->table) { PA.pkTable = quads->table; PA.pkCount = quads->count; PA.pkCap = quads->cap; }
     if (I2) { PA.rays2 = I2->rays; PA.hits2 = I2->hits; PA.flags2 = I2->flags; PA.nDev2 = I2->nDev; PA.nMul2 = I2->nMul; PA.nCap2 = I2->nCap; PA.scatter2 = I2->scatter; }
     if (tileCostDev) {   // which tile pays for a packet: the path of its first ray (closest-hit rays: the path list; shadow rays: their hit's slot record)
         PA.tileCost = tileCostDev; PA.tileBase = (int)T.pathBase; PA.tileShift = 9 + (T.gp.samples == 16 ? 4 : (T.gp.samples == 4 ? 2 : 0));
@@ -692,7 +709,7 @@ int FrameJob::launch_packets(const Step &T, const IntersectArgs &I, bool shadow,
     if (s->cfg.packetSplit && s->sceneMode != MODE_SCENE) {
         if ((rc = split_arena(s, W.splitItems, W.splitRecs, PA, st))) return rc;
         if (P.fast && !P.adaptive && !P.heap && s->cfg.packetLongUs > 0) {   // plain frames: the packets of launch #k are the same from frame to frame while the camera stands still, and nearly so while it moves
-            const size_t stride = (P.rayCap + 63) / 64 + ((size_t)P.shadowCap * (size_t)(nL > 0 ? nL : 1) + 63) / 64 + 2;
+            const size_t stride = std::max((P.rayCap + 63) / 64, P.pkEntries) + ((size_t)P.shadowCap * (size_t)(nL > 0 ? nL : 1) + 63) / 64 + 2;
             if (W.splitCostStride != stride || !W.splitCost.p) {
                 if ((rc = W.splitCost.ensure(stride * 2 * (size_t)(R + 2)))) return rc;
                 HIPCHECK(hipMemsetAsync(W.splitCost.p, 0, stride * 2 * (size_t)(R + 2) * sizeof(unsigned), st));
@@ -759,6 +776,14 @@ int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int P
         endArgs.list = W.composeList.p + 16; endArgs.cnt = listCnt; endArgs.listCap = (int)rayCap;
         endArgs.skipTiles = P.skipTiles ? 1 : 0;
     }
+    // launch #0 takes its packets from the table k_raygen writes beside the live list (kernels.h QuadTable); the context's two count words take turns
+    QuadTable quads;
+    // (level 0 of an adaptive frame is k_raygen's walk too, four sub-rays per pixel; the deeper levels are lists of quadrants and take no table)
+    if (P.pkEntries && !gp.batch && gp.quadLevel <= 0 && packet_closest(0) && (P.skipTiles || ((size_t)Pc + 63) / 64 <= P.pkEntries)) {
+        W.quadWord ^= 1;
+        quads.table = reinterpret_cast<uint2 *>(W.quadTable.p + QUAD_HEAD_WORDS); quads.cap = (int)P.pkEntries;
+        quads.count = W.quadTable.p + 64 * W.quadWord; quads.clear = W.quadTable.p + 64 * (W.quadWord ^ 1);
+    }
     if (P.givenHits) {   // the caller's rays AND their closest hits: the live slots get ray, hit and hit word here, launch #0 below does not happen (hits.hip)
         Range r("xrt ingest hits");
         IngestHitsArgs G;
@@ -768,7 +793,7 @@ int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int P
         launch_ingest_hits(S, G, st, startEvent ? e0 : nullptr);
         startEvent = false;
     } else
-    { Range r("xrt raygen"); launch_raygen(gb, S, rays[0], W.lvlB.p, W.index0.p, cnt, Pc, pathBase, heavy_for(0, hcnt), st, startEvent ? e0 : nullptr, (int)rayCap, &endArgs); startEvent = false; }
+    { Range r("xrt raygen"); launch_raygen(gb, S, rays[0], W.lvlB.p, W.index0.p, cnt, Pc, pathBase, heavy_for(0, hcnt), st, startEvent ? e0 : nullptr, (int)rayCap, &endArgs, &quads); startEvent = false; }
     // (one buffer serves every generation: the closest-hit answers of launch #k are read by part A of k_shade #k alone -- part B works from the
     // slot records -- and launch #k+1 starts after it on the frame's stream)
     xrt_hit *hitsOf[2] = {W.hits.p, W.hits.p};
@@ -802,7 +827,7 @@ int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int P
         // both populations of a step in ONE packet launch where both go to the packet kernel: one launch's tail instead of two
         if (pkC && pkB && s->cfg.packetMerge) { if ((rc = launch_packets(T, C, false, hint(s->genRays, k), &B))) return rc; }
         else {
-            if (pkC && (rc = launch_packets(T, C, false, k == 0 ? Pc : hint(s->genRays, k)))) return rc;
+            if (pkC && (rc = launch_packets(T, C, false, k == 0 ? Pc : hint(s->genRays, k), nullptr, k == 0 ? &quads : nullptr))) return rc;
             if (pkB && (rc = launch_packets(T, B, true, hint(s->genRays, k)))) return rc;
         }
         const bool laneC = traceClosest && !pkC, laneB = hasShadow && !pkB;
@@ -1336,6 +1361,9 @@ int frame_finish(xrt_scene *s, xrt_scene::FrameCtx &F, xrt_stats *stats) {
     if (P.endEarly) {   // (xrt_debug_end_counts: a frame that engaged has one chunk and its counters in `pinned`)
         s->endCounts[0] = (unsigned long long)hc0[P.cntStride + END_BY_RAYGEN] + P.endSkipped; s->endCounts[1] = (unsigned long long)hc0[P.cntStride + END_BY_SHADE]; s->endCounts[2] = (unsigned long long)hc0[P.cntStride + END_LISTED];
     } else s->endCounts[0] = s->endCounts[1] = s->endCounts[2] = 0;
+    // (xrt_debug_packet_table: the table and the live list of a one-chunk frame stay in its context until the context's next frame)
+    s->quadCtx = (P.pkEntries && P.firstPaths <= P.chunkPaths && (P.pkMask & 1) && !(P.adaptive && P.quality > 0)) ? (int)(&F - s->frames) : -1;
+    s->quadLive = s->quadCtx >= 0 ? F.live0 : 0;
     {
         float frameMs = 0;
         if (hipEventElapsedTime(&frameMs, F.events[0], F.events[1]) == hipSuccess) s->lastFrameMs = frameMs;
@@ -2934,6 +2962,31 @@ int xrt_debug_end_counts(xrt_scene *scene, uint64_t out[3]) {
         if (rc != XRT_OK) return rc;
         if (!out) return fail(XRT_E_INVALID_ARG, "xrt_debug_end_counts: null argument");
         for (int i = 0; i < 3; i++) out[i] = scene->endCounts[i];
+        return XRT_OK;
+    });
+}
+
+int xrt_debug_packet_table(xrt_scene *scene, uint64_t counts[2], uint32_t *entries_out, int64_t entries_cap, int32_t *paths_out, int64_t paths_cap) {
+    return guarded("xrt_debug_packet_table", [&]() -> int {
+        int rc = need_device(scene, "xrt_debug_packet_table");
+        if (rc != XRT_OK) return rc;
+        if (!counts || entries_cap < 0 || paths_cap < 0 || (!entries_out && entries_cap > 0) || (!paths_out && paths_cap > 0))
+            return fail(XRT_E_INVALID_ARG, "xrt_debug_packet_table: null argument or negative capacity");
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");
+        counts[0] = counts[1] = 0;
+        if (scene->quadCtx < 0) return XRT_OK;
+        const xrt_scene::WorkBufs &W = scene->frames[scene->quadCtx].w;
+        const FramePlan &P = scene->frames[scene->quadCtx].plan;
+        HIPCHECK(hipSetDevice(scene->device));
+        HIPCHECK(hipDeviceSynchronize());
+        unsigned n = 0;
+        HIPCHECK(hipMemcpy(&n, W.quadTable.p + 64 * W.quadWord, sizeof(n), hipMemcpyDeviceToHost));
+        if ((size_t)n > P.pkEntries) return fail(XRT_E_INTERNAL, "xrt_debug_packet_table: %u entries in a table sized for %zu", n, P.pkEntries);
+        counts[0] = n; counts[1] = scene->quadLive;
+        const size_t ne = std::min<size_t>(n, (size_t)entries_cap), np = std::min<size_t>((size_t)scene->quadLive, (size_t)paths_cap);
+        if (ne) HIPCHECK(hipMemcpy(entries_out, W.quadTable.p + QUAD_HEAD_WORDS, ne * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (np) HIPCHECK(hipMemcpy(paths_out, W.index0.p, np * sizeof(int32_t), hipMemcpyDeviceToHost));
         return XRT_OK;
     });
 }
