@@ -186,6 +186,15 @@ namespace RayTraceProject.Spatial
                 Xrt.Check(Xrt.xrt_render_pixels(this.scene, ref camera, lights, lights == null ? 0 : lights.Length, ref opts, centers, colors.Length, c, null, IntPtr.Zero));
         }
 
+        // RayTracer.IsLightPathObstructed (RayTracer.cs:465-502) for every (hit, light) pair of a batch: amounts[i * lights.Length + l] is what the
+        // reference returns for hits[i] and lights[l] -- 0 for a free path, 1 for an obstructed one, color.W of a Transparent blocker -- and 0 for an
+        // entry whose hit word is 0.  One call and one float per shadow ray, where IntersectBatch on host-formed shadow rays moves an XrtRay in and a
+        // 48-byte XrtHit out for each.  lightSums (nullable, 3 floats per hit) receives the unquantised light sum of RayTracer.cs:534-542.
+        public void IsLightPathObstructedBatch(XrtHit[] hits, XrtLight[] lights, float[] amounts, float[] lightSums = null)
+        {
+            Xrt.Check(Xrt.xrt_light_hits(this.scene, hits, hits.Length, lights, lights == null ? 0 : lights.Length, lightSums, amounts, IntPtr.Zero));
+        }
+
         // The single-ray signature of the interface, forwarded as a batch of one (correct, slow: a P/Invoke plus a kernel
         // launch per ray; RayTracer.RenderInternal should call xrt_render instead, see INTEGRATION.md).
         public bool GetRayIntersection(ref Ray ray, out IntersectionResult? result, Triangle ignoreTriangle, Mesh ignoreObject)

@@ -144,6 +144,12 @@ namespace RayTraceProject.Native
                                                                       XrtLight[] lights, int nLights, ref XrtRenderOpts opts, uint* rgbaOut, float* rgbF32Out, IntPtr stats);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_shade_hits_device(IntPtr scene, IntPtr dRays, IntPtr dHits, long n, int iteration, float currentRefIndex,
                                                                       XrtLight[] lights, int nLights, ref XrtRenderOpts opts, IntPtr dRgbaOut, IntPtr dRgbF32Out, IntPtr stream, IntPtr stats);
+        // CastRay's light loop alone (RT:534-542) on caller-given hits: per hit the fp32 light sum (3 floats) and / or IsLightPathObstructed's amount per
+        // light (RT:465-502), nothing quantised; either output may be null, not both (additive within ABI 203)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_light_hits(IntPtr scene, [In] XrtHit[] hits, long n, XrtLight[] lights, int nLights,
+                                                                      [Out] float[] lightF32Out, [Out] float[] amountOut, IntPtr stats);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_light_hits_device(IntPtr scene, IntPtr dHits, long n, XrtLight[] lights, int nLights,
+                                                                      IntPtr dLightF32Out, IntPtr dAmountOut, IntPtr stream, IntPtr stats);
         // SceneObject.Position / Rotation / Scale (SO:51-88) between frames: the dirty bodies' World / InverseWorld / WorldBoundingBox
         // (16 + 16 + 6 floats per id), also while RenderAsync tickets are open; the scene octree stays until xrt_scene_build_tree
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_poses(IntPtr scene, [In] int[] objectIds, int n,

@@ -468,6 +468,52 @@ int xrt_shade_hits_device(xrt_scene *scene, const void *d_rays, const void *d_hi
                           void *d_rgba_out, void *d_rgb_f32_out /* nullable */, void *stream,
                           xrt_stats *stats_out /* nullable */);
 
+/* ---- the light loop of CastRay alone (RT:534-542) on caller-given hits, in fp32 ---------------------------------------------------------
+ * Added within ABI 203: these two exports are additive; no existing struct, field or entry point changed.
+ * Behind its query CastRay asks IsLightPathObstructed once per light (RT:465-502) and sums ILight.GetLightForFragment (SPOT:37-62, DIR:23-30)
+ * scaled by 1 - lightAmount.  xrt_shade_hits hands that sum out only inside a colour -- multiplied by the surface colour, lerped with a
+ * reflection, quantised to RGBA8 per level; xrt_light_hits hands out the sum itself and the per-light amounts: for a host that keeps its own
+ * CastRay and wants its shadow queries answered in batches, for ray-traced shadow masks over a raster G-buffer, for light baking and probes.
+ * For every i, `result` is what RT:512 returned:
+ *   hits[i].hit == 0: the query returned false.  The light is (0, 0, 0) and every amount of the entry is 0.0f.
+ *   otherwise result.mesh, .triangle, .u, .v, .worldPosition = mesh, tri, u, v, (wx, wy, wz), taken bit for bit (NaN, infinities, -0.0 as given:
+ *   computed as the arithmetic gives it, and no other entry is affected).  fragmentNormal follows RT:520-531: with Material.InterpolateNormals
+ *   it is interpolated from n1..n3 with u, v and normalised, otherwise it is surfaceNormal as stored (the reference does not transform it).
+ *   object, leaf, d and reserved are not read and not checked.
+ * amount_out[i * n_lights + l] = IsLightPathObstructed(result, lights[l]): the shadow ray is (worldPosition, dirToLight) -- for a spot light
+ * dirToLight = Position - worldPosition, its Length() the distance, then normalised; for a directional light -Direction and float.MaxValue -- and
+ * the query ignores (mesh, tri).  The path is obstructed when the query hits and its d is below the distance -- the object-space d of OSM:373,450
+ * against a world-space length, as the reference compares them.  An obstructed path gives color.W of the blocker's triangle when the blocker's
+ * material is Transparent and 1 otherwise; a free path gives 0.
+ * light_f32_out[3i ..] = RT:534-542 from Vector3.Zero: for each light in order, when lightAmount != 1f,
+ * += GetLightForFragment(worldPosition, fragmentNormal) * (1 - lightAmount).  Nothing is quantised.  On a mesh that is untextured and whose
+ * Triangle.color.XYZ is (1, 1, 1) this is, bit for bit, the rgb_f32_out of xrt_shade_hits and of xrt_cast_rays on the rays that produced the
+ * hits with max_reflections <= iteration (RT:726 multiplies the light sum by the surface colour and by nothing else).
+ * Poses, materials and triangle values are the latest, as for xrt_cast_rays.  Any light count a frame accepts is accepted; with n_lights == 0
+ * every light sum is (0, 0, 0) and no traversal kernel is launched (intersect_launches == 0).  Long lists are split into chunks under the
+ * shadow byte budget (XRT_SHADOW_BYTES); nothing about the answers depends on the split.
+ * Either output may be NULL, not both.  In this order: XRT_E_INVALID_ARG -- said first, also on a host-only scene -- for n < 0, n_lights < 0,
+ * lights NULL with n_lights > 0, both outputs NULL with n > 0, a needed array NULL, and in the host form an entry with hit != 0 whose mesh is
+ * not in [0, n_meshes) or whose tri is not in [0, ntri(mesh)) (the message names the first offending index, nothing is computed); n == 0
+ * returns XRT_OK; then XRT_E_NO_DEVICE, XRT_E_NOT_BUILT, and XRT_E_BUSY under the rule of xrt_cast_rays.  Blocking.
+ * stats_out (may be NULL): pixels = n; shaded_hits the entries treated as hits; rays_shadow = shaded_hits * n_lights; rays_traversed the shadow
+ * rays handed to a traversal kernel (on a scene of one body with one mesh the library answers a ray itself when the whole mesh faces away from
+ * it); ms_total, ms_intersect and intersect_launches summed over the call's chunks; everything else 0.
+ * There is no begin / end form and no form for supersampled lists. */
+int xrt_light_hits(xrt_scene *scene, const xrt_hit *hits, int64_t n,
+                   const xrt_light *lights, int32_t n_lights,
+                   float *light_f32_out /* nullable, 3 n */, float *amount_out /* nullable, n * n_lights */,
+                   xrt_stats *stats_out /* nullable */);
+
+/* The same on HBM buffers (d_hits: n xrt_hit, d_light_f32_out: NULL or 3n floats, d_amount_out: NULL or n * n_lights floats; each 16-byte
+ * aligned, else XRT_E_INVALID_ARG), enqueued on `stream` (a hipStream_t; NULL = the scene's stream) and synchronised before it returns.  The
+ * hits must be ready on `stream`.  Nothing is inspected on the host: the kernels range-check mesh and tri of every entry, and an entry out
+ * of range is treated as a miss -- it affects no other entry and can never address outside the scene's arrays. */
+int xrt_light_hits_device(xrt_scene *scene, const void *d_hits, int64_t n,
+                          const xrt_light *lights, int32_t n_lights,
+                          void *d_light_f32_out, void *d_amount_out /* each nullable */, void *stream,
+                          xrt_stats *stats_out /* nullable */);
+
 /* ---- seam 3, second half: RayTracer.points (RT:504, 543, 701, 740-747) and CastRay's `ref Ray ray` (RT:692-694) ---------------------
  * Added within ABI 203: one struct and two exports, additive; no existing struct, field or entry point changed.
  * Every CastRay appends line segments to the public list RayTracer.points -- the reference's host draws it over its preview (G1:403-413) --

@@ -146,6 +146,8 @@ SYMBOLS = {
                                  _P(xrt_render_opts), _P(C.c_uint32), _F, _P(xrt_stats)]),
     "xrt_shade_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, _P(xrt_light), C.c_int32,
                                         _P(xrt_render_opts), C.c_void_p, C.c_void_p, C.c_void_p, _P(xrt_stats)]),
+    "xrt_light_hits": (C.c_int, [C.c_void_p, _P(xrt_hit), C.c_int64, _P(xrt_light), C.c_int32, _F, _F, _P(xrt_stats)]),
+    "xrt_light_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _P(xrt_light), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, _P(xrt_stats)]),
     "xrt_cast_rays_paths": (C.c_int, [C.c_void_p, _P(xrt_ray), C.c_int64, C.c_int32, C.c_float, _P(xrt_light), C.c_int32, _P(xrt_render_opts),
                                       _P(C.c_uint32), _F, _P(xrt_ray), _P(C.c_int64), _P(xrt_path_vertex), C.c_int64, _P(C.c_int64), _P(xrt_stats)]),
     "xrt_cast_rays_paths_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, _P(xrt_light), C.c_int32, _P(xrt_render_opts),

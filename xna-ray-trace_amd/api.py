@@ -1018,6 +1018,40 @@ class RayTracer:
         self.last_stats = st.as_dict()
         return (rgba, rgbf) if want_float else rgba
 
+    # ---- CastRay's light loop alone (RT:534-542) on caller-given hits, in fp32: xrt_light_hits ----
+    def LightHits(self, hits, want_amounts=False, want_light=True, device=False, stream=None):
+        """For every hit the light sum of RT:534-542 -- GetLightForFragment * (1 - lightAmount) over self.Lights, nothing quantised -- as
+        float32 (n, 3), and with want_amounts IsLightPathObstructed's amount per light (RT:465-502) as float32 (n, len(Lights)); an entry
+        with hit == 0 gives zeros.  Host form: `hits` the structured array IntersectBatch returns (HIT_DTYPE).  device=True: a contiguous
+        CUDA tensor of n x 12 32-bit words -> torch tensors on its device, enqueued on `stream` (a torch stream, default: the current
+        one).  want_light=False returns the amounts alone."""
+        if not want_light and not want_amounts:
+            raise ValueError("LightHits: nothing is wanted")
+        lights, nl = self._lights_abi(), len(self.Lights)
+        st, lib = abi.xrt_stats(), abi.lib()
+        if device:
+            import torch
+            if not hits.is_contiguous() or hits.element_size() != 4 or hits.numel() % 12:
+                raise ValueError("hits: a contiguous tensor of n x 12 32-bit words (xrt_hit records)")
+            n = hits.numel() // 12
+            light = torch.empty((n, 3), dtype=torch.float32, device=hits.device) if want_light else None
+            amounts = torch.empty((n, nl), dtype=torch.float32, device=hits.device) if want_amounts else None
+            s = stream if stream is not None else torch.cuda.current_stream(hits.device)
+            abi.check(lib.xrt_light_hits_device(self._scene_handle(), C.c_void_p(hits.data_ptr()), n, lights, nl,
+                                                C.c_void_p(light.data_ptr()) if want_light else None,
+                                                C.c_void_p(amounts.data_ptr()) if want_amounts else None, C.c_void_p(s.cuda_stream), C.byref(st)))
+        else:
+            hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+            n = hits.shape[0]
+            light = np.zeros((n, 3), dtype=np.float32) if want_light else None
+            amounts = np.zeros((n, nl), dtype=np.float32) if want_amounts else None
+            abi.check(lib.xrt_light_hits(self._scene_handle(), hits.ctypes.data_as(C.POINTER(abi.xrt_hit)), n, lights, nl,
+                                         _fp(light) if want_light else None, _fp(amounts) if want_amounts else None, C.byref(st)))
+        self.last_stats = st.as_dict()
+        if want_light and want_amounts:
+            return light, amounts
+        return light if want_light else amounts
+
     def CastRay(self, ray, iteration=0, origin=None, currentRefIndex=1.0, want_float=False):
         """RT:506: one ray = (position, direction) -> the packed Color (and its float colour vector with want_float).  origin: the
         triangle the ray leaves, (mesh, index in Mesh.Triangles[]) as GetRayIntersection's ignoreTriangle, or None.

@@ -166,6 +166,18 @@ struct xrt_scene {
     DevBuf<uint32_t> castRGBA;
     DevBuf<float> castF32;
     DevBuf<xrt_hit> castHits;     // xrt_shade_hits: the host's hits (its rays and colours go through castRays / castRGBA / castF32)
+    // xrt_light_hits (lights.hip): the work set of one chunk -- the compact shadow-ray list with its scatter words, the pairs' hits and hit / miss
+    // words, the two count words, the queue words of its traversal launch, the lights -- and the host form's outputs on the device (its hits go
+    // through castHits).  Allocated at the first call, freed with the scene; the work set of frames (WorkBufs) is not touched.
+    struct LightWork {
+        DevBuf<xrt_ray> rays;
+        DevBuf<xrt_hit> hits;
+        DevBuf<int> flags, scatter, counts;
+        DevBuf<unsigned> queue, splitItems, splitRecs;
+        DevBuf<LightRec> lights;
+        DevBuf<float> lightOut, amountOut;
+        Event ev[4];   // a chunk's start and end, its traversal launch's start and end
+    } lightWork;
     // xrt_cast_rays_paths (paths.hip): staging records of a chunk -- (hit position, tag) and (refraction direction, tag) per (node, path), allocated
     // only when a paths call is made --, the work arrays of the ordering pass, and the host form's copies of the caller's arrays
     DevBuf<f4> pathHit, pathDir;

@@ -21,6 +21,8 @@ using namespace xrt;
 #include "pixels.h"        // xrt_render_pixels: the list kernels (pixels.hip) ...
 #include "pixels_plan.h"   // ... and how a list is split into chunks
 #include "hits.h"          // xrt_shade_hits: generation 0 from a caller's hits (hits.hip)
+#include "lights.h"        // xrt_light_hits: the light loop on a caller's hits (lights.hip) ...
+#include "lights_plan.h"   // ... and how a list is split into chunks
 
 namespace {
 
@@ -2081,6 +2083,90 @@ int render_pixels_impl(xrt_scene *s, const xrt_camera *cam, const xrt_light *lig
     return rc;
 }
 
+// ---- xrt_light_hits: the light loop of CastRay (RT:534-542) on a caller's hits ---------------------------------------------------------------
+// n > 0 hits in HBM.  Per chunk (lights_plan.h): k_light_emit lists the shadow rays, ONE traversal launch answers them -- the launch a pass of
+// xrt_cast_rays would make for the shadow rays of its generation 0: the wave-packet kernel where that pass's mask names it for them, else the
+// per-lane kernel, with IntersectArgs::scatter / flags --, k_light_fold writes the caller's arrays, and the two count words come back behind one
+// synchronisation.  The latest poses, materials and triangle values.  The caller holds the scene (BusyGuard, no frame in flight).
+int light_hits_impl(xrt_scene *s, const xrt_hit *d_hits, int64_t n, const xrt_light *lights, int32_t nL, float *d_light, float *d_amount, hipStream_t st,
+                    xrt_stats *stats) {
+    xrt_scene::LightWork &W = s->lightWork;
+    int rc;
+    const std::vector<long long> b = light_chunks(n, nL, (uint64_t)s->cfg.shadowBytes);
+    const size_t pairsCap = (size_t)(b[1] - b[0]) * (size_t)nL;   // (the first chunk is the longest)
+    if ((rc = W.counts.ensure(4))) return rc;
+    if (nL > 0 && ((rc = W.rays.ensure(pairsCap)) || (rc = W.hits.ensure(pairsCap)) || (rc = W.flags.ensure(pairsCap)) || (rc = W.scatter.ensure(pairsCap)) ||
+                   (rc = W.queue.ensure(1 + PACKET_QUEUE_WORDS)) || (rc = W.lights.ensure((size_t)nL))))
+        return rc;
+    for (Event &e : W.ev) if ((rc = e.create(hipEventDefault))) return rc;
+    const int pv = s->poseCur, mv = s->matCur, sv = s->shadeCur;
+    if ((rc = pose_wait(s, pv, st)) || (rc = mat_acquire(s, mv, st)) || (rc = shade_wait(s, sv, st))) return rc;
+    std::vector<LightRec> hl((size_t)(nL > 0 ? nL : 1));
+    for (int i = 0; i < nL; i++) hl[(size_t)i] = make_light(lights[i]);
+    if (nL > 0) HIPCHECK(hipMemcpyAsync(W.lights.p, hl.data(), (size_t)nL * sizeof(LightRec), hipMemcpyHostToDevice, st));
+    const SceneView S = pose_view(s, pv);
+    ShadeView V;
+    V.shade = shade_records(s, sv).p; V.materials = mat_records(s, mv).p; V.texels = mat_texels(s, mv).p; V.meshes = s->meshes.p;
+    V.lights = W.lights.p; V.nLights = nL; V.addressMode = XRT_ADDRESS_WRAP; V.filtering = XRT_FILTER_POINT;   // (no texture is looked up)
+    // answered at emission: on the scenes where frames answer (plan_frame: one body with one mesh that CAN face away from a ray as a whole)
+    const bool ae = s->sceneMode == MODE_SINGLE && s->view.nodeCull != 0 && s->cfg.answerAtEmission && mesh_can_face_away(s->host->arrays.meshes[0]);
+    const int pkMask = !s->packetOk ? 0 : (s->cfg.packetMask >= 0 ? s->cfg.packetMask : (s->sceneMode == MODE_SCENE ? 23 : 0));   // (plan_frame's, for a plain batch)
+    const bool packets = (pkMask & 2) != 0;
+    unsigned long long live = 0, traced = 0;
+    double msTotal = 0.0, msIntersect = 0.0;
+    unsigned launches = 0;
+    Range rf("xrt light hits");
+    for (size_t c = 0; c + 1 < b.size(); c++) {
+        const int m = (int)(b[c + 1] - b[c]);
+        HIPCHECK(hipMemsetAsync(W.counts.p, 0, 4 * sizeof(int), st));
+        HIPCHECK(hipEventRecord(W.ev[0], st));
+        if (nL > 0) {
+            HIPCHECK(hipMemsetAsync(W.queue.p, 0, (1 + PACKET_QUEUE_WORDS) * sizeof(unsigned), st));
+            LightEmitArgs E;
+            E.hits = d_hits; E.base = b[c]; E.n = m; E.nLights = nL; E.lights = W.lights.p; E.ae = ae ? 1 : 0;
+            E.rays = W.rays.p; E.scatter = W.scatter.p; E.flags = W.flags.p; E.count = W.counts.p; E.cap = (int)((size_t)m * (size_t)nL);
+            launch_light_emit(S, E, st);
+            IntersectArgs B = IntersectArgs();
+            B.rays = W.rays.p; B.hits = W.hits.p; B.index = nullptr; B.nDev = W.counts.p; B.nMul = 1; B.n = 0; B.nCap = E.cap;
+            B.queue = W.queue.p; B.mode = s->sceneMode; B.meshId = 0;
+            B.flags = W.flags.p; B.missRecords = 0; B.scatter = W.scatter.p;
+            set_knobs(B, s);
+            if (packets) {
+                PacketArgs PA;
+                PA.rays = B.rays; PA.hits = B.hits; PA.flags = B.flags; PA.nDev = B.nDev; PA.nMul = 1; PA.n = 0; PA.nCap = B.nCap; PA.scatter = B.scatter;
+                PA.queue = W.queue.p + 1; PA.mode = s->sceneMode; PA.meshId = 0; PA.unmark = 0;
+                PA.staticDiv = s->cfg.packetStaticDiv; PA.grabMax = s->cfg.packetGrabMax; PA.cullMin = s->cfg.packetCullMin;
+                if (s->cfg.packetSplit && s->sceneMode != MODE_SCENE && (rc = split_arena(s, W.splitItems, W.splitRecs, PA, st))) return rc;
+                int grid = s->numCUs * s->blocksPerCUPacket;
+                const long long want = ((long long)E.cap + 255) / 256;
+                if (want < grid) grid = (int)(want < 1 ? 1 : want);
+                launch_packet(S, PA, grid, st, W.ev[2], W.ev[3]);
+            } else launch_intersect(S, B, s->stackNeeded, persistent_grid(s, E.cap), st, W.ev[2], W.ev[3]);
+            launches++;
+        }
+        LightFoldArgs F;
+        F.hits = d_hits; F.base = b[c]; F.n = m; F.flags = W.flags.p; F.shadowHits = W.hits.p;
+        F.lightOut = d_light; F.amountOut = d_amount; F.liveCount = W.counts.p + 1;
+        launch_light_fold(S, V, F, st);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipEventRecord(W.ev[1], st));
+        int hc[2] = {0, 0};
+        HIPCHECK(hipMemcpyAsync(hc, W.counts.p, sizeof(hc), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));   // (the one synchronisation of the chunk)
+        traced += (unsigned long long)hc[0]; live += (unsigned long long)hc[1];
+        float ms = 0.0f;
+        HIPCHECK(hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
+        msTotal += ms;
+        if (nL > 0) { HIPCHECK(hipEventElapsedTime(&ms, W.ev[2], W.ev[3])); msIntersect += ms; }
+    }
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->pixels = (uint64_t)n; stats->shaded_hits = live; stats->rays_shadow = live * (unsigned long long)nL; stats->rays_traversed = traced;
+        stats->ms_total = msTotal; stats->ms_intersect = msIntersect; stats->intersect_launches = launches;
+    }
+    return XRT_OK;
+}
+
 int pose_upload(xrt_scene *scene);
 
 // What is made from the scene octree and the poses (snodes, srefs, objects, scull, the positions of every body's records in scull, the
@@ -3134,6 +3220,74 @@ int xrt_shade_hits_device(xrt_scene *scene, const void *d_rays, const void *d_hi
                                  (float *)d_rgb_f32_out, st, stats_out, nullptr, (const xrt_hit *)d_hits, "xrt_shade_hits_device")))
             return rc;
         return guards_check("end of a batch of hits");
+    });
+}
+
+// What is wrong with the arguments of xrt_light_hits[_device] alone, in the order the header gives (the scene's device is not looked at).
+static int light_hits_check_args(const char *fn, const xrt_scene *scene, const void *hits, int64_t n, const xrt_light *lights, int32_t n_lights,
+                                 const void *light_out, const void *amount_out) {
+    if (!scene) return fail(XRT_E_INVALID_ARG, "%s: null scene", fn);
+    if (n < 0) return fail(XRT_E_INVALID_ARG, "%s: n = %lld out of range", fn, (long long)n);
+    if (n_lights < 0) return fail(XRT_E_INVALID_ARG, "%s: n_lights = %d out of range", fn, n_lights);
+    if (!lights && n_lights > 0) return fail(XRT_E_INVALID_ARG, "%s: null lights", fn);
+    if (n > 0 && !light_out && !amount_out) return fail(XRT_E_INVALID_ARG, "%s: both outputs are null", fn);
+    if (n > 0 && !hits) return fail(XRT_E_INVALID_ARG, "%s: null hits", fn);
+    for (int i = 0; i < n_lights; i++)
+        if (lights[i].kind != XRT_LIGHT_SPOT && lights[i].kind != XRT_LIGHT_DIRECTIONAL) return fail(XRT_E_INVALID_ARG, "%s: unknown light kind", fn);
+    return XRT_OK;
+}
+
+int xrt_light_hits(xrt_scene *scene, const xrt_hit *hits, int64_t n, const xrt_light *lights, int32_t n_lights, float *light_f32_out, float *amount_out,
+                   xrt_stats *stats_out) {
+    return guarded("xrt_light_hits", [&]() -> int {
+        int rc;
+        if ((rc = light_hits_check_args("xrt_light_hits", scene, hits, n, lights, n_lights, light_f32_out, amount_out))) return rc;
+        // a hit names a triangle of a mesh of the scene, as the query would have (the lists as they were added: known on a host-only scene too)
+        const auto &meshes = scene->host->meshes;
+        for (int64_t i = 0; i < n; i++) {
+            const xrt_hit &h = hits[i];
+            if (h.hit == 0) continue;
+            if (h.mesh < 0 || h.mesh >= (int)meshes.size())
+                return fail(XRT_E_INVALID_ARG, "xrt_light_hits: hit %lld names mesh %d, which does not exist", (long long)i, h.mesh);
+            if (h.tri < 0 || h.tri >= meshes[(size_t)h.mesh].ntri)
+                return fail(XRT_E_INVALID_ARG, "xrt_light_hits: hit %lld names triangle %d of mesh %d, which does not exist", (long long)i, h.tri, h.mesh);
+        }
+        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+        if (n == 0) return XRT_OK;
+        if ((rc = need_device(scene, "xrt_light_hits"))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        xrt_scene::LightWork &W = scene->lightWork;
+        const size_t nAmounts = (size_t)n * (size_t)n_lights;
+        if ((rc = scene->castHits.ensure((size_t)n)) || (light_f32_out && (rc = W.lightOut.ensure((size_t)n * 3))) || (amount_out && (rc = W.amountOut.ensure(nAmounts))))
+            return rc;
+        HIPCHECK(hipMemcpyAsync(scene->castHits.p, hits, (size_t)n * sizeof(xrt_hit), hipMemcpyHostToDevice, scene->stream));
+        if ((rc = light_hits_impl(scene, scene->castHits.p, n, lights, n_lights, light_f32_out ? W.lightOut.p : nullptr, amount_out ? W.amountOut.p : nullptr,
+                                  scene->stream, stats_out)))
+            return rc;
+        if (light_f32_out) HIPCHECK(hipMemcpyAsync(light_f32_out, W.lightOut.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, scene->stream));
+        if (amount_out && nAmounts) HIPCHECK(hipMemcpyAsync(amount_out, W.amountOut.p, nAmounts * sizeof(float), hipMemcpyDeviceToHost, scene->stream));
+        HIPCHECK(hipStreamSynchronize(scene->stream));
+        return guards_check("end of a batch of lit hits");
+    });
+}
+
+int xrt_light_hits_device(xrt_scene *scene, const void *d_hits, int64_t n, const xrt_light *lights, int32_t n_lights, void *d_light_f32_out, void *d_amount_out,
+                          void *stream, xrt_stats *stats_out) {
+    return guarded("xrt_light_hits_device", [&]() -> int {
+        int rc;
+        if ((rc = light_hits_check_args("xrt_light_hits_device", scene, d_hits, n, lights, n_lights, d_light_f32_out, d_amount_out))) return rc;
+        if (((uintptr_t)d_hits & 15) || ((uintptr_t)d_light_f32_out & 15) || ((uintptr_t)d_amount_out & 15))
+            return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
+        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+        if (n == 0) return XRT_OK;
+        if ((rc = need_device(scene, "xrt_light_hits_device"))) return rc;
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        hipStream_t st = (hipStream_t)stream;
+        if (!st) st = scene->stream;
+        if ((rc = light_hits_impl(scene, (const xrt_hit *)d_hits, n, lights, n_lights, (float *)d_light_f32_out, (float *)d_amount_out, st, stats_out))) return rc;
+        return guards_check("end of a batch of lit hits");
     });
 }
 
