@@ -42,7 +42,8 @@ namespace RayTraceProject.Native
         public int maxReflections, useMultisampling, multisampleQuality, addressMode, filtering, shardRank, shardCount, collectStats;
         public int nGpus;                          // > 1: the library spreads the frame's tiles over that many devices and gathers them with RCCL
         public int balanceTiles;                   // with nGpus > 1: 1 = the tiles are dealt by the previous frame's costs (the static counterpart of GetNextScanline, RayTracer.cs:48-52), 0 = round-robin
-        public int reserved0, reserved1;           // zero
+        public int listOrder;                      // XRT_LIST_*: 0 = nothing is assumed about the order of a list (xrt_render_pixels, xrt_cast_rays*), 1 = consecutive entries are neighbours on screen / in space: traced as a frame would be, same results
+        public int reserved;                       // zero
     }
 
     [StructLayout(LayoutKind.Sequential)]
@@ -73,6 +74,7 @@ namespace RayTraceProject.Native
         // and a cdecl callee would unbalance the stack: every import names its convention.  (The Avi.cs precedent binds Win32
         // stdcall APIs and does not carry over.)
         public const int OK = 0, E_INVALID_ARG = -1, E_BUSY = -2, E_NO_DEVICE = -3;
+        public const int LIST_UNORDERED = 0, LIST_COHERENT = 1;   // XrtRenderOpts.listOrder
 
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_version();
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern IntPtr xrt_last_error();

@@ -147,8 +147,24 @@ typedef struct xrt_render_opts {
      * parallel idea is DYNAMIC row stealing (RT:48-52, 105-120), which a static t % N assignment does not reproduce where rows differ in
      * cost (the horizon).  0: round-robin.  Scheduling only: the frame is the same. */
     int32_t balance_tiles;
-    int32_t reserved[2];          /* zero */
+    /* XRT_LIST_*: what the caller says about the ORDER of a list -- the centres of xrt_render_pixels[_device], the rays of xrt_cast_rays[_device] and
+     * xrt_cast_rays_paths[_device].  XRT_LIST_COHERENT: consecutive entries are neighbours on screen / in space (a row-major rectangle, a frame's tile
+     * order, the primary rays of a frame), and the list is traced as a frame of the same scene and sampling would be: in every generation the kernel a
+     * frame's rule picks -- the wave-packet kernel for the first rays of a two-level scene at any sample count, of a one-body scene with 16 samples --,
+     * XRT_PACKET / XRT_PACKET_HEAP overriding as always; xrt_render_pixels then also generates its rays where it compacts them, one kernel instead of
+     * two and no ray record for a position that cannot reach the scene.  Scheduling only, the hint never changes a result: rgba_out, rgb_f32_out, the
+     * reference work counters, rays_*, hits_*, vertices and rays_back are bit for bit those of the unhinted call.  A hint on a scattered list costs time
+     * and nothing else (a packet of scattered rays walks the union of their paths: 4096 random pixels of a two-level scene measured 16-18 % slower
+     * hinted), and so can a hint on a list of a few entries (one 16-sample entry of a one-body scene: 0.20 against 0.19 ms; the hint follows the
+     * frame's rule whatever the length; profiles/coherent_lists/README.md).  Any other value is XRT_E_INVALID_ARG in those calls.
+     * xrt_shade_hits[_device] accept both values and do nothing with them (their first level is not traced); xrt_render* and every other call never read
+     * the field.  Added within ABI 203: the first word of what was reserved[2], which callers were told to zero (= XRT_LIST_UNORDERED, the path as it
+     * was, launch for launch); size and offsets of the struct are unchanged. */
+    int32_t list_order;
+    int32_t reserved;             /* zero */
 } xrt_render_opts;
+#define XRT_LIST_UNORDERED 0   /* as before: nothing is assumed about the order */
+#define XRT_LIST_COHERENT  1   /* consecutive entries are neighbours on screen / in space */
 
 /* Exact work counters of the REFERENCE algorithm for the rays of one call and the
  * measured kernel times. Counts are those of the C# code path, not of the pruned GPU traversal. */
@@ -386,7 +402,11 @@ int xrt_debug_end_counts(xrt_scene *scene, uint64_t out[3]);
  * places of the frame that has a live ray; a packet of the first traversal launch is one entry.  For the last finished frame of the scene, if it had
  * one chunk: counts[0] entries of the table, counts[1] live primary rays; up to entries_cap entries go to entries_out (two words each: first slot,
  * rays) and up to paths_cap words of the live list -- the path of the frame whose ray sits in slot j -- to paths_out (either may be null with a capacity
- * of 0).  counts[0] == 0: the frame's first launch took no table (another kernel, a batch, an adaptive frame, XRT_PK_QUADS=0). */
+ * of 0).  counts[0] == 0: the frame's first launch took no table (another kernel, a batch, an adaptive frame, XRT_PK_QUADS=0).
+ * A list counts as the scene's last frame too.  After xrt_render_pixels[_device] with XRT_LIST_COHERENT whose last pass was one chunk and took a table
+ * (the packet kernel traced its first rays) the call reports that table: a unit is 64 aligned places of the pass -- place r is sample r % samples of
+ * entry r / samples of the pass's part of the list, so 4 entries with 16 samples, 16 level-0 quadrants, 64 one-sample entries --, counts[1] the live
+ * rays and paths_out[j] the place of the ray in slot j.  After any other list call (unhinted, xrt_cast_rays*, xrt_shade_hits) counts[0] == 0. */
 int xrt_debug_packet_table(xrt_scene *scene, uint64_t counts[2], uint32_t *entries_out, int64_t entries_cap, int32_t *paths_out, int64_t paths_cap);
 
 /* RayTracer.Progress (RT:43-46): fraction of the frame's ray generations completed; callable from

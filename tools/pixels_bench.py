@@ -3,7 +3,9 @@
     colours are checked against the frame's);
   - small lists: one centre, 4096 random pixels, a 128x128 rectangle -- the latency a pixel inspector or a region re-render sees.
 One process, warm-up, medians of `reps` blocking calls.  Prints one JSON line.
-    python tools/pixels_bench.py [config] [off|fixed16|adaptive] [reps]"""
+    python tools/pixels_bench.py [config] [off|fixed16|adaptive] [reps] [coherent]
+coherent (profiles/coherent_lists/README.md): 0 every list unhinted (the default, the rows as they were), 1 every list with XRT_LIST_COHERENT, both: each
+list unhinted under its key and hinted under <key>_coherent, in that order in one process."""
 import json
 import os
 import sys
@@ -19,6 +21,8 @@ xrt = importlib.import_module("xna-ray-trace_amd")
 name = sys.argv[1] if len(sys.argv) > 1 else "C5"
 mode = sys.argv[2] if len(sys.argv) > 2 else "fixed16"
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 20
+coherent = sys.argv[4] if len(sys.argv) > 4 else "0"
+hints = {"0": [(False, "")], "1": [(True, "")], "both": [(False, ""), (True, "_coherent")]}[coherent]
 abi = xrt.abi
 spec = xrt.configs.config(name)
 scene, tracer = xrt.configs.build_product(spec)
@@ -45,7 +49,7 @@ def timed(fn):
     return round(1e3 * float(np.median(t)), 3), round(1e3 * float(np.min(t)), 3)
 
 
-out = {"config": name, "mode": mode, "width": W, "height": H, "depth": spec.max_reflections, "reps": reps}
+out = {"config": name, "mode": mode, "width": W, "height": H, "depth": spec.max_reflections, "reps": reps, "coherent": coherent}
 out["frame_ms"], out["frame_ms_min"] = timed(render)
 ref = frame.cpu().numpy().view(np.uint32)
 
@@ -57,13 +61,14 @@ lists = {"listed_frame": np.arange(n), "one": np.array([(H // 2) * W + W // 2]),
          "rect_128x128": (ry * W + rx).ravel()}
 for key, at in lists.items():
     centers = torch.from_numpy(np.stack([xs[at], ys[at]], axis=1).astype(np.float32)).cuda()
-    got = {}
+    for hinted, suffix in hints:
+        got = {}
 
-    def call():
-        got["rgba"] = tracer.RenderPixels(centers, device=True)
-    t, tmin = timed(call)
-    st = tracer.last_stats
-    out[key] = {"n": int(len(at)), "ms": t, "ms_min": tmin, "vs_frame": round(t / out["frame_ms"], 3), "device_ms": round(st["ms_total"], 3),
-                "ms_intersect": round(st["ms_intersect"], 3), "launches": int(st["intersect_launches"]), "rays": int(st["rays_closest"] + st["rays_shadow"]),
-                "same_as_frame": bool(np.array_equal(got["rgba"].cpu().numpy().view(np.uint32), ref[at]))}
+        def call():
+            got["rgba"] = tracer.RenderPixels(centers, device=True, coherent=hinted)
+        t, tmin = timed(call)
+        st = tracer.last_stats
+        out[key + suffix] = {"n": int(len(at)), "ms": t, "ms_min": tmin, "vs_frame": round(t / out["frame_ms"], 3), "device_ms": round(st["ms_total"], 3),
+                             "ms_intersect": round(st["ms_intersect"], 3), "launches": int(st["intersect_launches"]), "rays": int(st["rays_closest"] + st["rays_shadow"]),
+                             "same_as_frame": bool(np.array_equal(got["rgba"].cpu().numpy().view(np.uint32), ref[at]))}
 print(json.dumps(out))

@@ -37,6 +37,7 @@ FILTER_POINT, FILTER_BILINEAR = 0, 1
 ADDRESS_CLAMP, ADDRESS_WRAP, ADDRESS_MIRROR = 0, 1, 2
 LIGHT_SPOT, LIGHT_DIRECTIONAL = 0, 1
 MS_OFF, MS_ADAPTIVE, MS_FIXED16 = 0, 1, 2
+LIST_UNORDERED, LIST_COHERENT = 0, 1   # xrt_render_opts.list_order (XRT_LIST_*)
 TILE_W, TILE_H = 64, 8
 
 
@@ -72,7 +73,8 @@ class xrt_light(C.Structure):
 class xrt_render_opts(C.Structure):
     _fields_ = [("max_reflections", C.c_int32), ("use_multisampling", C.c_int32), ("multisample_quality", C.c_int32),
                 ("address_mode", C.c_int32), ("filtering", C.c_int32), ("shard_rank", C.c_int32),
-                ("shard_count", C.c_int32), ("collect_stats", C.c_int32), ("n_gpus", C.c_int32), ("balance_tiles", C.c_int32), ("reserved", C.c_int32 * 2)]
+                ("shard_count", C.c_int32), ("collect_stats", C.c_int32), ("n_gpus", C.c_int32), ("balance_tiles", C.c_int32),
+                ("list_order", C.c_int32), ("reserved", C.c_int32)]   # (list_order: LIST_*, the first word of what was reserved[2])
 
 
 class xrt_stats(C.Structure):

@@ -862,13 +862,16 @@ class RayTracer:
         return begin
 
     # ---- GetColorForQuadrant / the body of Render's inner loop (RT:215-311, 412-425) on caller-chosen pixels: xrt_render_pixels ----
-    def RenderPixels(self, centers, want_float=False, device=False, stream=None):
+    def RenderPixels(self, centers, want_float=False, device=False, stream=None, coherent=False):
         """The colour of every screen position of a list, by the tracer's camera, lights and options as in Render (all three multisampling
         modes; an integer centre gets the frame's pixel bit for bit).  Host form: `centers` an (n, 2) float32 array -> uint32 colours (and
         float32 (n, 3) with want_float).  device=True: `centers` a contiguous CUDA tensor of n float32 pairs -> torch tensors on its device
-        (int32 holding the packed colours; float32 (n, 3)), enqueued on `stream` (a torch stream, default: the current one)."""
+        (int32 holding the packed colours; float32 (n, 3)), enqueued on `stream` (a torch stream, default: the current one).
+        coherent=True (xrt_render_opts.list_order = XRT_LIST_COHERENT): consecutive centres are neighbours on screen -- a row-major rectangle,
+        a frame's tile order -- and the list is traced as a frame would be.  Scheduling only: the colours and counters are the same."""
         cam, opts, lights = self._camera_abi(), self._opts_abi(shard_count=0), self._lights_abi()
         opts.n_gpus = 0
+        opts.list_order = int(coherent)   # (False / True are XRT_LIST_UNORDERED / XRT_LIST_COHERENT; the library refuses any other value)
         st, lib = abi.xrt_stats(), abi.lib()
         if device:
             import torch
@@ -892,7 +895,7 @@ class RayTracer:
         return (rgba, rgbf) if want_float else rgba
 
     # ---- RayTracer.CastRay (RT:506-737) on caller-given rays: xrt_cast_rays, xrt_cast_rays_paths ----
-    def CastRays(self, rays, iteration=0, currentRefIndex=1.0, want_float=False, device=False, stream=None, paths=False, vertex_capacity=None):
+    def CastRays(self, rays, iteration=0, currentRefIndex=1.0, want_float=False, device=False, stream=None, paths=False, vertex_capacity=None, coherent=False):
         """CastRay(ref rays[i], out color, iteration, origin_i, null, currentRefIndex) for every ray of a batch, origin_i = the ray's
         (ignore_mesh, ignore_tri).  Host form: `rays` an xrt_ray array (RAY_DTYPE) -> uint32 colours (and float32 (n, 3) colour vectors
         with want_float).  device=True: `rays` a contiguous CUDA tensor of n 32-byte records (e.g. (n, 8) float32) -> torch tensors on
@@ -905,9 +908,13 @@ class RayTracer:
         vertex_capacity=None a first call counts (no vertex array) and a second call of exactly that capacity fills it -- the batch is traced
         twice; a caller who knows a bound passes vertex_capacity and gets one call, the array cut to what fitted; last_n_vertices is what
         the batch needs either way.
-        With RecordPoints the segments are also appended to `points` and last_ray is the last ray's (position, direction) as left."""
+        With RecordPoints the segments are also appended to `points` and last_ray is the last ray's (position, direction) as left.
+
+        coherent=True (xrt_render_opts.list_order = XRT_LIST_COHERENT): consecutive rays are neighbours in space (a frame's primary rays in
+        screen order), and the batch is traced as a frame would be.  Scheduling only: every output is the same."""
         opts, lights = self._opts_abi(shard_count=0), self._lights_abi()
         opts.n_gpus = 0
+        opts.list_order = int(coherent)   # (False / True are XRT_LIST_UNORDERED / XRT_LIST_COHERENT; the library refuses any other value)
         st, lib = abi.xrt_stats(), abi.lib()
         record = paths or self.RecordPoints
         need = C.c_int64(0)

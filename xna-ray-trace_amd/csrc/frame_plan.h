@@ -6,6 +6,7 @@
 #include "kernels.h"
 
 struct xrt_scene;
+namespace xrt { struct PixelGenArgs; }   // pixels.h
 
 // A caller's ray list as the ray source of a pass (xrt_cast_rays): n rays in HBM, 16-byte aligned, and generation 0's curRef.
 struct BatchSrc {
@@ -22,6 +23,12 @@ struct BatchSrc {
     const Paths *paths = nullptr;
     // xrt_shade_hits: the closest hits of the rays (n xrt_hit in HBM, 16-byte aligned) -- generation 0 is ingested from them and not traced -- or null
     const xrt_hit *hits = nullptr;
+    // xrt_render_opts.list_order == XRT_LIST_COHERENT: consecutive rays are neighbours, the pass picks its kernels as a frame does (FramePlan::pkMask)
+    bool coherent = false;
+    int samples = 1;   // ... of which sampling: the rays per screen position the list was made with (1, 4, 16; read with `coherent` alone)
+    // xrt_render_pixels with that hint: generation 0 comes from a list of screen positions (pixels.h k_pixel_raygen) and `rays` is null -- no ray
+    // record exists before the live list -- or null
+    const xrt::PixelGenArgs *gen = nullptr;
 };
 
 constexpr int ADAPTIVE_LEVEL_WORDS = 16;   // adaptive frames in flight: words in front of the per-pass counters -- lvlCnt[0 .. quality], the overflow word at the end

@@ -30,43 +30,7 @@ struct LdsStack {
     __device__ __forceinline__ void set(int i, unsigned v) { base[i * 64] = v; }
 };
 
-__device__ __forceinline__ bool predict_heavy(const SceneView &S, v3 o, v3 d, float heavyPath) {
-    const f4 lo = S.snodes[0], hi = S.snodes[1];
-    float tmin = 0.0f, tmax = FLT_MAX;
-    const float ox[3] = {o.x, o.y, o.z}, dx[3] = {d.x, d.y, d.z}, bl[3] = {lo.x, lo.y, lo.z}, bh[3] = {hi.x, hi.y, hi.z};
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        if (fabsf(dx[k]) > 1e-6f) {
-            const float inv = __frcp_rn(dx[k]);
-            const float t1 = (bl[k] - ox[k]) * inv, t2 = (bh[k] - ox[k]) * inv;
-            tmin = fmaxf(tmin, fminf(t1, t2));
-            tmax = fminf(tmax, fmaxf(t1, t2));
-        }
-    }
-    return (tmax - tmin) > heavyPath;   // NaN compares false: not listed
-}
-// Feedback: a frame remembers, per path and generation, how many rounds of the traversal loop its ray was in flight
-// (the hit record's reserved word -> k_shade -> the cost map).  The next frames list a ray as long when the ray that
-// stood in its place cost more than a threshold the host steers to a few percent of the rays.  A camera that moves
-// makes the memory slightly stale, never wrong: the list only decides which rays start first.
-__device__ __forceinline__ bool long_ray(const SceneView &S, const HeavyArgs &H, int path, v3 o, v3 d) {
-    if (H.costMap) {
-        const unsigned e = H.costMap[path];
-        if (((H.epoch - (e >> 16)) & 0xffffu) - 1u < 4u) return (int)(e & 0xffffu) > H.costThreshold;   // written one to four frames ago
-    }
-    return H.path > 0.0f && predict_heavy(S, o, d, H.path);
-}
-
-// wave64 inclusive scans on the DPP network (row shifts, then the two row broadcasts): no LDS round trip
-__device__ __forceinline__ int wave_scan_add(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2 and 3
-    return v;
-}
+// (predict_heavy, long_ray and wave_scan_add: device_util.h -- pixels.hip appends to the same lists)
 __device__ __forceinline__ int wave_scan_max(int v) {   // values >= 0
     v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false));
     v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false));

@@ -15,6 +15,24 @@ enum { PIXEL_ONE = 0, PIXEL_QUADRANT = 1, PIXEL_FIXED16 = 2 };   // rays per ent
 void launch_pixel_rays(const RayGenParams &g, const float *cx, const float *cy, int stride, long long first, int count, float size, int mode,
                        xrt_ray *rays, hipStream_t st);
 
+// k_pixel_raygen: k_pixel_rays and generation 0 of the pass that traces them (k_ingest, kernels.hip) in one kernel, for a list the caller calls coherent
+// (xrt.h XRT_LIST_COHERENT).  It is k_raygen's structure on a centre list.  Place r = pathBase + p of the list's part -- entries from G.first on -- is sample
+// r % samples of entry G.first + r / samples, at k_pixel_rays' position; path p of the pass (p < P) is place pathBase + p.  A ray that cannot reach the scene's
+// root box (OSM:460) gets its miss record lvlB0[p] and is never stored; the live ones are compacted into rays[0 .. *count) with index[slot] = p (one
+// reservation per block and group of 4096 places), the long ones listed (H), refOut[slot] = refIndex for a ray-tree pass (nullable).  Q.table non-null
+// (launch #0 is a packet launch): one entry (first slot, live rays) per 64-aligned unit of the pass's places that has a live ray, reserved with the
+// slots in the same atomic instruction; Q.count / Q.clear as k_raygen uses them (kernels.h QuadTable).  Bounds: liveCap slots, Q.cap entries.
+struct PixelGenArgs {
+    RayGenParams cam;   // camera part only
+    const float *cx = nullptr, *cy = nullptr;
+    int stride = 1;
+    long long first = 0;
+    float size = 1.0f;
+    int mode = PIXEL_ONE;
+};
+void launch_pixel_raygen(const PixelGenArgs &G, const SceneView &S, xrt_ray *rays, f4 *lvlB0, int *index, int *count, int P, long long pathBase, const HeavyArgs &H,
+                         int liveCap, float *refOut, float refIndex, const QuadTable &Q, hipStream_t st, hipEvent_t startEvent = nullptr);
+
 // k_pixel_decide: RT:279-306 on a list of n quadrants with their four colours -- k_ms_decide for a level whose centres are listed with a
 // stride, which is what level 0 of a centre list is.  Children of a quadrant are appended together, in corner order, to nextCx / nextCy (room
 // for 4 n); *nextCount (zero before the launch) counts them.

@@ -2,13 +2,16 @@
 // The frame kernels of kernels.hip (k_raygen, k_ms_decide, k_resolve) walk a pixel grid in tiles; these walk a list in the caller's order and
 // know nothing of a frame.  The arithmetic is the same functions (xrt_core.h: unproject, normalize, unpack_color / pack_color, divf, length),
 // compiled with the same flags: contraction off, every addition below its own rounding.
-// Built: NOT fused -- k_pixel_rays writes 32-byte xrt_ray records and the pass of xrt_cast_rays (k_ingest, iteration 0, currentRefIndex 1.0f)
-// reads them back, one round trip through HBM per ray (profiles/pixels/README.md).
+// An unhinted list is NOT fused -- k_pixel_rays writes 32-byte xrt_ray records and the pass of xrt_cast_rays (k_ingest, iteration 0, currentRefIndex 1.0f)
+// reads them back, one round trip through HBM per ray (profiles/pixels/README.md).  A list the caller calls coherent (xrt.h XRT_LIST_COHERENT) is:
+// k_pixel_raygen makes the rays where the pass compacts them (profiles/coherent_lists/README.md).
 #include <hip/hip_runtime.h>
 
 #include "device_util.h"
 #include "pixels.h"
 #include "xrt_core.h"
+
+#include <hip/hip_ext.h>
 
 namespace xrt {
 
@@ -17,6 +20,19 @@ constexpr int PIXEL_BLOCK = 256;
 // aligned (device allocations) and holds whole groups of four.
 struct alignas(16) Color4 { uint32_t c[4]; };
 __device__ __forceinline__ Color4 load4(const uint32_t *p) { return *reinterpret_cast<const Color4 *>(p); }
+
+// Where sample s of an entry centred at (sx, sy) lies: the one statement of it for both ray generation kernels of this file.
+__device__ __forceinline__ void sample_position(int mode, float size, int s, float &sx, float &sy) {
+    if (mode == PIXEL_QUADRANT) {   // RT:223-276: four rays at centre -+ size/4, order UL, UR, LL, LR
+        const float quarter = size * 0.25f;
+        sx = (s & 1) ? sx + quarter : sx - quarter;
+        sy = (s & 2) ? sy + quarter : sy - quarter;
+    } else if (mode == PIXEL_FIXED16) {   // corner q = s/4 at +-0.25, sub-sample s%4 at +-0.125, in this association
+        const int q = s >> 2, rr = s & 3;
+        sx = (sx + ((q & 1) ? 0.25f : -0.25f)) + ((rr & 1) ? 0.125f : -0.125f);
+        sy = (sy + ((q & 2) ? 0.25f : -0.25f)) + ((rr & 2) ? 0.125f : -0.125f);
+    }
+}
 
 // One thread per ray: ray r of the launch is sample r % samples of entry first + r / samples, so a wave writes 2 KB of consecutive records.
 __global__ __launch_bounds__(PIXEL_BLOCK) void k_pixel_rays(RayGenParams g, const float *cx, const float *cy, int stride, long long first, int count,
@@ -27,15 +43,7 @@ __global__ __launch_bounds__(PIXEL_BLOCK) void k_pixel_rays(RayGenParams g, cons
         const size_t e = (size_t)(first + (r >> shift)) * (size_t)stride;
         const int s = (int)(r & ((1 << shift) - 1));
         float sx = cx[e], sy = cy[e];
-        if (mode == PIXEL_QUADRANT) {   // RT:223-276: four rays at centre -+ size/4, order UL, UR, LL, LR
-            const float quarter = size * 0.25f;
-            sx = (s & 1) ? sx + quarter : sx - quarter;
-            sy = (s & 2) ? sy + quarter : sy - quarter;
-        } else if (mode == PIXEL_FIXED16) {   // corner q = s/4 at +-0.25, sub-sample s%4 at +-0.125, in this association
-            const int q = s >> 2, rr = s & 3;
-            sx = (sx + ((q & 1) ? 0.25f : -0.25f)) + ((rr & 1) ? 0.125f : -0.125f);
-            sy = (sy + ((q & 2) ? 0.25f : -0.25f)) + ((rr & 2) ? 0.125f : -0.125f);
-        }
+        sample_position(mode, size, s, sx, sy);
         const v3 nearP = unproject(g, sx, sy, 0.0f);   // RT:415
         const v3 farP = unproject(g, sx, sy, 1.0f);    // RT:419
         const v3 dir = normalize(sub(farP, nearP));    // RT:420-421
@@ -48,6 +56,98 @@ void launch_pixel_rays(const RayGenParams &g, const float *cx, const float *cy, 
     long long blocks = (total + PIXEL_BLOCK - 1) / PIXEL_BLOCK;
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(k_pixel_rays, dim3(blocks < 1 ? 1 : (unsigned)blocks), dim3(PIXEL_BLOCK), 0, st, g, cx, cy, stride, first, count, size, mode, rays);
+}
+
+// k_pixel_rays and k_ingest in one (pixels.h): k_raygen's structure (kernels.hip) on a centre list.  A block takes groups of GEN_ROUNDS x 1024 consecutive
+// places; a wave holds 64 consecutive, 64-aligned places of the pass in every round -- the unit of the packet table: 4 entries of a 16-sample list, 16
+// level-0 quadrants, 64 one-sample entries.  The rays are kept in registers until the block knows its range of the live list: one atomic per list, block
+// and group, and where a table is written its entries are reserved by the lane next to the one that reserves the slots, in the same instruction.
+constexpr int GEN_BLOCK = 1024, GEN_ROUNDS = 4;
+static_assert(GEN_ROUNDS * (GEN_BLOCK / 64) == 64, "one wave scans the block's cells");
+__global__ __launch_bounds__(GEN_BLOCK) void k_pixel_raygen(PixelGenArgs G, SceneView S, xrt_ray *rays, f4 *lvlB0, int *index, int *count, int P, long long pathBase,
+                                                            HeavyArgs H, int liveCap, float *refOut, float refIndex, QuadTable Q) {
+    __shared__ int ldsLive[GEN_ROUNDS * 16], ldsHeavy[GEN_ROUNDS * 16];
+    if (Q.table && blockIdx.x == 0 && threadIdx.x == 0) *Q.clear = 0u;   // (the count word of the chunk before the last, kernels.h QuadTable)
+    const int shift = G.mode == PIXEL_FIXED16 ? 4 : (G.mode == PIXEL_QUADRANT ? 2 : 0);
+    const f4 rlo = S.snodes[0], rhi = S.snodes[1];
+    const int span = GEN_ROUNDS * GEN_BLOCK;
+    const int groups = (P + span - 1) / span;
+    const int wave = (int)(threadIdx.x >> 6), lane = lane_id();
+    for (int grp = (int)blockIdx.x; grp < groups; grp += (int)gridDim.x) {
+        int liveAt[GEN_ROUNDS], heavyAt[GEN_ROUNDS];   // rank among the flagged lanes of the wave, -1: not flagged
+        v3 keepO[GEN_ROUNDS], keepD[GEN_ROUNDS];       // the live rays of this thread, written once their places in the list are known
+#pragma unroll
+        for (int r = 0; r < GEN_ROUNDS; r++) {
+            const int p = grp * span + r * GEN_BLOCK + (int)threadIdx.x;
+            bool live = false, heavy = false;
+            keepO[r] = mk(0, 0, 0); keepD[r] = mk(0, 0, 0);
+            if (p < P) {
+                const long long place = pathBase + p;
+                const size_t e = (size_t)(G.first + (place >> shift)) * (size_t)G.stride;
+                const int s = (int)(place & ((1 << shift) - 1));
+                float sx = G.cx[e], sy = G.cy[e];
+                sample_position(G.mode, G.size, s, sx, sy);
+                const v3 nearP = unproject(G.cam, sx, sy, 0.0f);   // RT:415
+                const v3 farP = unproject(G.cam, sx, sy, 1.0f);    // RT:419
+                const v3 dir = normalize(sub(farP, nearP));        // RT:420-421
+                const RayPre w = make_ray(nearP, dir);
+                float key;
+                live = slab(w, rlo.x, rlo.y, rlo.z, rhi.x, rhi.y, rhi.z, key);   // OSM:460 on the root
+                heavy = live && H.list && long_ray(S, H, p, nearP, dir);
+                keepO[r] = nearP; keepD[r] = dir;
+                if (!live) lvlB0[p] = f4{0, 0, 0, i2f(FLAG_MISS)};   // generation 0 ends here (RT:729-733): the record k_ingest writes, and no ray
+            }
+            const unsigned long long ml = __ballot(live), mh = __ballot(heavy);
+            liveAt[r] = live ? lanes_below(ml) : -1;
+            heavyAt[r] = heavy ? lanes_below(mh) : -1;
+            if (lane == 0) { ldsLive[r * 16 + wave] = (int)__popcll(ml); ldsHeavy[r * 16 + wave] = (int)__popcll(mh); }
+        }
+        __syncthreads();
+        int quadLen = 0, quadAt = 0;   // wave 0 of a launch with a packet table: the live rays of this lane's cell and its entry
+        if (wave == 0 && Q.table) {
+            quadLen = ldsLive[lane];   // cell r * 16 + w: ascending place order
+            const int incl = wave_scan_add(quadLen);
+            const int total = __builtin_amdgcn_readlane(incl, 63);
+            const unsigned long long mq = __ballot(quadLen > 0);
+            int got = 0;   // lane 0 reserves the slots, lane 1 the entries (a word with a 256-byte line of its own): one atomic instruction
+            if (lane < 2 && total) got = lane == 0 ? atomicAdd(count, total) : (int)atomicAdd(Q.count, (unsigned)__popcll(mq));
+            quadAt = __builtin_amdgcn_readlane(got, 1) + lanes_below(mq);
+            ldsLive[lane] = __builtin_amdgcn_readlane(got, 0) + incl - quadLen;
+        } else if (wave < 2 && (wave == 0 || H.list)) {   // wave 0 reserves the block's range of the live list, wave 1 of the long-ray list
+            int *cells = wave == 0 ? ldsLive : ldsHeavy;
+            const int c = cells[lane];
+            const int incl = wave_scan_add(c);
+            const int total = __builtin_amdgcn_readlane(incl, 63);
+            int base = 0;
+            if (lane == 0 && total) base = atomicAdd(wave == 0 ? count : H.count, total);
+            base = __builtin_amdgcn_readfirstlane(base);
+            cells[lane] = base + incl - c;
+        }
+        __syncthreads();
+        // the block's entries, one coalesced store of wave 0 (Q.cap bounds the entries by construction, as liveCap the rays: the guards are against a wrong bound)
+        if (quadLen > 0 && quadAt < Q.cap) Q.table[quadAt] = make_uint2((unsigned)ldsLive[lane], (unsigned)quadLen);
+#pragma unroll
+        for (int r = 0; r < GEN_ROUNDS; r++) {
+            const int p = grp * span + r * GEN_BLOCK + (int)threadIdx.x;
+            if (liveAt[r] >= 0) {
+                const int slot = ldsLive[r * 16 + wave] + liveAt[r];
+                if (slot < liveCap) {
+                    index[slot] = p;
+                    store_ray(rays + slot, keepO[r], keepD[r], -1, heavyAt[r] >= 0 ? (-1 ^ HEAVY_BIT) : -1);   // origin null (RT:424)
+                    if (refOut) refOut[slot] = refIndex;
+                    if (heavyAt[r] >= 0) H.list[ldsHeavy[r * 16 + wave] + heavyAt[r]] = slot;
+                }
+            }
+        }
+        __syncthreads();   // the cells are reused by the next group
+    }
+}
+void launch_pixel_raygen(const PixelGenArgs &G, const SceneView &S, xrt_ray *rays, f4 *lvlB0, int *index, int *count, int P, long long pathBase, const HeavyArgs &H,
+                         int liveCap, float *refOut, float refIndex, const QuadTable &Q, hipStream_t st, hipEvent_t startEvent) {
+    int blocks = (int)(((long long)P + GEN_ROUNDS * GEN_BLOCK - 1) / (GEN_ROUNDS * GEN_BLOCK));
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    hipExtLaunchKernelGGL(k_pixel_raygen, dim3(blocks), dim3(GEN_BLOCK), 0, st, startEvent, nullptr, 0, G, S, rays, lvlB0, index, count, P, pathBase, H, liveCap, refOut, refIndex, Q);
 }
 
 // RT:279-306 on listed quadrants.  A corner whose colour-vector length differs from the length of the 4-mean by more than 0.5 (RT:340) is

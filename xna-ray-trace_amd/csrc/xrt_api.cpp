@@ -488,7 +488,8 @@ int plan_frame(const xrt_scene &s, int matVersion, const xrt_camera *cam, const 
     // records and the mesh walk of a body, and an 8x8-pixel block of a 1-sample frame sees one or two bodies: C3 2.28 -> 1.57 ms,
     // C4 6.64 -> 4.37 ms per pipelined frame (packets for the first two generations only: 1.78 / 5.0, profiles/r03/packet_masks.txt);
     // one-body scenes: only with 16 sub-rays, and only the first two generations, see above)
-    const int pkAuto = s.sceneMode == MODE_SCENE ? 23 : (g.samples >= 16 ? 7 : 0);
+    const int pkSamples = (batch && batch->coherent) ? batch->samples : g.samples;   // (a coherent list: the sampling its rays were made with, see below)
+    const int pkAuto = s.sceneMode == MODE_SCENE ? 23 : (pkSamples >= 16 ? 7 : 0);
     // (ray-tree frames -- Transparent materials -- of two-level scenes: the first two generations and the first shadow rays, where the image
     // is big enough for a launch to be more than its floor: G2 at 720p 1.12 -> 0.97 ms, the reference's default scene at 512x512 0.31 ->
     // 0.40 with packets, so not there; packets in every generation of a ray tree are 1.5-3 x slower (profiles/r03/packet_masks_ray_trees.txt))
@@ -497,11 +498,14 @@ int plan_frame(const xrt_scene &s, int matVersion, const xrt_camera *cam, const 
     // A batch's generation 0 is in the caller's order, which nothing says is coherent: 64 consecutive rays need not be a patch of the same
     // surface, and a packet of scattered rays walks the union of their paths.  It goes to the per-lane kernel unless XRT_PACKET / XRT_PACKET_HEAP
     // name the packet kernel for it (bit 0; both kernels give the same answers).  Its later generations follow the hits as a frame's do.
-    p.pkMask = (batch && (heap ? s.cfg.packetMaskHeap : s.cfg.packetMask) < 0) ? (pkScene & ~1) : pkScene;
+    // ... unless the caller says it is (xrt.h XRT_LIST_COHERENT): such a batch has the mask of a frame of the same scene and sampling -- the sampling is
+    // BatchSrc::samples (a list of xrt_render_pixels: 1, 4, 16; a batch's own g.samples is always 1), so a one-body scene gets packets with 16 samples alone, as its frames do.
+    p.pkMask = (batch && !batch->coherent && (heap ? s.cfg.packetMaskHeap : s.cfg.packetMask) < 0) ? (pkScene & ~1) : pkScene;
     // The packet table (kernels.h QuadTable): wherever launch #0 is a packet launch of k_raygen's rays -- not a batch's (k_ingest keeps the caller's order; of an
     // adaptive frame level 0 alone, the deeper levels are quadrant lists).  One entry per 64 places k_raygen's walk of a chunk can cover: the kept tiles where it
     // walks those alone, else the chunk.
-    if (s.cfg.packetQuads && (p.pkMask & 1) && !batch) {
+    // ... and of a coherent list of screen positions, whose fused ray generation (pixels.hip k_pixel_raygen) walks the chunk's places as k_raygen walks a frame's.
+    if (s.cfg.packetQuads && (p.pkMask & 1) && (!batch || (batch->coherent && batch->gen))) {
         const long long walk = p.skipTiles ? ((long long)lvl_kept_tiles(g) << g.lvl.shift) : (long long)p.P;
         p.pkEntries = (size_t)((walk + 63) / 64);
     }
@@ -771,7 +775,7 @@ int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int P
     float *refOf[2] = {W.ref0.p, W.ref1.p};
     // cnt[0] counts the primary rays that reach the scene's root box; index0 lists them
     RayGenParams gb = gp;
-    if (gp.batch && heap) gb.batchRef = refOf[0];
+    if (P.batch && heap) gb.batchRef = refOf[0];
     EndArgs endArgs;
     if (listCnt) {
         endArgs.on = 1; endArgs.sampleColor = sampleOut ? sampleOut : W.sampleColor.p;
@@ -781,7 +785,7 @@ int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int P
     // launch #0 takes its packets from the table k_raygen writes beside the live list (kernels.h QuadTable); the context's two count words take turns
     QuadTable quads;
     // (level 0 of an adaptive frame is k_raygen's walk too, four sub-rays per pixel; the deeper levels are lists of quadrants and take no table)
-    if (P.pkEntries && !gp.batch && gp.quadLevel <= 0 && packet_closest(0) && (P.skipTiles || ((size_t)Pc + 63) / 64 <= P.pkEntries)) {
+    if (P.pkEntries && (!P.batch || batch->gen) && gp.quadLevel <= 0 && packet_closest(0) && (P.skipTiles || ((size_t)Pc + 63) / 64 <= P.pkEntries)) {
         W.quadWord ^= 1;
         quads.table = reinterpret_cast<uint2 *>(W.quadTable.p + QUAD_HEAD_WORDS); quads.cap = (int)P.pkEntries;
         quads.count = W.quadTable.p + 64 * W.quadWord; quads.clear = W.quadTable.p + 64 * (W.quadWord ^ 1);
@@ -793,6 +797,11 @@ int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int P
         G.raysOut = rays[0]; G.hitsOut = W.hits.p; G.flagsOut = W.hitFlags0.p; G.index = W.index0.p; G.count = cnt; G.lvlB0 = W.lvlB.p;
         G.refOut = heap ? refOf[0] : nullptr; G.refIndex = batch->refIndex; G.liveCap = (int)rayCap;
         launch_ingest_hits(S, G, st, startEvent ? e0 : nullptr);
+        startEvent = false;
+    } else if (P.batch && batch->gen) {   // a coherent list of screen positions: its rays are made where they are compacted (pixels.hip), with the table where launch #0 takes one
+        Range r("xrt pixel raygen");
+        launch_pixel_raygen(*batch->gen, S, rays[0], W.lvlB.p, W.index0.p, cnt, Pc, pathBase, heavy_for(0, hcnt), (int)rayCap, heap ? refOf[0] : nullptr, batch->refIndex, quads, st,
+                            startEvent ? e0 : nullptr);
         startEvent = false;
     } else
     { Range r("xrt raygen"); launch_raygen(gb, S, rays[0], W.lvlB.p, W.index0.p, cnt, Pc, pathBase, heavy_for(0, hcnt), st, startEvent ? e0 : nullptr, (int)rayCap, &endArgs, &quads); startEvent = false; }
@@ -847,7 +856,7 @@ int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int P
         X.rays = rays[cur]; X.hits = hitsOf[cur]; X.hitFlags = flagsOf[cur]; X.shadowFlags = shadowFlagsOf[(k + 1) & 1]; X.nDev = nClosest; X.nHost = Pc; X.cap = (int)rayCap;
         X.index = nullptr; X.rayPath = k == 0 ? W.index0.p : paths[cur];   // (generation 0: the j-th live ray belongs to path index0[j])
         X.rayNode = (heap && k > 0) ? nodesOf[cur] : nullptr;
-        X.rayRef = (heap && (k > 0 || gp.batch)) ? refOf[cur] : nullptr;   // (a batch's generation 0 carries the caller's currentRefIndex, k_ingest)
+        X.rayRef = (heap && (k > 0 || P.batch)) ? refOf[cur] : nullptr;   // (a batch's generation 0 carries the caller's currentRefIndex, k_ingest)
         X.slotOut = slotOf[cur]; X.slotNodeOut = heap ? slotNodeOf[cur] : nullptr; X.scnt = scnt + k; X.shadowCap = (int)shadowCap; X.shadowRays = W.shadowRays.p;
         X.nextRays = rays[prv]; X.nextPath = paths[prv]; X.nextNode = heap ? nodesOf[prv] : nullptr; X.nextRef = heap ? refOf[prv] : nullptr;
         X.nextCnt = cnt + k + 1; X.nextCap = (int)rayCap;
@@ -874,8 +883,8 @@ int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int P
     Range rc_("xrt compose");
     // a batch: path p of the chunk is ray pathBase + p, and the compose kernel writes its colour straight into the caller's arrays (a ray-tree chunk
     // that overflowed is retried over the same range: the retry overwrites what the discarded attempt wrote)
-    uint32_t *const colorOut = gp.batch ? d_out + pathBase : (sampleOut ? sampleOut : W.sampleColor.p);
-    float *const f32Out = gp.batch ? (d_outF32 ? d_outF32 + 3 * (size_t)pathBase : nullptr) : (P.wantF32 ? W.sampleF32.p : nullptr);
+    uint32_t *const colorOut = P.batch ? d_out + pathBase : (sampleOut ? sampleOut : W.sampleColor.p);
+    float *const f32Out = P.batch ? (d_outF32 ? d_outF32 + 3 * (size_t)pathBase : nullptr) : (P.wantF32 ? W.sampleF32.p : nullptr);
     StampFold fold;
     fold.src = W.stamps.p; fold.host = F.stampHost.dev; fold.row0 = chunkRow0; fold.row1 = F.stampRows;
     if (heap) {
@@ -1911,13 +1920,14 @@ int batch_check_opts(const char *fn, const xrt_render_opts *opts, int32_t iterat
     // CastRay(.., iteration, ..) reflects while iteration < MaxReflections (RT:545): a frame's recursion of max(0, M - iteration) generations
     const long long depth = std::max(0LL, (long long)opts->max_reflections - (long long)iteration);
     if (depth > 64) return fail(XRT_E_INVALID_ARG, "%s: max_reflections - iteration = %lld is above 64", fn, depth);
+    if (opts->list_order != XRT_LIST_UNORDERED && opts->list_order != XRT_LIST_COHERENT) return fail(XRT_E_INVALID_ARG, "%s: list_order must be XRT_LIST_UNORDERED or XRT_LIST_COHERENT", fn);
     return XRT_OK;
 }
 
 // (d_hits, xrt_shade_hits: the closest hits of the rays, n xrt_hit in HBM -- generation 0 is not traced)
 int cast_rays_impl(xrt_scene *s, const xrt_ray *d_rays, int64_t n, int32_t iteration, float refIndex, const xrt_light *lights, int32_t nLights,
                    const xrt_render_opts *opts, uint32_t *d_out, float *d_outF32, hipStream_t st, xrt_stats *stats, const BatchSrc::Paths *paths = nullptr,
-                   const xrt_hit *d_hits = nullptr, const char *fn = "xrt_cast_rays") {
+                   const xrt_hit *d_hits = nullptr, const char *fn = "xrt_cast_rays", const PixelGenArgs *gen = nullptr) {
     if (int rc = batch_check_opts(fn, opts, iteration)) return rc;
     const long long depth = std::max(0LL, (long long)opts->max_reflections - (long long)iteration);
     if (stats) std::memset(stats, 0, sizeof(*stats));
@@ -1927,6 +1937,9 @@ int cast_rays_impl(xrt_scene *s, const xrt_ray *d_rays, int64_t n, int32_t itera
     o.use_multisampling = XRT_MS_OFF; o.shard_count = 0; o.shard_rank = 0; o.n_gpus = 0; o.balance_tiles = 0;
     BatchSrc b;
     b.rays = d_rays; b.n = n; b.refIndex = refIndex; b.paths = paths; b.hits = d_hits;
+    // (gen: the rays of a coherent centre list, made by the pass itself -- d_rays is null; given hits: nothing of generation 0 is traced, the hint has no reader)
+    b.coherent = !d_hits && opts->list_order == XRT_LIST_COHERENT; b.gen = b.coherent ? gen : nullptr;
+    if (b.gen) b.samples = gen->mode == PIXEL_FIXED16 ? 16 : (gen->mode == PIXEL_QUADRANT ? 4 : 1);
     xrt_scene::FrameCtx &F = s->frames[0];
     F.pose = s->poseCur;
     F.mat = s->matCur;   // (a ray batch reads the latest materials)
@@ -1957,6 +1970,7 @@ int pixels_check_args(const char *fn, const xrt_camera *cam, const xrt_light *li
     if (ms == XRT_MS_ADAPTIVE && (opts->multisample_quality < 0 || opts->multisample_quality > 6))
         return fail(XRT_E_UNSUPPORTED, "MultisampleQuality above 6 (4^7 sub-quadrants per pixel)");
     if (cam->vp_width <= 0 || cam->vp_height <= 0) return fail(XRT_E_INVALID_ARG, "viewport must be positive");
+    if (opts->list_order != XRT_LIST_UNORDERED && opts->list_order != XRT_LIST_COHERENT) return fail(XRT_E_INVALID_ARG, "%s: list_order must be XRT_LIST_UNORDERED or XRT_LIST_COHERENT", fn);
     return XRT_OK;
 }
 
@@ -1973,6 +1987,7 @@ struct PixelsJob {
     uint64_t budget;
     xrt_stats acc;
     bool any = false;
+    bool coherent = false;   // the call's xrt_render_opts.list_order is XRT_LIST_COHERENT (set by run)
 
     void tally(const xrt_stats &t) {   // counters and times add up over the casts of the call
         uint64_t *a = reinterpret_cast<uint64_t *>(&acc);
@@ -1985,18 +2000,31 @@ struct PixelsJob {
         any = true;
     }
     // The colours of entries [first, first + count) of a list, `samples` rays each: d_col[0 .. count * samples), d_f32 (nullable) likewise.
-    int cast(const float *cx, const float *cy, int stride, long long first, long long count, float size, int mode, uint32_t *d_col, float *d_f32) {
+    // hinted (XRT_LIST_COHERENT, levels whose entries are the caller's): the pass makes the rays itself (k_pixel_raygen) and picks its kernels as a frame does.
+    int cast(const float *cx, const float *cy, int stride, long long first, long long count, float size, int mode, uint32_t *d_col, float *d_f32, bool hinted = false) {
         const int ms = mode == PIXEL_FIXED16 ? XRT_MS_FIXED16 : (mode == PIXEL_QUADRANT ? XRT_MS_ADAPTIVE : XRT_MS_OFF);
         const long long samples = pixel_samples(ms);
-        const std::vector<long long> b = pixel_chunks(count, ms, 0, nL, budget);
+        const std::vector<long long> b = pixel_chunks(count, ms, 0, nL, budget, hinted);
+        xrt_render_opts oc = o;
+        oc.list_order = hinted ? XRT_LIST_COHERENT : XRT_LIST_UNORDERED;
         for (size_t c = 0; c + 1 < b.size(); c++) {
             const long long m = b[c + 1] - b[c], rays = m * samples;
             int rc;
+            if (hinted) {
+                PixelGenArgs G;
+                G.cam = g; G.cx = cx; G.cy = cy; G.stride = stride; G.first = first + b[c]; G.size = size; G.mode = mode;
+                xrt_stats t;
+                if ((rc = cast_rays_impl(s, nullptr, rays, 0, 1.0f, lights, nL, &oc, d_col + b[c] * samples, d_f32 ? d_f32 + 3 * b[c] * samples : nullptr, st, &t, nullptr, nullptr,
+                                         "xrt_render_pixels", &G)))
+                    return rc;
+                tally(t);
+                continue;
+            }
             if ((rc = s->pixelRays.ensure((size_t)rays))) return rc;
             launch_pixel_rays(g, cx, cy, stride, first + b[c], (int)m, size, mode, s->pixelRays.p, st);
             HIPCHECK(hipGetLastError());
             xrt_stats t;
-            if ((rc = cast_rays_impl(s, s->pixelRays.p, rays, 0, 1.0f, lights, nL, &o, d_col + b[c] * samples, d_f32 ? d_f32 + 3 * b[c] * samples : nullptr, st, &t)))
+            if ((rc = cast_rays_impl(s, s->pixelRays.p, rays, 0, 1.0f, lights, nL, &oc, d_col + b[c] * samples, d_f32 ? d_f32 + 3 * b[c] * samples : nullptr, st, &t)))
                 return rc;
             tally(t);
         }
@@ -2021,7 +2049,7 @@ struct PixelsJob {
             if ((rc = L.color.ensure((size_t)L.n * 4))) return rc;
             const float *cx = l == 0 ? centers + 2 * first : L.cx.p, *cy = l == 0 ? cx + 1 : L.cy.p;
             const int stride = l == 0 ? 2 : 1;
-            if ((rc = cast(cx, cy, stride, 0, L.n, size, PIXEL_QUADRANT, L.color.p, nullptr))) return rc;
+            if ((rc = cast(cx, cy, stride, 0, L.n, size, PIXEL_QUADRANT, L.color.p, nullptr, coherent && l == 0))) return rc;   // (the deeper levels are lists of quadrants in the order k_pixel_decide appended them)
             if (l < quality) {   // RT:279-306
                 Level &N = lv[l + 1];
                 if ((rc = L.childBase.ensure((size_t)L.n)) || (rc = L.childMask.ensure((size_t)L.n)) || (rc = N.cx.ensure((size_t)L.n * 4)) || (rc = N.cy.ensure((size_t)L.n * 4)))
@@ -2045,8 +2073,9 @@ struct PixelsJob {
     int run(const float *centers, int64_t n, uint32_t *d_out, float *d_outF32) {
         const int ms = o.use_multisampling, quality = o.multisample_quality;
         o.use_multisampling = XRT_MS_OFF; o.multisample_quality = 0;
-        if (ms == XRT_MS_OFF) return cast(centers, centers + 1, 2, 0, n, 1.0f, PIXEL_ONE, d_out, d_outF32);   // RT:412-425: the cast writes the caller's arrays
-        const std::vector<long long> b = pixel_chunks(n, ms, quality, nL, budget);
+        coherent = o.list_order == XRT_LIST_COHERENT;
+        if (ms == XRT_MS_OFF) return cast(centers, centers + 1, 2, 0, n, 1.0f, PIXEL_ONE, d_out, d_outF32, coherent);   // RT:412-425: the cast writes the caller's arrays
+        const std::vector<long long> b = pixel_chunks(n, ms, quality, nL, budget, coherent);
         for (size_t c = 0; c + 1 < b.size(); c++) {
             const long long first = b[c], m = b[c + 1] - b[c];
             int rc;
@@ -2055,7 +2084,7 @@ struct PixelsJob {
                 continue;
             }
             if ((rc = s->pixelSamples.ensure((size_t)m * 16))) return rc;
-            if ((rc = cast(centers, centers + 1, 2, first, m, 1.0f, PIXEL_FIXED16, s->pixelSamples.p, nullptr))) return rc;
+            if ((rc = cast(centers, centers + 1, 2, first, m, 1.0f, PIXEL_FIXED16, s->pixelSamples.p, nullptr, coherent))) return rc;
             launch_pixel_resolve(s->pixelSamples.p, (int)m, PIXEL_FIXED16, d_out + first, d_outF32 ? d_outF32 + 3 * first : nullptr, st);
             HIPCHECK(hipGetLastError());
         }
