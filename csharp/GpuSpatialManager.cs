@@ -186,6 +186,15 @@ namespace RayTraceProject.Spatial
                 Xrt.Check(Xrt.xrt_render_pixels(this.scene, ref camera, lights, lights == null ? 0 : lights.Length, ref opts, centers, colors.Length, c, null, IntPtr.Zero));
         }
 
+        // The primary rays and closest hits of caller-chosen screen positions -- RayTracer.cs:412-421 and the GetRayIntersection of RayTracer.cs:512 for each,
+        // nothing shaded: the picking seam (the triangle under the mouse, Game1.cs:296-325, is TracePixels on one centre; hits[0].mesh / .tri name it),
+        // the primary hits of a still that is relit afterwards (Game1.cs:152-190: xrt_shade_hits / IsLightPathObstructedBatch on these hits), a G-buffer.
+        // rays / hits: either may be null, not both; with opts.useMultisampling = 2 (the fixed sixteen) each holds 16 records per centre.
+        public void TracePixels(ref XrtCamera camera, ref XrtRenderOpts opts, float[] centers, XrtRay[] rays, XrtHit[] hits)
+        {
+            Xrt.Check(Xrt.xrt_trace_pixels(this.scene, ref camera, ref opts, centers, centers.Length / 2, rays, hits, IntPtr.Zero));
+        }
+
         // RayTracer.IsLightPathObstructed (RayTracer.cs:465-502) for every (hit, light) pair of a batch: amounts[i * lights.Length + l] is what the
         // reference returns for hits[i] and lights[l] -- 0 for a free path, 1 for an obstructed one, color.W of a Transparent blocker -- and 0 for an
         // entry whose hit word is 0.  One call and one float per shadow ray, where IntersectBatch on host-formed shadow rays moves an XrtRay in and a

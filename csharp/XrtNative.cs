@@ -181,6 +181,12 @@ namespace RayTraceProject.Native
                                                                      ref XrtRenderOpts opts, [In] float[] centers, long n, uint* rgbaOut, float* rgbF32Out, IntPtr stats);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_render_pixels_device(IntPtr scene, ref XrtCamera camera, XrtLight[] lights, int nLights,
                                                                      ref XrtRenderOpts opts, IntPtr dCenters, long n, IntPtr dRgbaOut, IntPtr dRgbF32Out, IntPtr stream, IntPtr stats);
+        // The first level of xrt_render_pixels alone: per listed screen position the ray of RayTracer.cs:412-421 and the IntersectionResult of RayTracer.cs:512,
+        // nothing shaded, no lights; XRT_MS_OFF or XRT_MS_FIXED16 (16 records per centre); either output may be null, not both (additive within ABI 203)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_trace_pixels(IntPtr scene, ref XrtCamera camera, ref XrtRenderOpts opts, [In] float[] centers, long n,
+                                                                     [Out] XrtRay[] raysOut, [Out] XrtHit[] hitsOut, IntPtr stats);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_trace_pixels_device(IntPtr scene, ref XrtCamera camera, ref XrtRenderOpts opts, IntPtr dCenters, long n,
+                                                                     IntPtr dRaysOut, IntPtr dHitsOut, IntPtr stream, IntPtr stats);
         // can n_gpus > 1 load RCCL?  OK or E_RCCL (-6) with the loader's message; no device is touched
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_rccl_probe();
         // diagnostics of the split walks of long packets (results never depend on them): subtrees handed over, taken, packets split, packets written by a taker

@@ -767,6 +767,55 @@ int xrt_render_pixels_device(xrt_scene *scene, const xrt_camera *camera, const x
                              const xrt_render_opts *opts, const void *d_centers, int64_t n,
                              void *d_rgba_out, void *d_rgb_f32_out /* nullable */, void *stream, xrt_stats *stats_out /* nullable */);
 
+/* ---- the first level of xrt_render_pixels alone: the ray of RT:412-421 and the IntersectionResult of RT:512 for caller-chosen pixels ------
+ * Added within ABI 203: these two exports are additive; no existing struct, field or entry point changed.
+ * What turns a camera into hits on the device: the primary hits of a still that is relit afterwards (xrt_shade_hits, xrt_light_hits), a G-buffer,
+ * the triangle under the mouse, depth or ids for compositing, a training batch of pixels.  Nothing is shaded and the call takes no lights.
+ *   - centres as for xrt_render_pixels: entry i is (centers[2i], centers[2i + 1]), any float is legal, duplicates too.
+ *   - opts->use_multisampling: XRT_MS_OFF (samples = 1) or XRT_MS_FIXED16 (samples = 16: the sixteen level-1 positions exactly as
+ *     xrt_render_pixels takes them).  Record i * samples + s is sample s of entry i.  XRT_MS_ADAPTIVE is XRT_E_INVALID_ARG: its quadrants
+ *     depend on colours -- list the sample positions as centres instead.
+ *   - rays_out[r] (nullable, n * samples): o = the unprojected near point, d = the normalised direction, bit for bit the ray xrt_render_pixels
+ *     casts; ignore_mesh = ignore_tri = -1.
+ *   - hits_out[r] (nullable, n * samples): the record xrt_scene_intersect gives for rays_out[r], field for field; `reserved` is scheduling
+ *     feedback and not part of the answer.  A ray that cannot reach the scene's root box gets the miss record: hit 0; object, mesh, tri,
+ *     leaf -1; u, v, d, wx, wy, wz 0.0f.
+ *   - either output may be NULL, not both.  With hits_out == NULL nothing is traced (intersect_launches == 0): the call is then the list and
+ *     device form of xrt_generate_primary_rays.
+ *   - opts->list_order: XRT_LIST_COHERENT says consecutive centres are neighbours on screen; the list is then traced as generation 0 of a plain
+ *     frame of the same scene and sampling would be -- the rays are generated where they are compacted, rays that cannot reach the root box are
+ *     answered there and never traced, the live ones go to the kernel a frame's launch #0 takes (XRT_PACKET overrides as always; materials do not
+ *     enter: a closest-hit query has no ray tree), with the packet table a frame writes (xrt_debug_packet_table reports the table of a hinted
+ *     one-chunk call).  Scheduling only: both outputs and the counters are bit for bit those of the unhinted call, also for a scrambled list.
+ *     A packet is 64 consecutive entries (4 with sixteen samples): a list in compact blocks of the screen (8x8 pixels) costs what a frame's primary
+ *     rays cost, a row-major list more (64x1 strips), a scattered one more than the unhinted call.
+ *   - opts fields read: use_multisampling, list_order, collect_stats, and shard_count / n_gpus (must be 0 or 1).  Everything else is ignored.
+ *     Poses: the latest.  Materials and triangle shading values are not read.
+ *   - identities: xrt_shade_hits(rays_out, hits_out, iteration 0, 1.0f) is xrt_render_pixels with XRT_MS_OFF on the same centres, bit for bit in
+ *     rgba and rgb_f32; with XRT_MS_FIXED16 the sixteen colours folded by the RT:309 mean of means are xrt_render_pixels XRT_MS_FIXED16;
+ *     row-major integer centres give xrt_scene_intersect(xrt_generate_primary_rays).
+ *   - errors, in this order, also on a host-only scene: NULL scene; n < 0; NULL camera or opts; the opts fields above; a viewport that is not
+ *     positive; both outputs NULL with n > 0; NULL centers with n > 0; a non-finite centre (host form: the message names the first one, nothing
+ *     is written) -- all XRT_E_INVALID_ARG.  Then n == 0 returns XRT_OK; then XRT_E_NO_DEVICE / XRT_E_NOT_BUILT; then XRT_E_BUSY under the rule
+ *     of xrt_render_pixels.
+ *   - stats_out (may be NULL): pixels = n; rays_closest = n * samples when hits are asked for; hits_closest; rays_traversed = the rays handed to
+ *     a traversal kernel (unhinted: all of them; hinted: the ones that reach the root box); ms_total, ms_intersect, ms_intersect_longest and
+ *     intersect_launches over the chunks; with collect_stats the reference work counters (and algorithmic_bytes from them).  Everything else 0.
+ *   - a long list is split into chunks under the byte budget of xrt_render_pixels (XRT_PIXEL_BYTES); the answers never depend on the split.
+ * Blocking.  There is no begin/end form. */
+int xrt_trace_pixels(xrt_scene *scene, const xrt_camera *camera, const xrt_render_opts *opts,
+                     const float *centers /* 2 n: x0 y0 x1 y1 .. */, int64_t n,
+                     xrt_ray *rays_out /* nullable, n * samples */, xrt_hit *hits_out /* nullable, n * samples */,
+                     xrt_stats *stats_out /* nullable */);
+
+/* The same on HBM buffers (d_centers: 2 n floats, d_rays_out: NULL or n * samples xrt_ray, d_hits_out: NULL or n * samples xrt_hit; each 16-byte
+ * aligned, else XRT_E_INVALID_ARG -- stated after the errors above), enqueued on `stream` (a hipStream_t; NULL = the scene's stream) and complete
+ * when the call returns: the stream is synchronised once per chunk.  Nothing is written at or behind n * samples records.  The centres must be
+ * ready on `stream`.  They are not inspected: an entry with a non-finite centre gets unspecified records and affects no other entry. */
+int xrt_trace_pixels_device(xrt_scene *scene, const xrt_camera *camera, const xrt_render_opts *opts,
+                            const void *d_centers, int64_t n, void *d_rays_out /* nullable */, void *d_hits_out /* nullable */,
+                            void *stream, xrt_stats *stats_out /* nullable */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,9 @@ SYMBOLS = {
                                     _P(xrt_stats)]),
     "xrt_render_pixels_device": (C.c_int, [C.c_void_p, _P(xrt_camera), _P(xrt_light), C.c_int32, _P(xrt_render_opts), C.c_void_p, C.c_int64,
                                            C.c_void_p, C.c_void_p, C.c_void_p, _P(xrt_stats)]),
+    "xrt_trace_pixels": (C.c_int, [C.c_void_p, _P(xrt_camera), _P(xrt_render_opts), _F, C.c_int64, _P(xrt_ray), _P(xrt_hit), _P(xrt_stats)]),
+    "xrt_trace_pixels_device": (C.c_int, [C.c_void_p, _P(xrt_camera), _P(xrt_render_opts), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          _P(xrt_stats)]),
 }
 
 _lib = None

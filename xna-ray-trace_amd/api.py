@@ -894,6 +894,48 @@ class RayTracer:
         self.last_stats = st.as_dict()
         return (rgba, rgbf) if want_float else rgba
 
+    # ---- the first level of RenderPixels alone: the ray of RT:412-421 and the IntersectionResult of RT:512 per listed pixel: xrt_trace_pixels ----
+    def TracePixels(self, centers, want_rays=True, want_hits=True, fixed16=False, device=False, stream=None, coherent=False):
+        """The primary ray and its closest hit for every screen position of a list, by the tracer's camera; nothing is shaded and no light is
+        read.  fixed16=True: the sixteen level-1 positions around every centre as RenderPixels takes them with MultisampleMode MS_FIXED16
+        (record i * 16 + s is sample s of entry i); the tracer's own multisampling settings are not read.  Host form: `centers` an (n, 2)
+        float32 array -> a RAY_DTYPE array and a HIT_DTYPE array (the one that is wanted alone, or both as a pair).  device=True: `centers` a
+        contiguous CUDA tensor of n float32 pairs -> int32 tensors of 8 words per ray record and 12 words per hit record on its device,
+        enqueued on `stream` (a torch stream, default: the current one).  want_hits=False traces nothing.  coherent=True
+        (xrt_render_opts.list_order = XRT_LIST_COHERENT): consecutive centres are neighbours on screen and the list is traced as a frame's
+        primary rays would be.  Scheduling only: the records and counters are the same."""
+        if not want_rays and not want_hits:
+            raise ValueError("TracePixels: nothing is wanted")
+        cam, opts = self._camera_abi(), self._opts_abi(shard_count=0)
+        opts.n_gpus = 0
+        opts.use_multisampling = abi.MS_FIXED16 if fixed16 else abi.MS_OFF
+        opts.list_order = int(coherent)   # (False / True are XRT_LIST_UNORDERED / XRT_LIST_COHERENT; the library refuses any other value)
+        samples = 16 if fixed16 else 1
+        st, lib = abi.xrt_stats(), abi.lib()
+        if device:
+            import torch
+            if centers.dtype != torch.float32 or not centers.is_contiguous() or centers.numel() % 2:
+                raise ValueError("centers: a contiguous float32 tensor of (x, y) pairs")
+            n = centers.numel() // 2
+            rays = torch.empty((n * samples, 8), dtype=torch.int32, device=centers.device) if want_rays else None
+            hits = torch.empty((n * samples, 12), dtype=torch.int32, device=centers.device) if want_hits else None
+            s = stream if stream is not None else torch.cuda.current_stream(centers.device)
+            abi.check(lib.xrt_trace_pixels_device(self._scene_handle(), C.byref(cam), C.byref(opts), C.c_void_p(centers.data_ptr()), n,
+                                                  C.c_void_p(rays.data_ptr()) if want_rays else None, C.c_void_p(hits.data_ptr()) if want_hits else None,
+                                                  C.c_void_p(s.cuda_stream), C.byref(st)))
+        else:
+            centers = np.ascontiguousarray(centers, dtype=np.float32).reshape(-1, 2)
+            n = centers.shape[0]
+            rays = np.zeros(n * samples, dtype=RAY_DTYPE) if want_rays else None
+            hits = np.zeros(n * samples, dtype=HIT_DTYPE) if want_hits else None
+            abi.check(lib.xrt_trace_pixels(self._scene_handle(), C.byref(cam), C.byref(opts), _fp(centers), n,
+                                           rays.ctypes.data_as(C.POINTER(abi.xrt_ray)) if want_rays else None,
+                                           hits.ctypes.data_as(C.POINTER(abi.xrt_hit)) if want_hits else None, C.byref(st)))
+        self.last_stats = st.as_dict()
+        if want_rays and want_hits:
+            return rays, hits
+        return rays if want_rays else hits
+
     # ---- RayTracer.CastRay (RT:506-737) on caller-given rays: xrt_cast_rays, xrt_cast_rays_paths ----
     def CastRays(self, rays, iteration=0, currentRefIndex=1.0, want_float=False, device=False, stream=None, paths=False, vertex_capacity=None, coherent=False):
         """CastRay(ref rays[i], out color, iteration, origin_i, null, currentRefIndex) for every ray of a batch, origin_i = the ray's

@@ -178,6 +178,19 @@ struct xrt_scene {
         DevBuf<float> lightOut, amountOut;
         Event ev[4];   // a chunk's start and end, its traversal launch's start and end
     } lightWork;
+    // xrt_trace_pixels (trace.hip): the work set of one chunk -- the work rays (the compact live list of a hinted chunk; the whole list where the caller
+    // wants no rays), the whole list again where a hinted call without a ray output counts the reference's work, the count words (live rays, hits), the
+    // queue words of its traversal launch -- and the host form's centres and outputs on the device.  The index list and the packet table of a hinted
+    // chunk are frame context 0's (WorkBufs::index0 / quadTable: where xrt_debug_packet_table looks; no frame is in flight during the call).
+    // Allocated at the first call, freed with the scene.
+    struct TraceWork {
+        DevBuf<xrt_ray> rays, countRays, raysOut;
+        DevBuf<xrt_hit> hitsOut;
+        DevBuf<float> centers;
+        DevBuf<int> counts;
+        DevBuf<unsigned> queue, splitItems, splitRecs;
+        Event ev[4];   // a chunk's start and end, its traversal launch's start and end
+    } traceWork;
     // xrt_cast_rays_paths (paths.hip): staging records of a chunk -- (hit position, tag) and (refraction direction, tag) per (node, path), allocated
     // only when a paths call is made --, the work arrays of the ordering pass, and the host form's copies of the caller's arrays
     DevBuf<f4> pathHit, pathDir;

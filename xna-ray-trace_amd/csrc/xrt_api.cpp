@@ -23,6 +23,8 @@ using namespace xrt;
 #include "hits.h"          // xrt_shade_hits: generation 0 from a caller's hits (hits.hip)
 #include "lights.h"        // xrt_light_hits: the light loop on a caller's hits (lights.hip) ...
 #include "lights_plan.h"   // ... and how a list is split into chunks
+#include "trace.h"         // xrt_trace_pixels: rays and closest hits of a centre list (trace.hip) ...
+#include "trace_plan.h"    // ... and how a list is split into chunks
 
 namespace {
 
@@ -1857,8 +1859,9 @@ int queue_word_for(xrt_scene *s, hipStream_t st, unsigned **word) {
 }
 
 // Caller holds apiMutex.
+// (t0 / t1: events the traversal launch carries where no stats are asked for -- xrt_trace_pixels times its chunks itself)
 int run_intersect(xrt_scene *s, const xrt_ray *d_rays, int64_t n, xrt_hit *d_hits, int mode, int meshId, hipStream_t st, xrt_stats *stats,
-                  bool sync) {
+                  bool sync, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
     if (n > 0x7fffffff / 2) return fail(XRT_E_INVALID_ARG, "too many rays in one call");
     int rc;
     unsigned *queue = nullptr;
@@ -1869,7 +1872,7 @@ int run_intersect(xrt_scene *s, const xrt_ray *d_rays, int64_t n, xrt_hit *d_hit
     IntersectArgs A;
     A.rays = d_rays; A.hits = d_hits; A.index = nullptr; A.nDev = nullptr; A.nMul = 1; A.n = (int)n; A.nCap = 0; A.queue = queue; A.mode = mode; A.meshId = meshId;
     set_knobs(A, s);
-    hipEvent_t a0 = nullptr, a1 = nullptr;
+    hipEvent_t a0 = t0, a1 = t1;
     if (stats) {
         a0 = get_event(s, 0); a1 = get_event(s, 1);
         if (!a0 || !a1) return fail(XRT_E_HIP, "hipEventCreate failed");
@@ -2110,6 +2113,167 @@ int render_pixels_impl(xrt_scene *s, const xrt_camera *cam, const xrt_light *lig
         stats->pieces = 1;
     }
     return rc;
+}
+
+// ---- xrt_trace_pixels: the ray of RT:412-421 and the IntersectionResult of RT:512 for a caller's list of centres ----------------------------------
+// What is wrong with the arguments alone (the scene is not looked at), in the order xrt.h states.
+int trace_check_args(const char *fn, const xrt_camera *cam, const xrt_render_opts *opts, int64_t n) {
+    if (n < 0) return fail(XRT_E_INVALID_ARG, "%s: n = %lld out of range", fn, (long long)n);
+    if (!cam || !opts) return fail(XRT_E_INVALID_ARG, "%s: null camera or opts", fn);
+    const int ms = opts->use_multisampling;
+    if (ms == XRT_MS_ADAPTIVE)
+        return fail(XRT_E_INVALID_ARG, "%s: use_multisampling XRT_MS_ADAPTIVE subdivides by colours, which this call does not make: list the sample positions as centres", fn);
+    if (ms != XRT_MS_OFF && ms != XRT_MS_FIXED16) return fail(XRT_E_INVALID_ARG, "%s: use_multisampling must be XRT_MS_OFF or XRT_MS_FIXED16", fn);
+    if (opts->list_order != XRT_LIST_UNORDERED && opts->list_order != XRT_LIST_COHERENT) return fail(XRT_E_INVALID_ARG, "%s: list_order must be XRT_LIST_UNORDERED or XRT_LIST_COHERENT", fn);
+    if (opts->shard_count < 0 || opts->shard_count > 1) return fail(XRT_E_INVALID_ARG, "%s: shard_count must be 0 or 1", fn);
+    if (opts->n_gpus < 0 || opts->n_gpus > 1) return fail(XRT_E_INVALID_ARG, "%s: n_gpus must be 0 or 1", fn);
+    if (cam->vp_width <= 0 || cam->vp_height <= 0) return fail(XRT_E_INVALID_ARG, "%s: viewport must be positive", fn);
+    return XRT_OK;
+}
+
+// n > 0 centres in HBM (interleaved x y); d_rays / d_hits: the caller's arrays, either may be null.  Per chunk (trace_plan.h):
+//   unhinted -- k_pixel_rays into the caller's rays (or the work buffer), then run_intersect's launch, as xrt_scene_intersect traces;
+//   hinted (XRT_LIST_COHERENT, hits wanted) -- k_trace_raygen answers the rays that cannot reach the root box and compacts the others, ONE traversal launch
+//   answers those straight into the caller's array (IntersectArgs / PacketArgs::scatter, flags null: full records): the kernel a plain frame of the same
+//   scene and sampling takes for launch #0 -- bit 0 of plan_frame's pkAuto, XRT_PACKET overriding --, with the packet table unless XRT_PK_QUADS=0;
+// the count words come back behind one synchronisation.  The latest poses; no material, no triangle value.  The caller holds the scene (BusyGuard, no frame
+// in flight), which is why a hinted chunk may keep its index list and table in frame context 0's buffers, where xrt_debug_packet_table looks.
+int trace_pixels_impl(xrt_scene *s, const xrt_camera *cam, const xrt_render_opts *opts, const float *d_centers, int64_t n, xrt_ray *d_rays, xrt_hit *d_hits,
+                      hipStream_t st, xrt_stats *stats) {
+    xrt_scene::TraceWork &W = s->traceWork;
+    xrt_scene::FrameCtx &F0 = s->frames[0];
+    int rc;
+    xrt_render_opts o;
+    std::memset(&o, 0, sizeof(o));
+    PixelGenArgs G;
+    if ((rc = make_raygen(cam, &o, G.cam))) return rc;
+    const int samples = opts->use_multisampling == XRT_MS_FIXED16 ? 16 : 1;
+    G.cx = d_centers; G.cy = d_centers + 1; G.stride = 2; G.size = 1.0f; G.mode = samples == 16 ? PIXEL_FIXED16 : PIXEL_ONE;
+    const bool hinted = d_hits && opts->list_order == XRT_LIST_COHERENT;
+    const bool collect = d_hits && stats && opts->collect_stats != 0;
+    // launch #0 of a plain frame (plan_frame): two-level scenes take packets at any sample count, one-body scenes with 16 sub-rays alone
+    const int pkAuto = s->sceneMode == MODE_SCENE ? 23 : (samples >= 16 ? 7 : 0);
+    const int pkMask = !s->packetOk ? 0 : (s->cfg.packetMask >= 0 ? s->cfg.packetMask : pkAuto);
+    const bool packets = hinted && (pkMask & 1) != 0, table = packets && s->cfg.packetQuads;
+    const std::vector<long long> b = trace_chunks(n, samples, (uint64_t)s->cfg.pixelBytes, hinted);
+    const size_t placesCap = (size_t)(b[1] - b[0]) * (size_t)samples;   // (the first chunk is the longest)
+    const size_t tableCap = (placesCap + 63) / 64;
+    if ((rc = W.counts.ensure(4)) || (rc = W.queue.ensure(1 + PACKET_QUEUE_WORDS))) return rc;
+    if ((hinted || !d_rays) && (rc = W.rays.ensure(placesCap))) return rc;
+    if (collect && hinted && !d_rays && (rc = W.countRays.ensure(placesCap))) return rc;
+    if (hinted && (rc = F0.w.index0.ensure(placesCap))) return rc;
+    if (table) {
+        const unsigned *before = F0.w.quadTable.p; const size_t capBefore = F0.w.quadTable.cap;
+        if ((rc = F0.w.quadTable.ensure((size_t)QUAD_HEAD_WORDS + 2 * tableCap))) return rc;
+        if (F0.w.quadTable.p != before || F0.w.quadTable.cap != capBefore) HIPCHECK(hipMemsetAsync(F0.w.quadTable.p, 0, QUAD_HEAD_WORDS * sizeof(unsigned), st));   // (the count words start at zero, ensure_frame_buffers)
+    }
+    if (collect) {
+        if ((rc = s->counters.ensure(2 * C_COUNT + 8))) return rc;
+        HIPCHECK(hipMemsetAsync(s->counters.p, 0, 2 * C_COUNT * sizeof(unsigned long long), st));
+    }
+    for (Event &e : W.ev) if ((rc = e.create(hipEventDefault))) return rc;
+    const int pv = s->poseCur;
+    if ((rc = pose_wait(s, pv, st))) return rc;
+    const SceneView S = pose_view(s, pv);
+    unsigned long long live = 0, found = 0;
+    double msTotal = 0.0, msIntersect = 0.0, msLongest = 0.0;
+    unsigned launches = 0;
+    s->quadCtx = -1; s->quadLive = 0;
+    Range rf("xrt trace pixels");
+    for (size_t c = 0; c + 1 < b.size(); c++) {
+        const long long m = b[c + 1] - b[c];
+        const int P = (int)(m * samples);
+        const size_t at = (size_t)b[c] * (size_t)samples;
+        xrt_ray *const raysOut = d_rays ? d_rays + at : nullptr;
+        xrt_hit *const hitsOut = d_hits ? d_hits + at : nullptr;
+        const xrt_ray *listRays = raysOut;   // the chunk's rays in list order, where somebody has them
+        bool traced = false;
+        G.first = b[c];
+        HIPCHECK(hipMemsetAsync(W.counts.p, 0, 4 * sizeof(int), st));
+        HIPCHECK(hipEventRecord(W.ev[0], st));
+        if (!hinted) {
+            if (!raysOut) listRays = W.rays.p;
+            launch_pixel_rays(G.cam, G.cx, G.cy, G.stride, G.first, (int)m, G.size, G.mode, raysOut ? raysOut : W.rays.p, st);
+            HIPCHECK(hipGetLastError());
+            if (hitsOut) {
+                std::lock_guard<std::mutex> lock(s->apiMutex);   // (run_intersect: the queue word of the stream)
+                if ((rc = run_intersect(s, listRays, P, hitsOut, s->sceneMode, 0, st, nullptr, false, W.ev[2], W.ev[3]))) return rc;
+                traced = true;
+            }
+        } else {
+            HIPCHECK(hipMemsetAsync(W.queue.p, 0, (1 + PACKET_QUEUE_WORDS) * sizeof(unsigned), st));
+            QuadTable Q;
+            if (table) {   // the context's two count words take turns (enqueue_chunk)
+                xrt_scene::WorkBufs &FW = F0.w;
+                FW.quadWord ^= 1;
+                Q.table = reinterpret_cast<uint2 *>(FW.quadTable.p + QUAD_HEAD_WORDS); Q.cap = (int)tableCap;
+                Q.count = FW.quadTable.p + 64 * FW.quadWord; Q.clear = FW.quadTable.p + 64 * (FW.quadWord ^ 1);
+            }
+            launch_trace_raygen(G, S, raysOut, hitsOut, W.rays.p, F0.w.index0.p, W.counts.p, P, P, Q, st);
+            IntersectArgs A = IntersectArgs();
+            A.rays = W.rays.p; A.hits = hitsOut; A.index = nullptr; A.nDev = W.counts.p; A.nMul = 1; A.n = P; A.nCap = P;
+            A.queue = W.queue.p; A.mode = s->sceneMode; A.meshId = 0;
+            A.flags = nullptr; A.missRecords = 0; A.scatter = F0.w.index0.p;   // every traced ray gets its full record, at its place
+            set_knobs(A, s);
+            if (packets) {
+                PacketArgs PA;
+                PA.rays = A.rays; PA.hits = A.hits; PA.flags = nullptr; PA.nDev = A.nDev; PA.nMul = 1; PA.n = P; PA.nCap = P; PA.scatter = A.scatter;
+                if (Q.table) { PA.pkTable = Q.table; PA.pkCount = Q.count; PA.pkCap = Q.cap; }
+                PA.queue = W.queue.p + 1; PA.mode = s->sceneMode; PA.meshId = 0; PA.unmark = 0;
+                PA.staticDiv = s->cfg.packetStaticDiv; PA.grabMax = s->cfg.packetGrabMax; PA.cullMin = s->cfg.packetCullMin;
+                if (s->cfg.packetSplit && s->sceneMode != MODE_SCENE && (rc = split_arena(s, W.splitItems, W.splitRecs, PA, st))) return rc;
+                int grid = s->numCUs * s->blocksPerCUPacket;
+                const long long want = ((long long)P + 255) / 256;
+                if (want < grid) grid = (int)(want < 1 ? 1 : want);
+                launch_packet(S, PA, grid, st, W.ev[2], W.ev[3]);
+            } else launch_intersect(S, A, s->stackNeeded, persistent_grid(s, P), st, W.ev[2], W.ev[3]);
+            traced = true;
+            if (collect && !listRays) {   // the counting pass walks the list, as the unhinted call's does
+                launch_pixel_rays(G.cam, G.cx, G.cy, G.stride, G.first, (int)m, G.size, G.mode, W.countRays.p, st);
+                listRays = W.countRays.p;
+            }
+        }
+        if (hitsOut && stats) launch_trace_hits(hitsOut, P, W.counts.p + 1, st);
+        if (collect) {
+            IntersectArgs K = IntersectArgs();
+            K.rays = listRays; K.hits = nullptr; K.index = nullptr; K.nDev = nullptr; K.nMul = 1; K.n = P; K.nCap = 0; K.queue = nullptr; K.mode = s->sceneMode; K.meshId = 0;
+            set_knobs(K, s);
+            launch_count(S, K, s->counters.p, st);
+        }
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipEventRecord(W.ev[1], st));
+        int hc[2] = {0, 0};
+        HIPCHECK(hipMemcpyAsync(hc, W.counts.p, sizeof(hc), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));   // (the one synchronisation of the chunk)
+        if (hinted && (hc[0] < 0 || hc[0] > P)) return fail(XRT_E_INTERNAL, "xrt_trace_pixels: %d live rays in a chunk of %d places", hc[0], P);
+        live += hitsOut ? (hinted ? (unsigned long long)hc[0] : (unsigned long long)P) : 0ull;
+        found += (unsigned long long)hc[1];
+        float ms = 0.0f;
+        HIPCHECK(hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
+        msTotal += ms;
+        if (traced) {
+            HIPCHECK(hipEventElapsedTime(&ms, W.ev[2], W.ev[3]));
+            msIntersect += ms; msLongest = std::max(msLongest, (double)ms); launches++;
+        }
+        if (table && b.size() == 2) {   // (xrt_debug_packet_table: the table and the index list of a one-chunk call stay in the context until its next frame or list)
+            F0.plan.pkEntries = tableCap;
+            s->quadCtx = 0; s->quadLive = (unsigned long long)hc[0];
+        }
+    }
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        if (collect) {
+            unsigned long long hcnt[2 * C_COUNT];
+            HIPCHECK(hipMemcpy(hcnt, s->counters.p, sizeof(hcnt), hipMemcpyDeviceToHost));
+            fill_stats(stats, hcnt, 0, (unsigned long long)n);
+        }
+        stats->pixels = (uint64_t)n;
+        stats->rays_closest = d_hits ? (uint64_t)n * (uint64_t)samples : 0;
+        stats->hits_closest = found;
+        stats->rays_traversed = live;
+        stats->ms_total = msTotal; stats->ms_intersect = msIntersect; stats->ms_intersect_longest = msLongest; stats->intersect_launches = launches;
+    }
+    return XRT_OK;
 }
 
 // ---- xrt_light_hits: the light loop of CastRay (RT:534-542) on a caller's hits ---------------------------------------------------------------
@@ -3458,6 +3622,56 @@ int xrt_render_pixels_device(xrt_scene *scene, const xrt_camera *camera, const x
         if (!st) st = scene->stream;
         if ((rc = render_pixels_impl(scene, camera, lights, n_lights, opts, (const float *)d_centers, n, (uint32_t *)d_rgba_out, (float *)d_rgb_f32_out, st, stats_out)))
             return rc;
+        return guards_check("end of a pixel list");
+    });
+}
+
+int xrt_trace_pixels(xrt_scene *scene, const xrt_camera *camera, const xrt_render_opts *opts, const float *centers, int64_t n, xrt_ray *rays_out, xrt_hit *hits_out,
+                     xrt_stats *stats_out) {
+    return guarded("xrt_trace_pixels", [&]() -> int {
+        if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_trace_pixels: null scene");
+        int rc;
+        if ((rc = trace_check_args("xrt_trace_pixels", camera, opts, n))) return rc;
+        if (n > 0 && !rays_out && !hits_out) return fail(XRT_E_INVALID_ARG, "xrt_trace_pixels: both outputs are null");
+        if (n > 0 && !centers) return fail(XRT_E_INVALID_ARG, "xrt_trace_pixels: null centers");
+        for (int64_t i = 0; i < 2 * n; i++)
+            if (!std::isfinite(centers[i]))
+                return fail(XRT_E_INVALID_ARG, "xrt_trace_pixels: centre %lld is not finite", (long long)(i / 2));
+        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+        if (n == 0) return XRT_OK;
+        if ((rc = need_device(scene, "xrt_trace_pixels"))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        xrt_scene::TraceWork &W = scene->traceWork;
+        const size_t recs = (size_t)n * (opts->use_multisampling == XRT_MS_FIXED16 ? 16u : 1u);
+        if ((rc = W.centers.ensure((size_t)n * 2)) || (rays_out && (rc = W.raysOut.ensure(recs))) || (hits_out && (rc = W.hitsOut.ensure(recs)))) return rc;
+        HIPCHECK(hipMemcpyAsync(W.centers.p, centers, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, scene->stream));
+        if ((rc = trace_pixels_impl(scene, camera, opts, W.centers.p, n, rays_out ? W.raysOut.p : nullptr, hits_out ? W.hitsOut.p : nullptr, scene->stream, stats_out))) return rc;
+        if (rays_out) HIPCHECK(hipMemcpyAsync(rays_out, W.raysOut.p, recs * sizeof(xrt_ray), hipMemcpyDeviceToHost, scene->stream));
+        if (hits_out) HIPCHECK(hipMemcpyAsync(hits_out, W.hitsOut.p, recs * sizeof(xrt_hit), hipMemcpyDeviceToHost, scene->stream));
+        HIPCHECK(hipStreamSynchronize(scene->stream));
+        return guards_check("end of a pixel list");
+    });
+}
+
+int xrt_trace_pixels_device(xrt_scene *scene, const xrt_camera *camera, const xrt_render_opts *opts, const void *d_centers, int64_t n, void *d_rays_out,
+                            void *d_hits_out, void *stream, xrt_stats *stats_out) {
+    return guarded("xrt_trace_pixels_device", [&]() -> int {
+        if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_trace_pixels_device: null scene");
+        int rc;
+        if ((rc = trace_check_args("xrt_trace_pixels_device", camera, opts, n))) return rc;
+        if (n > 0 && !d_rays_out && !d_hits_out) return fail(XRT_E_INVALID_ARG, "xrt_trace_pixels_device: both outputs are null");
+        if (n > 0 && !d_centers) return fail(XRT_E_INVALID_ARG, "xrt_trace_pixels_device: null centers");
+        if (((uintptr_t)d_centers & 15) || ((uintptr_t)d_rays_out & 15) || ((uintptr_t)d_hits_out & 15))
+            return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
+        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+        if (n == 0) return XRT_OK;
+        if ((rc = need_device(scene, "xrt_trace_pixels_device"))) return rc;
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        hipStream_t st = (hipStream_t)stream;
+        if (!st) st = scene->stream;
+        if ((rc = trace_pixels_impl(scene, camera, opts, (const float *)d_centers, n, (xrt_ray *)d_rays_out, (xrt_hit *)d_hits_out, st, stats_out))) return rc;
         return guards_check("end of a pixel list");
     });
 }
