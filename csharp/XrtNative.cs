@@ -60,6 +60,19 @@ namespace RayTraceProject.Native
     }
 
     [StructLayout(LayoutKind.Sequential)]
+    public struct XrtSurface                        // xrt_surface, 64 B: what CastRay computes at a hit without asking the scene anything (xrt_surface_hits)
+    {
+        public float nx, ny, nz;                    // fragmentNormal (RayTracer.cs:520-531)
+        public float reflectiveness;                // Material.Reflectiveness (RayTracer.cs:584)
+        public float r, g, b;                       // surfaceColor (RayTracer.cs:568-581)
+        public float alpha;                         // triangle.color.W (RayTracer.cs:699)
+        public float u, v;                          // interpolatedUV (RayTracer.cs:570-572)
+        public float refractionIndex, nextRefIndex; // Material.RefractionIndex; n2 of RayTracer.cs:656-667 when Transparent, else currentRefIndex
+        public int flags;                           // 1 hit, 2 Transparent, 4 InterpolateNormals, 8 UseTexture
+        public int reserved0, reserved1, reserved2;
+    }
+
+    [StructLayout(LayoutKind.Sequential)]
     public struct XrtStats
     {
         public ulong raysClosest, raysShadow, hitsClosest, hitsShadow, sceneNodeTests, instanceVisits, meshAabbTests, meshQueries,
@@ -152,6 +165,12 @@ namespace RayTraceProject.Native
                                                                       [Out] float[] lightF32Out, [Out] float[] amountOut, IntPtr stats);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_light_hits_device(IntPtr scene, IntPtr dHits, long n, XrtLight[] lights, int nLights,
                                                                       IntPtr dLightF32Out, IntPtr dAmountOut, IntPtr stream, IntPtr stats);
+        // What CastRay computes at a hit without asking the scene anything: the surface record, the reflected ray (RT:547-559) and the Snell refraction
+        // (RT:656-694) of caller-given hits; rays may be null without a ray output; any output may be null, not all three (additive within ABI 203)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_surface_hits(IntPtr scene, [In] XrtRay[] rays, [In] XrtHit[] hits, long n, float currentRefIndex,
+                                                                      ref XrtRenderOpts opts, [Out] XrtSurface[] surfaceOut, [Out] XrtRay[] reflectOut, [Out] XrtRay[] refractOut, IntPtr stats);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_surface_hits_device(IntPtr scene, IntPtr dRays, IntPtr dHits, long n, float currentRefIndex,
+                                                                      ref XrtRenderOpts opts, IntPtr dSurfaceOut, IntPtr dReflectOut, IntPtr dRefractOut, IntPtr stream, IntPtr stats);
         // SceneObject.Position / Rotation / Scale (SO:51-88) between frames: the dirty bodies' World / InverseWorld / WorldBoundingBox
         // (16 + 16 + 6 floats per id), also while RenderAsync tickets are open; the scene octree stays until xrt_scene_build_tree
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_poses(IntPtr scene, [In] int[] objectIds, int n,

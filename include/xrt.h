@@ -534,6 +534,64 @@ int xrt_light_hits_device(xrt_scene *scene, const void *d_hits, int64_t n,
                           void *d_light_f32_out, void *d_amount_out /* each nullable */, void *stream,
                           xrt_stats *stats_out /* nullable */);
 
+/* ---- what CastRay computes at a hit without asking the scene anything: surface terms and the two rays it casts next ---------------------
+ * Added within ABI 203: one struct and two exports, additive; no existing struct, field or entry point changed.
+ * Behind its query CastRay forms the fragment normal (RT:520-531), the surface colour with its texture lookup (RT:568-581 == RT:711-724), reads
+ * the material terms that weight its composition (Reflectiveness RT:584, color.W RT:699) and builds the reflected ray (RT:547-559) and, on a
+ * Transparent material, the Snell refraction (RT:656-694).  xrt_shade_hits hands these out only inside a colour; xrt_surface_hits hands them out
+ * themselves: a G-buffer (normal, albedo, alpha, reflectiveness, uv) of given hits, and the rays with which a host drives its own recursion --
+ * light with xrt_light_hits, continue with reflect_out / refract_out through xrt_cast_rays or xrt_scene_intersect, compose as RT:584/699/726 do.
+ * For every i, `result` is what RT:512 returned, as for xrt_light_hits:
+ *   hits[i].hit == 0: the query returned false.  The surface record is all zero; both ray records are o = d = 0, ignore_mesh = ignore_tri = -1.
+ *   otherwise mesh, tri, u, v are taken bit for bit (NaN, infinities, -0.0 as given; no other entry is affected).  object, leaf, d and reserved
+ *   are not read.  (wx, wy, wz) is read only for the ray outputs, whose Position it is (RT:548, 692), and of rays[i] only d is read, only for the
+ *   ray outputs (RT:549, 675, 685): `rays` may be NULL when both ray outputs are NULL.
+ * surface_out[i]: normal, color and uv exactly as a frame computes them, LookupUV (MAT:71-160) with opts->address_mode and opts->filtering
+ * included (bilinear filtering reads the premultiplied words); no other field of opts is read.  uv is formed whether or not the material uses
+ * its texture.  next_ref_index is the n2 the nested CastRay of RT:698 receives when the material is Transparent, else current_ref_index.
+ * reflect_out[i] of a hit = (worldPosition, Normalize(Reflect(ray.Direction, fragmentNormal))), ignore = (mesh, tri): origin = result.triangle
+ * (RT:557/559).  It is formed for every hit; the `iteration < MaxReflections` test of RT:545 is the caller's.
+ * refract_out[i] of a hit with XRT_SURF_TRANSPARENT = RT:656-694 with current_ref_index, the System.Math calls in double; a total internal
+ * reflection gives a NaN direction, written as it is; ignore = (mesh, tri).  A hit that is not Transparent gets the record of a miss.
+ * Materials and triangle shading values are the latest, as for xrt_cast_rays; poses are not read (the reference does not transform the normal).
+ * Any output may be NULL, not all three when n > 0; what is not asked for is not loaded or computed.
+ * In this order: XRT_E_INVALID_ARG -- said first, also on a host-only scene -- for a NULL scene or opts, n < 0, all outputs NULL with n > 0, a
+ * needed array NULL (hits; rays with a ray output), and in the host form an entry with hit != 0 whose mesh is not in [0, n_meshes) or whose tri
+ * is not in [0, ntri(mesh)) (the message names the first offending index, nothing is written); n == 0 returns XRT_OK; then XRT_E_NO_DEVICE,
+ * XRT_E_NOT_BUILT, and XRT_E_BUSY under the rule of xrt_cast_rays.  Blocking.
+ * stats_out (may be NULL): pixels = n; shaded_hits the entries treated as hits; ms_total; intersect_launches = 0; everything else 0.
+ * There is no begin / end form, no form for supersampled lists and no view-space depth (it would need a camera). */
+#define XRT_SURF_HIT          1   /* the entry was treated as a hit */
+#define XRT_SURF_TRANSPARENT  2   /* Material.Transparent: refract_out[i] is a ray */
+#define XRT_SURF_INTERPOLATED 4   /* Material.InterpolateNormals */
+#define XRT_SURF_TEXTURED     8   /* Material.UseTexture: color came from LookupUV */
+
+typedef struct xrt_surface {      /* 64 bytes, 16-byte aligned quarters */
+    float   normal[3];            /* fragmentNormal, RT:520-531 */
+    float   reflectiveness;       /* Material.Reflectiveness, RT:584 */
+    float   color[3];             /* surfaceColor, RT:568-581 == RT:711-724 */
+    float   alpha;                /* result.triangle.color.W, RT:699 / RT:491 */
+    float   uv[2];                /* interpolatedUV, RT:570-572, formed whether or not UseTexture */
+    float   refraction_index;     /* Material.RefractionIndex */
+    float   next_ref_index;       /* n2 of RT:656-667 when TRANSPARENT, else current_ref_index */
+    int32_t flags;                /* XRT_SURF_* */
+    int32_t reserved[3];          /* written as 0 */
+} xrt_surface;
+
+int xrt_surface_hits(xrt_scene *scene, const xrt_ray *rays /* nullable without a ray output */, const xrt_hit *hits, int64_t n,
+                     float current_ref_index, const xrt_render_opts *opts,
+                     xrt_surface *surface_out /* nullable, n */, xrt_ray *reflect_out /* nullable, n */,
+                     xrt_ray *refract_out /* nullable, n */, xrt_stats *stats_out /* nullable */);
+
+/* The same on HBM buffers (d_rays: NULL or n xrt_ray, d_hits: n xrt_hit, the outputs NULL or n records each; each 16-byte aligned, else
+ * XRT_E_INVALID_ARG), enqueued on `stream` (a hipStream_t; NULL = the scene's stream) and synchronised once before it returns.  The inputs
+ * must be ready on `stream`.  Nothing is inspected on the host: the kernel range-checks mesh and tri of every entry, and an entry out of range
+ * is treated as a miss -- it affects no other entry and can never address outside the scene's arrays.  No device memory is allocated per call. */
+int xrt_surface_hits_device(xrt_scene *scene, const void *d_rays, const void *d_hits, int64_t n,
+                            float current_ref_index, const xrt_render_opts *opts,
+                            void *d_surface_out, void *d_reflect_out, void *d_refract_out /* each nullable */, void *stream,
+                            xrt_stats *stats_out /* nullable */);
+
 /* ---- seam 3, second half: RayTracer.points (RT:504, 543, 701, 740-747) and CastRay's `ref Ray ray` (RT:692-694) ---------------------
  * Added within ABI 203: one struct and two exports, additive; no existing struct, field or entry point changed.
  * Every CastRay appends line segments to the public list RayTracer.points -- the reference's host draws it over its preview (G1:403-413) --

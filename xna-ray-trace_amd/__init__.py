@@ -7,8 +7,8 @@ Import with importlib (the directory name is not a Python identifier):
 from . import _abi as abi
 from . import xna, fixtures, configs, dist
 from .api import (Material, Mesh, MeshOctree, SceneObject, ISpatialManager, OctreeSpatialManager, Camera, SpotLight,
-                  DirectionalLight, RenderTarget, RayTracer, rays_array, RAY_DTYPE, HIT_DTYPE, NODE_DTYPE, VERTEX_DTYPE)
+                  DirectionalLight, RenderTarget, RayTracer, rays_array, RAY_DTYPE, HIT_DTYPE, NODE_DTYPE, VERTEX_DTYPE, SURFACE_DTYPE)
 
 __all__ = ["abi", "xna", "fixtures", "configs", "dist", "Material", "Mesh", "MeshOctree", "SceneObject", "ISpatialManager",
            "OctreeSpatialManager", "Camera", "SpotLight", "DirectionalLight", "RenderTarget", "RayTracer", "rays_array",
-           "RAY_DTYPE", "HIT_DTYPE", "NODE_DTYPE", "VERTEX_DTYPE"]
+           "RAY_DTYPE", "HIT_DTYPE", "NODE_DTYPE", "VERTEX_DTYPE", "SURFACE_DTYPE"]

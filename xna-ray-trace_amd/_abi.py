@@ -98,6 +98,17 @@ class xrt_path_vertex(C.Structure):   # VertexPositionColor: one end of a segmen
     _fields_ = [("position", C.c_float * 3), ("color", C.c_uint32)]
 
 
+class xrt_surface(C.Structure):   # what CastRay computes at a hit without asking the scene anything (xrt_surface_hits)
+    _fields_ = [("normal", C.c_float * 3), ("reflectiveness", C.c_float), ("color", C.c_float * 3), ("alpha", C.c_float),
+                ("uv", C.c_float * 2), ("refraction_index", C.c_float), ("next_ref_index", C.c_float), ("flags", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+SURF_HIT, SURF_TRANSPARENT, SURF_INTERPOLATED, SURF_TEXTURED = 1, 2, 4, 8   # xrt_surface.flags (XRT_SURF_*)
+# numpy's view of xrt_surface (the fields of the ctypes structure, in order): a list of (name, format, shape) that np.dtype takes
+SURFACE_DTYPE = [("normal", "<f4", 3), ("reflectiveness", "<f4"), ("color", "<f4", 3), ("alpha", "<f4"), ("uv", "<f4", 2),
+                 ("refraction_index", "<f4"), ("next_ref_index", "<f4"), ("flags", "<i4"), ("reserved", "<i4", 3)]
+assert C.sizeof(xrt_surface) == 64
 assert C.sizeof(xrt_path_vertex) == 16
 assert C.sizeof(xrt_ray) == 32 and C.sizeof(xrt_hit) == 48 and C.sizeof(xrt_render_opts) == 48
 XRT_VERSION = 203
@@ -150,6 +161,10 @@ SYMBOLS = {
                                         _P(xrt_render_opts), C.c_void_p, C.c_void_p, C.c_void_p, _P(xrt_stats)]),
     "xrt_light_hits": (C.c_int, [C.c_void_p, _P(xrt_hit), C.c_int64, _P(xrt_light), C.c_int32, _F, _F, _P(xrt_stats)]),
     "xrt_light_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _P(xrt_light), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, _P(xrt_stats)]),
+    "xrt_surface_hits": (C.c_int, [C.c_void_p, _P(xrt_ray), _P(xrt_hit), C.c_int64, C.c_float, _P(xrt_render_opts), _P(xrt_surface), _P(xrt_ray), _P(xrt_ray),
+                                   _P(xrt_stats)]),
+    "xrt_surface_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, _P(xrt_render_opts), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, _P(xrt_stats)]),
     "xrt_cast_rays_paths": (C.c_int, [C.c_void_p, _P(xrt_ray), C.c_int64, C.c_int32, C.c_float, _P(xrt_light), C.c_int32, _P(xrt_render_opts),
                                       _P(C.c_uint32), _F, _P(xrt_ray), _P(C.c_int64), _P(xrt_path_vertex), C.c_int64, _P(C.c_int64), _P(xrt_stats)]),
     "xrt_cast_rays_paths_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, _P(xrt_light), C.c_int32, _P(xrt_render_opts),

@@ -163,6 +163,8 @@ NODE_DTYPE = np.dtype([("bmin", np.float32, 3), ("bmax", np.float32, 3), ("is_le
                        ("dfs_index", np.int32), ("depth", np.int32), ("first_ref", np.int32), ("reserved", np.int32)])
 VERTEX_DTYPE = np.dtype([("position", np.float32, 3), ("color", np.uint32)])   # xrt_path_vertex: VertexPositionColor of RayTracer.points
 assert VERTEX_DTYPE.itemsize == C.sizeof(abi.xrt_path_vertex)
+SURFACE_DTYPE = np.dtype(abi.SURFACE_DTYPE)   # xrt_surface
+assert SURFACE_DTYPE.itemsize == C.sizeof(abi.xrt_surface) == 64
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 48 and NODE_DTYPE.itemsize == C.sizeof(abi.xrt_node_info)
 
 
@@ -1100,6 +1102,55 @@ class RayTracer:
         if want_light and want_amounts:
             return light, amounts
         return light if want_light else amounts
+
+    # ---- what CastRay computes at a hit without asking the scene anything, and the rays it casts next: xrt_surface_hits ----
+    def SurfaceHits(self, hits, rays=None, currentRefIndex=1.0, want_surface=True, want_reflect=False, want_refract=False, device=False, stream=None):
+        """For every hit the surface record (SURFACE_DTYPE: fragment normal RT:520-531, surface colour with its texture lookup RT:568-581,
+        color.W, Reflectiveness, RefractionIndex, uv, the refraction index below the surface, flags), the reflected ray (RT:547-559) and the
+        Snell refraction (RT:656-694, the record of a miss where the material is not Transparent); an entry with hit == 0 gives the zero
+        record and rays of o = d = 0, ignore (-1, -1).  `rays` (the rays that produced the hits; only their directions are read) is needed
+        for the ray outputs alone.  Host form: structured arrays (HIT_DTYPE, RAY_DTYPE) -> SURFACE_DTYPE / RAY_DTYPE arrays.  device=True:
+        contiguous CUDA tensors of n x 12 words (hits) and n 32-byte records (rays) -> torch tensors on their device, float32 (n, 16) for
+        the surface records and (n, 8) for each ray list, enqueued on `stream` (a torch stream, default: the current one).  Returns the
+        outputs that are wanted, in the order (surface, reflect, refract): one alone, or a tuple."""
+        if not (want_surface or want_reflect or want_refract):
+            raise ValueError("SurfaceHits: nothing is wanted")
+        want_rays = want_reflect or want_refract
+        if want_rays and rays is None:
+            raise ValueError("SurfaceHits: the ray outputs need the rays that produced the hits")
+        opts = self._opts_abi()
+        st, lib = abi.xrt_stats(), abi.lib()
+        if device:
+            import torch
+            if not hits.is_contiguous() or hits.element_size() != 4 or hits.numel() % 12:
+                raise ValueError("hits: a contiguous tensor of n x 12 32-bit words (xrt_hit records)")
+            n = hits.numel() // 12
+            if want_rays and (not rays.is_contiguous() or rays.numel() * rays.element_size() != 32 * n or rays.device != hits.device):
+                raise ValueError("rays: a contiguous tensor of n 32-byte xrt_ray records on the hits' device")
+            surf = torch.empty((n, 16), dtype=torch.float32, device=hits.device) if want_surface else None
+            refl = torch.empty((n, 8), dtype=torch.float32, device=hits.device) if want_reflect else None
+            refr = torch.empty((n, 8), dtype=torch.float32, device=hits.device) if want_refract else None
+            s = stream if stream is not None else torch.cuda.current_stream(hits.device)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+            abi.check(lib.xrt_surface_hits_device(self._scene_handle(), ptr(rays) if want_rays else None, ptr(hits), n, float(currentRefIndex), C.byref(opts),
+                                                  ptr(surf), ptr(refl), ptr(refr), C.c_void_p(s.cuda_stream), C.byref(st)))
+        else:
+            hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+            n = hits.shape[0]
+            if want_rays:
+                rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+                if rays.shape[0] != n:
+                    raise ValueError("rays: one xrt_ray per hit")
+            surf = np.zeros(n, dtype=SURFACE_DTYPE) if want_surface else None
+            refl = np.zeros(n, dtype=RAY_DTYPE) if want_reflect else None
+            refr = np.zeros(n, dtype=RAY_DTYPE) if want_refract else None
+            rp = lambda a: a.ctypes.data_as(C.POINTER(abi.xrt_ray)) if a is not None else None
+            abi.check(lib.xrt_surface_hits(self._scene_handle(), rp(rays) if want_rays else None, hits.ctypes.data_as(C.POINTER(abi.xrt_hit)), n,
+                                           float(currentRefIndex), C.byref(opts), surf.ctypes.data_as(C.POINTER(abi.xrt_surface)) if want_surface else None,
+                                           rp(refl), rp(refr), C.byref(st)))
+        self.last_stats = st.as_dict()
+        out = tuple(o for o, w in ((surf, want_surface), (refl, want_reflect), (refr, want_refract)) if w)
+        return out[0] if len(out) == 1 else out
 
     def CastRay(self, ray, iteration=0, origin=None, currentRefIndex=1.0, want_float=False):
         """RT:506: one ray = (position, direction) -> the packed Color (and its float colour vector with want_float).  origin: the

@@ -178,6 +178,14 @@ struct xrt_scene {
         DevBuf<float> lightOut, amountOut;
         Event ev[4];   // a chunk's start and end, its traversal launch's start and end
     } lightWork;
+    // xrt_surface_hits (surface.hip): the counter word of a call, and the host form's outputs on the device (its rays and hits go through
+    // castRays / castHits).  Allocated at the first call, freed with the scene; the device form allocates nothing else.
+    struct SurfaceWork {
+        DevBuf<unsigned long long> count;
+        DevBuf<xrt_surface> surfaceOut;
+        DevBuf<xrt_ray> reflectOut, refractOut;
+        Event ev[2];   // the call's start and end
+    } surfaceWork;
     // xrt_trace_pixels (trace.hip): the work set of one chunk -- the work rays (the compact live list of a hinted chunk; the whole list where the caller
     // wants no rays), the whole list again where a hinted call without a ray output counts the reference's work, the count words (live rays, hits), the
     // queue words of its traversal launch -- and the host form's centres and outputs on the device.  The index list and the packet table of a hinted

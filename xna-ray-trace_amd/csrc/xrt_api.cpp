@@ -25,6 +25,7 @@ using namespace xrt;
 #include "lights_plan.h"   // ... and how a list is split into chunks
 #include "trace.h"         // xrt_trace_pixels: rays and closest hits of a centre list (trace.hip) ...
 #include "trace_plan.h"    // ... and how a list is split into chunks
+#include "surface.h"       // xrt_surface_hits: surface terms and next rays of a caller's hits (surface.hip)
 
 namespace {
 
@@ -2360,6 +2361,47 @@ int light_hits_impl(xrt_scene *s, const xrt_hit *d_hits, int64_t n, const xrt_li
     return XRT_OK;
 }
 
+// ---- xrt_surface_hits: CastRay's surface terms and next rays (RT:520-531, 547-559, 568-581, 656-694) on a caller's hits -----------------------
+// n > 0 hits (and rays, where a ray output is asked) in HBM.  One kernel, k_surface, launched in pieces of at most SURFACE_PIECE entries (an int
+// indexes the entries of a launch; the base offsets are size_t); the counter word comes back behind the call's one synchronisation.  The latest
+// materials and triangle values; poses are not read.  The caller holds the scene (BusyGuard, no frame in flight).
+int surface_hits_impl(xrt_scene *s, const xrt_ray *d_rays, const xrt_hit *d_hits, int64_t n, float curRef, const xrt_render_opts *opts, xrt_surface *d_surface,
+                      xrt_ray *d_reflect, xrt_ray *d_refract, hipStream_t st, xrt_stats *stats) {
+    xrt_scene::SurfaceWork &W = s->surfaceWork;
+    int rc;
+    if ((rc = W.count.ensure(1))) return rc;
+    for (Event &e : W.ev) if ((rc = e.create(hipEventDefault))) return rc;
+    const int mv = s->matCur, sv = s->shadeCur;
+    if ((rc = mat_acquire(s, mv, st)) || (rc = shade_wait(s, sv, st))) return rc;
+    ShadeView V;
+    V.shade = shade_records(s, sv).p; V.materials = mat_records(s, mv).p; V.texels = mat_texels(s, mv).p; V.meshes = s->meshes.p;
+    V.lights = nullptr; V.nLights = 0; V.addressMode = opts->address_mode; V.filtering = opts->filtering;
+    Range rf("xrt surface hits");
+    HIPCHECK(hipMemsetAsync(W.count.p, 0, sizeof(unsigned long long), st));
+    HIPCHECK(hipEventRecord(W.ev[0], st));
+    for (size_t base = 0; base < (size_t)n; base += (size_t)SURFACE_PIECE) {
+        const size_t left = (size_t)n - base;
+        SurfaceArgs A;
+        A.hits = d_hits; A.rays = d_rays; A.base = base; A.n = (int)(left < (size_t)SURFACE_PIECE ? left : (size_t)SURFACE_PIECE);
+        A.nMeshes = (int)s->host->meshes.size(); A.curRef = curRef;
+        A.wantSurface = d_surface ? 1 : 0; A.wantReflect = d_reflect ? 1 : 0; A.wantRefract = d_refract ? 1 : 0;
+        A.surfaceOut = d_surface; A.reflectOut = d_reflect; A.refractOut = d_refract; A.liveCount = W.count.p;
+        launch_surface(V, A, st);
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(W.ev[1], st));
+    unsigned long long live = 0;
+    HIPCHECK(hipMemcpyAsync(&live, W.count.p, sizeof(live), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));   // (the one synchronisation of the call)
+    float ms = 0.0f;
+    HIPCHECK(hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->pixels = (uint64_t)n; stats->shaded_hits = live; stats->ms_total = ms; stats->intersect_launches = 0;
+    }
+    return XRT_OK;
+}
+
 int pose_upload(xrt_scene *scene);
 
 // What is made from the scene octree and the poses (snodes, srefs, objects, scull, the positions of every body's records in scull, the
@@ -3481,6 +3523,78 @@ int xrt_light_hits_device(xrt_scene *scene, const void *d_hits, int64_t n, const
         if (!st) st = scene->stream;
         if ((rc = light_hits_impl(scene, (const xrt_hit *)d_hits, n, lights, n_lights, (float *)d_light_f32_out, (float *)d_amount_out, st, stats_out))) return rc;
         return guards_check("end of a batch of lit hits");
+    });
+}
+
+// What is wrong with the arguments of xrt_surface_hits[_device] alone, in the order the header gives (the scene's device is not looked at).
+static int surface_hits_check_args(const char *fn, const xrt_scene *scene, const void *rays, const void *hits, int64_t n, const xrt_render_opts *opts,
+                                   const void *surface_out, const void *reflect_out, const void *refract_out) {
+    if (!scene) return fail(XRT_E_INVALID_ARG, "%s: null scene", fn);
+    if (!opts) return fail(XRT_E_INVALID_ARG, "%s: null opts", fn);
+    if (n < 0) return fail(XRT_E_INVALID_ARG, "%s: n = %lld out of range", fn, (long long)n);
+    if (n > 0 && !surface_out && !reflect_out && !refract_out) return fail(XRT_E_INVALID_ARG, "%s: all outputs are null", fn);
+    if (n > 0 && !hits) return fail(XRT_E_INVALID_ARG, "%s: null hits", fn);
+    if (n > 0 && !rays && (reflect_out || refract_out)) return fail(XRT_E_INVALID_ARG, "%s: null rays with a ray output", fn);
+    return XRT_OK;
+}
+
+int xrt_surface_hits(xrt_scene *scene, const xrt_ray *rays, const xrt_hit *hits, int64_t n, float current_ref_index, const xrt_render_opts *opts,
+                     xrt_surface *surface_out, xrt_ray *reflect_out, xrt_ray *refract_out, xrt_stats *stats_out) {
+    return guarded("xrt_surface_hits", [&]() -> int {
+        int rc;
+        if ((rc = surface_hits_check_args("xrt_surface_hits", scene, rays, hits, n, opts, surface_out, reflect_out, refract_out))) return rc;
+        // a hit names a triangle of a mesh of the scene, as the query would have (the lists as they were added: known on a host-only scene too)
+        const auto &meshes = scene->host->meshes;
+        for (int64_t i = 0; i < n; i++) {
+            const xrt_hit &h = hits[i];
+            if (h.hit == 0) continue;
+            if (h.mesh < 0 || h.mesh >= (int)meshes.size())
+                return fail(XRT_E_INVALID_ARG, "xrt_surface_hits: hit %lld names mesh %d, which does not exist", (long long)i, h.mesh);
+            if (h.tri < 0 || h.tri >= meshes[(size_t)h.mesh].ntri)
+                return fail(XRT_E_INVALID_ARG, "xrt_surface_hits: hit %lld names triangle %d of mesh %d, which does not exist", (long long)i, h.tri, h.mesh);
+        }
+        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+        if (n == 0) return XRT_OK;
+        if ((rc = need_device(scene, "xrt_surface_hits"))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        xrt_scene::SurfaceWork &W = scene->surfaceWork;
+        const bool wantRays = reflect_out || refract_out;
+        if ((rc = scene->castHits.ensure((size_t)n)) || (wantRays && (rc = scene->castRays.ensure((size_t)n))) || (surface_out && (rc = W.surfaceOut.ensure((size_t)n))) ||
+            (reflect_out && (rc = W.reflectOut.ensure((size_t)n))) || (refract_out && (rc = W.refractOut.ensure((size_t)n))))
+            return rc;
+        HIPCHECK(hipMemcpyAsync(scene->castHits.p, hits, (size_t)n * sizeof(xrt_hit), hipMemcpyHostToDevice, scene->stream));
+        if (wantRays) HIPCHECK(hipMemcpyAsync(scene->castRays.p, rays, (size_t)n * sizeof(xrt_ray), hipMemcpyHostToDevice, scene->stream));
+        if ((rc = surface_hits_impl(scene, wantRays ? scene->castRays.p : nullptr, scene->castHits.p, n, current_ref_index, opts, surface_out ? W.surfaceOut.p : nullptr,
+                                    reflect_out ? W.reflectOut.p : nullptr, refract_out ? W.refractOut.p : nullptr, scene->stream, stats_out)))
+            return rc;
+        if (surface_out) HIPCHECK(hipMemcpyAsync(surface_out, W.surfaceOut.p, (size_t)n * sizeof(xrt_surface), hipMemcpyDeviceToHost, scene->stream));
+        if (reflect_out) HIPCHECK(hipMemcpyAsync(reflect_out, W.reflectOut.p, (size_t)n * sizeof(xrt_ray), hipMemcpyDeviceToHost, scene->stream));
+        if (refract_out) HIPCHECK(hipMemcpyAsync(refract_out, W.refractOut.p, (size_t)n * sizeof(xrt_ray), hipMemcpyDeviceToHost, scene->stream));
+        HIPCHECK(hipStreamSynchronize(scene->stream));
+        return guards_check("end of a batch of surface records");
+    });
+}
+
+int xrt_surface_hits_device(xrt_scene *scene, const void *d_rays, const void *d_hits, int64_t n, float current_ref_index, const xrt_render_opts *opts,
+                            void *d_surface_out, void *d_reflect_out, void *d_refract_out, void *stream, xrt_stats *stats_out) {
+    return guarded("xrt_surface_hits_device", [&]() -> int {
+        int rc;
+        if ((rc = surface_hits_check_args("xrt_surface_hits_device", scene, d_rays, d_hits, n, opts, d_surface_out, d_reflect_out, d_refract_out))) return rc;
+        if (((uintptr_t)d_rays & 15) || ((uintptr_t)d_hits & 15) || ((uintptr_t)d_surface_out & 15) || ((uintptr_t)d_reflect_out & 15) || ((uintptr_t)d_refract_out & 15))
+            return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
+        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+        if (n == 0) return XRT_OK;
+        if ((rc = need_device(scene, "xrt_surface_hits_device"))) return rc;
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        hipStream_t st = (hipStream_t)stream;
+        if (!st) st = scene->stream;
+        const bool wantRays = d_reflect_out || d_refract_out;
+        if ((rc = surface_hits_impl(scene, wantRays ? (const xrt_ray *)d_rays : nullptr, (const xrt_hit *)d_hits, n, current_ref_index, opts, (xrt_surface *)d_surface_out,
+                                    (xrt_ray *)d_reflect_out, (xrt_ray *)d_refract_out, st, stats_out)))
+            return rc;
+        return guards_check("end of a batch of surface records");
     });
 }
 
