@@ -1,6 +1,7 @@
 // host_coherent.cpp -- what xrt_render_opts.list_order == XRT_LIST_COHERENT decides on the host, checked without a device: the byte accounting of a hinted
 // chunk of xrt_render_pixels (csrc/pixels_plan.h: the packet table is part of it), the capacity of that table, and the packet mask plan_frame (csrc/frame_plan.h)
-// gives a hinted batch -- the mask of a frame of the same scene and sampling -- against the mask of an unhinted one.  The scenes are filled by hand as in
+// gives a hinted batch -- the mask of a frame of the same scene and sampling -- against the mask of an unhinted one, and scene_packet_mask / scene_answers_at_emission
+// (the one statement of both rules, read by plan_frame and by the list calls that trace outside a frame) against plan_frame over every scene kind, packetOk and XRT_PACKET.  The scenes are filled by hand as in
 // tests/frame_plan/host_plan.cpp (device -1: no HIP function is called).  Built by `make hostcheck_coherent` (csrc/Makefile) from the library's own sources,
 // host code under ASan and UBSan, and run by tests/test_coherent_cpu.py.  Prints "host_coherent: ok".
 #include <cinttypes>
@@ -149,6 +150,45 @@ static void check_masks(Kind kind, int ms, int packetEnv) {
     CHECK(rc == XRT_OK && fused.pkEntries == 0 && fused.pkMask == frame.pkMask, "%s: XRT_PK_QUADS=0", kn);
 }
 
+// scene_packet_mask (csrc/frame_plan.h), the rule the list calls outside a frame read (xrt_trace_pixels bit 0, xrt_light_hits bit 1), is the mask plan_frame gives a
+// coherent batch of the same sampling -- and, at one ray per entry and bit 0 cleared, an unordered one where XRT_PACKET is not set -- whatever the scene kind, packetOk and XRT_PACKET; and
+// scene_answers_at_emission is the `ae` of a one-chunk batch.  A material version without Transparent materials (no ray tree).
+static int check_scene_masks() {
+    int n = 0;
+    for (Kind kind : {ONE_BODY, TWO_LEVEL})
+        for (bool packetOk : {false, true})
+            for (int env : {-1, 0, 1, 2, 7, 23, 31})
+                for (int samples : {1, 4, 16}) {
+                    xrt_scene s;
+                    fill_scene(s, kind);
+                    s.packetOk = packetOk; s.cfg.packetMask = env;
+                    xrt_light light;
+                    std::memset(&light, 0, sizeof(light));
+                    light.kind = XRT_LIGHT_SPOT; light.direction[1] = -1.0f; light.intensity = 1.0f; light.spot_angle = 1.0f; light.decay_exponent = 1.3f;
+                    const xrt_render_opts ob = opts_of(XRT_MS_OFF);
+                    xrt_ray dummy;
+                    std::memset(&dummy, 0, sizeof(dummy));
+                    BatchSrc b;
+                    b.rays = &dummy; b.n = 64LL * 27 * samples; b.refIndex = 1.0f;
+                    FramePlan plain, hinted;
+                    int rc = plan_frame(s, 0, nullptr, &light, 1, &ob, false, false, 0, 1, true, &b, plain);
+                    CHECK(rc == XRT_OK, "unordered batch: %d", rc);
+                    b.coherent = true; b.samples = samples;
+                    rc = plan_frame(s, 0, nullptr, &light, 1, &ob, false, false, 0, 1, true, &b, hinted);
+                    CHECK(rc == XRT_OK, "coherent batch: %d", rc);
+                    const int mask = scene_packet_mask(s, samples);
+                    CHECK(mask == hinted.pkMask, "kind %d packetOk %d XRT_PACKET %d, %d samples: scene_packet_mask %d, the coherent batch's plan %d", (int)kind, (int)packetOk, env, samples, mask, hinted.pkMask);
+                    // (an unordered batch knows nothing of the sampling its rays were made with: its own is one ray per entry, so a one-body scene's 16-sample rule does not reach it)
+                    if (env < 0) CHECK((scene_packet_mask(s, 1) & ~1) == plain.pkMask, "kind %d packetOk %d, %d samples: scene_packet_mask(1) %d, the unordered batch's plan %d", (int)kind, (int)packetOk, samples, scene_packet_mask(s, 1), plain.pkMask);
+                    if (env < 0 && (kind == TWO_LEVEL || samples < 16)) CHECK((mask & ~1) == plain.pkMask, "kind %d, %d samples: %d against %d", (int)kind, samples, mask, plain.pkMask);
+                    CHECK(mask == (!packetOk ? 0 : (env >= 0 ? env : (kind == TWO_LEVEL ? 23 : (samples >= 16 ? 7 : 0)))), "kind %d packetOk %d XRT_PACKET %d, %d samples: mask %d", (int)kind, (int)packetOk, env, samples, mask);
+                    CHECK(hinted.P == (int)b.n && hinted.ae == scene_answers_at_emission(s) && plain.ae == hinted.ae && hinted.ae == (kind == ONE_BODY),
+                          "kind %d: ae %d / %d, scene_answers_at_emission %d", (int)kind, (int)plain.ae, (int)hinted.ae, (int)scene_answers_at_emission(s));
+                    n++;
+                }
+    return n;
+}
+
 int main() {
     const int modes[3] = {XRT_MS_OFF, XRT_MS_ADAPTIVE, XRT_MS_FIXED16};
     // chunk sizes with the table included
@@ -188,6 +228,7 @@ int main() {
     static_assert(sizeof(xrt_render_opts) == 48 && offsetof(xrt_render_opts, list_order) == 40 && offsetof(xrt_render_opts, reserved) == 44, "xrt_render_opts keeps its size and offsets");
     static_assert(XRT_LIST_UNORDERED == 0 && XRT_LIST_COHERENT == 1 && XRT_VERSION == 203, "xrt.h");
     std::printf("plans %d masks %d\n", plans, masks);
+    std::printf("scene masks %d\n", check_scene_masks());
     if (g_failures) { std::printf("host_coherent: %d FAILED\n", g_failures); return 1; }
     std::printf("host_coherent: ok\n");
     return 0;

@@ -101,3 +101,5 @@ def test_host_program():
     assert "host_coherent: ok" in p.stdout
     m = re.search(r"plans (\d+) masks (\d+)", p.stdout)
     assert m and int(m.group(1)) > 1000 and int(m.group(2)) == 30
+    m = re.search(r"scene masks (\d+)", p.stdout)   # scene_packet_mask against plan_frame: 2 scene kinds x packetOk x 7 settings of XRT_PACKET x 3 samplings
+    assert m and int(m.group(1)) == 2 * 2 * 7 * 3

@@ -83,3 +83,7 @@ struct FramePlan {
 // (cam is not read).  Returns XRT_OK or the code frame_begin reports for the arguments (message in g_err).
 int plan_frame(const xrt_scene &s, int matVersion, const xrt_camera *cam, const xrt_light *lights, int nLights, const xrt_render_opts *opts, bool wantsF32,
                bool hasStream, int part, int nParts, bool heapFastAllowed, const BatchSrc *batch, FramePlan &plan);
+
+// What list calls outside a frame share with that decision (pure, beside plan_frame): pkMask of a plain frame or coherent list of `samples` rays per position; the scene's part of `ae`.
+int scene_packet_mask(const xrt_scene &s, int samples);
+bool scene_answers_at_emission(const xrt_scene &s);

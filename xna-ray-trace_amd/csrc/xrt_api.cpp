@@ -115,6 +115,13 @@ int mat_texel_room(xrt_scene *s, DevBuf<uint32_t> &b, size_t n) {
 
 // ---- triangle-shading versions (xrt_scene_set_triangle_shading) ------------------------------------------------------------
 DevBuf<f4> &shade_records(xrt_scene *s, int v) { return v == 0 ? s->shade : s->shadeVer[v].shade; }
+// What a shading kernel reads of the scene, with the materials of version mv and the triangle values of version sv (the lights and the texture lookup are the call's).
+ShadeView shade_view(xrt_scene *s, int mv, int sv) {
+    ShadeView V;
+    V.shade = shade_records(s, sv).p; V.materials = mat_records(s, mv).p; V.texels = mat_texels(s, mv).p; V.meshes = s->meshes.p;
+    V.lights = nullptr; V.nLights = 0; V.addressMode = XRT_ADDRESS_WRAP; V.filtering = XRT_FILTER_POINT;
+    return V;
+}
 // Work on `st` that reads version v starts after the version's last write (no event: the version holds what the upload left).
 int shade_wait(xrt_scene *s, int v, hipStream_t st) {
     if (s->shadeVer[v].ready) HIPCHECK(hipStreamWaitEvent(st, s->shadeVer[v].ready, 0));
@@ -138,10 +145,39 @@ int persistent_grid(xrt_scene *s, long long nHost, int raysPerBlock = 256) {
     return full;
 }
 
+// Every light is of a kind the kernels know (fn: the entry point the message names, or null).
+int lights_known(const char *fn, const xrt_light *lights, int n) {
+    for (int i = 0; i < n; i++)
+        if (lights[i].kind != XRT_LIGHT_SPOT && lights[i].kind != XRT_LIGHT_DIRECTIONAL)
+            return fn ? fail(XRT_E_INVALID_ARG, "%s: unknown light kind", fn) : fail(XRT_E_INVALID_ARG, "unknown light kind");
+    return XRT_OK;
+}
+
 // The scheduling knobs of a k_intersect launch: the scene's where it derives them (scene_upload), else the switches'.
 void set_knobs(IntersectArgs &a, const xrt_scene *s) {
     a.refillMin = s->refillMin; a.nodeBurst = s->cfg.tune[1]; a.leafBurst = s->cfg.tune[2]; a.coopMax = s->cfg.tune[3];
     a.batchMax = s->cfg.batchMax; a.batchMin = s->cfg.batchMin; a.spreadMin = s->cfg.spreadMin; a.heavyShift = s->heavyShift; a.firstBatch = s->firstBatch;
+}
+
+// The wave-packet launch of the population(s) a per-lane launch would trace (I2: a second segment for the same launch, or null; quads: the packet table written for
+// the first segment, or null): the one place that knows which fields the two argument structs share.  The packet heads sit behind the per-lane head of the launch's
+// queue words.  Tile costs, the split arena and the timing stay with the caller.
+PacketArgs packet_args(const xrt_scene *s, const IntersectArgs &I, const IntersectArgs *I2 = nullptr, const QuadTable *quads = nullptr) {
+    PacketArgs PA;
+    PA.rays = I.rays; PA.hits = I.hits; PA.flags = I.flags; PA.index = I.index; PA.nDev = I.nDev; PA.nMul = I.nMul; PA.n = I.n; PA.nCap = I.nCap; PA.scatter = I.scatter;
+    if (I2) { PA.rays2 = I2->rays; PA.hits2 = I2->hits; PA.flags2 = I2->flags; PA.nDev2 = I2->nDev; PA.nMul2 = I2->nMul; PA.nCap2 = I2->nCap; PA.scatter2 = I2->scatter; }
+    if (quads && quads->table) { PA.pkTable = quads->table; PA.pkCount = quads->count; PA.pkCap = quads->cap; }
+    PA.queue = I.queue + 1; PA.mode = I.mode; PA.meshId = I.meshId; PA.unmark = 0;
+    PA.staticDiv = s->cfg.packetStaticDiv; PA.grabMax = s->cfg.packetGrabMax; PA.cullMin = s->cfg.packetCullMin;
+    return PA;
+}
+
+// ... and its grid: every CU filled, or one block per 256 rays where the host knows (a bound of) their number (nHost >= 0).
+int packet_grid(const xrt_scene *s, int blocksPerCU, long long nHost) {
+    const int full = s->numCUs * blocksPerCU;
+    if (nHost < 0) return full;
+    const long long want = std::max(1LL, (nHost + 255) / 256);
+    return want < full ? (int)want : full;
 }
 
 void fill_stats(xrt_stats *st, const unsigned long long *c /* 2*C_COUNT: closest, shadow */, unsigned long long shaded, unsigned long long pixels) {
@@ -296,6 +332,19 @@ long long tile_of_slot(const xrt_scene &s, const FramePlan &P, long long sl) {
 }
 
 }  // namespace
+
+// The packet mask of a plain (no ray tree) frame or coherent list of `samples` rays per screen position: XRT_PACKET where it is set; else two-level scenes take
+// packets at any sample count and in every generation, one-body scenes with 16 sub-rays alone and in the first two generations (the measurements: plan_frame).
+// The ONE statement of that rule: plan_frame and the list calls that trace outside a frame (xrt_trace_pixels, xrt_light_hits) read it here.
+int scene_packet_mask(const xrt_scene &s, int samples) {
+    return !s.packetOk ? 0 : (s.cfg.packetMask >= 0 ? s.cfg.packetMask : (s.sceneMode == MODE_SCENE ? 23 : (samples >= 16 ? 7 : 0)));
+}
+
+// The scene's part of "answered at emission" (kernels.h ShadeArgs::ae): one body with one mesh that CAN face away from a ray as a whole -- its normal box or its
+// diagonal box does not hold the origin (a fan of normals 50 degrees to either side of (1, 1, 0) holds 0 in every axis interval, not in that of N_x + N_y).
+bool scene_answers_at_emission(const xrt_scene &s) {
+    return s.sceneMode == MODE_SINGLE && s.view.nodeCull != 0 && s.cfg.answerAtEmission && mesh_can_face_away(s.host->arrays.meshes[0]);
+}
 
 // The frame: for every chunk of paths  raygen -> [intersect(closest k + shadow k-1) -> shade(A: k, B: k-1)] x (R+2) -> compose,
 // then resolve (pixel grid, fixed 16 sub-rays) or the quadrant levels of adaptive supersampling (RT:170-311).
@@ -457,9 +506,7 @@ int plan_frame(const xrt_scene &s, int matVersion, const xrt_camera *cam, const 
     // Answered at emission (kernels.h ShadeArgs::ae): plain one-chunk frames of one-body scenes whose mesh CAN face away from a ray as a whole (its normal
     // box or its diagonal box does not hold the origin: traverse.h mesh_can_face_away).  Not with the counting pass -- it counts the reference's work for every query from the ray lists --, not for ray trees.
     // (a batch of one chunk too: what part A answers depends on the hits alone, not on where generation 0 came from)
-    if ((p.fast || (batch && oneChunk && !p.collect)) && !heap && !adaptive && nParts == 1 && s.sceneMode == MODE_SINGLE && s.view.nodeCull != 0 && s.cfg.answerAtEmission) {
-        p.ae = mesh_can_face_away(s.host->arrays.meshes[0]);   // (a fan of normals 50 degrees to either side of (1, 1, 0) holds 0 in every axis interval, not in that of N_x + N_y)
-    }
+    p.ae = (p.fast || (batch && oneChunk && !p.collect)) && !heap && !adaptive && nParts == 1 && scene_answers_at_emission(s);
     // Finished in part A (kernels.h ShadeArgs::finish): such a frame's hits whose shadow rays are all answered at emission take no slot.  Not with path capture --
     // k_paths_capture reads every hit's position from its slot record --, and the lights have to fit part A's bit mask.
     p.finishA = p.ae && !p.capturePaths && nL <= 32 && s.cfg.finishInPartA;
@@ -492,12 +539,11 @@ int plan_frame(const xrt_scene &s, int matVersion, const xrt_camera *cam, const 
     // C4 6.64 -> 4.37 ms per pipelined frame (packets for the first two generations only: 1.78 / 5.0, profiles/r03/packet_masks.txt);
     // one-body scenes: only with 16 sub-rays, and only the first two generations, see above)
     const int pkSamples = (batch && batch->coherent) ? batch->samples : g.samples;   // (a coherent list: the sampling its rays were made with, see below)
-    const int pkAuto = s.sceneMode == MODE_SCENE ? 23 : (pkSamples >= 16 ? 7 : 0);
     // (ray-tree frames -- Transparent materials -- of two-level scenes: the first two generations and the first shadow rays, where the image
     // is big enough for a launch to be more than its floor: G2 at 720p 1.12 -> 0.97 ms, the reference's default scene at 512x512 0.31 ->
     // 0.40 with packets, so not there; packets in every generation of a ray tree are 1.5-3 x slower (profiles/r03/packet_masks_ray_trees.txt))
     const int pkHeap = s.cfg.packetMaskHeap >= 0 ? s.cfg.packetMaskHeap : ((s.sceneMode == MODE_SCENE && (long long)g.width * g.height * g.samples >= 600000LL) ? 7 : 0);
-    const int pkScene = !s.packetOk ? 0 : (heap ? pkHeap : (s.cfg.packetMask >= 0 ? s.cfg.packetMask : pkAuto));
+    const int pkScene = heap ? (s.packetOk ? pkHeap : 0) : scene_packet_mask(s, pkSamples);
     // A batch's generation 0 is in the caller's order, which nothing says is coherent: 64 consecutive rays need not be a patch of the same
     // surface, and a packet of scattered rays walks the union of their paths.  It goes to the per-lane kernel unless XRT_PACKET / XRT_PACKET_HEAP
     // name the packet kernel for it (bit 0; both kernels give the same answers).  Its later generations follow the hits as a frame's do.
@@ -530,8 +576,7 @@ int plan_frame(const xrt_scene &s, int matVersion, const xrt_camera *cam, const 
             p.validPixels += (unsigned long long)w * h;
         }
     }
-    for (int i = 0; i < nL; i++)
-        if (lights[i].kind != XRT_LIGHT_SPOT && lights[i].kind != XRT_LIGHT_DIRECTIONAL) return fail(XRT_E_INVALID_ARG, "unknown light kind");
+    if (int rc = lights_known(nullptr, lights, nL)) return rc;
     plan = p;
     return XRT_OK;
 }
@@ -703,18 +748,14 @@ int FrameJob::pick_timing(int grid, unsigned long long *&stamps, hipEvent_t &a0,
 int FrameJob::launch_packets(const Step &T, const IntersectArgs &I, bool shadow, long long nHost, const IntersectArgs *I2, const QuadTable *quads) {
     const int k = T.k, word = shadow ? 1 : 0, R = P.R, nL = P.nL;
     int rc;
-    PacketArgs PA;
-    PA.rays = I.rays; PA.hits = I.hits; PA.flags = I.flags; PA.index = I.index; PA.nDev = I.nDev; PA.nMul = I.nMul; PA.n = I.n; PA.nCap = I.nCap;
-    PA.scatter = I.scatter;
-    if (quads && quads->table) { PA.pkTable = quads->table; PA.pkCount = quads->count; PA.pkCap = quads->cap; }
-    if (I2) { PA.rays2 = I2->rays; PA.hits2 = I2->hits; PA.flags2 = I2->flags; PA.nDev2 = I2->nDev; PA.nMul2 = I2->nMul; PA.nCap2 = I2->nCap; PA.scatter2 = I2->scatter; }
+    PacketArgs PA = packet_args(s, I, I2, quads);
+    PA.queue += PACKET_QUEUE_WORDS * word;   // (a step's queue words: the per-lane head, the packet heads of its closest-hit rays, those of its shadow rays)
     if (tileCostDev) {   // which tile pays for a packet: the path of its first ray (closest-hit rays: the path list; shadow rays: their hit's slot record)
         PA.tileCost = tileCostDev; PA.tileBase = (int)T.pathBase; PA.tileShift = 9 + (T.gp.samples == 16 ? 4 : (T.gp.samples == 4 ? 2 : 0));
         if (shadow) { PA.slotOf1 = T.slotPrev; PA.nL1 = nL; }
         else PA.pathOf1 = T.pathOfClosest;
         if (I2) { PA.slotOf2 = T.slotPrev; PA.nL2 = nL; }
     }
-    PA.queue = T.q + QW * k + 1 + PACKET_QUEUE_WORDS * word; PA.mode = s->sceneMode; PA.meshId = 0; PA.unmark = 0; PA.staticDiv = s->cfg.packetStaticDiv; PA.grabMax = s->cfg.packetGrabMax; PA.cullMin = s->cfg.packetCullMin;
     if (s->cfg.packetSplit && s->sceneMode != MODE_SCENE) {
         if ((rc = split_arena(s, W.splitItems, W.splitRecs, PA, st))) return rc;
         if (P.fast && !P.adaptive && !P.heap && s->cfg.packetLongUs > 0) {   // plain frames: the packets of launch #k are the same from frame to frame while the camera stands still, and nearly so while it moves
@@ -728,8 +769,7 @@ int FrameJob::launch_packets(const Step &T, const IntersectArgs &I, bool shadow,
             PA.splitLong = s->cfg.packetLongUs; PA.splitBudgetLong = std::max(1, s->cfg.packetBudgetLongUs);
         }
     }
-    int grid = s->numCUs * s->blocksPerCUPacket;
-    if (nHost >= 0) { const long long want = (nHost + 255) / 256; if (want < grid) grid = (int)(want < 1 ? 1 : want); }
+    const int grid = packet_grid(s, s->blocksPerCUPacket, nHost);
     hipEvent_t a0, a1;
     if ((rc = pick_timing(grid, PA.stamps, a0, a1))) return rc;
     launch_packet(S, PA, grid, st, a0, a1);
@@ -1236,8 +1276,7 @@ int frame_begin(xrt_scene *s, xrt_scene::FrameCtx &F, const xrt_camera *cam, con
         W.lightsOnDevice.assign(hl.begin(), hl.begin() + nL);
         W.lightsDevPtr = W.lights.p;
     }
-    ShadeView V;
-    V.shade = shade_records(s, F.shade).p; V.materials = mat_records(s, F.mat).p; V.texels = mat_texels(s, F.mat).p; V.meshes = s->meshes.p;
+    ShadeView V = shade_view(s, F.mat, F.shade);
     V.lights = W.lights.p; V.nLights = nL; V.addressMode = P.addressMode; V.filtering = P.filtering;
     F.ev = 0;
     F.pairs.clear();
@@ -1859,6 +1898,21 @@ int queue_word_for(xrt_scene *s, hipStream_t st, unsigned **word) {
     return XRT_OK;
 }
 
+// THE traversal launch of a list call that traces outside a frame (xrt_trace_pixels, xrt_light_hits): the launch a frame of the scene would make for the same
+// population.  A: the population, filled but for the scheduling knobs; packets: it takes the wave-packet kernel (a bit of scene_packet_mask) -- with the table
+// `quads` where one was written for it and the split arena (items, recs) where walks are split --, else the per-lane kernel; cap: the host's bound of the ray count,
+// which sizes the grid; e0 / e1: the events the launch carries.
+int launch_list_traversal(xrt_scene *s, const SceneView &S, IntersectArgs &A, bool packets, const QuadTable *quads, DevBuf<unsigned> &items, DevBuf<unsigned> &recs,
+                          long long cap, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+    set_knobs(A, s);
+    if (!packets) { launch_intersect(S, A, s->stackNeeded, persistent_grid(s, cap), st, e0, e1); return XRT_OK; }
+    PacketArgs PA = packet_args(s, A, nullptr, quads);
+    if (s->cfg.packetSplit && s->sceneMode != MODE_SCENE)
+        if (int rc = split_arena(s, items, recs, PA, st)) return rc;
+    launch_packet(S, PA, packet_grid(s, s->blocksPerCUPacket, cap), st, e0, e1);
+    return XRT_OK;
+}
+
 // Caller holds apiMutex.
 // (t0 / t1: events the traversal launch carries where no stats are asked for -- xrt_trace_pixels times its chunks itself)
 int run_intersect(xrt_scene *s, const xrt_ray *d_rays, int64_t n, xrt_hit *d_hits, int mode, int meshId, hipStream_t st, xrt_stats *stats,
@@ -1883,16 +1937,12 @@ int run_intersect(xrt_scene *s, const xrt_ray *d_rays, int64_t n, xrt_hit *d_hit
     if ((rc = pose_wait(s, s->poseCur, st))) return rc;
     const bool meshOk = mode != MODE_MESH || (meshId >= 0 && meshId < (int)s->host->meshTrees.size() && !s->host->meshTrees[(size_t)meshId].rootIsLeaf);
     if (n > 0 && s->cfg.packetMask >= 0 && (s->cfg.packetMask & 8) && packet_supported(mode, s->host->arrays.meshDepth, s->host->arrays.sceneDepth) && meshOk) {   // (testing aid: arbitrary batches through the packet kernel)
-        PacketArgs PA;
-        PA.rays = d_rays; PA.hits = d_hits; PA.n = (int)n; PA.queue = queue + 1; PA.mode = mode; PA.meshId = meshId;
+        PacketArgs PA = packet_args(s, A);
         if (s->cfg.packetSplit && mode != MODE_SCENE) {
             auto &ar = s->apiSplit[(int)((queue - s->queues.p) / (1 + PACKET_QUEUE_WORDS))];
             if ((rc = split_arena(s, ar.first, ar.second, PA, st))) return rc;
         }
-        int grid = s->numCUs * packet_blocks_per_cu(mode);
-        const long long want = (n + 255) / 256;
-        if (want < grid) grid = (int)want;
-        launch_packet(S, PA, grid, st, a0, a1);
+        launch_packet(S, PA, packet_grid(s, packet_blocks_per_cu(mode), n), st, a0, a1);   // (the grid of the call's own mode: xrt_mesh_intersect is MODE_MESH whatever the scene)
     } else if (n > 0) launch_intersect(S, A, s->stackNeeded, persistent_grid(s, n), st, a0, a1);
     if (stats) {
         if (n > 0) launch_count(S, A, s->counters.p, st);
@@ -1959,7 +2009,8 @@ int cast_rays_impl(xrt_scene *s, const xrt_ray *d_rays, int64_t n, int32_t itera
 
 // ---- xrt_render_pixels: GetColorForQuadrant / the body of Render's inner loop (RT:215-311, 412-425) on a caller's list of centres ----------
 // What is wrong with the arguments alone (the scene is not looked at): the codes of a frame for the fields a frame reads.
-int pixels_check_args(const char *fn, const xrt_camera *cam, const xrt_light *lights, int32_t nLights, const xrt_render_opts *opts, int64_t n) {
+int pixels_check_args(const char *fn, const xrt_camera *cam, const xrt_light *lights, int32_t nLights, const xrt_render_opts *opts, int64_t n, const void *centers,
+                      const void *rgbaOut) {
     if (n < 0) return fail(XRT_E_INVALID_ARG, "%s: n = %lld out of range", fn, (long long)n);
     if (!cam || !opts || (!lights && nLights > 0) || nLights < 0) return fail(XRT_E_INVALID_ARG, "%s: null argument", fn);
     const int ms = opts->use_multisampling;
@@ -1975,6 +2026,7 @@ int pixels_check_args(const char *fn, const xrt_camera *cam, const xrt_light *li
         return fail(XRT_E_UNSUPPORTED, "MultisampleQuality above 6 (4^7 sub-quadrants per pixel)");
     if (cam->vp_width <= 0 || cam->vp_height <= 0) return fail(XRT_E_INVALID_ARG, "viewport must be positive");
     if (opts->list_order != XRT_LIST_UNORDERED && opts->list_order != XRT_LIST_COHERENT) return fail(XRT_E_INVALID_ARG, "%s: list_order must be XRT_LIST_UNORDERED or XRT_LIST_COHERENT", fn);
+    if (n > 0 && (!centers || !rgbaOut)) return fail(XRT_E_INVALID_ARG, "%s: null argument", fn);
     return XRT_OK;
 }
 
@@ -2014,21 +2066,16 @@ struct PixelsJob {
         for (size_t c = 0; c + 1 < b.size(); c++) {
             const long long m = b[c + 1] - b[c], rays = m * samples;
             int rc;
-            if (hinted) {
-                PixelGenArgs G;
-                G.cam = g; G.cx = cx; G.cy = cy; G.stride = stride; G.first = first + b[c]; G.size = size; G.mode = mode;
-                xrt_stats t;
-                if ((rc = cast_rays_impl(s, nullptr, rays, 0, 1.0f, lights, nL, &oc, d_col + b[c] * samples, d_f32 ? d_f32 + 3 * b[c] * samples : nullptr, st, &t, nullptr, nullptr,
-                                         "xrt_render_pixels", &G)))
-                    return rc;
-                tally(t);
-                continue;
+            PixelGenArgs G;   // (hinted: the pass makes the chunk's rays itself; else they are made here)
+            G.cam = g; G.cx = cx; G.cy = cy; G.stride = stride; G.first = first + b[c]; G.size = size; G.mode = mode;
+            if (!hinted) {
+                if ((rc = s->pixelRays.ensure((size_t)rays))) return rc;
+                launch_pixel_rays(g, cx, cy, stride, first + b[c], (int)m, size, mode, s->pixelRays.p, st);
+                HIPCHECK(hipGetLastError());
             }
-            if ((rc = s->pixelRays.ensure((size_t)rays))) return rc;
-            launch_pixel_rays(g, cx, cy, stride, first + b[c], (int)m, size, mode, s->pixelRays.p, st);
-            HIPCHECK(hipGetLastError());
             xrt_stats t;
-            if ((rc = cast_rays_impl(s, s->pixelRays.p, rays, 0, 1.0f, lights, nL, &oc, d_col + b[c] * samples, d_f32 ? d_f32 + 3 * b[c] * samples : nullptr, st, &t)))
+            if ((rc = cast_rays_impl(s, hinted ? nullptr : s->pixelRays.p, rays, 0, 1.0f, lights, nL, &oc, d_col + b[c] * samples, d_f32 ? d_f32 + 3 * b[c] * samples : nullptr, st, &t,
+                                     nullptr, nullptr, "xrt_render_pixels", hinted ? &G : nullptr)))
                 return rc;
             tally(t);
         }
@@ -2118,7 +2165,7 @@ int render_pixels_impl(xrt_scene *s, const xrt_camera *cam, const xrt_light *lig
 
 // ---- xrt_trace_pixels: the ray of RT:412-421 and the IntersectionResult of RT:512 for a caller's list of centres ----------------------------------
 // What is wrong with the arguments alone (the scene is not looked at), in the order xrt.h states.
-int trace_check_args(const char *fn, const xrt_camera *cam, const xrt_render_opts *opts, int64_t n) {
+int trace_check_args(const char *fn, const xrt_camera *cam, const xrt_render_opts *opts, int64_t n, const void *centers, const void *raysOut, const void *hitsOut) {
     if (n < 0) return fail(XRT_E_INVALID_ARG, "%s: n = %lld out of range", fn, (long long)n);
     if (!cam || !opts) return fail(XRT_E_INVALID_ARG, "%s: null camera or opts", fn);
     const int ms = opts->use_multisampling;
@@ -2129,6 +2176,8 @@ int trace_check_args(const char *fn, const xrt_camera *cam, const xrt_render_opt
     if (opts->shard_count < 0 || opts->shard_count > 1) return fail(XRT_E_INVALID_ARG, "%s: shard_count must be 0 or 1", fn);
     if (opts->n_gpus < 0 || opts->n_gpus > 1) return fail(XRT_E_INVALID_ARG, "%s: n_gpus must be 0 or 1", fn);
     if (cam->vp_width <= 0 || cam->vp_height <= 0) return fail(XRT_E_INVALID_ARG, "%s: viewport must be positive", fn);
+    if (n > 0 && !raysOut && !hitsOut) return fail(XRT_E_INVALID_ARG, "%s: both outputs are null", fn);
+    if (n > 0 && !centers) return fail(XRT_E_INVALID_ARG, "%s: null centers", fn);
     return XRT_OK;
 }
 
@@ -2136,7 +2185,8 @@ int trace_check_args(const char *fn, const xrt_camera *cam, const xrt_render_opt
 //   unhinted -- k_pixel_rays into the caller's rays (or the work buffer), then run_intersect's launch, as xrt_scene_intersect traces;
 //   hinted (XRT_LIST_COHERENT, hits wanted) -- k_trace_raygen answers the rays that cannot reach the root box and compacts the others, ONE traversal launch
 //   answers those straight into the caller's array (IntersectArgs / PacketArgs::scatter, flags null: full records): the kernel a plain frame of the same
-//   scene and sampling takes for launch #0 -- bit 0 of plan_frame's pkAuto, XRT_PACKET overriding --, with the packet table unless XRT_PK_QUADS=0;
+//   scene and sampling takes for launch #0 -- bit 0 of scene_packet_mask, the rule plan_frame reads too --, with the packet table unless XRT_PK_QUADS=0,
+//   through launch_list_traversal;
 // the count words come back behind one synchronisation.  The latest poses; no material, no triangle value.  The caller holds the scene (BusyGuard, no frame
 // in flight), which is why a hinted chunk may keep its index list and table in frame context 0's buffers, where xrt_debug_packet_table looks.
 int trace_pixels_impl(xrt_scene *s, const xrt_camera *cam, const xrt_render_opts *opts, const float *d_centers, int64_t n, xrt_ray *d_rays, xrt_hit *d_hits,
@@ -2152,10 +2202,7 @@ int trace_pixels_impl(xrt_scene *s, const xrt_camera *cam, const xrt_render_opts
     G.cx = d_centers; G.cy = d_centers + 1; G.stride = 2; G.size = 1.0f; G.mode = samples == 16 ? PIXEL_FIXED16 : PIXEL_ONE;
     const bool hinted = d_hits && opts->list_order == XRT_LIST_COHERENT;
     const bool collect = d_hits && stats && opts->collect_stats != 0;
-    // launch #0 of a plain frame (plan_frame): two-level scenes take packets at any sample count, one-body scenes with 16 sub-rays alone
-    const int pkAuto = s->sceneMode == MODE_SCENE ? 23 : (samples >= 16 ? 7 : 0);
-    const int pkMask = !s->packetOk ? 0 : (s->cfg.packetMask >= 0 ? s->cfg.packetMask : pkAuto);
-    const bool packets = hinted && (pkMask & 1) != 0, table = packets && s->cfg.packetQuads;
+    const bool packets = hinted && (scene_packet_mask(*s, samples) & 1) != 0, table = packets && s->cfg.packetQuads;   // (bit 0: launch #0 of a plain frame)
     const std::vector<long long> b = trace_chunks(n, samples, (uint64_t)s->cfg.pixelBytes, hinted);
     const size_t placesCap = (size_t)(b[1] - b[0]) * (size_t)samples;   // (the first chunk is the longest)
     const size_t tableCap = (placesCap + 63) / 64;
@@ -2215,19 +2262,7 @@ int trace_pixels_impl(xrt_scene *s, const xrt_camera *cam, const xrt_render_opts
             A.rays = W.rays.p; A.hits = hitsOut; A.index = nullptr; A.nDev = W.counts.p; A.nMul = 1; A.n = P; A.nCap = P;
             A.queue = W.queue.p; A.mode = s->sceneMode; A.meshId = 0;
             A.flags = nullptr; A.missRecords = 0; A.scatter = F0.w.index0.p;   // every traced ray gets its full record, at its place
-            set_knobs(A, s);
-            if (packets) {
-                PacketArgs PA;
-                PA.rays = A.rays; PA.hits = A.hits; PA.flags = nullptr; PA.nDev = A.nDev; PA.nMul = 1; PA.n = P; PA.nCap = P; PA.scatter = A.scatter;
-                if (Q.table) { PA.pkTable = Q.table; PA.pkCount = Q.count; PA.pkCap = Q.cap; }
-                PA.queue = W.queue.p + 1; PA.mode = s->sceneMode; PA.meshId = 0; PA.unmark = 0;
-                PA.staticDiv = s->cfg.packetStaticDiv; PA.grabMax = s->cfg.packetGrabMax; PA.cullMin = s->cfg.packetCullMin;
-                if (s->cfg.packetSplit && s->sceneMode != MODE_SCENE && (rc = split_arena(s, W.splitItems, W.splitRecs, PA, st))) return rc;
-                int grid = s->numCUs * s->blocksPerCUPacket;
-                const long long want = ((long long)P + 255) / 256;
-                if (want < grid) grid = (int)(want < 1 ? 1 : want);
-                launch_packet(S, PA, grid, st, W.ev[2], W.ev[3]);
-            } else launch_intersect(S, A, s->stackNeeded, persistent_grid(s, P), st, W.ev[2], W.ev[3]);
+            if ((rc = launch_list_traversal(s, S, A, packets, &Q, W.splitItems, W.splitRecs, P, st, W.ev[2], W.ev[3]))) return rc;
             traced = true;
             if (collect && !listRays) {   // the counting pass walks the list, as the unhinted call's does
                 launch_pixel_rays(G.cam, G.cx, G.cy, G.stride, G.first, (int)m, G.size, G.mode, W.countRays.p, st);
@@ -2278,8 +2313,8 @@ int trace_pixels_impl(xrt_scene *s, const xrt_camera *cam, const xrt_render_opts
 }
 
 // ---- xrt_light_hits: the light loop of CastRay (RT:534-542) on a caller's hits ---------------------------------------------------------------
-// n > 0 hits in HBM.  Per chunk (lights_plan.h): k_light_emit lists the shadow rays, ONE traversal launch answers them -- the launch a pass of
-// xrt_cast_rays would make for the shadow rays of its generation 0: the wave-packet kernel where that pass's mask names it for them, else the
+// n > 0 hits in HBM.  Per chunk (lights_plan.h): k_light_emit lists the shadow rays, ONE traversal launch (launch_list_traversal) answers them -- the launch a
+// pass of xrt_cast_rays would make for the shadow rays of its generation 0: the wave-packet kernel where bit 1 of scene_packet_mask names it for them, else the
 // per-lane kernel, with IntersectArgs::scatter / flags --, k_light_fold writes the caller's arrays, and the two count words come back behind one
 // synchronisation.  The latest poses, materials and triangle values.  The caller holds the scene (BusyGuard, no frame in flight).
 int light_hits_impl(xrt_scene *s, const xrt_hit *d_hits, int64_t n, const xrt_light *lights, int32_t nL, float *d_light, float *d_amount, hipStream_t st,
@@ -2299,13 +2334,10 @@ int light_hits_impl(xrt_scene *s, const xrt_hit *d_hits, int64_t n, const xrt_li
     for (int i = 0; i < nL; i++) hl[(size_t)i] = make_light(lights[i]);
     if (nL > 0) HIPCHECK(hipMemcpyAsync(W.lights.p, hl.data(), (size_t)nL * sizeof(LightRec), hipMemcpyHostToDevice, st));
     const SceneView S = pose_view(s, pv);
-    ShadeView V;
-    V.shade = shade_records(s, sv).p; V.materials = mat_records(s, mv).p; V.texels = mat_texels(s, mv).p; V.meshes = s->meshes.p;
-    V.lights = W.lights.p; V.nLights = nL; V.addressMode = XRT_ADDRESS_WRAP; V.filtering = XRT_FILTER_POINT;   // (no texture is looked up)
-    // answered at emission: on the scenes where frames answer (plan_frame: one body with one mesh that CAN face away from a ray as a whole)
-    const bool ae = s->sceneMode == MODE_SINGLE && s->view.nodeCull != 0 && s->cfg.answerAtEmission && mesh_can_face_away(s->host->arrays.meshes[0]);
-    const int pkMask = !s->packetOk ? 0 : (s->cfg.packetMask >= 0 ? s->cfg.packetMask : (s->sceneMode == MODE_SCENE ? 23 : 0));   // (plan_frame's, for a plain batch)
-    const bool packets = (pkMask & 2) != 0;
+    ShadeView V = shade_view(s, mv, sv);   // (no texture is looked up)
+    V.lights = W.lights.p; V.nLights = nL;
+    const bool ae = scene_answers_at_emission(*s);              // on the scenes where frames answer at emission
+    const bool packets = (scene_packet_mask(*s, 1) & 2) != 0;   // (bit 1: the shadow rays of a plain batch, one ray per entry)
     unsigned long long live = 0, traced = 0;
     double msTotal = 0.0, msIntersect = 0.0;
     unsigned launches = 0;
@@ -2324,18 +2356,7 @@ int light_hits_impl(xrt_scene *s, const xrt_hit *d_hits, int64_t n, const xrt_li
             B.rays = W.rays.p; B.hits = W.hits.p; B.index = nullptr; B.nDev = W.counts.p; B.nMul = 1; B.n = 0; B.nCap = E.cap;
             B.queue = W.queue.p; B.mode = s->sceneMode; B.meshId = 0;
             B.flags = W.flags.p; B.missRecords = 0; B.scatter = W.scatter.p;
-            set_knobs(B, s);
-            if (packets) {
-                PacketArgs PA;
-                PA.rays = B.rays; PA.hits = B.hits; PA.flags = B.flags; PA.nDev = B.nDev; PA.nMul = 1; PA.n = 0; PA.nCap = B.nCap; PA.scatter = B.scatter;
-                PA.queue = W.queue.p + 1; PA.mode = s->sceneMode; PA.meshId = 0; PA.unmark = 0;
-                PA.staticDiv = s->cfg.packetStaticDiv; PA.grabMax = s->cfg.packetGrabMax; PA.cullMin = s->cfg.packetCullMin;
-                if (s->cfg.packetSplit && s->sceneMode != MODE_SCENE && (rc = split_arena(s, W.splitItems, W.splitRecs, PA, st))) return rc;
-                int grid = s->numCUs * s->blocksPerCUPacket;
-                const long long want = ((long long)E.cap + 255) / 256;
-                if (want < grid) grid = (int)(want < 1 ? 1 : want);
-                launch_packet(S, PA, grid, st, W.ev[2], W.ev[3]);
-            } else launch_intersect(S, B, s->stackNeeded, persistent_grid(s, E.cap), st, W.ev[2], W.ev[3]);
+            if ((rc = launch_list_traversal(s, S, B, packets, nullptr, W.splitItems, W.splitRecs, E.cap, st, W.ev[2], W.ev[3]))) return rc;
             launches++;
         }
         LightFoldArgs F;
@@ -2373,9 +2394,8 @@ int surface_hits_impl(xrt_scene *s, const xrt_ray *d_rays, const xrt_hit *d_hits
     for (Event &e : W.ev) if ((rc = e.create(hipEventDefault))) return rc;
     const int mv = s->matCur, sv = s->shadeCur;
     if ((rc = mat_acquire(s, mv, st)) || (rc = shade_wait(s, sv, st))) return rc;
-    ShadeView V;
-    V.shade = shade_records(s, sv).p; V.materials = mat_records(s, mv).p; V.texels = mat_texels(s, mv).p; V.meshes = s->meshes.p;
-    V.lights = nullptr; V.nLights = 0; V.addressMode = opts->address_mode; V.filtering = opts->filtering;
+    ShadeView V = shade_view(s, mv, sv);   // (no light is read)
+    V.addressMode = opts->address_mode; V.filtering = opts->filtering;
     Range rf("xrt surface hits");
     HIPCHECK(hipMemsetAsync(W.count.p, 0, sizeof(unsigned long long), st));
     HIPCHECK(hipEventRecord(W.ev[0], st));
@@ -3326,210 +3346,242 @@ int xrt_split_stats(xrt_scene *scene, uint64_t out[4], int32_t reset) {
     });
 }
 
+// ---- the list calls (xrt_cast_rays, xrt_shade_hits, xrt_light_hits, xrt_surface_hits, xrt_cast_rays_paths, xrt_render_pixels, xrt_trace_pixels) -------------
+// Every host form reads: its checks, hold the scene, stage, the *_impl its _device form calls, finish.  What the forms share is below; what differs between the
+// families -- which checks come before the device is asked for, which messages carry the function name, what n == 0 does -- is what is left in them
+// (tests/list_calls/host_list_calls.cpp records all of it).
+}  // extern "C"
+
+namespace {
+
+// An entry point: no exception leaves it, and a null scene is said before anything else, by every one of them.
+template <class F>
+int list_call(const char *fn, const xrt_scene *scene, F &&body) {
+    return guarded(fn, [&]() -> int { return scene ? body(fn) : fail(XRT_E_INVALID_ARG, "%s: null scene", fn); });
+}
+
+// The arguments are in order: the stats start at zero, and a list without entries is done.
+bool empty_list(int64_t n, xrt_stats *stats) {
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    return n == 0;
+}
+
+// A hit names a triangle of a mesh of the scene -- withBody: and a body of the scene that holds that mesh --, as the query would have (the lists as they were
+// added: known on a host-only scene too).  A miss names nothing.
+int hits_name_scene(const char *fn, const xrt_scene *scene, const xrt_hit *hits, int64_t n, bool withBody) {
+    const auto &meshes = scene->host->meshes; const auto &bodies = scene->host->objects;
+    for (int64_t i = 0; i < n; i++) {
+        const xrt_hit &h = hits[i];
+        if (h.hit == 0) continue;
+        if (h.mesh < 0 || h.mesh >= (int)meshes.size()) return fail(XRT_E_INVALID_ARG, "%s: hit %lld names mesh %d, which does not exist", fn, (long long)i, h.mesh);
+        if (h.tri < 0 || h.tri >= meshes[(size_t)h.mesh].ntri)
+            return fail(XRT_E_INVALID_ARG, "%s: hit %lld names triangle %d of mesh %d, which does not exist", fn, (long long)i, h.tri, h.mesh);
+        if (!withBody) continue;
+        if (h.object < 0 || h.object >= (int)bodies.size()) return fail(XRT_E_INVALID_ARG, "%s: hit %lld names body %d, which does not exist", fn, (long long)i, h.object);
+        const std::vector<int> &bm = bodies[(size_t)h.object].meshes;
+        if (std::find(bm.begin(), bm.end(), h.mesh) == bm.end())
+            return fail(XRT_E_INVALID_ARG, "%s: hit %lld names mesh %d, which is not a mesh of body %d", fn, (long long)i, h.mesh, h.object);
+    }
+    return XRT_OK;
+}
+
+// A ray's origin is (mesh id, index in Mesh.Triangles[]) of a triangle of the scene, or null (ignore_tri < 0).
+int rays_name_scene(const char *fn, const xrt_scene *scene, const xrt_ray *rays, int64_t n) {
+    const auto &meshes = scene->host->arrays.meshes;
+    for (int64_t i = 0; i < n; i++) {
+        const xrt_ray &r = rays[i];
+        if (r.ignore_tri < 0) continue;
+        if (r.ignore_mesh < 0 || r.ignore_mesh >= (int)meshes.size() || r.ignore_tri >= meshes[(size_t)r.ignore_mesh].ntri)
+            return fail(XRT_E_INVALID_ARG, "%s: ray %lld names triangle %d of mesh %d, which does not exist", fn, (long long)i, r.ignore_tri, r.ignore_mesh);
+    }
+    return XRT_OK;
+}
+
+int centres_finite(const char *fn, const float *centers, int64_t n) {
+    for (int64_t i = 0; i < 2 * n; i++)
+        if (!std::isfinite(centers[i])) return fail(XRT_E_INVALID_ARG, "%s: centre %lld is not finite", fn, (long long)(i / 2));
+    return XRT_OK;
+}
+
+int aligned16(std::initializer_list<const void *> pointers) {
+    for (const void *p : pointers)
+        if ((uintptr_t)p & 15) return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
+    return XRT_OK;
+}
+
+// The count and the pointers of a ray batch: `always` must not be null, `lists` must not be when there is an entry.
+int batch_check_args(const char *fn, int64_t n, std::initializer_list<const void *> always, std::initializer_list<const void *> lists, const xrt_light *lights,
+                     int32_t n_lights) {
+    if (n < 0 || n > 0x7fffffff / 2) return fail(XRT_E_INVALID_ARG, "%s: n = %lld out of range", fn, (long long)n);
+    bool missing = (!lights && n_lights > 0) || n_lights < 0;
+    for (const void *p : always) missing |= !p;
+    for (const void *p : lists) missing |= n > 0 && !p;
+    return missing ? fail(XRT_E_INVALID_ARG, "%s: null argument", fn) : XRT_OK;
+}
+
+// The scene for the length of a list call: refused while another call or a frame has it.  The call's stream is the caller's, or the scene's.
+struct SceneHold {
+    BusyGuard guard;
+    hipStream_t st;
+    explicit SceneHold(xrt_scene *scene, void *stream = nullptr) : guard(scene), st(stream ? (hipStream_t)stream : scene->stream) {}
+    int refused() const {
+        const bool busy = !guard.owned || guard.s->frames[0].pending || guard.s->frames[1].pending;
+        return busy ? fail(XRT_E_BUSY, "Current render operation not finished.") : XRT_OK;   // RT:62-63
+    }
+    int begin(const char *fn) const { int rc = need_device(guard.s, fn); return rc ? rc : refused(); }   // (the forms that ask for the device last)
+};
+
+// A host form's arrays on their way through the scene's buffers.  in: room for `count` elements and the upload enqueued; out: room, and the download remembered;
+// both hand back the device array, or null for an array the caller did not give (nothing is done for it).  finish: the downloads, ONE synchronisation, the guards.
+// The first thing that fails is kept in `rc` and makes everything after it a no-op.
+struct Staging {
+    hipStream_t st;
+    int rc = XRT_OK;
+    bool any = false;
+    struct Down { void *host; const void *dev; size_t bytes; };
+    std::vector<Down> downs;
+    explicit Staging(hipStream_t stream) : st(stream) {}
+    int copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) { HIPCHECK(hipMemcpyAsync(dst, src, bytes, kind, st)); return XRT_OK; }
+    void down(void *host, const void *dev, size_t bytes) { any = true; if (bytes) downs.push_back({host, dev, bytes}); }
+    template <class T> T *in(DevBuf<T> &buf, const void *host, size_t count) {
+        if (!host || rc) return nullptr;
+        any = true;
+        if ((rc = buf.ensure(count)) == XRT_OK && count) rc = copy(buf.p, host, count * sizeof(T), hipMemcpyHostToDevice);
+        return rc ? nullptr : buf.p;
+    }
+    template <class T> T *out(DevBuf<T> &buf, void *host, size_t count) {
+        if (!host || rc || (rc = buf.ensure(count))) return nullptr;
+        down(host, buf.p, count * sizeof(T));
+        return buf.p;
+    }
+    int finish(const char *label) {
+        if (rc) return rc;
+        for (const Down &d : downs)
+            if ((rc = copy(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost))) return rc;
+        if (any) HIPCHECK(hipStreamSynchronize(st));
+        return guards_check(label);
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
 int xrt_cast_rays(xrt_scene *scene, const xrt_ray *rays, int64_t n, int32_t iteration, float current_ref_index, const xrt_light *lights, int32_t n_lights,
                   const xrt_render_opts *opts, uint32_t *rgba_out, float *rgb_f32_out, xrt_stats *stats_out) {
-    return guarded("xrt_cast_rays", [&]() -> int {
-        int rc = need_device(scene, "xrt_cast_rays");
-        if (rc != XRT_OK) return rc;
-        if (n < 0 || n > 0x7fffffff / 2) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: n = %lld out of range", (long long)n);
-        if (!opts || (n > 0 && (!rays || !rgba_out)) || (!lights && n_lights > 0) || n_lights < 0) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: null argument");
-        // an origin is (mesh id, index in Mesh.Triangles[]) of a triangle of the scene, or null (ignore_tri < 0)
-        const auto &meshes = scene->host->arrays.meshes;
-        for (int64_t i = 0; i < n; i++) {
-            const xrt_ray &r = rays[i];
-            if (r.ignore_tri < 0) continue;
-            if (r.ignore_mesh < 0 || r.ignore_mesh >= (int)meshes.size() || r.ignore_tri >= meshes[(size_t)r.ignore_mesh].ntri)
-                return fail(XRT_E_INVALID_ARG, "xrt_cast_rays: ray %lld names triangle %d of mesh %d, which does not exist", (long long)i, r.ignore_tri, r.ignore_mesh);
-        }
-        BusyGuard guard(scene);
-        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
-        if (n > 0) {
-            if ((rc = scene->castRays.ensure((size_t)n)) || (rc = scene->castRGBA.ensure((size_t)n)) || (rgb_f32_out && (rc = scene->castF32.ensure((size_t)n * 3)))) return rc;
-            HIPCHECK(hipMemcpyAsync(scene->castRays.p, rays, (size_t)n * sizeof(xrt_ray), hipMemcpyHostToDevice, scene->stream));
-        }
-        if ((rc = cast_rays_impl(scene, scene->castRays.p, n, iteration, current_ref_index, lights, n_lights, opts, scene->castRGBA.p,
-                                 rgb_f32_out ? scene->castF32.p : nullptr, scene->stream, stats_out)))
-            return rc;
-        if (n > 0) {
-            HIPCHECK(hipMemcpyAsync(rgba_out, scene->castRGBA.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, scene->stream));
-            if (rgb_f32_out) HIPCHECK(hipMemcpyAsync(rgb_f32_out, scene->castF32.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, scene->stream));
-            HIPCHECK(hipStreamSynchronize(scene->stream));
-        }
-        return guards_check("end of a ray batch");
+    return list_call("xrt_cast_rays", scene, [&](const char *fn) -> int {
+        int rc;
+        if ((rc = need_device(scene, fn))) return rc;   // (this family asks for the device first)
+        if ((rc = batch_check_args(fn, n, {opts}, {rays, rgba_out}, lights, n_lights)) || (rc = rays_name_scene(fn, scene, rays, n))) return rc;
+        SceneHold hold(scene);
+        if ((rc = hold.refused())) return rc;
+        Staging S(hold.st);
+        const xrt_ray *d_rays = nullptr; uint32_t *d_rgba = nullptr; float *d_f32 = nullptr;
+        if (n > 0) { d_rays = S.in(scene->castRays, rays, (size_t)n); d_rgba = S.out(scene->castRGBA, rgba_out, (size_t)n); d_f32 = S.out(scene->castF32, rgb_f32_out, (size_t)n * 3); }
+        if ((rc = S.rc) || (rc = cast_rays_impl(scene, d_rays, n, iteration, current_ref_index, lights, n_lights, opts, d_rgba, d_f32, hold.st, stats_out))) return rc;   // (n == 0 too: its opts are checked)
+        return S.finish("end of a ray batch");
     });
 }
 
 int xrt_cast_rays_device(xrt_scene *scene, const void *d_rays, int64_t n, int32_t iteration, float current_ref_index, const xrt_light *lights,
                          int32_t n_lights, const xrt_render_opts *opts, void *d_rgba_out, void *d_rgb_f32_out, void *stream, xrt_stats *stats_out) {
-    return guarded("xrt_cast_rays_device", [&]() -> int {
-        int rc = need_device(scene, "xrt_cast_rays_device");
-        if (rc != XRT_OK) return rc;
-        if (n < 0 || n > 0x7fffffff / 2) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_device: n = %lld out of range", (long long)n);
-        if (!opts || (n > 0 && (!d_rays || !d_rgba_out)) || (!lights && n_lights > 0) || n_lights < 0) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_device: null argument");
-        if (((uintptr_t)d_rays & 15) || ((uintptr_t)d_rgba_out & 15) || ((uintptr_t)d_rgb_f32_out & 15))
-            return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
-        BusyGuard guard(scene);
-        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
-        hipStream_t st = (hipStream_t)stream;
-        if (!st) st = scene->stream;
-        if ((rc = cast_rays_impl(scene, (const xrt_ray *)d_rays, n, iteration, current_ref_index, lights, n_lights, opts, (uint32_t *)d_rgba_out,
-                                 (float *)d_rgb_f32_out, st, stats_out)))
+    return list_call("xrt_cast_rays_device", scene, [&](const char *fn) -> int {
+        int rc;
+        if ((rc = need_device(scene, fn))) return rc;
+        if ((rc = batch_check_args(fn, n, {opts}, {d_rays, d_rgba_out}, lights, n_lights)) || (rc = aligned16({d_rays, d_rgba_out, d_rgb_f32_out}))) return rc;
+        SceneHold hold(scene, stream);
+        if ((rc = hold.refused()) || (rc = cast_rays_impl(scene, (const xrt_ray *)d_rays, n, iteration, current_ref_index, lights, n_lights, opts, (uint32_t *)d_rgba_out,
+                                                          (float *)d_rgb_f32_out, hold.st, stats_out)))
             return rc;
         return guards_check("end of a ray batch");
     });
 }
 
-// What is wrong with the arguments of xrt_shade_hits[_device] alone, in the order the header gives (the scene's device is not looked at).
-static int shade_hits_check_args(const char *fn, const xrt_scene *scene, const void *rays, const void *hits, int64_t n, int32_t iteration, const xrt_light *lights,
+// What is wrong with the arguments of xrt_shade_hits[_device] alone, in the order the header gives (the scene is not looked at).
+static int shade_hits_check_args(const char *fn, const void *rays, const void *hits, int64_t n, int32_t iteration, const xrt_light *lights,
                                  int32_t n_lights, const xrt_render_opts *opts, const void *rgba_out) {
-    if (!scene) return fail(XRT_E_INVALID_ARG, "%s: null scene", fn);
-    if (n < 0 || n > 0x7fffffff / 2) return fail(XRT_E_INVALID_ARG, "%s: n = %lld out of range", fn, (long long)n);
-    if (!opts || (n > 0 && (!rays || !hits || !rgba_out)) || (!lights && n_lights > 0) || n_lights < 0) return fail(XRT_E_INVALID_ARG, "%s: null argument", fn);
+    if (int rc = batch_check_args(fn, n, {opts}, {rays, hits, rgba_out}, lights, n_lights)) return rc;
     return batch_check_opts(fn, opts, iteration);
-}
-// ... and with its lights, once there is something to shade (n > 0)
-static int shade_hits_check_lights(const xrt_light *lights, int32_t n_lights) {
-    for (int i = 0; i < n_lights; i++)
-        if (lights[i].kind != XRT_LIGHT_SPOT && lights[i].kind != XRT_LIGHT_DIRECTIONAL) return fail(XRT_E_INVALID_ARG, "unknown light kind");
-    return XRT_OK;
 }
 
 int xrt_shade_hits(xrt_scene *scene, const xrt_ray *rays, const xrt_hit *hits, int64_t n, int32_t iteration, float current_ref_index, const xrt_light *lights,
                    int32_t n_lights, const xrt_render_opts *opts, uint32_t *rgba_out, float *rgb_f32_out, xrt_stats *stats_out) {
-    return guarded("xrt_shade_hits", [&]() -> int {
+    return list_call("xrt_shade_hits", scene, [&](const char *fn) -> int {
         int rc;
-        if ((rc = shade_hits_check_args("xrt_shade_hits", scene, rays, hits, n, iteration, lights, n_lights, opts, rgba_out))) return rc;
-        // a hit names a triangle of a mesh of a body of the scene, as the query would have (the lists as they were added: known on a host-only scene too)
-        const auto &meshes = scene->host->meshes;
-        const auto &bodies = scene->host->objects;
-        for (int64_t i = 0; i < n; i++) {
-            const xrt_hit &h = hits[i];
-            if (h.hit == 0) continue;
-            if (h.mesh < 0 || h.mesh >= (int)meshes.size())
-                return fail(XRT_E_INVALID_ARG, "xrt_shade_hits: hit %lld names mesh %d, which does not exist", (long long)i, h.mesh);
-            if (h.tri < 0 || h.tri >= meshes[(size_t)h.mesh].ntri)
-                return fail(XRT_E_INVALID_ARG, "xrt_shade_hits: hit %lld names triangle %d of mesh %d, which does not exist", (long long)i, h.tri, h.mesh);
-            if (h.object < 0 || h.object >= (int)bodies.size())
-                return fail(XRT_E_INVALID_ARG, "xrt_shade_hits: hit %lld names body %d, which does not exist", (long long)i, h.object);
-            const std::vector<int> &bm = bodies[(size_t)h.object].meshes;
-            if (std::find(bm.begin(), bm.end(), h.mesh) == bm.end())
-                return fail(XRT_E_INVALID_ARG, "xrt_shade_hits: hit %lld names mesh %d, which is not a mesh of body %d", (long long)i, h.mesh, h.object);
-        }
-        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
-        if (n == 0) return XRT_OK;
-        if ((rc = shade_hits_check_lights(lights, n_lights))) return rc;
-        if ((rc = need_device(scene, "xrt_shade_hits"))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
-        BusyGuard guard(scene);
-        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
-        if ((rc = scene->castRays.ensure((size_t)n)) || (rc = scene->castHits.ensure((size_t)n)) || (rc = scene->castRGBA.ensure((size_t)n)) ||
-            (rgb_f32_out && (rc = scene->castF32.ensure((size_t)n * 3))))
-            return rc;
-        HIPCHECK(hipMemcpyAsync(scene->castRays.p, rays, (size_t)n * sizeof(xrt_ray), hipMemcpyHostToDevice, scene->stream));
-        HIPCHECK(hipMemcpyAsync(scene->castHits.p, hits, (size_t)n * sizeof(xrt_hit), hipMemcpyHostToDevice, scene->stream));
-        if ((rc = cast_rays_impl(scene, scene->castRays.p, n, iteration, current_ref_index, lights, n_lights, opts, scene->castRGBA.p,
-                                 rgb_f32_out ? scene->castF32.p : nullptr, scene->stream, stats_out, nullptr, scene->castHits.p, "xrt_shade_hits")))
-            return rc;
-        HIPCHECK(hipMemcpyAsync(rgba_out, scene->castRGBA.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, scene->stream));
-        if (rgb_f32_out) HIPCHECK(hipMemcpyAsync(rgb_f32_out, scene->castF32.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, scene->stream));
-        HIPCHECK(hipStreamSynchronize(scene->stream));
-        return guards_check("end of a batch of hits");
+        if ((rc = shade_hits_check_args(fn, rays, hits, n, iteration, lights, n_lights, opts, rgba_out)) || (rc = hits_name_scene(fn, scene, hits, n, true))) return rc;
+        if (empty_list(n, stats_out)) return XRT_OK;
+        if ((rc = lights_known(nullptr, lights, n_lights))) return rc;   // (its lights, once there is something to shade)
+        SceneHold hold(scene);
+        if ((rc = hold.begin(fn))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
+        Staging S(hold.st);
+        const xrt_ray *d_rays = S.in(scene->castRays, rays, (size_t)n); const xrt_hit *d_hits = S.in(scene->castHits, hits, (size_t)n);
+        uint32_t *d_rgba = S.out(scene->castRGBA, rgba_out, (size_t)n); float *d_f32 = S.out(scene->castF32, rgb_f32_out, (size_t)n * 3);
+        if ((rc = S.rc) || (rc = cast_rays_impl(scene, d_rays, n, iteration, current_ref_index, lights, n_lights, opts, d_rgba, d_f32, hold.st, stats_out, nullptr, d_hits, fn))) return rc;
+        return S.finish("end of a batch of hits");
     });
 }
 
 int xrt_shade_hits_device(xrt_scene *scene, const void *d_rays, const void *d_hits, int64_t n, int32_t iteration, float current_ref_index, const xrt_light *lights,
                           int32_t n_lights, const xrt_render_opts *opts, void *d_rgba_out, void *d_rgb_f32_out, void *stream, xrt_stats *stats_out) {
-    return guarded("xrt_shade_hits_device", [&]() -> int {
+    return list_call("xrt_shade_hits_device", scene, [&](const char *fn) -> int {
         int rc;
-        if ((rc = shade_hits_check_args("xrt_shade_hits_device", scene, d_rays, d_hits, n, iteration, lights, n_lights, opts, d_rgba_out))) return rc;
-        if (((uintptr_t)d_rays & 15) || ((uintptr_t)d_hits & 15) || ((uintptr_t)d_rgba_out & 15) || ((uintptr_t)d_rgb_f32_out & 15))
-            return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
-        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
-        if (n == 0) return XRT_OK;
-        if ((rc = shade_hits_check_lights(lights, n_lights))) return rc;
-        if ((rc = need_device(scene, "xrt_shade_hits_device"))) return rc;
-        BusyGuard guard(scene);
-        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
-        hipStream_t st = (hipStream_t)stream;
-        if (!st) st = scene->stream;
-        if ((rc = cast_rays_impl(scene, (const xrt_ray *)d_rays, n, iteration, current_ref_index, lights, n_lights, opts, (uint32_t *)d_rgba_out,
-                                 (float *)d_rgb_f32_out, st, stats_out, nullptr, (const xrt_hit *)d_hits, "xrt_shade_hits_device")))
+        if ((rc = shade_hits_check_args(fn, d_rays, d_hits, n, iteration, lights, n_lights, opts, d_rgba_out)) ||
+            (rc = aligned16({d_rays, d_hits, d_rgba_out, d_rgb_f32_out})))
+            return rc;
+        if (empty_list(n, stats_out)) return XRT_OK;
+        if ((rc = lights_known(nullptr, lights, n_lights))) return rc;   // (its lights, once there is something to shade)
+        SceneHold hold(scene, stream);
+        if ((rc = hold.begin(fn)) || (rc = cast_rays_impl(scene, (const xrt_ray *)d_rays, n, iteration, current_ref_index, lights, n_lights, opts, (uint32_t *)d_rgba_out,
+                                                          (float *)d_rgb_f32_out, hold.st, stats_out, nullptr, (const xrt_hit *)d_hits, fn)))
             return rc;
         return guards_check("end of a batch of hits");
     });
 }
 
-// What is wrong with the arguments of xrt_light_hits[_device] alone, in the order the header gives (the scene's device is not looked at).
-static int light_hits_check_args(const char *fn, const xrt_scene *scene, const void *hits, int64_t n, const xrt_light *lights, int32_t n_lights,
+// What is wrong with the arguments of xrt_light_hits[_device] alone, in the order the header gives (the scene is not looked at).
+static int light_hits_check_args(const char *fn, const void *hits, int64_t n, const xrt_light *lights, int32_t n_lights,
                                  const void *light_out, const void *amount_out) {
-    if (!scene) return fail(XRT_E_INVALID_ARG, "%s: null scene", fn);
     if (n < 0) return fail(XRT_E_INVALID_ARG, "%s: n = %lld out of range", fn, (long long)n);
     if (n_lights < 0) return fail(XRT_E_INVALID_ARG, "%s: n_lights = %d out of range", fn, n_lights);
     if (!lights && n_lights > 0) return fail(XRT_E_INVALID_ARG, "%s: null lights", fn);
     if (n > 0 && !light_out && !amount_out) return fail(XRT_E_INVALID_ARG, "%s: both outputs are null", fn);
     if (n > 0 && !hits) return fail(XRT_E_INVALID_ARG, "%s: null hits", fn);
-    for (int i = 0; i < n_lights; i++)
-        if (lights[i].kind != XRT_LIGHT_SPOT && lights[i].kind != XRT_LIGHT_DIRECTIONAL) return fail(XRT_E_INVALID_ARG, "%s: unknown light kind", fn);
-    return XRT_OK;
+    return lights_known(fn, lights, n_lights);
 }
 
 int xrt_light_hits(xrt_scene *scene, const xrt_hit *hits, int64_t n, const xrt_light *lights, int32_t n_lights, float *light_f32_out, float *amount_out,
                    xrt_stats *stats_out) {
-    return guarded("xrt_light_hits", [&]() -> int {
+    return list_call("xrt_light_hits", scene, [&](const char *fn) -> int {
         int rc;
-        if ((rc = light_hits_check_args("xrt_light_hits", scene, hits, n, lights, n_lights, light_f32_out, amount_out))) return rc;
-        // a hit names a triangle of a mesh of the scene, as the query would have (the lists as they were added: known on a host-only scene too)
-        const auto &meshes = scene->host->meshes;
-        for (int64_t i = 0; i < n; i++) {
-            const xrt_hit &h = hits[i];
-            if (h.hit == 0) continue;
-            if (h.mesh < 0 || h.mesh >= (int)meshes.size())
-                return fail(XRT_E_INVALID_ARG, "xrt_light_hits: hit %lld names mesh %d, which does not exist", (long long)i, h.mesh);
-            if (h.tri < 0 || h.tri >= meshes[(size_t)h.mesh].ntri)
-                return fail(XRT_E_INVALID_ARG, "xrt_light_hits: hit %lld names triangle %d of mesh %d, which does not exist", (long long)i, h.tri, h.mesh);
-        }
-        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
-        if (n == 0) return XRT_OK;
-        if ((rc = need_device(scene, "xrt_light_hits"))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
-        BusyGuard guard(scene);
-        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        if ((rc = light_hits_check_args(fn, hits, n, lights, n_lights, light_f32_out, amount_out)) || (rc = hits_name_scene(fn, scene, hits, n, false))) return rc;
+        if (empty_list(n, stats_out)) return XRT_OK;
+        SceneHold hold(scene);
+        if ((rc = hold.begin(fn))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
         xrt_scene::LightWork &W = scene->lightWork;
-        const size_t nAmounts = (size_t)n * (size_t)n_lights;
-        if ((rc = scene->castHits.ensure((size_t)n)) || (light_f32_out && (rc = W.lightOut.ensure((size_t)n * 3))) || (amount_out && (rc = W.amountOut.ensure(nAmounts))))
-            return rc;
-        HIPCHECK(hipMemcpyAsync(scene->castHits.p, hits, (size_t)n * sizeof(xrt_hit), hipMemcpyHostToDevice, scene->stream));
-        if ((rc = light_hits_impl(scene, scene->castHits.p, n, lights, n_lights, light_f32_out ? W.lightOut.p : nullptr, amount_out ? W.amountOut.p : nullptr,
-                                  scene->stream, stats_out)))
-            return rc;
-        if (light_f32_out) HIPCHECK(hipMemcpyAsync(light_f32_out, W.lightOut.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, scene->stream));
-        if (amount_out && nAmounts) HIPCHECK(hipMemcpyAsync(amount_out, W.amountOut.p, nAmounts * sizeof(float), hipMemcpyDeviceToHost, scene->stream));
-        HIPCHECK(hipStreamSynchronize(scene->stream));
-        return guards_check("end of a batch of lit hits");
+        Staging S(hold.st);
+        const xrt_hit *d_hits = S.in(scene->castHits, hits, (size_t)n);
+        float *d_light = S.out(W.lightOut, light_f32_out, (size_t)n * 3), *d_amount = S.out(W.amountOut, amount_out, (size_t)n * (size_t)n_lights);   // (no light: no element)
+        if ((rc = S.rc) || (rc = light_hits_impl(scene, d_hits, n, lights, n_lights, d_light, d_amount, hold.st, stats_out))) return rc;
+        return S.finish("end of a batch of lit hits");
     });
 }
 
 int xrt_light_hits_device(xrt_scene *scene, const void *d_hits, int64_t n, const xrt_light *lights, int32_t n_lights, void *d_light_f32_out, void *d_amount_out,
                           void *stream, xrt_stats *stats_out) {
-    return guarded("xrt_light_hits_device", [&]() -> int {
+    return list_call("xrt_light_hits_device", scene, [&](const char *fn) -> int {
         int rc;
-        if ((rc = light_hits_check_args("xrt_light_hits_device", scene, d_hits, n, lights, n_lights, d_light_f32_out, d_amount_out))) return rc;
-        if (((uintptr_t)d_hits & 15) || ((uintptr_t)d_light_f32_out & 15) || ((uintptr_t)d_amount_out & 15))
-            return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
-        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
-        if (n == 0) return XRT_OK;
-        if ((rc = need_device(scene, "xrt_light_hits_device"))) return rc;
-        BusyGuard guard(scene);
-        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
-        hipStream_t st = (hipStream_t)stream;
-        if (!st) st = scene->stream;
-        if ((rc = light_hits_impl(scene, (const xrt_hit *)d_hits, n, lights, n_lights, (float *)d_light_f32_out, (float *)d_amount_out, st, stats_out))) return rc;
+        if ((rc = light_hits_check_args(fn, d_hits, n, lights, n_lights, d_light_f32_out, d_amount_out)) || (rc = aligned16({d_hits, d_light_f32_out, d_amount_out})))
+            return rc;
+        if (empty_list(n, stats_out)) return XRT_OK;
+        SceneHold hold(scene, stream);
+        if ((rc = hold.begin(fn)) || (rc = light_hits_impl(scene, (const xrt_hit *)d_hits, n, lights, n_lights, (float *)d_light_f32_out, (float *)d_amount_out, hold.st, stats_out))) return rc;
         return guards_check("end of a batch of lit hits");
     });
 }
 
-// What is wrong with the arguments of xrt_surface_hits[_device] alone, in the order the header gives (the scene's device is not looked at).
-static int surface_hits_check_args(const char *fn, const xrt_scene *scene, const void *rays, const void *hits, int64_t n, const xrt_render_opts *opts,
+// What is wrong with the arguments of xrt_surface_hits[_device] alone, in the order the header gives (the scene is not looked at).
+static int surface_hits_check_args(const char *fn, const void *rays, const void *hits, int64_t n, const xrt_render_opts *opts,
                                    const void *surface_out, const void *reflect_out, const void *refract_out) {
-    if (!scene) return fail(XRT_E_INVALID_ARG, "%s: null scene", fn);
     if (!opts) return fail(XRT_E_INVALID_ARG, "%s: null opts", fn);
     if (n < 0) return fail(XRT_E_INVALID_ARG, "%s: n = %lld out of range", fn, (long long)n);
     if (n > 0 && !surface_out && !reflect_out && !refract_out) return fail(XRT_E_INVALID_ARG, "%s: all outputs are null", fn);
@@ -3540,59 +3592,35 @@ static int surface_hits_check_args(const char *fn, const xrt_scene *scene, const
 
 int xrt_surface_hits(xrt_scene *scene, const xrt_ray *rays, const xrt_hit *hits, int64_t n, float current_ref_index, const xrt_render_opts *opts,
                      xrt_surface *surface_out, xrt_ray *reflect_out, xrt_ray *refract_out, xrt_stats *stats_out) {
-    return guarded("xrt_surface_hits", [&]() -> int {
+    return list_call("xrt_surface_hits", scene, [&](const char *fn) -> int {
         int rc;
-        if ((rc = surface_hits_check_args("xrt_surface_hits", scene, rays, hits, n, opts, surface_out, reflect_out, refract_out))) return rc;
-        // a hit names a triangle of a mesh of the scene, as the query would have (the lists as they were added: known on a host-only scene too)
-        const auto &meshes = scene->host->meshes;
-        for (int64_t i = 0; i < n; i++) {
-            const xrt_hit &h = hits[i];
-            if (h.hit == 0) continue;
-            if (h.mesh < 0 || h.mesh >= (int)meshes.size())
-                return fail(XRT_E_INVALID_ARG, "xrt_surface_hits: hit %lld names mesh %d, which does not exist", (long long)i, h.mesh);
-            if (h.tri < 0 || h.tri >= meshes[(size_t)h.mesh].ntri)
-                return fail(XRT_E_INVALID_ARG, "xrt_surface_hits: hit %lld names triangle %d of mesh %d, which does not exist", (long long)i, h.tri, h.mesh);
-        }
-        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
-        if (n == 0) return XRT_OK;
-        if ((rc = need_device(scene, "xrt_surface_hits"))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
-        BusyGuard guard(scene);
-        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        if ((rc = surface_hits_check_args(fn, rays, hits, n, opts, surface_out, reflect_out, refract_out)) || (rc = hits_name_scene(fn, scene, hits, n, false))) return rc;
+        if (empty_list(n, stats_out)) return XRT_OK;
+        SceneHold hold(scene);
+        if ((rc = hold.begin(fn))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
         xrt_scene::SurfaceWork &W = scene->surfaceWork;
-        const bool wantRays = reflect_out || refract_out;
-        if ((rc = scene->castHits.ensure((size_t)n)) || (wantRays && (rc = scene->castRays.ensure((size_t)n))) || (surface_out && (rc = W.surfaceOut.ensure((size_t)n))) ||
-            (reflect_out && (rc = W.reflectOut.ensure((size_t)n))) || (refract_out && (rc = W.refractOut.ensure((size_t)n))))
-            return rc;
-        HIPCHECK(hipMemcpyAsync(scene->castHits.p, hits, (size_t)n * sizeof(xrt_hit), hipMemcpyHostToDevice, scene->stream));
-        if (wantRays) HIPCHECK(hipMemcpyAsync(scene->castRays.p, rays, (size_t)n * sizeof(xrt_ray), hipMemcpyHostToDevice, scene->stream));
-        if ((rc = surface_hits_impl(scene, wantRays ? scene->castRays.p : nullptr, scene->castHits.p, n, current_ref_index, opts, surface_out ? W.surfaceOut.p : nullptr,
-                                    reflect_out ? W.reflectOut.p : nullptr, refract_out ? W.refractOut.p : nullptr, scene->stream, stats_out)))
-            return rc;
-        if (surface_out) HIPCHECK(hipMemcpyAsync(surface_out, W.surfaceOut.p, (size_t)n * sizeof(xrt_surface), hipMemcpyDeviceToHost, scene->stream));
-        if (reflect_out) HIPCHECK(hipMemcpyAsync(reflect_out, W.reflectOut.p, (size_t)n * sizeof(xrt_ray), hipMemcpyDeviceToHost, scene->stream));
-        if (refract_out) HIPCHECK(hipMemcpyAsync(refract_out, W.refractOut.p, (size_t)n * sizeof(xrt_ray), hipMemcpyDeviceToHost, scene->stream));
-        HIPCHECK(hipStreamSynchronize(scene->stream));
-        return guards_check("end of a batch of surface records");
+        Staging S(hold.st);
+        const xrt_hit *d_hits = S.in(scene->castHits, hits, (size_t)n);
+        const xrt_ray *d_rays = S.in(scene->castRays, (reflect_out || refract_out) ? rays : nullptr, (size_t)n);   // (the rays are read for a ray output alone)
+        xrt_surface *d_surface = S.out(W.surfaceOut, surface_out, (size_t)n);
+        xrt_ray *d_reflect = S.out(W.reflectOut, reflect_out, (size_t)n), *d_refract = S.out(W.refractOut, refract_out, (size_t)n);
+        if ((rc = S.rc) || (rc = surface_hits_impl(scene, d_rays, d_hits, n, current_ref_index, opts, d_surface, d_reflect, d_refract, hold.st, stats_out))) return rc;
+        return S.finish("end of a batch of surface records");
     });
 }
 
 int xrt_surface_hits_device(xrt_scene *scene, const void *d_rays, const void *d_hits, int64_t n, float current_ref_index, const xrt_render_opts *opts,
                             void *d_surface_out, void *d_reflect_out, void *d_refract_out, void *stream, xrt_stats *stats_out) {
-    return guarded("xrt_surface_hits_device", [&]() -> int {
+    return list_call("xrt_surface_hits_device", scene, [&](const char *fn) -> int {
         int rc;
-        if ((rc = surface_hits_check_args("xrt_surface_hits_device", scene, d_rays, d_hits, n, opts, d_surface_out, d_reflect_out, d_refract_out))) return rc;
-        if (((uintptr_t)d_rays & 15) || ((uintptr_t)d_hits & 15) || ((uintptr_t)d_surface_out & 15) || ((uintptr_t)d_reflect_out & 15) || ((uintptr_t)d_refract_out & 15))
-            return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
-        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
-        if (n == 0) return XRT_OK;
-        if ((rc = need_device(scene, "xrt_surface_hits_device"))) return rc;
-        BusyGuard guard(scene);
-        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
-        hipStream_t st = (hipStream_t)stream;
-        if (!st) st = scene->stream;
+        if ((rc = surface_hits_check_args(fn, d_rays, d_hits, n, opts, d_surface_out, d_reflect_out, d_refract_out)) ||
+            (rc = aligned16({d_rays, d_hits, d_surface_out, d_reflect_out, d_refract_out})))
+            return rc;
+        if (empty_list(n, stats_out)) return XRT_OK;
+        SceneHold hold(scene, stream);
         const bool wantRays = d_reflect_out || d_refract_out;
-        if ((rc = surface_hits_impl(scene, wantRays ? (const xrt_ray *)d_rays : nullptr, (const xrt_hit *)d_hits, n, current_ref_index, opts, (xrt_surface *)d_surface_out,
-                                    (xrt_ray *)d_reflect_out, (xrt_ray *)d_refract_out, st, stats_out)))
+        if ((rc = hold.begin(fn)) || (rc = surface_hits_impl(scene, wantRays ? (const xrt_ray *)d_rays : nullptr, (const xrt_hit *)d_hits, n, current_ref_index, opts,
+                                                             (xrt_surface *)d_surface_out, (xrt_ray *)d_reflect_out, (xrt_ray *)d_refract_out, hold.st, stats_out)))
             return rc;
         return guards_check("end of a batch of surface records");
     });
@@ -3606,86 +3634,76 @@ static long long paths_bound(const xrt_scene *scene, const xrt_render_opts *opts
     return path_vertex_bound((int)depth, tree) * (long long)n;
 }
 
+// What is wrong with the arguments of xrt_cast_rays_paths[_device] alone; then the scene's device is asked for (before the entries and the alignment are looked at).
+static int paths_check_args(const char *fn, xrt_scene *scene, const void *rays, int64_t n, const xrt_light *lights, int32_t n_lights, const xrt_render_opts *opts,
+                            const void *rgba_out, const void *vertices, int64_t vertex_capacity, const int64_t *n_vertices_out) {
+    if (int rc = batch_check_args(fn, n, {opts, n_vertices_out}, {rays, rgba_out}, lights, n_lights)) return rc;
+    if (vertex_capacity < 0 || (vertex_capacity > 0 && !vertices))
+        return fail(XRT_E_INVALID_ARG, "%s: vertex_capacity = %lld with%s vertices", fn, (long long)vertex_capacity, vertices ? "" : " null");
+    return need_device(scene, fn);
+}
+
 int xrt_cast_rays_paths(xrt_scene *scene, const xrt_ray *rays, int64_t n, int32_t iteration, float current_ref_index, const xrt_light *lights, int32_t n_lights,
                         const xrt_render_opts *opts, uint32_t *rgba_out, float *rgb_f32_out, xrt_ray *rays_back, int64_t *vertex_start, xrt_path_vertex *vertices,
                         int64_t vertex_capacity, int64_t *n_vertices_out, xrt_stats *stats_out) {
-    return guarded("xrt_cast_rays_paths", [&]() -> int {
-        if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths: null scene");
+    return list_call("xrt_cast_rays_paths", scene, [&](const char *fn) -> int {
         int rc;
-        if (n < 0 || n > 0x7fffffff / 2) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths: n = %lld out of range", (long long)n);
-        if (!opts || !n_vertices_out || (n > 0 && (!rays || !rgba_out)) || (!lights && n_lights > 0) || n_lights < 0) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths: null argument");
-        if (vertex_capacity < 0 || (vertex_capacity > 0 && !vertices)) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths: vertex_capacity = %lld with%s vertices", (long long)vertex_capacity, vertices ? "" : " null");
-        if ((rc = need_device(scene, "xrt_cast_rays_paths"))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
-        const auto &meshes = scene->host->arrays.meshes;
-        for (int64_t i = 0; i < n; i++) {   // (an origin names a triangle of the scene, as for xrt_cast_rays)
-            const xrt_ray &r = rays[i];
-            if (r.ignore_tri < 0) continue;
-            if (r.ignore_mesh < 0 || r.ignore_mesh >= (int)meshes.size() || r.ignore_tri >= meshes[(size_t)r.ignore_mesh].ntri)
-                return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths: ray %lld names triangle %d of mesh %d, which does not exist", (long long)i, r.ignore_tri, r.ignore_mesh);
-        }
-        BusyGuard guard(scene);
-        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        if ((rc = paths_check_args(fn, scene, rays, n, lights, n_lights, opts, rgba_out, vertices, vertex_capacity, n_vertices_out)) ||
+            (rc = rays_name_scene(fn, scene, rays, n)))
+            return rc;
+        SceneHold hold(scene);
+        if ((rc = hold.refused())) return rc;
+        Staging S(hold.st);
         BatchSrc::Paths P;
+        const xrt_ray *d_rays = nullptr; uint32_t *d_rgba = nullptr; float *d_f32 = nullptr;
         if (n > 0) {
             // the device never needs more room than the deepest recursion of every ray could fill, whatever capacity the caller names
-            const long long bound = paths_bound(scene, opts, iteration, n);
-            P.capacity = vertices ? std::min<long long>(vertex_capacity, std::max(0LL, bound)) : 0;
-            if ((rc = scene->castRays.ensure((size_t)n)) || (rc = scene->castRGBA.ensure((size_t)n)) || (rgb_f32_out && (rc = scene->castF32.ensure((size_t)n * 3))) ||
-                (rc = scene->pathStart.ensure((size_t)n + 1)) || (rays_back && (rc = scene->pathBack.ensure((size_t)n))) || (P.capacity > 0 && (rc = scene->pathVerts.ensure((size_t)P.capacity))))
-                return rc;
-            P.vertices = P.capacity > 0 ? scene->pathVerts.p : nullptr; P.vertexStart = scene->pathStart.p; P.raysBack = rays_back ? scene->pathBack.p : nullptr;
-            HIPCHECK(hipMemcpyAsync(scene->castRays.p, rays, (size_t)n * sizeof(xrt_ray), hipMemcpyHostToDevice, scene->stream));
+            P.capacity = vertices ? std::min<long long>(vertex_capacity, std::max(0LL, paths_bound(scene, opts, iteration, n))) : 0;
+            d_rays = S.in(scene->castRays, rays, (size_t)n); d_rgba = S.out(scene->castRGBA, rgba_out, (size_t)n); d_f32 = S.out(scene->castF32, rgb_f32_out, (size_t)n * 3);
+            P.raysBack = S.out(scene->pathBack, rays_back, (size_t)n);
+            if (S.rc) return S.rc;
+            // the ordering pass needs the running offsets whether or not the caller wants them; how many vertices come back is known after the pass
+            if ((rc = scene->pathStart.ensure((size_t)n + 1)) || (P.capacity > 0 && (rc = scene->pathVerts.ensure((size_t)P.capacity)))) return rc;
+            P.vertexStart = scene->pathStart.p; P.vertices = P.capacity > 0 ? scene->pathVerts.p : nullptr;
+            if (vertex_start) S.down(vertex_start, scene->pathStart.p, ((size_t)n + 1) * sizeof(int64_t));
         }
-        if ((rc = cast_rays_impl(scene, scene->castRays.p, n, iteration, current_ref_index, lights, n_lights, opts, scene->castRGBA.p,
-                                 rgb_f32_out ? scene->castF32.p : nullptr, scene->stream, stats_out, &P)))
-            return rc;
+        if ((rc = cast_rays_impl(scene, d_rays, n, iteration, current_ref_index, lights, n_lights, opts, d_rgba, d_f32, hold.st, stats_out, &P))) return rc;
         *n_vertices_out = 0;
         if (n == 0 && vertex_start) vertex_start[0] = 0;
         if (n > 0) {
             const long long need = *scene->pathPinned.p;   // (arrived with the pass: cast_rays_impl waited for it)
             *n_vertices_out = need;
             const long long wrote = std::min(need, P.capacity & ~1LL);
-            HIPCHECK(hipMemcpyAsync(rgba_out, scene->castRGBA.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, scene->stream));
-            if (rgb_f32_out) HIPCHECK(hipMemcpyAsync(rgb_f32_out, scene->castF32.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, scene->stream));
-            if (vertex_start) HIPCHECK(hipMemcpyAsync(vertex_start, scene->pathStart.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, scene->stream));
-            if (rays_back) HIPCHECK(hipMemcpyAsync(rays_back, scene->pathBack.p, (size_t)n * sizeof(xrt_ray), hipMemcpyDeviceToHost, scene->stream));
-            if (wrote > 0) HIPCHECK(hipMemcpyAsync(vertices, scene->pathVerts.p, (size_t)wrote * sizeof(xrt_path_vertex), hipMemcpyDeviceToHost, scene->stream));
-            HIPCHECK(hipStreamSynchronize(scene->stream));
+            if (wrote > 0) S.down(vertices, scene->pathVerts.p, (size_t)wrote * sizeof(xrt_path_vertex));
         }
-        return guards_check("end of a ray batch");
+        return S.finish("end of a ray batch");
     });
 }
 
 int xrt_cast_rays_paths_device(xrt_scene *scene, const void *d_rays, int64_t n, int32_t iteration, float current_ref_index, const xrt_light *lights,
                                int32_t n_lights, const xrt_render_opts *opts, void *d_rgba_out, void *d_rgb_f32_out, void *d_rays_back, void *d_vertex_start,
                                void *d_vertices, int64_t vertex_capacity, void *stream, int64_t *n_vertices_out, xrt_stats *stats_out) {
-    return guarded("xrt_cast_rays_paths_device", [&]() -> int {
-        if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths_device: null scene");
+    return list_call("xrt_cast_rays_paths_device", scene, [&](const char *fn) -> int {
         int rc;
-        if (n < 0 || n > 0x7fffffff / 2) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths_device: n = %lld out of range", (long long)n);
-        if (!opts || !n_vertices_out || (n > 0 && (!d_rays || !d_rgba_out)) || (!lights && n_lights > 0) || n_lights < 0) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths_device: null argument");
-        if (vertex_capacity < 0 || (vertex_capacity > 0 && !d_vertices)) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths_device: vertex_capacity = %lld with%s vertices", (long long)vertex_capacity, d_vertices ? "" : " null");
-        if ((rc = need_device(scene, "xrt_cast_rays_paths_device"))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
-        if (((uintptr_t)d_rays & 15) || ((uintptr_t)d_rgba_out & 15) || ((uintptr_t)d_rgb_f32_out & 15) || ((uintptr_t)d_rays_back & 15) || ((uintptr_t)d_vertex_start & 15) || ((uintptr_t)d_vertices & 15))
-            return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
-        if (d_rays_back && d_rays_back == d_rays) return fail(XRT_E_INVALID_ARG, "xrt_cast_rays_paths_device: d_rays_back must not be d_rays (a chunk that is redone reads its rays again)");
-        BusyGuard guard(scene);
-        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
-        hipStream_t st = (hipStream_t)stream;
-        if (!st) st = scene->stream;
+        if ((rc = paths_check_args(fn, scene, d_rays, n, lights, n_lights, opts, d_rgba_out, d_vertices, vertex_capacity, n_vertices_out)) ||
+            (rc = aligned16({d_rays, d_rgba_out, d_rgb_f32_out, d_rays_back, d_vertex_start, d_vertices})))
+            return rc;
+        if (d_rays_back && d_rays_back == d_rays) return fail(XRT_E_INVALID_ARG, "%s: d_rays_back must not be d_rays (a chunk that is redone reads its rays again)", fn);
+        SceneHold hold(scene, stream);
+        if ((rc = hold.refused())) return rc;
         BatchSrc::Paths P;
         P.vertices = vertex_capacity > 0 ? (xrt_path_vertex *)d_vertices : nullptr; P.capacity = vertex_capacity; P.vertexStart = (long long *)d_vertex_start; P.raysBack = (xrt_ray *)d_rays_back;
         if (n > 0 && !P.vertexStart) {   // the ordering pass needs the running offsets whether or not the caller wants them
             if ((rc = scene->pathStart.ensure((size_t)n + 1))) return rc;
             P.vertexStart = scene->pathStart.p;
         }
-        if ((rc = cast_rays_impl(scene, (const xrt_ray *)d_rays, n, iteration, current_ref_index, lights, n_lights, opts, (uint32_t *)d_rgba_out,
-                                 (float *)d_rgb_f32_out, st, stats_out, &P)))
+        if ((rc = cast_rays_impl(scene, (const xrt_ray *)d_rays, n, iteration, current_ref_index, lights, n_lights, opts, (uint32_t *)d_rgba_out, (float *)d_rgb_f32_out,
+                                 hold.st, stats_out, &P)))
             return rc;
         *n_vertices_out = n > 0 ? *scene->pathPinned.p : 0;
         if (n == 0 && d_vertex_start) {
-            HIPCHECK(hipMemsetAsync(d_vertex_start, 0, sizeof(int64_t), st));
-            HIPCHECK(hipStreamSynchronize(st));
+            HIPCHECK(hipMemsetAsync(d_vertex_start, 0, sizeof(int64_t), hold.st));
+            HIPCHECK(hipStreamSynchronize(hold.st));
         }
         return guards_check("end of a ray batch");
     });
@@ -3693,48 +3711,29 @@ int xrt_cast_rays_paths_device(xrt_scene *scene, const void *d_rays, int64_t n, 
 
 int xrt_render_pixels(xrt_scene *scene, const xrt_camera *camera, const xrt_light *lights, int32_t n_lights, const xrt_render_opts *opts, const float *centers,
                       int64_t n, uint32_t *rgba_out, float *rgb_f32_out, xrt_stats *stats_out) {
-    return guarded("xrt_render_pixels", [&]() -> int {
-        if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_render_pixels: null scene");
+    return list_call("xrt_render_pixels", scene, [&](const char *fn) -> int {
         int rc;
-        if ((rc = pixels_check_args("xrt_render_pixels", camera, lights, n_lights, opts, n))) return rc;
-        if (n > 0 && (!centers || !rgba_out)) return fail(XRT_E_INVALID_ARG, "xrt_render_pixels: null argument");
-        for (int64_t i = 0; i < 2 * n; i++)
-            if (!std::isfinite(centers[i]))
-                return fail(XRT_E_INVALID_ARG, "xrt_render_pixels: centre %lld is not finite", (long long)(i / 2));
-        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
-        if (n == 0) return XRT_OK;
-        if ((rc = need_device(scene, "xrt_render_pixels"))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
-        BusyGuard guard(scene);
-        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
-        if ((rc = scene->pixelCenters.ensure((size_t)n * 2)) || (rc = scene->castRGBA.ensure((size_t)n)) || (rgb_f32_out && (rc = scene->castF32.ensure((size_t)n * 3)))) return rc;
-        HIPCHECK(hipMemcpyAsync(scene->pixelCenters.p, centers, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, scene->stream));
-        if ((rc = render_pixels_impl(scene, camera, lights, n_lights, opts, scene->pixelCenters.p, n, scene->castRGBA.p, rgb_f32_out ? scene->castF32.p : nullptr,
-                                     scene->stream, stats_out)))
-            return rc;
-        HIPCHECK(hipMemcpyAsync(rgba_out, scene->castRGBA.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, scene->stream));
-        if (rgb_f32_out) HIPCHECK(hipMemcpyAsync(rgb_f32_out, scene->castF32.p, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, scene->stream));
-        HIPCHECK(hipStreamSynchronize(scene->stream));
-        return guards_check("end of a pixel list");
+        if ((rc = pixels_check_args(fn, camera, lights, n_lights, opts, n, centers, rgba_out)) || (rc = centres_finite(fn, centers, n))) return rc;
+        if (empty_list(n, stats_out)) return XRT_OK;
+        SceneHold hold(scene);
+        if ((rc = hold.begin(fn))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
+        Staging S(hold.st);
+        const float *d_centers = S.in(scene->pixelCenters, centers, (size_t)n * 2);
+        uint32_t *d_rgba = S.out(scene->castRGBA, rgba_out, (size_t)n); float *d_f32 = S.out(scene->castF32, rgb_f32_out, (size_t)n * 3);
+        if ((rc = S.rc) || (rc = render_pixels_impl(scene, camera, lights, n_lights, opts, d_centers, n, d_rgba, d_f32, hold.st, stats_out))) return rc;
+        return S.finish("end of a pixel list");
     });
 }
 
 int xrt_render_pixels_device(xrt_scene *scene, const xrt_camera *camera, const xrt_light *lights, int32_t n_lights, const xrt_render_opts *opts,
                              const void *d_centers, int64_t n, void *d_rgba_out, void *d_rgb_f32_out, void *stream, xrt_stats *stats_out) {
-    return guarded("xrt_render_pixels_device", [&]() -> int {
-        if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_render_pixels_device: null scene");
+    return list_call("xrt_render_pixels_device", scene, [&](const char *fn) -> int {
         int rc;
-        if ((rc = pixels_check_args("xrt_render_pixels_device", camera, lights, n_lights, opts, n))) return rc;
-        if (n > 0 && (!d_centers || !d_rgba_out)) return fail(XRT_E_INVALID_ARG, "xrt_render_pixels_device: null argument");
-        if (((uintptr_t)d_centers & 15) || ((uintptr_t)d_rgba_out & 15) || ((uintptr_t)d_rgb_f32_out & 15))
-            return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
-        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
-        if (n == 0) return XRT_OK;
-        if ((rc = need_device(scene, "xrt_render_pixels_device"))) return rc;
-        BusyGuard guard(scene);
-        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
-        hipStream_t st = (hipStream_t)stream;
-        if (!st) st = scene->stream;
-        if ((rc = render_pixels_impl(scene, camera, lights, n_lights, opts, (const float *)d_centers, n, (uint32_t *)d_rgba_out, (float *)d_rgb_f32_out, st, stats_out)))
+        if ((rc = pixels_check_args(fn, camera, lights, n_lights, opts, n, d_centers, d_rgba_out)) || (rc = aligned16({d_centers, d_rgba_out, d_rgb_f32_out}))) return rc;
+        if (empty_list(n, stats_out)) return XRT_OK;
+        SceneHold hold(scene, stream);
+        if ((rc = hold.begin(fn)) ||
+            (rc = render_pixels_impl(scene, camera, lights, n_lights, opts, (const float *)d_centers, n, (uint32_t *)d_rgba_out, (float *)d_rgb_f32_out, hold.st, stats_out)))
             return rc;
         return guards_check("end of a pixel list");
     });
@@ -3742,50 +3741,30 @@ int xrt_render_pixels_device(xrt_scene *scene, const xrt_camera *camera, const x
 
 int xrt_trace_pixels(xrt_scene *scene, const xrt_camera *camera, const xrt_render_opts *opts, const float *centers, int64_t n, xrt_ray *rays_out, xrt_hit *hits_out,
                      xrt_stats *stats_out) {
-    return guarded("xrt_trace_pixels", [&]() -> int {
-        if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_trace_pixels: null scene");
+    return list_call("xrt_trace_pixels", scene, [&](const char *fn) -> int {
         int rc;
-        if ((rc = trace_check_args("xrt_trace_pixels", camera, opts, n))) return rc;
-        if (n > 0 && !rays_out && !hits_out) return fail(XRT_E_INVALID_ARG, "xrt_trace_pixels: both outputs are null");
-        if (n > 0 && !centers) return fail(XRT_E_INVALID_ARG, "xrt_trace_pixels: null centers");
-        for (int64_t i = 0; i < 2 * n; i++)
-            if (!std::isfinite(centers[i]))
-                return fail(XRT_E_INVALID_ARG, "xrt_trace_pixels: centre %lld is not finite", (long long)(i / 2));
-        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
-        if (n == 0) return XRT_OK;
-        if ((rc = need_device(scene, "xrt_trace_pixels"))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
-        BusyGuard guard(scene);
-        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
+        if ((rc = trace_check_args(fn, camera, opts, n, centers, rays_out, hits_out)) || (rc = centres_finite(fn, centers, n))) return rc;
+        if (empty_list(n, stats_out)) return XRT_OK;
+        SceneHold hold(scene);
+        if ((rc = hold.begin(fn))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
         xrt_scene::TraceWork &W = scene->traceWork;
-        const size_t recs = (size_t)n * (opts->use_multisampling == XRT_MS_FIXED16 ? 16u : 1u);
-        if ((rc = W.centers.ensure((size_t)n * 2)) || (rays_out && (rc = W.raysOut.ensure(recs))) || (hits_out && (rc = W.hitsOut.ensure(recs)))) return rc;
-        HIPCHECK(hipMemcpyAsync(W.centers.p, centers, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, scene->stream));
-        if ((rc = trace_pixels_impl(scene, camera, opts, W.centers.p, n, rays_out ? W.raysOut.p : nullptr, hits_out ? W.hitsOut.p : nullptr, scene->stream, stats_out))) return rc;
-        if (rays_out) HIPCHECK(hipMemcpyAsync(rays_out, W.raysOut.p, recs * sizeof(xrt_ray), hipMemcpyDeviceToHost, scene->stream));
-        if (hits_out) HIPCHECK(hipMemcpyAsync(hits_out, W.hitsOut.p, recs * sizeof(xrt_hit), hipMemcpyDeviceToHost, scene->stream));
-        HIPCHECK(hipStreamSynchronize(scene->stream));
-        return guards_check("end of a pixel list");
+        const size_t recs = (size_t)n * (opts->use_multisampling == XRT_MS_FIXED16 ? 16u : 1u);   // (a record per sub-ray)
+        Staging S(hold.st);
+        const float *d_centers = S.in(W.centers, centers, (size_t)n * 2);
+        xrt_ray *d_rays = S.out(W.raysOut, rays_out, recs); xrt_hit *d_hits = S.out(W.hitsOut, hits_out, recs);
+        if ((rc = S.rc) || (rc = trace_pixels_impl(scene, camera, opts, d_centers, n, d_rays, d_hits, hold.st, stats_out))) return rc;
+        return S.finish("end of a pixel list");
     });
 }
 
 int xrt_trace_pixels_device(xrt_scene *scene, const xrt_camera *camera, const xrt_render_opts *opts, const void *d_centers, int64_t n, void *d_rays_out,
                             void *d_hits_out, void *stream, xrt_stats *stats_out) {
-    return guarded("xrt_trace_pixels_device", [&]() -> int {
-        if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_trace_pixels_device: null scene");
+    return list_call("xrt_trace_pixels_device", scene, [&](const char *fn) -> int {
         int rc;
-        if ((rc = trace_check_args("xrt_trace_pixels_device", camera, opts, n))) return rc;
-        if (n > 0 && !d_rays_out && !d_hits_out) return fail(XRT_E_INVALID_ARG, "xrt_trace_pixels_device: both outputs are null");
-        if (n > 0 && !d_centers) return fail(XRT_E_INVALID_ARG, "xrt_trace_pixels_device: null centers");
-        if (((uintptr_t)d_centers & 15) || ((uintptr_t)d_rays_out & 15) || ((uintptr_t)d_hits_out & 15))
-            return fail(XRT_E_INVALID_ARG, "device buffers must be 16-byte aligned");
-        if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
-        if (n == 0) return XRT_OK;
-        if ((rc = need_device(scene, "xrt_trace_pixels_device"))) return rc;
-        BusyGuard guard(scene);
-        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");   // RT:62-63
-        hipStream_t st = (hipStream_t)stream;
-        if (!st) st = scene->stream;
-        if ((rc = trace_pixels_impl(scene, camera, opts, (const float *)d_centers, n, (xrt_ray *)d_rays_out, (xrt_hit *)d_hits_out, st, stats_out))) return rc;
+        if ((rc = trace_check_args(fn, camera, opts, n, d_centers, d_rays_out, d_hits_out)) || (rc = aligned16({d_centers, d_rays_out, d_hits_out}))) return rc;
+        if (empty_list(n, stats_out)) return XRT_OK;
+        SceneHold hold(scene, stream);
+        if ((rc = hold.begin(fn)) || (rc = trace_pixels_impl(scene, camera, opts, (const float *)d_centers, n, (xrt_ray *)d_rays_out, (xrt_hit *)d_hits_out, hold.st, stats_out))) return rc;
         return guards_check("end of a pixel list");
     });
 }
