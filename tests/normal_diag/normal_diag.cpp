@@ -21,7 +21,7 @@
 //              rays   6 floats: origin, direction
 //              hits   9 floats: hit position, direction of the ray that hit, fragment normal -> the reflection normalize(reflect(d, n)) from the hit (RT:549-550)
 //              light  6 floats: hit position, a spot light's position -> the shadow ray normalize(light - hit) from the hit (RT:469-479)
-//            OUT: per ray one byte, 1 = answered "nothing there" as kernels.hip faces_away_single answers it, then four bytes: the mesh record's axis,
+//            OUT: per ray one byte, 1 = answered "nothing there" as shade_math.h faces_away_single answers it, then four bytes: the mesh record's axis,
 //            can-face-away, 0, 0
 #include <cmath>
 #include <cstdint>
@@ -242,7 +242,7 @@ static int answer_mode(char **a) {
     if (!build(s, m, atoi(a[1]), IDENT, inv.data())) return 1;   // (the world matrix takes no part in the test)
     const MeshRec &mr = s.arrays.meshes[0];
     std::vector<unsigned char> out;
-    for (size_t i = 0; i < rays.size(); i += rec) {   // kernels.hip faces_away_single, operation for operation (OSM:358-364)
+    for (size_t i = 0; i < rays.size(); i += rec) {   // shade_math.h faces_away_single, operation for operation (OSM:358-364)
         const v3 o = mk(rays[i], rays[i + 1], rays[i + 2]), q = mk(rays[i + 3], rays[i + 4], rays[i + 5]);
         const v3 d = kind == 0 ? q : kind == 1 ? normalize(reflect(q, mk(rays[i + 6], rays[i + 7], rays[i + 8]))) : normalize(sub(q, o));
         const v3 v1 = transform(o, inv.data()), v2 = transform(add(o, d), inv.data());

@@ -5,7 +5,7 @@ may change: every frame here -- 96 x 54 pixels, 16 sub-rays per pixel, MaxReflec
 Which rays the device answered shows in the frame's end counts (xrt_debug_end_counts, tests/test_gpu_end_early.py): the paths left on k_compose's list are
 the generation-0 hits that emitted a shadow ray or a reflection.  The test computes that number from the ORACLE's generation-0 hits with the host build of
 the very function the kernels call (tests/normal_diag_py.py: scene_host.cpp's mesh record, traverse.h mesh_faces_away, the object-space direction formed as
-kernels.hip faces_away_single forms it), which tests/test_normal_diag_cpu.py proves sound; the two numbers must be equal.
+shade_math.h faces_away_single forms it), which tests/test_normal_diag_cpu.py proves sound; the two numbers must be equal.
 
 The sub-rays of a pixel are the oracle's primary rays of a viewport 8 times as wide and high, moved by 4: sub-sample offsets are odd multiples of 1/8, so
 pixel 8 x + 4 + k of that viewport is screen position x + k / 8 of the frame's, with (sx - vp_x) / vp_width the same quotient bit for bit."""

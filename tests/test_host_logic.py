@@ -724,3 +724,30 @@ def test_env_switches_read_in_one_place_and_documented():
     listed = re.findall(r"^\| `(XRT_[A-Z0-9_]+)` \|", table, re.M)
     assert len(listed) == len(set(listed)), sorted(listed)
     assert set(listed) == read, {"undocumented": sorted(read - set(listed)), "not read": sorted(set(listed) - read)}
+
+
+def test_shared_device_statements_are_defined_once():
+    """CastRay's per-hit arithmetic (shade_math.h), the list compaction (device_util.h) and the sample positions of a centre list (pixels.h)
+    are each stated in ONE file of csrc: results are bit-identical to the reference statement by statement, so a second copy is a second
+    place to fix.  A definition under a prefixed name (lights_fragment_normal, hits_scan_add) is a copy too."""
+    csrc = os.path.join(ROOT, "xna-ray-trace_amd", "csrc")
+    home = {"fragment_normal": "shade_math.h", "light_dir": "shade_math.h", "interpolated_uv": "shade_math.h", "lookup_uv": "shade_math.h",
+            "faces_away_single": "shade_math.h", "refraction_indices": "shade_math.h", "refract_dir": "shade_math.h", "hit_names_scene": "shade_math.h",
+            "reserve_cells": "device_util.h", "reserve_cells_and_entries": "device_util.h", "scan_add": "device_util.h", "W4": "device_util.h",
+            "sample_position": "pixels.h"}
+    found = {name: [] for name in home}
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".cpp", ".h", ".hip")):
+            continue
+        src = open(os.path.join(csrc, f)).read()
+        defined = re.findall(r"^\s*__device__ __forceinline__ [\w:]+ [*&]?(\w+)\(", src, re.M) + re.findall(r"^\s*typedef [^;]*?\b(\w+)(?: __attribute__\(\([^;]*\)\))?;", src, re.M)
+        for d in defined:
+            for name in home:
+                if d == name or d.endswith("_" + name):
+                    found[name].append((f, d))
+        # the statements themselves, whatever they are called: the scan's first DPP step, Snell's square root, the mirror address mode's parity
+        for name, text in (("scan_add", "v += __builtin_amdgcn_update_dpp(0, v, 0x111"), ("refract_dir", "sqrt(1 - (ratio * ratio)"), ("lookup_uv", "cvt_i32(ox - ux) % 2")):
+            if text in src and not any(g == f for g, _ in found[name]):
+                found[name].append((f, "<unnamed>"))
+    for name, where in home.items():
+        assert [f for f, _ in found[name]] == [where], (name, found[name])

@@ -64,29 +64,47 @@ def f64_units():
     return _UNITS
 
 
+UNITS = ("kernels", "packet", "paths", "pixels", "hits", "lights", "trace", "surface")   # what `make asm` builds
+
+
+def check_no_contracted_fma(name, text):
+    """The rule, on the ISA of one kernel: no v_mad / v_mac / v_pk_fma f32; every v_fma / v_fmac f32 belongs to a division (5 per
+    v_div_fixup_f32), a square root (2 per v_sqrt_f32) or the float-assisted 64-bit integer division (its 2^32 constants); every f64 fma
+    to the library expansions of the double-precision division, square root and remainder, whose sizes are measured on a probe built with
+    the same flags.  Returns what it counted: the f32 divisions, square roots and integer-division fmas, and the f64 expansions."""
+    assert not re.search(r"\bv_(mad|mac)_f32|\bv_pk_fma_f32|\bv_fma_mix", text), name
+    fma = len(re.findall(r"\bv_(?:fma|fmac)_f32", text))
+    div = text.count("v_div_fixup_f32")
+    sqrt = len(re.findall(r"\bv_sqrt_f32", text))
+    # 64-bit integer division helper: v_fmac with 0x4f800000 (2^32) and 0xcf800000 (-2^32)
+    idiv = len(re.findall(r"v_fmac_f32_e32 v\d+, 0x4f800000", text)) + len(re.findall(r"v_fmac_f32_e32 v\d+, 0xcf800000", text))
+    assert fma == 5 * div + 2 * sqrt + idiv, (name, fma, div, sqrt, idiv)
+    c = f64_census(text)
+    u = f64_units()
+    n_rem = c["rndne"] // u["rem"]["rndne"]
+    n_div = c["fixup"] - n_rem * u["rem"]["fixup"]
+    n_sqrt = c["rsq"] - n_rem * u["rem"]["rsq"]
+    assert c["rndne"] % u["rem"]["rndne"] == 0 and n_div >= 0 and n_sqrt >= 0, (name, c)
+    assert c["fma"] == n_div * u["div"]["fma"] + n_sqrt * u["sqrt"]["fma"] + n_rem * u["rem"]["fma"], (name, "contracted double-precision multiply-add", c, n_div, n_sqrt, n_rem)
+    return {"div": div, "sqrt": sqrt, "idiv": idiv, "f64": (n_div, n_sqrt, n_rem)}
+
+
 def test_no_contracted_fma_in_any_kernel(isa):
+    """Every kernel of every unit `make asm` builds.  k_shade's doubles: the SPOT:54 division, RT:676-679 Snell square root and the two
+    Math.IEEERemainder of MAT:168-169."""
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    assert re.search(r"for k in ([^;]*);", mk).group(1).split() == list(UNITS)
     ks = kernels(isa)
-    assert any("k_intersect" in k for k in ks) and any("k_shade" in k for k in ks) and any("k_packet" in k for k in ks)
+    for unit in UNITS[2:]:
+        more = kernels(open(os.path.join(CSRC, unit + ".s")).read())
+        assert more and not set(more) & set(ks), unit
+        ks.update(more)
+    for want in ("k_intersect", "k_shade", "k_packet", "k_paths", "k_pixel_raygen", "k_ingest_hits", "k_light_fold", "k_trace_raygen", "k_surface"):
+        assert any(want in k for k in ks), want
     for name, lines in ks.items():
-        text = "\n".join(lines)
-        assert not re.search(r"\bv_(mad|mac)_f32|\bv_pk_fma_f32|\bv_fma_mix", text), name
-        fma = len(re.findall(r"\bv_(?:fma|fmac)_f32", text))
-        div = text.count("v_div_fixup_f32")
-        sqrt = len(re.findall(r"\bv_sqrt_f32", text))
-        # 64-bit integer division helper: v_fmac with 0x4f800000 (2^32) and 0xcf800000 (-2^32)
-        idiv = len(re.findall(r"v_fmac_f32_e32 v\d+, 0x4f800000", text)) + len(re.findall(r"v_fmac_f32_e32 v\d+, 0xcf800000", text))
-        assert fma == 5 * div + 2 * sqrt + idiv, (name, fma, div, sqrt, idiv)
-        # double precision (k_shade: SPOT:54 division, RT:676-679 Snell square root, MAT:168-169 Math.IEEERemainder): every
-        # f64 fma must belong to one of those library expansions, whose sizes are measured on a probe built with the same flags
-        c = f64_census(text)
-        u = f64_units()
-        n_rem = c["rndne"] // u["rem"]["rndne"]
-        n_div = c["fixup"] - n_rem * u["rem"]["fixup"]
-        n_sqrt = c["rsq"] - n_rem * u["rem"]["rsq"]
-        assert c["rndne"] % u["rem"]["rndne"] == 0 and n_div >= 0 and n_sqrt >= 0, (name, c)
-        assert c["fma"] == n_div * u["div"]["fma"] + n_sqrt * u["sqrt"]["fma"] + n_rem * u["rem"]["fma"], (name, "contracted double-precision multiply-add", c, n_div, n_sqrt, n_rem)
+        got = check_no_contracted_fma(name, "\n".join(lines))
         if "k_shade" in name:
-            assert (n_div, n_sqrt, n_rem) == (1, 1, 2), (n_div, n_sqrt, n_rem)
+            assert got["f64"] == (1, 1, 2), got
 
 
 def test_hot_kernel_resources(isa):

@@ -16,7 +16,7 @@ import lights_py as lp
 import paths_py
 import surface_py as sp
 from test_gpu_cast_rays import scenes, two_mesh_spec
-from test_numerics_contract import f64_census, f64_units, kernels
+from test_numerics_contract import check_no_contracted_fma, kernels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "xna-ray-trace_amd", "csrc")
@@ -226,10 +226,9 @@ def test_python_binding_checks_its_arguments(xrt):
 
 
 def test_no_contracted_multiply_add_in_the_kernel(tmp_path):
-    """The rule of test_numerics_contract.py on the ISA of surface.hip, compiled with the Makefile's flags: no v_mad / v_mac / v_pk_fma f32,
-    every v_fma / v_fmac f32 belongs to a division (5 per v_div_fixup_f32) or a square root (2 per v_sqrt_f32), every f64 fma to the
-    expansions of the double-precision division, square root (RT:676-679) and remainder (MAT:168-169), measured on that test's probe.  And
-    the kernel's resources: no scratch, 16 bytes of LDS (the count cells)."""
+    """The rule of test_numerics_contract.py (check_no_contracted_fma) on the ISA of surface.hip, compiled with the Makefile's flags, and what
+    this kernel adds to it: its f32 fmas are divisions' and square roots' alone, its doubles the square root of RT:676-679 and the two
+    remainders of MAT:168-169.  And the kernel's resources: no scratch, 16 bytes of LDS (the count cells)."""
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert re.search(r"^SRCS\s*:=.*\bsurface\.hip\b", mk, flags=re.M) and re.search(r"for k in [^;]*\bsurface\b", mk)
     flags = re.search(r"^FLAGS\s*:=\s*(.*)$", mk, flags=re.M).group(1).split()
@@ -242,19 +241,8 @@ def test_no_contracted_multiply_add_in_the_kernel(tmp_path):
     ks = kernels(open(out).read())
     assert [k for k in ks if "k_surface" in k] and len(ks) == 1
     for name, lines in ks.items():
-        text = "\n".join(lines)
-        assert not re.search(r"\bv_(mad|mac)_f32|\bv_pk_fma_f32|\bv_fma_mix", text), name
-        fma = len(re.findall(r"\bv_(?:fma|fmac)_f32", text))
-        div = text.count("v_div_fixup_f32")
-        sqrt = len(re.findall(r"\bv_sqrt_f32", text))
-        assert div > 0 and sqrt > 0
-        assert fma == 5 * div + 2 * sqrt, (name, fma, div, sqrt)
-        c, u = f64_census(text), f64_units()
-        n_rem = c["rndne"] // u["rem"]["rndne"]
-        n_div = c["fixup"] - n_rem * u["rem"]["fixup"]
-        n_sqrt = c["rsq"] - n_rem * u["rem"]["rsq"]
-        assert c["rndne"] % u["rem"]["rndne"] == 0 and n_div >= 0 and n_sqrt >= 0, (name, c)
-        assert c["fma"] == n_div * u["div"]["fma"] + n_sqrt * u["sqrt"]["fma"] + n_rem * u["rem"]["fma"], (name, c, n_div, n_sqrt, n_rem)
-        assert (n_div, n_sqrt, n_rem) == (0, 1, 2), (n_div, n_sqrt, n_rem)   # Snell's square root and the two IEEERemainders; no light, so no SPOT:54 division
+        got = check_no_contracted_fma(name, "\n".join(lines))
+        assert got["div"] > 0 and got["sqrt"] > 0 and got["idiv"] == 0, (name, got)   # (no 64-bit integer division here: every f32 fma is a division's or a square root's)
+        assert got["f64"] == (0, 1, 2), got   # Snell's square root and the two IEEERemainders; no light, so no SPOT:54 division
     usage = p.stderr
     assert re.search(r"ScratchSize \[bytes/lane\]: 0\b", usage) and re.search(r"LDS Size \[bytes/block\]: 16\b", usage), usage[-2000:]

@@ -1,4 +1,4 @@
-// device_util.h — small device helpers shared by kernels.hip, packet.hip and pixels.hip (gfx950, wave64).
+// device_util.h — small device helpers shared by the kernel files (gfx950, wave64).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -136,5 +136,50 @@ __device__ __forceinline__ int wave_scan_add(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
     v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2 and 3
     return v;
+}
+
+// A quarter of a record as four 32-bit words in registers: one 16-byte load or store, and nothing for the compiler to keep in memory
+typedef int W4 __attribute__((ext_vector_type(4)));
+
+// Stream compaction of a block whose waves left their ballot counts in 64 LDS cells (cell r * 16 + w: round r, wave w -- ascending order of the list).  ONE wave
+// calls this between two barriers: it scans the cells, reserves the block's range of the list with one atomic (none for an empty block) and leaves in every
+// cell the first slot of its lanes.
+__device__ __forceinline__ void reserve_cells(int *cells, int *count) {
+    const int lane = lane_id();
+    const int c = cells[lane];
+    const int incl = wave_scan_add(c);
+    const int total = __builtin_amdgcn_readlane(incl, 63);
+    int base = 0;
+    if (lane == 0 && total) base = atomicAdd(count, total);
+    base = __builtin_amdgcn_readfirstlane(base);
+    cells[lane] = base + incl - c;
+}
+// The same for a launch that writes a packet table (kernels.h QuadTable): the wave reserves the block's range of the list AND its entries of the table -- one
+// per cell that has a live ray, in the order of the slots -- with ONE atomic instruction: lane 0 adds the rays to `count`, lane 1 the entries to the table's
+// count word (a 256-byte line of its own), both requests are under way together.  quadLen: the live rays of this lane's cell, quadAt: its entry.  The
+// entries themselves are stored behind the barrier, with the rays: a store in front of it is a round trip the whole block waits for.
+__device__ __forceinline__ void reserve_cells_and_entries(int *cells, int *count, unsigned *tableCount, int &quadLen, int &quadAt) {
+    const int lane = lane_id();
+    quadLen = cells[lane];
+    const int incl = wave_scan_add(quadLen);
+    const int total = __builtin_amdgcn_readlane(incl, 63);
+    const unsigned long long mq = __ballot(quadLen > 0);
+    int got = 0;
+    if (lane < 2 && total) got = lane == 0 ? atomicAdd(count, total) : (int)atomicAdd(tableCount, (unsigned)__popcll(mq));
+    quadAt = __builtin_amdgcn_readlane(got, 1) + lanes_below(mq);
+    cells[lane] = __builtin_amdgcn_readlane(got, 0) + incl - quadLen;
+}
+// Counting without positions, for a kernel that ends with it: the block's sum of n goes to *counter with one atomic (none for zero) -- a wave reduction,
+// one cell of LDS per wave.  Called once by all threads of the block.
+template <int WAVES, class T>
+__device__ __forceinline__ void block_count_once(T *counter, int n, int *ldsCells /* [WAVES] */) {
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+    if (lane_id() == 0) ldsCells[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int total = 0;
+        for (int k = 0; k < WAVES; k++) total += ldsCells[k];
+        if (total) atomicAdd(counter, (T)total);
+    }
 }
 }  // namespace xrt

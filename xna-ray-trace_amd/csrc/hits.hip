@@ -8,28 +8,16 @@
 
 #include "device_util.h"
 #include "hits.h"
+#include "shade_math.h"
 #include "xrt_core.h"
 
 namespace xrt {
 
-// wave64 inclusive scan on the DPP network (row shifts, then the two row broadcasts), as kernels.hip's
-__device__ __forceinline__ int hits_scan_add(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2 and 3
-    return v;
-}
-
-// A quarter of a record as four 32-bit words in registers: one 16-byte load or store, and nothing for the compiler to keep in memory
-typedef int W4 __attribute__((ext_vector_type(4)));
-
 // Path p of the chunk is (rays[pathBase + p], hits[pathBase + p]).  "The query returned hits[p]": hit == 0 is a miss and the path ends as k_ingest
-// ends a ray that cannot reach the root box (RT:729-733); so does an entry whose mesh or triangle the scene does not have -- it is shaded
-// as a miss and can address nothing.  The others are compacted into the live list with one ballot per round, one wave scan of the block's
-// 64 cells and one atomic per block and group, and get what the skipped launch would have left at their slot: the ray (CastRay reads its
+// ends a ray that cannot reach the root box (RT:729-733); so does an entry whose mesh or triangle the scene does not have (shade_math.h
+// hit_names_scene) -- it is shaded as a miss and can address nothing.  The others are compacted into the live list with one ballot per round,
+// one wave scan of the block's 64 cells and one atomic per block and group (device_util.h reserve_cells), and get what the skipped launch
+// would have left at their slot: the ray (CastRay reads its
 // direction, RT:549; the origin triangle only entered the query, so the record names none and carries no long-ray mark -- nothing is traced),
 // the 48-byte hit with hit = 1 and a zero feedback word, the hit word, the path, and for a ray tree the caller's currentRefIndex (RT:658).
 // Two phases, so that a thread keeps 16 bytes per round across the barriers and a miss costs 16 bytes of reads: the first loads the
@@ -49,9 +37,7 @@ __global__ __launch_bounds__(INGEST_HITS_BLOCK) void k_ingest_hits(SceneView S, 
             head[r] = W4{0, -1, -1, -1};
             if (p < A.P) {
                 const W4 a = reinterpret_cast<const W4 *>(A.hits + (A.pathBase + p))[0];   // hit object mesh tri
-                const int mesh = a.z, tri = a.w;
-                live = a.x != 0 && mesh >= 0 && mesh < S.nMeshes && tri >= 0;
-                if (live) live = tri < S.meshes[mesh].ntri;
+                live = hit_names_scene(S.meshes, S.nMeshes, a);
                 head[r] = a;
                 if (!live) A.lvlB0[p] = f4{0, 0, 0, i2f(FLAG_MISS)};   // generation 0 ends here (RT:729-733)
             }
@@ -60,15 +46,7 @@ __global__ __launch_bounds__(INGEST_HITS_BLOCK) void k_ingest_hits(SceneView S, 
             if (lane == 0) ldsLive[r * 16 + wave] = (int)__popcll(ml);
         }
         __syncthreads();
-        if (wave == 0) {   // reserves the block's range of the live list
-            const int c = ldsLive[lane];   // entry r * 16 + w: ascending path order
-            const int incl = hits_scan_add(c);
-            const int total = __builtin_amdgcn_readlane(incl, 63);
-            int base = 0;
-            if (lane == 0 && total) base = atomicAdd(A.count, total);
-            base = __builtin_amdgcn_readfirstlane(base);
-            ldsLive[lane] = base + incl - c;
-        }
+        if (wave == 0) reserve_cells(ldsLive, A.count);   // the block's range of the live list (cell r * 16 + w: ascending path order)
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < INGEST_HITS_ROUNDS; r++) {

@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "device_util.h"
 #include "pose.h"
+#include "shade_math.h"
 
 #include <hip/hip_ext.h>
 
@@ -689,29 +690,9 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_raygen(RayGenParams g, SceneVi
         if (!index) continue;   // grid-uniform: no lists
         __syncthreads();
         int quadLen = 0, quadAt = 0;   // wave 0 of a launch with a packet table: the live rays of this lane's cell and its entry
-        if (wave == 0 && Q.table) {
-            // Wave 0 reserves the block's range of the live list AND its entries of the packet table -- one per cell (wave and round) that has a live ray, in the
-            // order of the slots -- with ONE atomic instruction: lane 0 adds the rays to `count`, lane 1 the entries to the table's count word (a 256-byte line of
-            // its own), both requests are under way together.  The entries themselves are stored behind the barrier, with the rays: a store in front of it is a
-            // round trip the whole block waits for.
-            quadLen = ldsLive[lane];   // entry r * 16 + w: ascending path order
-            const int incl = wave_scan_add(quadLen);
-            const int total = __builtin_amdgcn_readlane(incl, 63);
-            const unsigned long long mq = __ballot(quadLen > 0);
-            int got = 0;
-            if (lane < 2 && total) got = lane == 0 ? atomicAdd(count, total) : (int)atomicAdd(Q.count, (unsigned)__popcll(mq));
-            quadAt = __builtin_amdgcn_readlane(got, 1) + lanes_below(mq);
-            ldsLive[lane] = __builtin_amdgcn_readlane(got, 0) + incl - quadLen;
-        } else if (wave < 2 && (wave == 0 || H.list)) {   // wave 0 reserves the block's range of the live list, wave 1 of the long-ray list
-            int *cells = wave == 0 ? ldsLive : ldsHeavy;
-            const int c = cells[lane];   // entry r * 16 + w: ascending path order
-            const int incl = wave_scan_add(c);
-            const int total = __builtin_amdgcn_readlane(incl, 63);
-            int base = 0;
-            if (lane == 0 && total) base = atomicAdd(wave == 0 ? count : H.count, total);
-            base = __builtin_amdgcn_readfirstlane(base);
-            cells[lane] = base + incl - c;
-        }
+        // (cell r * 16 + w: ascending path order)
+        if (wave == 0 && Q.table) reserve_cells_and_entries(ldsLive, count, Q.count, quadLen, quadAt);   // the live list and the packet table's entries, one atomic instruction
+        else if (wave < 2 && (wave == 0 || H.list)) reserve_cells(wave == 0 ? ldsLive : ldsHeavy, wave == 0 ? count : H.count);   // wave 0: the live list, wave 1: the long-ray list
         __syncthreads();
         // the block's entries, one coalesced store of wave 0 (Q.cap bounds the entries by construction, as liveCap the rays)
         if (quadLen > 0 && quadAt < Q.cap) Q.table[quadAt] = make_uint2((unsigned)ldsLive[lane], (unsigned)quadLen);
@@ -772,16 +753,7 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_ingest(RayGenParams g, SceneVi
             if (lane == 0) { ldsLive[r * 16 + wave] = (int)__popcll(ml); ldsHeavy[r * 16 + wave] = (int)__popcll(mh); }
         }
         __syncthreads();
-        if (wave < 2 && (wave == 0 || H.list)) {   // wave 0 reserves the block's range of the live list, wave 1 of the long-ray list
-            int *cells = wave == 0 ? ldsLive : ldsHeavy;
-            const int c = cells[lane];
-            const int incl = wave_scan_add(c);
-            const int total = __builtin_amdgcn_readlane(incl, 63);
-            int base = 0;
-            if (lane == 0 && total) base = atomicAdd(wave == 0 ? count : H.count, total);
-            base = __builtin_amdgcn_readfirstlane(base);
-            cells[lane] = base + incl - c;
-        }
+        if (wave < 2 && (wave == 0 || H.list)) reserve_cells(wave == 0 ? ldsLive : ldsHeavy, wave == 0 ? count : H.count);   // wave 0: the live list, wave 1: the long-ray list
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < RG_ROUNDS; r++) {
@@ -830,94 +802,9 @@ __device__ __forceinline__ void load_hit(const xrt_hit *src, int &hit, int &obje
     u = i2f(b.i1); v = i2f(b.i2); d = i2f(b.i3);
     w = mk(i2f(c.i0), i2f(c.i1), i2f(c.i2));
 }
-// RT:520-531 fragment normal
-__device__ __forceinline__ v3 fragment_normal(const ShadeView &V, int gtri, int matFlags, float u, float v) {
-    const f4 *s = V.shade + (size_t)gtri * 6;
-    if (matFlags & MAT_INTERP) {
-        f4 s0 = s[0], s1 = s[1], s2 = s[2];
-        v3 n1 = mk(s0.x, s0.y, s0.z), n2 = mk(s1.x, s1.y, s1.z), n3 = mk(s2.x, s2.y, s2.z);
-        v3 a = sub(n2, n1), b = sub(n3, n1);
-        return normalize(add(add(n1, scale(a, u)), scale(b, v)));
-    }
-    f4 s5 = s[5];
-    return mk(s5.x, s5.y, s5.z);
-}
-// RT:469-479 direction and distance towards a light
-__device__ __forceinline__ void light_dir(const LightRec &L, v3 world, v3 &dir, float &dist) {
-    if (L.kind == 0) {
-        v3 t = sub(mk(L.px, L.py, L.pz), world);
-        dist = length(t);
-        dir = normalize(t);
-    } else {
-        dir = neg(mk(L.dx, L.dy, L.dz));
-        dist = FLT_MAX;
-    }
-}
-
-// MAT:71-160 LookupUV: address mode + point sample
-__device__ __forceinline__ v3 lookup_uv(const ShadeView &V, const MaterialRec &M, float ux, float uy) {
-    if (V.addressMode == XRT_ADDRESS_WRAP) {   // MAT:125-136
-        if (ux > 1.0f) ux = fmod1(ux);
-        if (uy > 1.0f) uy = fmod1(uy);
-        if (ux < 0.0f) ux = 1.0f + fmod1(ux);
-        if (uy < 0.0f) uy = 1.0f + fmod1(uy);
-    } else if (V.addressMode == XRT_ADDRESS_CLAMP) {   // MAT:138-143
-        ux = (ux > 1.0f) ? 1.0f : ux; ux = (ux < 0.0f) ? 0.0f : ux;
-        uy = (uy > 1.0f) ? 1.0f : uy; uy = (uy < 0.0f) ? 0.0f : uy;
-    } else {   // MAT:102-123
-        float ox = ux, oy = uy;
-        if (ux > 1.0f) ux = fmod1(ux);
-        if (uy > 1.0f) uy = fmod1(uy);
-        if (ux < 0.0f) ux = 1.0f + fmod1(ux);
-        if (uy < 0.0f) uy = 1.0f + fmod1(uy);
-        if (cvt_i32(ox - ux) % 2 == 0) ux = 1.0f - ux;
-        if (cvt_i32(oy - uy) % 2 == 0) uy = 1.0f - uy;
-    }
-    if (V.filtering == XRT_FILTER_BILINEAR) {   // MAT:162-232
-        // A coordinate that is not a number (the reference throws: its texel index is 0x80000000) makes every weight below NaN.  Which NaN is no property
-        // of the arithmetic: ocml's remainder() returns the canonical one where glibc's hands its argument's on, and a subtraction here flips the sign
-        // of a NaN subtrahend where SSE keeps it.  So the answer is stated: the canonical quiet NaN in every channel (texture lookup).
-        if (is_nan(ux) || is_nan(uy)) { const float qnan = i2f(0x7fc00000); return mk(qnan, qnan, qnan); }
-        const float tdx = 1.0f / (float)M.texWidth, tdy = 1.0f / (float)M.texHeight;   // MAT:67
-        const double remX = remainder((double)ux, (double)tdx), remY = remainder((double)uy, (double)tdy);   // Math.IEEERemainder, exact
-        ux -= (float)remX;
-        uy -= (float)remY;
-        const int bx = (int)(ux * (float)(M.texWidth - 1)), by = (int)(uy * (float)(M.texHeight - 1));   // (numbers in [0, W] by now: no cvt_i32)
-        const int bx2 = (int)((ux + tdx) * (float)(M.texWidth - 1)), by2 = (int)((uy + tdy) * (float)(M.texHeight - 1));
-        auto texel = [&](int xx, int yy) {
-            long long idx = (long long)M.texWidth * yy + xx;
-            if (idx < 0 || idx >= (long long)M.texWidth * M.texHeight) idx = 0;
-            uint32_t w = V.texels[M.texOffsetP + idx];   // MAT:186-189: Texture.ColorData
-            return mk((float)((w >> 16) & 0xffu), (float)((w >> 8) & 0xffu), (float)(w & 0xffu));
-        };
-        const v3 c00 = texel(bx, by), c10 = texel(bx2, by), c01 = texel(bx, by2), c11 = texel(bx2, by2);
-        const float dx = (float)(remX * (double)M.texWidth) + 0.5f, dy = (float)(remY * (double)M.texHeight) + 0.5f;
-        const float ix = 1.0f - dx, iy = 1.0f - dy;
-        v3 sum = add(add(add(scale(scale(c00, ix), iy), scale(scale(c01, ix), dy)), scale(scale(c10, dx), iy)), scale(scale(c11, dx), dy));
-        return scale(sum, 1.0f / 255.0f);
-    }
-    int x = cvt_i32(ux * (float)(M.texWidth - 1));    // MAT:147
-    int y = cvt_i32(uy * (float)(M.texHeight - 1));   // MAT:148
-    long long idx = (long long)M.texWidth * y + x;
-    if (idx < 0 || idx >= (long long)M.texWidth * M.texHeight) idx = 0;   // the C# reads through a raw pointer; a NaN uv (x or y = 0x80000000) reads texel 0
-    uint32_t argb = V.texels[M.texOffset + idx];
-    const float BYTE_RECIPROCAL = 1.0f / 255.0f;   // MAT:27
-    return mk((float)((argb >> 16) & 0xffu) * BYTE_RECIPROCAL, (float)((argb >> 8) & 0xffu) * BYTE_RECIPROCAL, (float)(argb & 0xffu) * BYTE_RECIPROCAL);
-}
+// (fragment_normal, light_dir, interpolated_uv, lookup_uv, faces_away_single, refraction_indices and refract_dir: shade_math.h -- the list calls shade with them too)
 
 // CastRay's shading for one step of the wavefront.  After intersect launch #k two independent pieces of work exist and
-// ShadeArgs::ae: would the one body's one mesh answer this world-space ray "no intersection" because all its triangles face away from it?  The
-// object-space direction is formed exactly as the traversal kernels form it (traverse.h lane_begin, OSM:358-364), the test is theirs
-// (traverse.h mesh_faces_away: the mesh's normal box and its diagonal box, each with its margin; a NaN anywhere makes it false: such a ray is traced).
-__device__ __forceinline__ bool faces_away_single(const SceneView &S, v3 o, v3 d) {
-    const ObjRec &ob = S.objects[0];
-    const MeshRec &mr = S.meshes[0];
-    const v3 v1 = transform(o, ob.invWorld);
-    const v3 v2 = transform(add(o, d), ob.invWorld);
-    const v3 dir = normalize(sub(v2, v1));
-    return mesh_faces_away(mr, dir);
-}
-
 // one kernel does both:
 //   part A, generation k   : the closest-hit answers.  Misses end their path (RT:729-733); every hit takes a slot, emits one
 //                            shadow ray per light (RT:535-537 -> RT:482-485) and -- the reflected / refracted directions
@@ -1071,10 +958,8 @@ __global__ __launch_bounds__(APPEND_BLOCK) __attribute__((amdgpu_waves_per_eu(6)
                     v3 surf;
                     const f4 *sr = V.shade + (size_t)gtri * 6;
                     if (M.flags & MAT_TEXTURE) {   // RT:568-575
-                        f4 s0 = sr[0], s1 = sr[1], s2 = sr[2], s4 = sr[4];
-                        float uv1x = s0.w, uv1y = s1.w, uv2x = s2.w, uv2y = s4.x, uv3x = s4.y, uv3y = s4.z;
-                        float ax = uv2x - uv1x, ay = uv2y - uv1y, bx = uv3x - uv1x, by = uv3y - uv1y;
-                        float ix = (uv1x + ax * u) + bx * v, iy = (uv1y + ay * u) + by * v;
+                        float ix, iy;
+                        interpolated_uv(sr, u, v, ix, iy);
                         surf = lookup_uv(V, M, ix, iy);
                     } else {
                         f4 c = sr[3];
@@ -1095,16 +980,10 @@ __global__ __launch_bounds__(APPEND_BLOCK) __attribute__((amdgpu_waves_per_eu(6)
                     v3 o, dd; int im, itri;
                     load_ray(X.rays + i, o, dd, im, itri);
                     rdir = normalize(reflect(dd, normal));   // RT:549-550
-                    if (X.heap && (M.flags & MAT_TRANSPARENT)) {   // RT:656-694: Snell refraction, the System.Math calls in double
+                    if (X.heap && (M.flags & MAT_TRANSPARENT)) {   // RT:656-694: Snell refraction
                         float n1;
-                        if (curRef == M.refractionIndex) { n1 = 1.0f; n2 = curRef; }
-                        else { n1 = M.refractionIndex; n2 = 1.0f; }
-                        const float cos1 = dot(normal, neg(dd));
-                        const double ratio = (double)(n1 / n2), c1 = (double)cos1;
-                        const float cos2 = (float)sqrt(1 - (ratio * ratio) * (1 - (c1 * c1)));   // Math.Pow(x, 2.0) == x*x exactly here
-                        const float q = n1 / n2;
-                        const v3 a = scale(dd, q), b = scale(normal, q * cos1 - cos2);
-                        tdir = normalize(cos1 >= 0 ? add(a, b) : sub(a, b));
+                        refraction_indices(curRef, M.refractionIndex, n1, n2);
+                        tdir = refract_dir(dd, normal, n1, n2);
                         refracts = true;
                     }
                 }

@@ -3,73 +3,15 @@
 // GetLightForFragment scaled by 1 - lightAmount.  Frames do this inside k_shade (kernels.hip: part A emits the shadow rays, part B folds their
 // answers); here the same three steps stand alone, on a caller's list: k_light_emit forms the shadow rays, the traversal kernels answer them
 // unchanged (IntersectArgs::scatter / flags), k_light_fold turns the answers into the amounts and the fp32 light sum.  The arithmetic is
-// k_shade's, restated (kernels.hip stays as it is) and compiled with the same flags: contraction off, every operation its own rounding.
+// k_shade's: the statements of shade_math.h and xrt_core.h, compiled with the same flags: contraction off, every operation its own rounding.
 #include <hip/hip_runtime.h>
 
 #include "device_util.h"
 #include "lights.h"
+#include "shade_math.h"
 #include "xrt_core.h"
 
 namespace xrt {
-
-namespace {
-
-// wave64 inclusive scan on the DPP network (row shifts, then the two row broadcasts), as hits.hip's
-__device__ __forceinline__ int lights_scan_add(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2 and 3
-    return v;
-}
-
-// A quarter of a record as four 32-bit words in registers: one 16-byte load
-typedef int W4 __attribute__((ext_vector_type(4)));
-
-// RT:469-479 direction and distance towards a light (kernels.hip light_dir)
-__device__ __forceinline__ void lights_dir(const LightRec &L, v3 world, v3 &dir, float &dist) {
-    if (L.kind == 0) {
-        v3 t = sub(mk(L.px, L.py, L.pz), world);
-        dist = length(t);
-        dir = normalize(t);
-    } else {
-        dir = neg(mk(L.dx, L.dy, L.dz));
-        dist = FLT_MAX;
-    }
-}
-// RT:520-531 fragment normal (kernels.hip fragment_normal)
-__device__ __forceinline__ v3 lights_fragment_normal(const ShadeView &V, int gtri, int matFlags, float u, float v) {
-    const f4 *s = V.shade + (size_t)gtri * 6;
-    if (matFlags & MAT_INTERP) {
-        f4 s0 = s[0], s1 = s[1], s2 = s[2];
-        v3 n1 = mk(s0.x, s0.y, s0.z), n2 = mk(s1.x, s1.y, s1.z), n3 = mk(s2.x, s2.y, s2.z);
-        v3 a = sub(n2, n1), b = sub(n3, n1);
-        return normalize(add(add(n1, scale(a, u)), scale(b, v)));
-    }
-    f4 s5 = s[5];
-    return mk(s5.x, s5.y, s5.z);
-}
-// Would the one body's one mesh answer this world-space ray "no intersection" because all its triangles face away from it (kernels.hip
-// faces_away_single: the object-space direction as the traversal kernels form it, OSM:358-364, and their test; a NaN anywhere makes it false)?
-__device__ __forceinline__ bool lights_faces_away_single(const SceneView &S, v3 o, v3 d) {
-    const ObjRec &ob = S.objects[0];
-    const MeshRec &mr = S.meshes[0];
-    const v3 v1 = transform(o, ob.invWorld);
-    const v3 v2 = transform(add(o, d), ob.invWorld);
-    const v3 dir = normalize(sub(v2, v1));
-    return mesh_faces_away(mr, dir);
-}
-// "The query returned this record": hit != 0 with a mesh and a triangle the scene has.  Anything else is a miss and addresses nothing.
-__device__ __forceinline__ bool lights_live(const SceneView &S, const W4 head) {
-    const int mesh = head.z, tri = head.w;
-    bool live = head.x != 0 && mesh >= 0 && mesh < S.nMeshes && tri >= 0;
-    if (live) live = tri < S.meshes[mesh].ntri;
-    return live;
-}
-
-}  // namespace
 
 // Entry e of the chunk is hits[base + e].  A thread reads the (hit, object, mesh, tri) quarter of its entry first and the position only of a
 // live one, so a miss costs 16 bytes and no ray.  Then, LIGHT_EMIT_LIGHTS lights at a time: the shadow ray of every (live entry, light) pair
@@ -89,7 +31,7 @@ __global__ __launch_bounds__(LIGHT_EMIT_BLOCK) void k_light_emit(SceneView S, Li
         if (e < A.n) {
             const W4 *rec = reinterpret_cast<const W4 *>(A.hits + (A.base + e));
             const W4 a = rec[0];   // hit object mesh tri
-            live = lights_live(S, a);
+            live = hit_names_scene(S.meshes, S.nMeshes, a);
             if (live) {
                 const W4 c = rec[2];   // w.xyz reserved
                 mesh = a.z; tri = a.w;
@@ -106,8 +48,8 @@ __global__ __launch_bounds__(LIGHT_EMIT_BLOCK) void k_light_emit(SceneView S, Li
                 dir[r] = mk(0, 0, 0);
                 if (live && l < A.nLights) {
                     float dist;
-                    lights_dir(A.lights[l], w, dir[r], dist);
-                    emit = !(A.ae && lights_faces_away_single(S, w, dir[r]));
+                    light_dir(A.lights[l], w, dir[r], dist);
+                    emit = !(A.ae && faces_away_single(S, w, dir[r]));
                     if (!emit) A.flags[(size_t)e * (size_t)A.nLights + (size_t)l] = 0;   // IsLightPathObstructed's query finds nothing (RT:482-485)
                 }
                 const unsigned long long m = __ballot(emit);
@@ -115,15 +57,7 @@ __global__ __launch_bounds__(LIGHT_EMIT_BLOCK) void k_light_emit(SceneView S, Li
                 if (lane == 0) ldsCells[r * 16 + wave] = (int)__popcll(m);
             }
             __syncthreads();
-            if (wave == 0) {   // reserves the block's range of the list
-                const int c = ldsCells[lane];   // cell r * 16 + w: light by light, ascending entries
-                const int incl = lights_scan_add(c);
-                const int total = __builtin_amdgcn_readlane(incl, 63);
-                int first = 0;
-                if (lane == 0 && total) first = atomicAdd(A.count, total);
-                first = __builtin_amdgcn_readfirstlane(first);
-                ldsCells[lane] = first + incl - c;
-            }
+            if (wave == 0) reserve_cells(ldsCells, A.count);   // the block's range of the list (cell r * 16 + w: light by light, ascending entries)
             __syncthreads();
 #pragma unroll
             for (int r = 0; r < LIGHT_EMIT_LIGHTS; r++) {
@@ -159,14 +93,14 @@ __global__ __launch_bounds__(LIGHT_FOLD_BLOCK) void k_light_fold(SceneView S, Sh
     for (int e = (int)blockIdx.x * LIGHT_FOLD_BLOCK + (int)threadIdx.x; e < A.n; e += step) {
         const W4 *rec = reinterpret_cast<const W4 *>(A.hits + (A.base + e));
         const W4 a = rec[0];   // hit object mesh tri
-        const bool live = lights_live(S, a);
+        const bool live = hit_names_scene(S.meshes, S.nMeshes, a);
         v3 w = mk(0, 0, 0), normal = mk(0, 0, 0);
         if (live) {
             const W4 b = rec[1], c = rec[2];   // leaf u v d | w.xyz reserved
             w = mk(i2f(c.x), i2f(c.y), i2f(c.z));
             const int gtri = V.meshes[a.z].triBase + a.w;
             const MaterialRec M = V.materials[V.meshes[a.z].material];
-            normal = lights_fragment_normal(V, gtri, M.flags, i2f(b.y), i2f(b.z));
+            normal = fragment_normal(V, gtri, M.flags, i2f(b.y), i2f(b.z));
             nLive++;
         }
         v3 lightResult = mk(0, 0, 0);
@@ -176,7 +110,7 @@ __global__ __launch_bounds__(LIGHT_FOLD_BLOCK) void k_light_fold(SceneView S, Sh
             if (live) {
                 const LightRec &Lt = V.lights[l];
                 v3 dir; float dist;
-                lights_dir(Lt, w, dir, dist);
+                light_dir(Lt, w, dir, dist);
                 const size_t pair = (size_t)e * nL + (size_t)l;
                 if (A.flags[pair] != 0) {   // (a miss has no record)
                     const W4 *sh = reinterpret_cast<const W4 *>(A.shadowHits + pair);
@@ -197,15 +131,7 @@ __global__ __launch_bounds__(LIGHT_FOLD_BLOCK) void k_light_fold(SceneView S, Sh
             o[0] = lightResult.x; o[1] = lightResult.y; o[2] = lightResult.z;
         }
     }
-    // the entries treated as hits are only counted: one atomic per block
-    for (int o = 32; o > 0; o >>= 1) nLive += __shfl_xor(nLive, o);
-    if (lane_id() == 0) ldsLive[threadIdx.x >> 6] = nLive;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int total = 0;
-        for (int k = 0; k < LIGHT_FOLD_BLOCK / 64; k++) total += ldsLive[k];
-        if (total) atomicAdd(A.liveCount, total);
-    }
+    block_count_once<LIGHT_FOLD_BLOCK / 64>(A.liveCount, nLive, ldsLive);   // the entries treated as hits are only counted
 }
 
 void launch_light_fold(const SceneView &S, const ShadeView &V, const LightFoldArgs &A, hipStream_t st) {

@@ -10,6 +10,23 @@ namespace xrt {
 
 enum { PIXEL_ONE = 0, PIXEL_QUADRANT = 1, PIXEL_FIXED16 = 2 };   // rays per entry: 1, 4, 16
 
+#ifdef __HIPCC__   // (device code; plain host code includes this header for the launch interface)
+// Where sample s of an entry centred at (sx, sy) lies: the one statement of it for the ray generation kernels of a centre list (k_pixel_rays and
+// k_pixel_raygen in pixels.hip, k_trace_raygen in trace.hip).  QUADRANT false: a call without a quadrant mode (xrt_trace_pixels) compiles no branch for it.
+template <bool QUADRANT = true>
+__device__ __forceinline__ void sample_position(int mode, float size, int s, float &sx, float &sy) {
+    if (QUADRANT && mode == PIXEL_QUADRANT) {   // RT:223-276: four rays at centre -+ size/4, order UL, UR, LL, LR
+        const float quarter = size * 0.25f;
+        sx = (s & 1) ? sx + quarter : sx - quarter;
+        sy = (s & 2) ? sy + quarter : sy - quarter;
+    } else if (mode == PIXEL_FIXED16) {   // corner q = s/4 at +-0.25, sub-sample s%4 at +-0.125, in this association
+        const int q = s >> 2, rr = s & 3;
+        sx = (sx + ((q & 1) ? 0.25f : -0.25f)) + ((rr & 1) ? 0.125f : -0.125f);
+        sy = (sy + ((q & 2) ? 0.25f : -0.25f)) + ((rr & 2) ? 0.125f : -0.125f);
+    }
+}
+#endif
+
 // k_pixel_rays: entries [first, first + count) of a list -> rays[0 .. count * samples), entry-major, as xrt_ray records with a null origin
 // (RT:412-421 / RT:223-276 / the sixteen level-1 positions); `size` is the quadrant's (PIXEL_QUADRANT only).  g: camera part only.
 void launch_pixel_rays(const RayGenParams &g, const float *cx, const float *cy, int stride, long long first, int count, float size, int mode,

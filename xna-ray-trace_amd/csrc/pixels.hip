@@ -21,18 +21,7 @@ constexpr int PIXEL_BLOCK = 256;
 struct alignas(16) Color4 { uint32_t c[4]; };
 __device__ __forceinline__ Color4 load4(const uint32_t *p) { return *reinterpret_cast<const Color4 *>(p); }
 
-// Where sample s of an entry centred at (sx, sy) lies: the one statement of it for both ray generation kernels of this file.
-__device__ __forceinline__ void sample_position(int mode, float size, int s, float &sx, float &sy) {
-    if (mode == PIXEL_QUADRANT) {   // RT:223-276: four rays at centre -+ size/4, order UL, UR, LL, LR
-        const float quarter = size * 0.25f;
-        sx = (s & 1) ? sx + quarter : sx - quarter;
-        sy = (s & 2) ? sy + quarter : sy - quarter;
-    } else if (mode == PIXEL_FIXED16) {   // corner q = s/4 at +-0.25, sub-sample s%4 at +-0.125, in this association
-        const int q = s >> 2, rr = s & 3;
-        sx = (sx + ((q & 1) ? 0.25f : -0.25f)) + ((rr & 1) ? 0.125f : -0.125f);
-        sy = (sy + ((q & 2) ? 0.25f : -0.25f)) + ((rr & 2) ? 0.125f : -0.125f);
-    }
-}
+// (sample_position, where sample s of an entry lies: pixels.h -- trace.hip generates the same rays)
 
 // One thread per ray: ray r of the launch is sample r % samples of entry first + r / samples, so a wave writes 2 KB of consecutive records.
 __global__ __launch_bounds__(PIXEL_BLOCK) void k_pixel_rays(RayGenParams g, const float *cx, const float *cy, int stride, long long first, int count,
@@ -104,25 +93,9 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_pixel_raygen(PixelGenArgs G, Scen
         }
         __syncthreads();
         int quadLen = 0, quadAt = 0;   // wave 0 of a launch with a packet table: the live rays of this lane's cell and its entry
-        if (wave == 0 && Q.table) {
-            quadLen = ldsLive[lane];   // cell r * 16 + w: ascending place order
-            const int incl = wave_scan_add(quadLen);
-            const int total = __builtin_amdgcn_readlane(incl, 63);
-            const unsigned long long mq = __ballot(quadLen > 0);
-            int got = 0;   // lane 0 reserves the slots, lane 1 the entries (a word with a 256-byte line of its own): one atomic instruction
-            if (lane < 2 && total) got = lane == 0 ? atomicAdd(count, total) : (int)atomicAdd(Q.count, (unsigned)__popcll(mq));
-            quadAt = __builtin_amdgcn_readlane(got, 1) + lanes_below(mq);
-            ldsLive[lane] = __builtin_amdgcn_readlane(got, 0) + incl - quadLen;
-        } else if (wave < 2 && (wave == 0 || H.list)) {   // wave 0 reserves the block's range of the live list, wave 1 of the long-ray list
-            int *cells = wave == 0 ? ldsLive : ldsHeavy;
-            const int c = cells[lane];
-            const int incl = wave_scan_add(c);
-            const int total = __builtin_amdgcn_readlane(incl, 63);
-            int base = 0;
-            if (lane == 0 && total) base = atomicAdd(wave == 0 ? count : H.count, total);
-            base = __builtin_amdgcn_readfirstlane(base);
-            cells[lane] = base + incl - c;
-        }
+        // (cell r * 16 + w: ascending place order)
+        if (wave == 0 && Q.table) reserve_cells_and_entries(ldsLive, count, Q.count, quadLen, quadAt);   // the live list and the packet table's entries, one atomic instruction
+        else if (wave < 2 && (wave == 0 || H.list)) reserve_cells(wave == 0 ? ldsLive : ldsHeavy, wave == 0 ? count : H.count);   // wave 0: the live list, wave 1: the long-ray list
         __syncthreads();
         // the block's entries, one coalesced store of wave 0 (Q.cap bounds the entries by construction, as liveCap the rays: the guards are against a wrong bound)
         if (quadLen > 0 && quadAt < Q.cap) Q.table[quadAt] = make_uint2((unsigned)ldsLive[lane], (unsigned)quadLen);

@@ -3,8 +3,8 @@
 // A list the caller calls coherent (xrt.h XRT_LIST_COHERENT) is traced as generation 0 of a frame: k_trace_raygen makes the rays where it compacts them,
 // answers the ones that cannot reach the scene's root box itself, and writes the packet table where the traversal launch is a packet launch.  It is
 // k_pixel_raygen (pixels.hip) with the sinks of a closest-hit query instead of a pass's: no level record, no reference index, no long-ray list.
-// sample_position and the unproject / normalize statements are RESTATED from pixels.hip (moving them to a shared header changed that file's code by a
-// few scheduling decisions, profiles/trace_pixels/README.md): the equalities of tests/test_gpu_trace_pixels.py pin the restatement, bit for bit.
+// sample_position is pixels.h's, the one k_pixel_raygen calls; the unproject / normalize statements are xrt_core.h's, called in pixels.hip's order: the
+// equalities of tests/test_gpu_trace_pixels.py pin the two kernels' rays against each other, bit for bit.
 // The arithmetic is xrt_core.h's, compiled with the same flags: contraction off, every addition below its own rounding.
 #include <hip/hip_runtime.h>
 
@@ -13,15 +13,6 @@
 #include "xrt_core.h"
 
 namespace xrt {
-
-// Where sample s of an entry centred at (sx, sy) lies (pixels.hip sample_position; this call has no quadrant mode).
-__device__ __forceinline__ void trace_sample_position(int mode, int s, float &sx, float &sy) {
-    if (mode == PIXEL_FIXED16) {   // corner q = s/4 at +-0.25, sub-sample s%4 at +-0.125, in this association
-        const int q = s >> 2, rr = s & 3;
-        sx = (sx + ((q & 1) ? 0.25f : -0.25f)) + ((rr & 1) ? 0.125f : -0.125f);
-        sy = (sy + ((q & 2) ? 0.25f : -0.25f)) + ((rr & 2) ? 0.125f : -0.125f);
-    }
-}
 
 // What lane_result (traverse.h) leaves for a miss: hit 0; object, mesh, tri, leaf -1; u, v, d, wx, wy, wz 0.0f; no scheduling feedback.
 __device__ __forceinline__ void store_miss(xrt_hit *dst) {
@@ -58,7 +49,7 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_trace_raygen(PixelGenArgs G, Scen
                 const size_t e = (size_t)(G.first + (long long)(p >> shift)) * (size_t)G.stride;
                 const int s = p & ((1 << shift) - 1);
                 float sx = G.cx[e], sy = G.cy[e];
-                trace_sample_position(G.mode, s, sx, sy);
+                sample_position<false>(G.mode, G.size, s, sx, sy);   // (this call has no quadrant mode)
                 const v3 nearP = unproject(G.cam, sx, sy, 0.0f);   // RT:415
                 const v3 farP = unproject(G.cam, sx, sy, 1.0f);    // RT:419
                 const v3 dir = normalize(sub(farP, nearP));        // RT:420-421
@@ -75,6 +66,8 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_trace_raygen(PixelGenArgs G, Scen
         }
         __syncthreads();
         int quadLen = 0, quadAt = 0;   // wave 0 of a launch with a packet table: the live rays of this lane's cell and its entry
+        // device_util.h's reserve_cells / reserve_cells_and_entries with the scan in front of the branch on Q.table: calling the two helpers moved the scan into both
+        // arms and changed this kernel's code and registers, so the one site keeps its own form
         if (wave == 0) {
             const int c = ldsLive[lane];   // cell r * 16 + w: ascending place order
             const int incl = wave_scan_add(c);

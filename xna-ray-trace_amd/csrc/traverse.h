@@ -473,7 +473,7 @@ XRT_HD bool normal_bounds_can_pass(f4 nmin, f4 nmax, f4 dg) {
 }
 
 // "Does the whole mesh face away from a ray of direction d (object space)?" -- the ONE place that decides it, for the walks (begin_mesh_query, packet.hip),
-// the emission test of k_shade (kernels.hip faces_away_single), the counting pass and, through mesh_can_face_away, the frame plan: the larger of the two
+// the emission test of k_shade (shade_math.h faces_away_single), the counting pass and, through mesh_can_face_away, the frame plan: the larger of the two
 // lower bounds decides, each against its own margin.
 XRT_HD f4 mesh_nb_min(const MeshRec &mr) { return f4{mr.nbMin[0], mr.nbMin[1], mr.nbMin[2], mr.nbMin[3]}; }
 XRT_HD f4 mesh_nb_max(const MeshRec &mr) { return f4{mr.nbMax[0], mr.nbMax[1], mr.nbMax[2], mr.nbMax[3]}; }
