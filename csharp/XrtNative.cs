@@ -171,6 +171,17 @@ namespace RayTraceProject.Native
                                                                       ref XrtRenderOpts opts, [Out] XrtSurface[] surfaceOut, [Out] XrtRay[] reflectOut, [Out] XrtRay[] refractOut, IntPtr stats);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_surface_hits_device(IntPtr scene, IntPtr dRays, IntPtr dHits, long n, float currentRefIndex,
                                                                       ref XrtRenderOpts opts, IntPtr dSurfaceOut, IntPtr dReflectOut, IntPtr dRefractOut, IntPtr stream, IntPtr stats);
+        // The way back up CastRay, one level: RT:726 (reflectRgba null), RT:584, RT:699 (refractRgba given, Transparent entries), RT:732 for an entry
+        // without XRT_SURF_HIT, RT:705 -- from xrt_surface_hits records, xrt_light_hits sums and the packed colours of the nested calls; either
+        // output may be null, not both.  And RT:309: the mean of 4 colours, or of four such means (samples 16).  (additive within ABI 203)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_compose_hits(IntPtr scene, [In] XrtSurface[] surface, [In] float[] lightF32, [In] uint[] reflectRgba,
+                                                                      [In] uint[] refractRgba, long n, [Out] uint[] rgbaOut, [Out] float[] rgbF32Out, IntPtr stats);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_compose_hits_device(IntPtr scene, IntPtr dSurface, IntPtr dLightF32, IntPtr dReflectRgba,
+                                                                      IntPtr dRefractRgba, long n, IntPtr dRgbaOut, IntPtr dRgbF32Out, IntPtr stream, IntPtr stats);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_fold_samples(IntPtr scene, [In] uint[] rgbaIn, long n, int samples, [Out] uint[] rgbaOut,
+                                                                      [Out] float[] rgbF32Out, IntPtr stats);
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_fold_samples_device(IntPtr scene, IntPtr dRgbaIn, long n, int samples, IntPtr dRgbaOut,
+                                                                      IntPtr dRgbF32Out, IntPtr stream, IntPtr stats);
         // SceneObject.Position / Rotation / Scale (SO:51-88) between frames: the dirty bodies' World / InverseWorld / WorldBoundingBox
         // (16 + 16 + 6 floats per id), also while RenderAsync tickets are open; the scene octree stays until xrt_scene_build_tree
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_poses(IntPtr scene, [In] int[] objectIds, int n,

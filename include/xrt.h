@@ -540,7 +540,7 @@ int xrt_light_hits_device(xrt_scene *scene, const void *d_hits, int64_t n,
  * the material terms that weight its composition (Reflectiveness RT:584, color.W RT:699) and builds the reflected ray (RT:547-559) and, on a
  * Transparent material, the Snell refraction (RT:656-694).  xrt_shade_hits hands these out only inside a colour; xrt_surface_hits hands them out
  * themselves: a G-buffer (normal, albedo, alpha, reflectiveness, uv) of given hits, and the rays with which a host drives its own recursion --
- * light with xrt_light_hits, continue with reflect_out / refract_out through xrt_cast_rays or xrt_scene_intersect, compose as RT:584/699/726 do.
+ * light with xrt_light_hits, continue with reflect_out / refract_out through xrt_cast_rays or xrt_scene_intersect, compose with xrt_compose_hits (RT:584/699/726).
  * For every i, `result` is what RT:512 returned, as for xrt_light_hits:
  *   hits[i].hit == 0: the query returned false.  The surface record is all zero; both ray records are o = d = 0, ignore_mesh = ignore_tri = -1.
  *   otherwise mesh, tri, u, v are taken bit for bit (NaN, infinities, -0.0 as given; no other entry is affected).  object, leaf, d and reserved
@@ -591,6 +591,61 @@ int xrt_surface_hits_device(xrt_scene *scene, const void *d_rays, const void *d_
                             float current_ref_index, const xrt_render_opts *opts,
                             void *d_surface_out, void *d_reflect_out, void *d_refract_out /* each nullable */, void *stream,
                             xrt_stats *stats_out /* nullable */);
+
+/* ---- the way back up CastRay: one level of its composition, and the RT:309 fold, on caller-given terms ------------------------------------
+ * Added within ABI 203: four exports, additive; no existing struct, field or entry point changed.
+ * Behind its light loop CastRay either multiplies the light sum by the surface colour (RT:726, iteration >= MaxReflections) or casts the
+ * reflected ray, lerps the colour that came back with the surface colour by 1.0f - Reflectiveness and multiplies by the light sum (RT:584),
+ * and on a Transparent material casts the refracted ray and lerps what came back with that by color.W (RT:699); the result goes through
+ * `new Color(Vector3)` -- clamp, * 255, round half to even (RT:705) -- and what a level hands up is that packed colour, read back with
+ * ToVector3() (/ 255).  Every operation is rounded on its own in binary32, once per level: arithmetic a host cannot restate approximately.
+ * xrt_compose_hits is those statements as the library's frames execute them, so that a recursion the host drives with xrt_surface_hits,
+ * xrt_light_hits and xrt_cast_rays / xrt_scene_intersect ends in the colours the library renders, bit for bit.
+ * For every i:
+ *   surface[i] is the record xrt_surface_hits writes; only color, reflectiveness, alpha and the bits XRT_SURF_HIT / XRT_SURF_TRANSPARENT of
+ *   flags are read.  light_f32[3i ..] is the light sum xrt_light_hits writes.  reflect_rgba[i] / refract_rgba[i] are the packed colours the two
+ *   nested CastRay calls returned, as rgba_out of xrt_cast_rays packs them (their alpha byte is ignored).
+ *   XRT_SURF_HIT clear: RT:732 -- colour 0xFF000000, vector (0, 0, 0); nothing else of the entry is read.
+ *   reflect_rgba == NULL (the caller's `iteration >= MaxReflections`, chosen per call as the reference chooses it per generation): RT:726,
+ *   colorVector = lightResult * surfaceColor.  refract_rgba must then be NULL too.
+ *   reflect_rgba != NULL: RT:584, Lerp(ToVector3(reflect_rgba[i]), color, 1.0f - reflectiveness) * light; and with refract_rgba != NULL on an
+ *   entry with XRT_SURF_TRANSPARENT additionally RT:699, Lerp(ToVector3(refract_rgba[i]), colorVector, alpha).  With refract_rgba == NULL
+ *   RT:586 is skipped for every entry.
+ * rgb_f32_out[3i ..] is the vector handed to `new Color(...)`, rgba_out[i] that colour (RT:705).  Either may be NULL, not both when n > 0.
+ * Values are taken bit for bit: NaN, infinities, -0.0 and colours outside [0, 1] go through the arithmetic as a frame's would (a NaN packs to 0).
+ * In this order, also on a host-only scene: XRT_E_INVALID_ARG for a NULL scene, n < 0, both outputs NULL with n > 0, surface or light_f32 NULL
+ * with n > 0, refract_rgba without reflect_rgba; n == 0 returns XRT_OK; then XRT_E_NO_DEVICE, XRT_E_NOT_BUILT, and XRT_E_BUSY under the rule of
+ * xrt_cast_rays (the scene is read only for its device, its stream and that rule).  Blocking, one synchronisation.
+ * stats_out (may be NULL): pixels = n; shaded_hits the entries with XRT_SURF_HIT; ms_total; intersect_launches = 0; everything else 0.
+ * Not here: a per-entry current_ref_index for xrt_cast_rays (a host groups refract_out by next_ref_index and casts each group with its index),
+ * a begin / end form, and adaptive quadrant trees (xrt_fold_samples with samples == 4 is one level of them). */
+int xrt_compose_hits(xrt_scene *scene, const xrt_surface *surface, const float *light_f32 /* 3 n */,
+                     const uint32_t *reflect_rgba /* nullable, n */, const uint32_t *refract_rgba /* nullable, n */,
+                     int64_t n, uint32_t *rgba_out /* nullable, n */, float *rgb_f32_out /* nullable, 3 n */,
+                     xrt_stats *stats_out /* nullable */);
+
+/* The same on HBM buffers, each 16-byte aligned (else XRT_E_INVALID_ARG, stated after the errors above and before n == 0), enqueued on `stream`
+ * (a hipStream_t; NULL = the scene's stream) and synchronised once before it returns.  The inputs must be ready on `stream`.  d_rgba_out may be
+ * d_reflect_rgba or d_refract_rgba itself -- an entry is read before it is written, so a recursion composes in place --; any other overlap is
+ * undefined.  No device memory is allocated per call. */
+int xrt_compose_hits_device(xrt_scene *scene, const void *d_surface, const void *d_light_f32,
+                            const void *d_reflect_rgba /* nullable */, const void *d_refract_rgba /* nullable */,
+                            int64_t n, void *d_rgba_out, void *d_rgb_f32_out /* each nullable */, void *stream,
+                            xrt_stats *stats_out /* nullable */);
+
+/* RT:309 on caller-given colours.  samples == 4: rgba_out[i] = new Color((a.ToVector3() + b.ToVector3() + c.ToVector3() + d.ToVector3()) / 4.0f)
+ * over rgba_in[4i .. 4i + 3], summed left to right.  samples == 16: four such means over rgba_in[16i + 4q ..], each re-quantised, then their
+ * mean -- the record order xrt_trace_pixels and xrt_render_pixels give XRT_MS_FIXED16 (corner q = s / 4, sub-sample s % 4).  rgb_f32_out[3i ..]
+ * (nullable) is ToVector3() of the result, as the supersampled modes of xrt_render_pixels report it.  The alpha bytes are ignored; the result's
+ * is 0xFF.  Errors in the order of xrt_compose_hits: NULL scene, n < 0, samples neither 4 nor 16, rgba_out NULL with n > 0, rgba_in NULL with
+ * n > 0, (device form) alignment -- all XRT_E_INVALID_ARG --; n == 0 returns XRT_OK; XRT_E_NO_DEVICE, XRT_E_NOT_BUILT, XRT_E_BUSY.
+ * stats_out: pixels = n, ms_total, everything else 0. */
+int xrt_fold_samples(xrt_scene *scene, const uint32_t *rgba_in /* n * samples */, int64_t n, int32_t samples /* 4 or 16 */,
+                     uint32_t *rgba_out /* n */, float *rgb_f32_out /* nullable, 3 n */, xrt_stats *stats_out /* nullable */);
+
+/* The same on HBM buffers, each 16-byte aligned; d_rgba_out must not overlap d_rgba_in. */
+int xrt_fold_samples_device(xrt_scene *scene, const void *d_rgba_in, int64_t n, int32_t samples,
+                            void *d_rgba_out, void *d_rgb_f32_out /* nullable */, void *stream, xrt_stats *stats_out /* nullable */);
 
 /* ---- seam 3, second half: RayTracer.points (RT:504, 543, 701, 740-747) and CastRay's `ref Ray ray` (RT:692-694) ---------------------
  * Added within ABI 203: one struct and two exports, additive; no existing struct, field or entry point changed.
@@ -850,7 +905,7 @@ int xrt_render_pixels_device(xrt_scene *scene, const xrt_camera *camera, const x
  *   - opts fields read: use_multisampling, list_order, collect_stats, and shard_count / n_gpus (must be 0 or 1).  Everything else is ignored.
  *     Poses: the latest.  Materials and triangle shading values are not read.
  *   - identities: xrt_shade_hits(rays_out, hits_out, iteration 0, 1.0f) is xrt_render_pixels with XRT_MS_OFF on the same centres, bit for bit in
- *     rgba and rgb_f32; with XRT_MS_FIXED16 the sixteen colours folded by the RT:309 mean of means are xrt_render_pixels XRT_MS_FIXED16;
+ *     rgba and rgb_f32; with XRT_MS_FIXED16 the sixteen colours folded by xrt_fold_samples (RT:309) are xrt_render_pixels XRT_MS_FIXED16;
  *     row-major integer centres give xrt_scene_intersect(xrt_generate_primary_rays).
  *   - errors, in this order, also on a host-only scene: NULL scene; n < 0; NULL camera or opts; the opts fields above; a viewport that is not
  *     positive; both outputs NULL with n > 0; NULL centers with n > 0; a non-finite centre (host form: the message names the first one, nothing

@@ -165,6 +165,11 @@ SYMBOLS = {
                                    _P(xrt_stats)]),
     "xrt_surface_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, _P(xrt_render_opts), C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, _P(xrt_stats)]),
+    "xrt_compose_hits": (C.c_int, [C.c_void_p, _P(xrt_surface), _F, _P(C.c_uint32), _P(C.c_uint32), C.c_int64, _P(C.c_uint32), _F, _P(xrt_stats)]),
+    "xrt_compose_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          _P(xrt_stats)]),
+    "xrt_fold_samples": (C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_int64, C.c_int32, _P(C.c_uint32), _F, _P(xrt_stats)]),
+    "xrt_fold_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, _P(xrt_stats)]),
     "xrt_cast_rays_paths": (C.c_int, [C.c_void_p, _P(xrt_ray), C.c_int64, C.c_int32, C.c_float, _P(xrt_light), C.c_int32, _P(xrt_render_opts),
                                       _P(C.c_uint32), _F, _P(xrt_ray), _P(C.c_int64), _P(xrt_path_vertex), C.c_int64, _P(C.c_int64), _P(xrt_stats)]),
     "xrt_cast_rays_paths_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, _P(xrt_light), C.c_int32, _P(xrt_render_opts),

@@ -1152,6 +1152,86 @@ class RayTracer:
         out = tuple(o for o, w in ((surf, want_surface), (refl, want_reflect), (refr, want_refract)) if w)
         return out[0] if len(out) == 1 else out
 
+    # ---- the way back up CastRay, one level (RT:584, 699, 705, 726, 732), on caller-given terms: xrt_compose_hits ----
+    def ComposeHits(self, surface, light, reflect=None, refract=None, want_float=False, device=False, stream=None):
+        """For every entry the colour CastRay returns from its surface record (SurfaceHits), its light sum (LightHits) and the packed colours
+        its two nested calls returned (CastRays on the reflected and the refracted rays): without `reflect` RT:726 (light * colour: the
+        caller's iteration >= MaxReflections), with it RT:584, and with `refract` RT:699 on the Transparent entries; an entry without
+        SURF_HIT is black (RT:732).  Host form: SURFACE_DTYPE (n), float32 (n, 3), uint32 (n) -> uint32 (n), and with want_float the vector
+        handed to `new Color` as float32 (n, 3).  device=True: contiguous CUDA tensors on one device -- float32 (n, 16), float32 (n, 3),
+        int32 (n) -> int32 (n) and float32 (n, 3) --, enqueued on `stream` (a torch stream, default: the current one)."""
+        if refract is not None and reflect is None:
+            raise ValueError("ComposeHits: refract without reflect")
+        st, lib = abi.xrt_stats(), abi.lib()
+        if device:
+            import torch
+            if surface.dtype != torch.float32 or surface.dim() != 2 or surface.shape[1] != 16 or not surface.is_contiguous() or not surface.is_cuda:
+                raise ValueError("surface: a contiguous float32 CUDA tensor (n, 16) of xrt_surface records")
+            n = surface.shape[0]
+            if light.dtype != torch.float32 or tuple(light.shape) != (n, 3) or not light.is_contiguous() or light.device != surface.device:
+                raise ValueError("light: a contiguous float32 tensor (n, 3) on the surface records' device")
+            for name, t in (("reflect", reflect), ("refract", refract)):
+                if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous() or t.device != surface.device):
+                    raise ValueError("%s: a contiguous int32 tensor (n) of packed colours on the surface records' device" % name)
+            rgba = torch.empty(n, dtype=torch.int32, device=surface.device)
+            rgbf = torch.empty((n, 3), dtype=torch.float32, device=surface.device) if want_float else None
+            s = stream if stream is not None else torch.cuda.current_stream(surface.device)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+            abi.check(lib.xrt_compose_hits_device(self._scene_handle(), ptr(surface), ptr(light), ptr(reflect), ptr(refract), n, ptr(rgba), ptr(rgbf),
+                                                  C.c_void_p(s.cuda_stream), C.byref(st)))
+        else:
+            surface = np.ascontiguousarray(surface)
+            if surface.dtype != SURFACE_DTYPE or surface.ndim != 1:
+                raise ValueError("surface: an array of SURFACE_DTYPE records")
+            n = surface.shape[0]
+            light = np.ascontiguousarray(light)
+            if light.dtype != np.float32 or light.shape != (n, 3):
+                raise ValueError("light: float32 (n, 3)")
+            cols = []
+            for name, a in (("reflect", reflect), ("refract", refract)):
+                if a is not None:
+                    a = np.ascontiguousarray(a)
+                    if a.dtype != np.uint32 or a.shape != (n,):
+                        raise ValueError("%s: uint32 (n) packed colours" % name)
+                cols.append(a)
+            rgba = np.zeros(n, dtype=np.uint32)
+            rgbf = np.zeros((n, 3), dtype=np.float32) if want_float else None
+            up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32)) if a is not None else None
+            abi.check(lib.xrt_compose_hits(self._scene_handle(), surface.ctypes.data_as(C.POINTER(abi.xrt_surface)), _fp(light), up(cols[0]), up(cols[1]), n,
+                                           up(rgba), _fp(rgbf) if want_float else None, C.byref(st)))
+        self.last_stats = st.as_dict()
+        return (rgba, rgbf) if want_float else rgba
+
+    # ---- RT:309 on caller-given colours: xrt_fold_samples ----
+    def FoldSamples(self, colors, samples=16, want_float=False, device=False, stream=None):
+        """The mean of four packed colours, re-quantised (samples=4), or the mean of four such means (samples=16, the record order of
+        TracePixels / RenderPixels with sixteen samples) of every entry: n * samples colours -> n colours, and with want_float their
+        ToVector3() as float32 (n, 3).  Host form: a uint32 array; device=True: a contiguous int32 CUDA tensor."""
+        if samples not in (4, 16):
+            raise ValueError("FoldSamples: samples is 4 or 16")
+        st, lib = abi.xrt_stats(), abi.lib()
+        if device:
+            import torch
+            if colors.dtype != torch.int32 or not colors.is_contiguous() or not colors.is_cuda or colors.numel() % samples:
+                raise ValueError("colors: a contiguous int32 CUDA tensor of n * samples packed colours")
+            n = colors.numel() // samples
+            rgba = torch.empty(n, dtype=torch.int32, device=colors.device)
+            rgbf = torch.empty((n, 3), dtype=torch.float32, device=colors.device) if want_float else None
+            s = stream if stream is not None else torch.cuda.current_stream(colors.device)
+            abi.check(lib.xrt_fold_samples_device(self._scene_handle(), C.c_void_p(colors.data_ptr()), n, int(samples), C.c_void_p(rgba.data_ptr()),
+                                                  C.c_void_p(rgbf.data_ptr()) if want_float else None, C.c_void_p(s.cuda_stream), C.byref(st)))
+        else:
+            colors = np.ascontiguousarray(colors)
+            if colors.dtype != np.uint32 or colors.size % samples:
+                raise ValueError("colors: uint32, n * samples packed colours")
+            n = colors.size // samples
+            rgba = np.zeros(n, dtype=np.uint32)
+            rgbf = np.zeros((n, 3), dtype=np.float32) if want_float else None
+            abi.check(lib.xrt_fold_samples(self._scene_handle(), colors.ctypes.data_as(C.POINTER(C.c_uint32)), n, int(samples),
+                                           rgba.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(rgbf) if want_float else None, C.byref(st)))
+        self.last_stats = st.as_dict()
+        return (rgba, rgbf) if want_float else rgba
+
     def CastRay(self, ray, iteration=0, origin=None, currentRefIndex=1.0, want_float=False):
         """RT:506: one ray = (position, direction) -> the packed Color (and its float colour vector with want_float).  origin: the
         triangle the ray leaves, (mesh, index in Mesh.Triangles[]) as GetRayIntersection's ignoreTriangle, or None.

@@ -104,7 +104,9 @@ inline int guard_alloc(void **p, size_t bytes) {
     return XRT_OK;
 }
 inline void guard_free(void *p) {
-    if (g_guardMode.load() != 0) { std::lock_guard<std::mutex> lk(g_guards.m); g_guards.bytesOf.erase(p); }
+    // (whatever the mode is NOW: a buffer registered while the mode was on and freed after it was switched off must not stay in the registry --
+    // its address is handed out again, to this library without a guard or to somebody else, and the next check under the mode would read it)
+    { std::lock_guard<std::mutex> lk(g_guards.m); g_guards.bytesOf.erase(p); }
     (void)hipFree(p);
 }
 // All guards of the process (buffers of every scene on the CURRENT device are readable; others are skipped on error).

@@ -594,11 +594,7 @@ __device__ __forceinline__ void path_color_out(const RayGenParams &g, int fused,
     }
     sample_color_out(sampleColor, sampleF32, p, col, cv);
 }
-// The return path of the CastRay recursion, one level: the deepest hit of a path that reached generation MaxReflections has no reflection term
-// (RT:708-727); every other level blends what came back from below -- quantised, RT:705 -- with its surface colour by its Reflectiveness (RT:584).
-// The caller quantises the result (pack_color).
-__device__ __forceinline__ v3 compose_last(v3 light, v3 surf) { return mul(light, surf); }
-__device__ __forceinline__ v3 compose_step(uint32_t below, v3 surf, float refl, v3 light) { return mul(lerp(unpack_color(below), surf, 1.0f - refl), light); }
+// (the return path of the CastRay recursion, one level: compose_last / compose_step / compose_refraction, shade_math.h)
 
 // Rays that miss the scene octree's root box are answered here (OSM:318-320: no cuboid collected -> return
 // false) and the others are appended, wave by wave, to a compact index list for the traversal kernel.
@@ -1190,7 +1186,7 @@ __global__ __launch_bounds__(256) void k_compose_tree(const f4 *lvlA, const f4 *
                 if (!(flag & FLAG_HIT)) { ret = pack_color(mk(0, 0, 0)); retCv = mk(0, 0, 0); sp--; continue; }   // RT:732
                 if (sp == maxReflections) {   // RT:708-727
                     const f4 a = lvlA[(size_t)node * P + p];
-                    retCv = mul(mk(a.x, a.y, a.z), mk(b.x, b.y, b.z));
+                    retCv = compose_last(mk(a.x, a.y, a.z), mk(b.x, b.y, b.z));
                     ret = pack_color(retCv);
                     sp--;
                     continue;
@@ -1209,13 +1205,13 @@ __global__ __launch_bounds__(256) void k_compose_tree(const f4 *lvlA, const f4 *
                     stNode[sp] = 2 * node + 2; stPhase[sp] = 0;
                     continue;
                 }
-                retCv = mul(lerp(unpack_color(stRefl[sp]), mk(b.x, b.y, b.z), 1.0f - a.w), mk(a.x, a.y, a.z));   // RT:584
+                retCv = compose_step(stRefl[sp], mk(b.x, b.y, b.z), a.w, mk(a.x, a.y, a.z));   // RT:584
                 ret = pack_color(retCv);   // RT:705
                 sp--;
                 continue;
             }
-            v3 cv = mul(lerp(unpack_color(stRefl[sp]), mk(b.x, b.y, b.z), 1.0f - a.w), mk(a.x, a.y, a.z));   // RT:584
-            retCv = lerp(unpack_color(ret), cv, lvlAlpha[(size_t)node * P + p]);                               // RT:699
+            const v3 cv = compose_step(stRefl[sp], mk(b.x, b.y, b.z), a.w, mk(a.x, a.y, a.z));   // RT:584
+            retCv = compose_refraction(ret, cv, lvlAlpha[(size_t)node * P + p]);                 // RT:699
             ret = pack_color(retCv);
             sp--;
         }
@@ -1258,8 +1254,7 @@ __global__ __launch_bounds__(256) void k_resolve(RayGenParams g, const uint32_t 
             cv = unpack_color(col);
         } else if (g.quadLevel == 0) {   // adaptive: the pixel's level-0 quadrant after all folds (RT:309)
             const uint32_t *s = sampleColor + (size_t)i * 4;
-            v3 sum = add(add(add(unpack_color(s[0]), unpack_color(s[1])), unpack_color(s[2])), unpack_color(s[3]));
-            col = pack_color(divf(sum, 4.0f));
+            col = mean4(s);
             cv = unpack_color(col);
         } else if (g.samples == 1) {
             col = sampleColor[i];
@@ -1268,11 +1263,9 @@ __global__ __launch_bounds__(256) void k_resolve(RayGenParams g, const uint32_t 
             uint32_t corner[4];
             for (int q = 0; q < 4; q++) {
                 const uint32_t *s = sampleColor + (size_t)i * 16 + q * 4;
-                v3 sum = add(add(add(unpack_color(s[0]), unpack_color(s[1])), unpack_color(s[2])), unpack_color(s[3]));
-                corner[q] = pack_color(divf(sum, 4.0f));
+                corner[q] = mean4(s);
             }
-            v3 sum = add(add(add(unpack_color(corner[0]), unpack_color(corner[1])), unpack_color(corner[2])), unpack_color(corner[3]));
-            col = pack_color(divf(sum, 4.0f));
+            col = mean4(corner);
             cv = unpack_color(col);
         }
         if (g.shardCount > 1) {
@@ -1377,8 +1370,7 @@ __global__ __launch_bounds__(256) void k_ms_fold(uint32_t *quadColor, const uint
         for (int j = 0; j < 4; j++)
             if (mask & (1 << j)) {
                 const uint32_t *s = childColor + 4 * (size_t)o;
-                v3 sum = add(add(add(unpack_color(s[0]), unpack_color(s[1])), unpack_color(s[2])), unpack_color(s[3]));
-                const uint32_t col = pack_color(divf(sum, 4.0f));   // RT:309 of the child call
+                const uint32_t col = mean4(s);   // RT:309 of the child call
                 quadColor[4 * (size_t)q + (j == 3 ? 1 : j)] = col;
                 o++;
             }

@@ -9,6 +9,7 @@
 
 #include "device_util.h"
 #include "pixels.h"
+#include "shade_math.h"
 #include "xrt_core.h"
 
 #include <hip/hip_ext.h>
@@ -183,19 +184,17 @@ void launch_pixel_decide(const uint32_t *quadColor, const float *cx, const float
                        nextCx, nextCy, nextCount);
 }
 
-__device__ __forceinline__ uint32_t mean4(const Color4 &s) {   // RT:309: the mean of four quantised colours, re-quantised
-    const v3 sum = add(add(add(unpack_color(s.c[0]), unpack_color(s.c[1])), unpack_color(s.c[2])), unpack_color(s.c[3]));
-    return pack_color(divf(sum, 4.0f));
-}
+// (RT:309, the mean of four quantised colours, re-quantised: mean4, shade_math.h)
 __global__ __launch_bounds__(PIXEL_BLOCK) void k_pixel_resolve(const uint32_t *sampleColor, int n, int mode, uint32_t *out, float *outF32) {
     for (int i = (int)(blockIdx.x * PIXEL_BLOCK + threadIdx.x); i < n; i += (int)(gridDim.x * PIXEL_BLOCK)) {
         uint32_t col;
         if (mode == PIXEL_QUADRANT) {   // the entry's level-0 quadrant after all folds
-            col = mean4(load4(sampleColor + (size_t)i * 4));
+            const Color4 s = load4(sampleColor + (size_t)i * 4);
+            col = mean4(s.c);
         } else {                        // PIXEL_FIXED16: four means of four
             Color4 corner;
-            for (int q = 0; q < 4; q++) corner.c[q] = mean4(load4(sampleColor + (size_t)i * 16 + q * 4));
-            col = mean4(corner);
+            for (int q = 0; q < 4; q++) { const Color4 s = load4(sampleColor + (size_t)i * 16 + q * 4); corner.c[q] = mean4(s.c); }
+            col = mean4(corner.c);
         }
         out[i] = col;
         if (outF32) { const v3 cv = unpack_color(col); outF32[3 * (size_t)i] = cv.x; outF32[3 * (size_t)i + 1] = cv.y; outF32[3 * (size_t)i + 2] = cv.z; }

@@ -186,6 +186,15 @@ struct xrt_scene {
         DevBuf<xrt_ray> reflectOut, refractOut;
         Event ev[2];   // the call's start and end
     } surfaceWork;
+    // xrt_compose_hits / xrt_fold_samples (compose.hip; the fold is k_pixel_resolve of pixels.hip): the counter word of a call, and the host
+    // forms' inputs and outputs on the device.  Allocated at the first call, freed with the scene; the device forms allocate nothing else.
+    struct ComposeWork {
+        DevBuf<unsigned long long> count;
+        DevBuf<xrt_surface> surfaceIn;
+        DevBuf<float> lightIn, f32Out;
+        DevBuf<uint32_t> reflectIn, refractIn, samplesIn, rgbaOut;
+        Event ev[2];   // the call's start and end
+    } composeWork;
     // xrt_trace_pixels (trace.hip): the work set of one chunk -- the work rays (the compact live list of a hinted chunk; the whole list where the caller
     // wants no rays), the whole list again where a hinted call without a ray output counts the reference's work, the count words (live rays, hits), the
     // queue words of its traversal launch -- and the host form's centres and outputs on the device.  The index list and the packet table of a hinted

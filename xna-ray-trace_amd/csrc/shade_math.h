@@ -1,7 +1,8 @@
 // shade_math.h — RayTracer.CastRay's arithmetic at one hit, stated once for every kernel that shades (gfx950, device code only): the fragment normal, the
-// way to a light, the texture lookup with its interpolated coordinates, "the one mesh faces away from this ray", Snell's refraction, and which hit records
-// name something the scene has.  k_shade (kernels.hip) is their first user; the list calls -- k_ingest_hits (hits.hip), k_light_emit / k_light_fold
-// (lights.hip), k_surface (surface.hip) -- call the same functions.  Results must be bit-identical to the oracle: the association order, where a double
+// way to a light, the texture lookup with its interpolated coordinates, "the one mesh faces away from this ray", Snell's refraction, which hit records
+// name something the scene has, and the way back up: one level of the composition and the supersampling mean.  k_shade (kernels.hip) is their first
+// user; the list calls -- k_ingest_hits (hits.hip), k_light_emit / k_light_fold (lights.hip), k_surface (surface.hip), k_compose_hits (compose.hip),
+// k_pixel_resolve (pixels.hip) -- call the same functions.  Results must be bit-identical to the oracle: the association order, where a double
 // is used and which NaN comes out are properties of the statements below, so a fix is made here and nowhere else.  Every user is built with
 // -ffp-contract=off: each operation its own rounding.
 #pragma once
@@ -128,6 +129,19 @@ __device__ __forceinline__ bool hit_names_scene(const MeshRec *meshes, int nMesh
     bool live = head.x != 0 && mesh >= 0 && mesh < nMeshes && tri >= 0;
     if (live) live = tri < meshes[mesh].ntri;
     return live;
+}
+
+// The return path of the CastRay recursion, one level: the deepest hit of a path that reached generation MaxReflections has no reflection term
+// (RT:708-727); every other level blends what came back from below -- quantised, RT:705 -- with its surface colour by its Reflectiveness (RT:584),
+// and on a Transparent material blends what came back through the surface with that by color.W (RT:699).  The caller quantises the result
+// (pack_color).  Users: k_shade, k_compose, k_compose_tree (kernels.hip) and k_compose_hits (compose.hip).
+__device__ __forceinline__ v3 compose_last(v3 light, v3 surf) { return mul(light, surf); }
+__device__ __forceinline__ v3 compose_step(uint32_t below, v3 surf, float refl, v3 light) { return mul(lerp(unpack_color(below), surf, 1.0f - refl), light); }
+__device__ __forceinline__ v3 compose_refraction(uint32_t through, v3 cv, float alpha) { return lerp(unpack_color(through), cv, alpha); }
+// RT:309: the mean of four quantised colours, summed left to right, re-quantised.  Users: k_resolve (kernels.hip), k_pixel_resolve (pixels.hip).
+__device__ __forceinline__ uint32_t mean4(const uint32_t *s /* four colours */) {
+    const v3 sum = add(add(add(unpack_color(s[0]), unpack_color(s[1])), unpack_color(s[2])), unpack_color(s[3]));
+    return pack_color(divf(sum, 4.0f));
 }
 
 }  // namespace xrt

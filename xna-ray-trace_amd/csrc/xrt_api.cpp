@@ -26,6 +26,7 @@ using namespace xrt;
 #include "trace.h"         // xrt_trace_pixels: rays and closest hits of a centre list (trace.hip) ...
 #include "trace_plan.h"    // ... and how a list is split into chunks
 #include "surface.h"       // xrt_surface_hits: surface terms and next rays of a caller's hits (surface.hip)
+#include "compose.h"       // xrt_compose_hits: CastRay's return path on a caller's terms (compose.hip)
 
 namespace {
 
@@ -2422,6 +2423,68 @@ int surface_hits_impl(xrt_scene *s, const xrt_ray *d_rays, const xrt_hit *d_hits
     return XRT_OK;
 }
 
+// ---- xrt_compose_hits: the return path of CastRay, one level (RT:584, 699, 705, 726, 732), on a caller's terms ---------------------------------
+// n > 0 entries in HBM.  One kernel, k_compose_hits, launched in pieces of at most COMPOSE_PIECE entries (an int indexes the entries of a launch;
+// the base offsets are size_t); the counter word comes back behind the call's one synchronisation.  Nothing of the scene is read but its
+// stream.  The caller holds the scene (BusyGuard, no frame in flight).
+int compose_hits_impl(xrt_scene *s, const xrt_surface *d_surface, const float *d_light, const uint32_t *d_reflect, const uint32_t *d_refract, int64_t n,
+                      uint32_t *d_rgba, float *d_f32, hipStream_t st, xrt_stats *stats) {
+    xrt_scene::ComposeWork &W = s->composeWork;
+    int rc;
+    if ((rc = W.count.ensure(1))) return rc;
+    for (Event &e : W.ev) if ((rc = e.create(hipEventDefault))) return rc;
+    Range rf("xrt compose hits");
+    HIPCHECK(hipMemsetAsync(W.count.p, 0, sizeof(unsigned long long), st));
+    HIPCHECK(hipEventRecord(W.ev[0], st));
+    for (size_t base = 0; base < (size_t)n; base += (size_t)COMPOSE_PIECE) {
+        const size_t left = (size_t)n - base;
+        ComposeArgs A;
+        A.surface = d_surface; A.light = d_light; A.reflect = d_reflect; A.refract = d_refract;
+        A.base = base; A.n = (int)(left < (size_t)COMPOSE_PIECE ? left : (size_t)COMPOSE_PIECE);
+        A.haveReflect = d_reflect ? 1 : 0; A.haveRefract = d_refract ? 1 : 0; A.wantRgba = d_rgba ? 1 : 0; A.wantF32 = d_f32 ? 1 : 0;
+        A.rgbaOut = d_rgba; A.f32Out = d_f32; A.hitCount = W.count.p;
+        launch_compose_hits(A, st);
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(W.ev[1], st));
+    unsigned long long live = 0;
+    HIPCHECK(hipMemcpyAsync(&live, W.count.p, sizeof(live), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));   // (the one synchronisation of the call)
+    float ms = 0.0f;
+    HIPCHECK(hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->pixels = (uint64_t)n; stats->shaded_hits = live; stats->ms_total = ms; stats->intersect_launches = 0;
+    }
+    return XRT_OK;
+}
+
+// ---- xrt_fold_samples: RT:309 on a caller's colours: the mean of four, or the mean of four such means ------------------------------------------
+// n > 0 entries of `samples` colours in HBM, through k_pixel_resolve (pixels.hip: what xrt_render_pixels folds its own samples with), launched in
+// pieces of at most COMPOSE_PIECE entries.  One synchronisation.
+int fold_samples_impl(xrt_scene *s, const uint32_t *d_in, int64_t n, int32_t samples, uint32_t *d_rgba, float *d_f32, hipStream_t st, xrt_stats *stats) {
+    xrt_scene::ComposeWork &W = s->composeWork;
+    int rc;
+    for (Event &e : W.ev) if ((rc = e.create(hipEventDefault))) return rc;
+    Range rf("xrt fold samples");
+    HIPCHECK(hipEventRecord(W.ev[0], st));
+    for (size_t base = 0; base < (size_t)n; base += (size_t)COMPOSE_PIECE) {
+        const size_t left = (size_t)n - base;
+        launch_pixel_resolve(d_in + base * (size_t)samples, (int)(left < (size_t)COMPOSE_PIECE ? left : (size_t)COMPOSE_PIECE),
+                             samples == 4 ? PIXEL_QUADRANT : PIXEL_FIXED16, d_rgba + base, d_f32 ? d_f32 + 3 * base : nullptr, st);
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(W.ev[1], st));
+    HIPCHECK(hipStreamSynchronize(st));   // (the one synchronisation of the call)
+    float ms = 0.0f;
+    HIPCHECK(hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->pixels = (uint64_t)n; stats->ms_total = ms; stats->intersect_launches = 0;
+    }
+    return XRT_OK;
+}
+
 int pose_upload(xrt_scene *scene);
 
 // What is made from the scene octree and the poses (snodes, srefs, objects, scull, the positions of every body's records in scull, the
@@ -3623,6 +3686,92 @@ int xrt_surface_hits_device(xrt_scene *scene, const void *d_rays, const void *d_
                                                              (xrt_surface *)d_surface_out, (xrt_ray *)d_reflect_out, (xrt_ray *)d_refract_out, hold.st, stats_out)))
             return rc;
         return guards_check("end of a batch of surface records");
+    });
+}
+
+// What is wrong with the arguments of xrt_compose_hits[_device] alone, in the order the header gives (the scene is not looked at).
+static int compose_hits_check_args(const char *fn, const void *surface, const void *light, const void *reflect, const void *refract, int64_t n,
+                                   const void *rgba_out, const void *rgb_f32_out) {
+    if (n < 0) return fail(XRT_E_INVALID_ARG, "%s: n = %lld out of range", fn, (long long)n);
+    if (n > 0 && !rgba_out && !rgb_f32_out) return fail(XRT_E_INVALID_ARG, "%s: both outputs are null", fn);
+    if (n > 0 && !surface) return fail(XRT_E_INVALID_ARG, "%s: null surface", fn);
+    if (n > 0 && !light) return fail(XRT_E_INVALID_ARG, "%s: null light", fn);
+    if (refract && !reflect) return fail(XRT_E_INVALID_ARG, "%s: refract_rgba without reflect_rgba", fn);
+    return XRT_OK;
+}
+
+int xrt_compose_hits(xrt_scene *scene, const xrt_surface *surface, const float *light_f32, const uint32_t *reflect_rgba, const uint32_t *refract_rgba, int64_t n,
+                     uint32_t *rgba_out, float *rgb_f32_out, xrt_stats *stats_out) {
+    return list_call("xrt_compose_hits", scene, [&](const char *fn) -> int {
+        int rc;
+        if ((rc = compose_hits_check_args(fn, surface, light_f32, reflect_rgba, refract_rgba, n, rgba_out, rgb_f32_out))) return rc;
+        if (empty_list(n, stats_out)) return XRT_OK;
+        SceneHold hold(scene);
+        if ((rc = hold.begin(fn))) return rc;   // (what is wrong with the arguments alone is said first, also on a host-only scene)
+        xrt_scene::ComposeWork &W = scene->composeWork;
+        Staging S(hold.st);
+        const xrt_surface *d_surface = S.in(W.surfaceIn, surface, (size_t)n);
+        const float *d_light = S.in(W.lightIn, light_f32, (size_t)n * 3);
+        const uint32_t *d_reflect = S.in(W.reflectIn, reflect_rgba, (size_t)n), *d_refract = S.in(W.refractIn, refract_rgba, (size_t)n);
+        uint32_t *d_rgba = S.out(W.rgbaOut, rgba_out, (size_t)n);
+        float *d_f32 = S.out(W.f32Out, rgb_f32_out, (size_t)n * 3);
+        if ((rc = S.rc) || (rc = compose_hits_impl(scene, d_surface, d_light, d_reflect, d_refract, n, d_rgba, d_f32, hold.st, stats_out))) return rc;
+        return S.finish("end of a batch of composed hits");
+    });
+}
+
+int xrt_compose_hits_device(xrt_scene *scene, const void *d_surface, const void *d_light_f32, const void *d_reflect_rgba, const void *d_refract_rgba, int64_t n,
+                            void *d_rgba_out, void *d_rgb_f32_out, void *stream, xrt_stats *stats_out) {
+    return list_call("xrt_compose_hits_device", scene, [&](const char *fn) -> int {
+        int rc;
+        if ((rc = compose_hits_check_args(fn, d_surface, d_light_f32, d_reflect_rgba, d_refract_rgba, n, d_rgba_out, d_rgb_f32_out)) ||
+            (rc = aligned16({d_surface, d_light_f32, d_reflect_rgba, d_refract_rgba, d_rgba_out, d_rgb_f32_out})))
+            return rc;
+        if (empty_list(n, stats_out)) return XRT_OK;
+        SceneHold hold(scene, stream);
+        if ((rc = hold.begin(fn)) || (rc = compose_hits_impl(scene, (const xrt_surface *)d_surface, (const float *)d_light_f32, (const uint32_t *)d_reflect_rgba,
+                                                             (const uint32_t *)d_refract_rgba, n, (uint32_t *)d_rgba_out, (float *)d_rgb_f32_out, hold.st, stats_out)))
+            return rc;
+        return guards_check("end of a batch of composed hits");
+    });
+}
+
+// What is wrong with the arguments of xrt_fold_samples[_device] alone, in the order the header gives (the scene is not looked at).
+static int fold_samples_check_args(const char *fn, const void *rgba_in, int64_t n, int32_t samples, const void *rgba_out) {
+    if (n < 0) return fail(XRT_E_INVALID_ARG, "%s: n = %lld out of range", fn, (long long)n);
+    if (samples != 4 && samples != 16) return fail(XRT_E_INVALID_ARG, "%s: samples = %d is neither 4 nor 16", fn, samples);
+    if (n > 0 && !rgba_out) return fail(XRT_E_INVALID_ARG, "%s: null rgba_out", fn);
+    if (n > 0 && !rgba_in) return fail(XRT_E_INVALID_ARG, "%s: null rgba_in", fn);
+    return XRT_OK;
+}
+
+int xrt_fold_samples(xrt_scene *scene, const uint32_t *rgba_in, int64_t n, int32_t samples, uint32_t *rgba_out, float *rgb_f32_out, xrt_stats *stats_out) {
+    return list_call("xrt_fold_samples", scene, [&](const char *fn) -> int {
+        int rc;
+        if ((rc = fold_samples_check_args(fn, rgba_in, n, samples, rgba_out))) return rc;
+        if (empty_list(n, stats_out)) return XRT_OK;
+        SceneHold hold(scene);
+        if ((rc = hold.begin(fn))) return rc;
+        xrt_scene::ComposeWork &W = scene->composeWork;
+        Staging S(hold.st);
+        const uint32_t *d_in = S.in(W.samplesIn, rgba_in, (size_t)n * (size_t)samples);
+        uint32_t *d_rgba = S.out(W.rgbaOut, rgba_out, (size_t)n);
+        float *d_f32 = S.out(W.f32Out, rgb_f32_out, (size_t)n * 3);
+        if ((rc = S.rc) || (rc = fold_samples_impl(scene, d_in, n, samples, d_rgba, d_f32, hold.st, stats_out))) return rc;
+        return S.finish("end of a batch of folded samples");
+    });
+}
+
+int xrt_fold_samples_device(xrt_scene *scene, const void *d_rgba_in, int64_t n, int32_t samples, void *d_rgba_out, void *d_rgb_f32_out, void *stream,
+                            xrt_stats *stats_out) {
+    return list_call("xrt_fold_samples_device", scene, [&](const char *fn) -> int {
+        int rc;
+        if ((rc = fold_samples_check_args(fn, d_rgba_in, n, samples, d_rgba_out)) || (rc = aligned16({d_rgba_in, d_rgba_out, d_rgb_f32_out}))) return rc;
+        if (empty_list(n, stats_out)) return XRT_OK;
+        SceneHold hold(scene, stream);
+        if ((rc = hold.begin(fn)) || (rc = fold_samples_impl(scene, (const uint32_t *)d_rgba_in, n, samples, (uint32_t *)d_rgba_out, (float *)d_rgb_f32_out, hold.st, stats_out)))
+            return rc;
+        return guards_check("end of a batch of folded samples");
     });
 }
 
