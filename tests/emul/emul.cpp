@@ -18,6 +18,17 @@ struct EmuStack {
     void set(int i, unsigned v) { w[i] = v; }
 };
 
+// The same stack with the capacity the device kernel would get: an index at or beyond it is recorded, never touched (a read of it answers 0),
+// and the highest index touched is kept (emu_intersect_bounded; tests/test_tree_shapes_cpu.py).
+struct BoundedStack {
+    unsigned w[256];
+    int cap, high = -1, outside = 0;
+    explicit BoundedStack(int c) : cap(c < 256 ? c : 256) {}
+    bool in(int i) { if (i > high) high = i; if (i >= 0 && i < cap) return true; outside++; return false; }
+    unsigned get(int i) { return in(i) ? w[i] : 0u; }
+    void set(int i, unsigned v) { if (in(i)) w[i] = v; }
+};
+
 struct emu_scene { HostScene hs; std::string err; };
 
 extern "C" {
@@ -73,6 +84,35 @@ int emu_intersect(emu_scene *s, int mode, int mesh, const xrt_ray *rays, int64_t
     }
     return 0;
 }
+
+// emu_intersect on a stack of `capacity` words (BoundedStack).  out[0]: the highest stack index any ray touched (-1: none), out[1]: accesses at
+// or beyond the capacity (the answers are meaningless unless 0), out[2], out[3]: sceneDepth and meshDepth of the view, the stack words the scene
+// cursor and the mesh walk are given (scene tree depth + 1, deepest mesh tree depth + 1).
+int emu_intersect_bounded(emu_scene *s, int mode, int mesh, const xrt_ray *rays, int64_t n, xrt_hit *hits, int capacity, int *out) {
+    if (!s->hs.built) return -1;
+    SceneView S = s->hs.host_view();
+    BoundedStack stk(capacity);
+    for (int64_t i = 0; i < n; i++) {
+        Lane L;
+        std::memset(&L, 0, sizeof(L));
+        lane_begin(L, S, mk(rays[i].o[0], rays[i].o[1], rays[i].o[2]), mk(rays[i].d[0], rays[i].d[1], rays[i].d[2]),
+                   rays[i].ignore_mesh, rays[i].ignore_tri, (int)i, mode, mesh);
+        while (L.state != ST_FINISH) {
+            if (L.state == ST_SCENE) advance_scene(L, S, stk);
+            else if (L.state == ST_NODE) advance_node(L, S, stk, mode, fast_mode != 0 && L.r.par == 0 && !L.weird);
+            else if (L.state == ST_LEAF) advance_leaf(L, S);
+        }
+        HitOut h = lane_result(L, S, mode);
+        xrt_hit &o = hits[i];
+        std::memset(&o, 0, sizeof(o));
+        o.hit = h.hit; o.object = h.object; o.mesh = h.mesh; o.tri = h.tri; o.leaf = h.leaf;
+        o.u = h.u; o.v = h.v; o.d = h.d; o.wx = h.wx; o.wy = h.wy; o.wz = h.wz;
+    }
+    out[0] = stk.high; out[1] = stk.outside; out[2] = S.sceneDepth; out[3] = S.meshDepth;
+    return 0;
+}
+// the capacity the library picks for a scene that needs `needed` stack words (traverse.h intersect_stack_capacity), or -1: refused
+int emu_stack_capacity(int needed) { return intersect_stack_capacity(needed); }
 
 // Wave-level model of k_intersect's scheduling (development aid): 64 lanes, the same refill rule and phase
 // bursts as kernels.hip; reports how many wave-steps each phase takes and how many lanes were active in them.

@@ -46,13 +46,21 @@ def lib():
         l.emu_get_tree.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)]
         l.emu_tree_stats.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         l.emu_intersect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        l.emu_wave_sim.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        l.emu_intersect_bounded.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        l.emu_stack_capacity.argtypes = [C.c_int]
+        l.emu_wave_sim.argtypes =[C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         _lib = l
     return _lib
 
 
 def _fp(a):
     return a.ctypes.data_as(_F)
+
+
+def stack_capacity(needed):
+    """The library's own choice (traverse.h intersect_stack_capacity): the per-lane stack capacity of k_intersect for a scene that needs `needed`
+    words, or -1 where xrt_scene_build refuses the scene."""
+    return int(lib().emu_stack_capacity(int(needed)))
 
 
 class EmulScene:
@@ -107,6 +115,16 @@ class EmulScene:
         rc = lib().emu_intersect(self.h, mode, mesh, rays.ctypes.data, rays.shape[0], hits.ctypes.data, st.ctypes.data if steps else None)
         assert rc == 0, rc
         return (hits, st) if steps else hits
+
+    def intersect_bounded(self, rays, capacity, mode=0, mesh=0):
+        """intersect() on a stack of `capacity` words -> (hits, dict): `high` the highest stack index touched (-1: none), `outside` the accesses at
+        or beyond the capacity (refused, not made), `scene_words` / `mesh_words` the stack words the two walks are given."""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+        hits = np.zeros(rays.shape[0], dtype=HIT_DTYPE)
+        out = (C.c_int * 4)()
+        rc = lib().emu_intersect_bounded(self.h, mode, mesh, rays.ctypes.data, rays.shape[0], hits.ctypes.data, int(capacity), out)
+        assert rc == 0, rc
+        return hits, dict(zip(("high", "outside", "scene_words", "mesh_words"), list(out)))
 
     def wave_sim(self, rays, mode=0, mesh=0, n_waves=64, tune=(24, 16, 48)):
         """Wave-level scheduling model of the traversal kernel: step and active-lane counts per phase."""

@@ -222,7 +222,7 @@ struct ShadeArgs {
     EndArgs end;
 };
 
-int  intersect_stack_capacity(int needed);   // smallest compiled capacity >= needed, or -1
+// (intersect_stack_capacity(needed), the smallest compiled capacity >= needed or -1: traverse.h)
 void launch_intersect(const SceneView &S, const IntersectArgs &A, int stackNeeded, int gridBlocks, hipStream_t st, hipEvent_t e0 = nullptr,
                       hipEvent_t e1 = nullptr);
 int  intersect_blocks_per_cu(int stackNeeded, int mode);

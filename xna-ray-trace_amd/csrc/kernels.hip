@@ -357,11 +357,7 @@ __global__ __launch_bounds__(256, (M == MODE_SCENE) ? 4 : 5) void k_intersect(Sc
     stamp_end(A.stamps);
 }
 
-int intersect_stack_capacity(int needed) {
-    const int caps[] = {8, 12, 16, 24, 40};
-    for (int c : caps) if (needed <= c) return c;
-    return -1;
-}
+// (intersect_stack_capacity and the capacities themselves: traverse.h INTERSECT_STACK_CAPS; one instantiation per entry below)
 template <int T, int M> static int bpc() {
     int nb = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_intersect<T, M>, 256, 0) != hipSuccess || nb < 1) nb = 1;

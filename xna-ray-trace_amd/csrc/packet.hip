@@ -523,7 +523,7 @@ __device__ __forceinline__ void pk_walk(const float *__restrict__ pblocks, const
         }
         const unsigned long long LL = __ballot(go);
         if (LL == 0ull) continue;
-        if (sp >= PK_LEVELS - 1) continue;   // (cannot happen: packet_supported checks the depth)
+        if (sp >= PK_LEVELS - 1) continue;   // (cannot happen: packet_supported checks the depth -- the deepest mesh tree the builder accepts, 20 levels, walks here in tests/test_gpu_tree_shapes.py test_hits[mesh_md20-packet])
         if (U.p != 0) {   // something is left to do at this level: come back
             cbOf[sp * 64] = (unsigned char)cb;   // (every lane: its own accepted children of this level's block)
             if (lane == 0) *reinterpret_cast<Frame4 *>(stk + sp * PK_FRAME_WORDS) = Frame4{(unsigned)U.blk, (unsigned)U.p, (unsigned)U.lanes, (unsigned)(U.lanes >> 32)};
@@ -867,7 +867,7 @@ __global__ __launch_bounds__(256, (M == MODE_SCENE) ? PK_SCENE_WAVES : (PK_SINGL
                 if (hm == 0ull) continue;
                 const int a_ = rfl(f2i(lo.w)), b_ = rfl(f2i(hi.w));
                 if (b_ >= 0) {   // interior
-                    if (ssp >= PK_SLEVELS - 1) continue;   // (cannot happen: packet_supported checks the depth)
+                    if (ssp >= PK_SLEVELS - 1) continue;   // (cannot happen: packet_supported checks the depth -- tests/test_gpu_tree_shapes.py test_which_kernel_ran stands on both sides of that seam: scene depth 10 walks here, 11 and 24 go to k_intersect)
                     if (smask) {
                         if (lane == 0) {
                             unsigned *f = sfr + ssp * PK_SFRAME_WORDS;

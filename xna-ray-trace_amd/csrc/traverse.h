@@ -42,6 +42,16 @@ struct SceneView {
                                  // normal box): 0 off, 1 for rays that lately met back faces only / packets of rays leaving a surface, 2 always
 };
 
+// The per-lane stack of a query: words [0, sceneDepth) belong to the scene cursor (advance_scene), words [sceneDepth, sceneDepth + meshDepth)
+// to the mesh walk (advance_node), so a scene needs (scene tree depth + 1) + (deepest mesh tree depth + 1) words.  k_intersect is compiled for
+// the capacities below (kernels.hip launch_mode) and a scene that needs more is refused when it is built.  Stated here, once, for the
+// library and for the single-stepper of tests/emul, which bounds its own stack by it (tests/test_tree_shapes_cpu.py).
+constexpr int INTERSECT_STACK_CAPS[] = {8, 12, 16, 24, 40};
+inline int intersect_stack_capacity(int needed) {   // smallest compiled capacity >= needed, or -1
+    for (int c : INTERSECT_STACK_CAPS) if (needed <= c) return c;
+    return -1;
+}
+
 // k_packet's block record (SceneView::pblocks), PBLOCK_WORDS floats per block:
 //   [0..7]   the block descriptor (the two f4 of `blocks`)
 //   [8..11]  x0, x1, x2, hx0   [12..15] y0, y1, y2, hy0   [16..19] z0, z1, z2, hz0
