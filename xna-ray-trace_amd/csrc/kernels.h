@@ -230,7 +230,14 @@ void launch_count(const SceneView &S, const IntersectArgs &A, unsigned long long
 void launch_raygen(const RayGenParams &g, const SceneView &S, xrt_ray *rays, f4 *lvlB0, int *index, int *count, int P, long long pathBase,
                    const HeavyArgs &H, hipStream_t st, hipEvent_t startEvent = nullptr, int liveCap = 0x7fffffff, const EndArgs *end = nullptr,
                    const QuadTable *quads = nullptr);
-void launch_shade(const SceneView &S, const ShadeView &V, const ShadeArgs &X, hipStream_t st, int blocks = 1024, int threads = 1024);   // (any grid is correct: grid-stride loops)
+// k_shade over a generation of at most `rays` work items (< 0: unknown, the largest grid) in blocks of `threads` threads: whole waves, SHADE_BLOCK_MIN .. SHADE_BLOCK_MAX
+// (any grid is correct: grid-stride loops; the largest grid is SHADE_GRID_THREADS threads at every block size)
+constexpr int SHADE_BLOCK_MIN = 256, SHADE_BLOCK_MAX = 1024, SHADE_GRID_THREADS = 1 << 20;
+inline int shade_grid_blocks(long long rays, int threads) {
+    const long long cap = (SHADE_GRID_THREADS + threads - 1) / threads, want = rays < 0 ? cap : (rays + threads - 1) / threads;
+    return (int)(want < 1 ? 1 : (want > cap ? cap : want));
+}
+void launch_shade(const SceneView &S, const ShadeView &V, const ShadeArgs &X, hipStream_t st, long long rays = -1, int threads = SHADE_BLOCK_MAX);
 // Frame epilogue of the compose kernels: the clock stamps of traversal launches row0 .. row1-1 are folded into (start, latest
 // end) pairs in host-visible memory (device_util.h)
 struct StampFold {

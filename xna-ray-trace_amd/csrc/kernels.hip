@@ -1056,10 +1056,13 @@ __global__ __launch_bounds__(APPEND_BLOCK) __attribute__((amdgpu_waves_per_eu(6)
     }
     if constexpr (END) block_count(X.end.cnt + END_BY_SHADE, nEnded, ldsCounts);
 }
-void launch_shade(const SceneView &S, const ShadeView &V, const ShadeArgs &X, hipStream_t st, int blocks, int threads) {
-    if (threads != 256) threads = APPEND_BLOCK;   // 256-thread blocks spread a small generation over the CUs (block_append takes any block of whole waves)
-    const int cap = threads == 256 ? 4096 : 1024;
-    const dim3 grid(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
+static_assert(SHADE_BLOCK_MAX == APPEND_BLOCK && SHADE_BLOCK_MIN >= 128, "k_shade: ldsCounts holds 16 waves' cells, block_append2 needs two waves");
+void launch_shade(const SceneView &S, const ShadeView &V, const ShadeArgs &X, hipStream_t st, long long rays, int threads) {
+    // Any block of 4 .. 16 whole waves (block_append, block_append2 and block_count take their wave count from blockDim): 256 threads spread a small
+    // generation over the CUs; of a big one a CU holds one block of 1024 (16 of the 24 waves k_shade is compiled for), two of 768, three of 512 --
+    // the frame plan chooses (FramePlan::shadeBlock, profiles/shade_blocks).  Anything else is a caller's mistake and runs as 1024.
+    if (threads < SHADE_BLOCK_MIN || threads > SHADE_BLOCK_MAX || threads % 64 != 0) threads = APPEND_BLOCK;
+    const dim3 grid(shade_grid_blocks(rays, threads));
     if (X.finish && X.end.on) hipLaunchKernelGGL((k_shade<true, true>), grid, dim3(threads), 0, st, S, V, X);
     else if (X.finish) hipLaunchKernelGGL((k_shade<true, false>), grid, dim3(threads), 0, st, S, V, X);
     else hipLaunchKernelGGL((k_shade<false, false>), grid, dim3(threads), 0, st, S, V, X);

@@ -83,6 +83,10 @@ struct Settings {
     long long adaptiveCap = 0;   // XRT_ADAPTIVE_CAP=<quadrants> (tests): capacity of the deeper levels instead of one quadrant per pixel
     bool heapFast = true;        // single-chunk ray-tree frames go the optimistic way (no host round trip) until one overflows; XRT_HEAP_FAST=0
     bool gridHints = true;       // XRT_GRID_HINTS=0: every launch is sized for the whole chip
+    // Threads per block of k_shade over a big generation (XRT_SHADE_BLOCK=<256 .. 1024, a multiple of 64>; scheduling only).  The kernel is compiled for 24 waves
+    // per CU and its 16 waves of a 1024-thread block move in lockstep from barrier to barrier, so a CU held one block and waited with it.  Two blocks of 768:
+    // k_shade #0 of C5 485 -> 426 us, the pipelined frame 2.962 -> 2.907 ms; three of 512 the same on C5 but C4 +0.03 ms (profiles/shade_blocks).
+    int shadeBlock = 768;
     bool launchTiming = true;    // XRT_LAUNCH_TIMING=0: single-chunk frames do not time their traversal launches (xrt_stats.ms_intersect = 0)
     std::string waveTimesPath;   // XRT_WAVE_TIMES=<file>: per-wave clocks of the last frame's launches (development aid, make WAVE_TIMES=1)
     std::string stampDumpPath;   // XRT_STAMP_DUMP=<file>: the stamp rows of the last frame (start, waves, every wave's end) -- how long a launch's waves lived
@@ -162,6 +166,7 @@ inline Settings read_settings() {
     env_int("XRT_ADAPTIVE_CAP", c.adaptiveCap, 1, LLONG_MAX);
     env_flag("XRT_HEAP_FAST", c.heapFast);
     env_flag("XRT_GRID_HINTS", c.gridHints);
+    env_int("XRT_SHADE_BLOCK", c.shadeBlock, 256, 1024, 64);
     env_flag("XRT_LAUNCH_TIMING", c.launchTiming);
     env_str("XRT_WAVE_TIMES", c.waveTimesPath);
     env_str("XRT_STAMP_DUMP", c.stampDumpPath);

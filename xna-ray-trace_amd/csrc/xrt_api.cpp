@@ -564,6 +564,7 @@ int plan_frame(const xrt_scene &s, int matVersion, const xrt_camera *cam, const 
     // "long ray first" (kernels.hip): the producer of generation k lists its long rays, launch #k takes them first
     p.listLong = s.heavyPath > 0.0f || p.wantFeedback;
     p.hinted = p.fast && nParts == 1 && s.genKey == firstPaths * 64 + nL && s.genHeap == heap && s.cfg.gridHints;
+    p.shadeBlock = s.cfg.shadeBlock;
     // valid pixels of this part
     if (batch) p.validPixels = (unsigned long long)batch->n;
     else {
@@ -911,10 +912,10 @@ int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int P
         X.lvlA = W.lvlA.p; X.lvlB = W.lvlB.p; X.lvlAlpha = heap ? W.lvlAlpha.p : nullptr;
         if (k < R) X.heavy = heavy_for(k + 1, hcnt);
         if (feedback && hasClosest && !packet_closest(k)) { X.costOut = s->costMap.p + (size_t)k * (size_t)P.framePaths + (size_t)P.partStart; X.epoch = s->epoch & 0xffffu; }
-        {   // (a small generation: 256-thread blocks, so that its work items land on many CUs instead of on the first few)
+        {   // (a small generation: 256-thread blocks, so that its work items land on many CUs instead of on the first few; a big or unknown one: the plan's size.
+            //  The hint is in rays, launch_shade turns it into blocks of either size)
             const long long h = hint(s->genShade, k);
-            if (h >= 0 && h < 4 * 131072 + 4096) launch_shade(S, V, X, st, (int)((h + 255) / 256), 256);
-            else launch_shade(S, V, X, st, h < 0 ? 1024 : (int)((h + 1023) / 1024 < 1024 ? (h + 1023) / 1024 : 1024));
+            launch_shade(S, V, X, st, h, (h >= 0 && h < 4 * 131072 + 4096) ? SHADE_BLOCK_MIN : P.shadeBlock);
         }
         if (P.capturePaths && hasClosest) {   // the generation's hits and the refraction rays it cast, before slots and ray buffers are reused
             PathsCaptureArgs Cp;
