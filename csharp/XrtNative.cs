@@ -226,6 +226,8 @@ namespace RayTraceProject.Native
         // diagnostics of the primary packets (results never depend on them): the last one-chunk frame's packet table (first slot, rays per packet) and its live list
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_debug_packet_table(IntPtr scene, [Out] ulong[] counts2, [Out] uint[] entriesOut, long entriesCap,
                                                                      [Out] int[] pathsOut, long pathsCap);
+        // diagnostics of the screen boxes (results never depend on them): the last one-chunk frame's table, two words per leaf reference (x0 | x1 << 16, y0 | y1 << 16)
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_debug_screen_table(IntPtr scene, int hostEval, out ulong count, [Out] uint[] entriesOut, long entriesCap);
 
         // error convention of the reference: InvalidOperationException when busy (RayTracer.cs:26-27,62-63),
         // ArgumentException for bad arguments (SceneObject.cs:123-124, Material.cs:85,97)

@@ -409,6 +409,15 @@ int xrt_debug_end_counts(xrt_scene *scene, uint64_t out[3]);
  * rays and paths_out[j] the place of the ray in slot j.  After any other list call (unhinted, xrt_cast_rays*, xrt_shade_hits) counts[0] == 0. */
 int xrt_debug_packet_table(xrt_scene *scene, uint64_t counts[2], uint32_t *entries_out, int64_t entries_cap, int32_t *paths_out, int64_t paths_cap);
 
+/* Diagnostics of the screen boxes (testing aid; XRT_PK_SCREEN, results never depend on it).  A camera frame of a one-body scene whose primary rays the
+ * packet kernel traces writes, every frame, one entry per leaf reference of the body's mesh octree: the screen bounding box, in sixteenths of a pixel and
+ * rounded outwards, outside which no primary ray of the frame can be accepted by the reference's triangle -- two words, x0 | x1 << 16 and y0 | y1 << 16,
+ * each field 16 x + 8 clamped to 0 .. 65534; both words all ones: no box is proven for that triangle.  For the last finished frame of the scene, if it
+ * had one chunk: *count entries (0: the frame took no table), up to entries_cap of them to entries_out (null with a capacity of 0) -- the table the
+ * device wrote, or with host_eval != 0 the same entries evaluated by the host's build of the same functions from the host's copy of the scene (the two
+ * are equal word for word). */
+int xrt_debug_screen_table(xrt_scene *scene, int32_t host_eval, uint64_t *count, uint32_t *entries_out, int64_t entries_cap);
+
 /* RayTracer.Progress (RT:43-46): fraction of the frame's ray generations completed; callable from
  * another thread during xrt_render. */
 float xrt_progress(const xrt_scene *scene);

@@ -150,6 +150,7 @@ SYMBOLS = {
     "xrt_split_stats": (C.c_int, [C.c_void_p, _P(C.c_uint64), C.c_int32]),
     "xrt_debug_end_counts": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "xrt_debug_packet_table": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint32), C.c_int64, _P(C.c_int32), C.c_int64]),
+    "xrt_debug_screen_table": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_uint64), _P(C.c_uint32), C.c_int64]),
     "xrt_generate_primary_rays": (C.c_int, [C.c_void_p, _P(xrt_camera), _P(xrt_ray)]),
     "xrt_cast_rays": (C.c_int, [C.c_void_p, _P(xrt_ray), C.c_int64, C.c_int32, C.c_float, _P(xrt_light), C.c_int32, _P(xrt_render_opts),
                                 _P(C.c_uint32), _F, _P(xrt_stats)]),

@@ -579,6 +579,16 @@ class OctreeSpatialManager(ISpatialManager):
                                                    paths.ctypes.data_as(C.POINTER(C.c_int32)), paths.shape[0]))
         return entries, paths
 
+    def ScreenTable(self, host_eval=False):
+        """xrt_debug_screen_table: the last finished one-chunk frame's table of screen boxes, an (entries, 2) array of (x0 | x1 << 16, y0 | y1 << 16) per leaf
+        reference (no entries: the frame took no table); host_eval: evaluated by the host's build of the same functions instead of copied from the device."""
+        count = C.c_uint64(0)
+        abi.check(abi.lib().xrt_debug_screen_table(self.handle, 1 if host_eval else 0, C.byref(count), None, 0))
+        entries = np.zeros((int(count.value), 2), dtype=np.uint32)
+        if entries.shape[0]:
+            abi.check(abi.lib().xrt_debug_screen_table(self.handle, 1 if host_eval else 0, C.byref(count), entries.ctypes.data_as(C.POINTER(C.c_uint32)), entries.shape[0]))
+        return entries
+
     def IntersectBatch(self, rays, stats=False):
         """Batched ISpatialManager.GetRayIntersection (ISM:15): xrt_ray array -> xrt_hit array."""
         rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)

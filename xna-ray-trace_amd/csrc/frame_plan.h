@@ -75,6 +75,7 @@ struct FramePlan {
     bool useStamps = false;          // traversal launches time themselves on the device clock
     int pkMask = 0;                  // which ray populations take the packet kernel
     size_t pkEntries = 0;            // entries of the packet table of the primary rays (kernels.h QuadTable): one per 64 places of a chunk's generation-0 walk; 0: launch #0 takes no table
+    size_t scrRefs = 0;              // entries of the frame's table of screen boxes (screen_rects.h): one per leaf reference of the one body; 0: launch #0 takes no such table
     int shadeBlock = 1024;           // threads per block of every k_shade launch over a big or unknown generation (Settings::shadeBlock; a small hinted one takes 256)
     bool ownStream = false;          // no stream given and the frame is worth the context's own
     int cntBase = 0, levelCap = 0;   // adaptive in flight: words in front of the per-pass counters in `pinned`; quadrant capacity of a deeper level

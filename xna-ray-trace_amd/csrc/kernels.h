@@ -123,6 +123,11 @@ struct PacketArgs {
     const uint2 *pkTable = nullptr;
     const unsigned *pkCount = nullptr;
     int pkCap = 0;
+    // The screen boxes of a camera frame's primary packets in a one-body scene (screen_rects.h): scrTable[r] is the entry of reference r (refT order), pkRect[pk]
+    // the screen rectangle of packet pk of the packet table.  A triangle whose entry misses the packet's rectangle gets no triangle step: no ray of the packet
+    // can be accepted by it.  Null (every other launch): the walk tests every triangle of a run, as before.
+    const uint2 *scrTable = nullptr;
+    const uint2 *pkRect = nullptr;
 };
 // The packet table of a frame's primary rays.  A wave of k_raygen holds 64 consecutive, 64-aligned places of the walk: one aligned unit of the screen (a 2x2
 // pixel quad x 16 samples, a 4x4 block x 4 samples, an 8x8 block at one sample -- xrt_core.h tile_slot_xy is Z-order).  The live rays are compacted densely, so 64
@@ -136,7 +141,11 @@ struct QuadTable {
     uint2 *table = nullptr;      // null: off
     unsigned *count = nullptr, *clear = nullptr;
     int cap = 0;                 // entries the table has room for: one per 64 places of the walk
+    uint2 *rect = nullptr;       // optional, [cap]: the screen rectangle of every entry's unit (screen_rects.h screen_packet_rect), written beside the entry
 };
+// The frame's table of screen boxes (screen_rects.hip): table[r] = screen_entry of reference r of refT, for the camera g and the body objects[0].
+constexpr int SCREEN_XF_SLOTS = 64;   // (`table` has room for nRefs entries and this many more: the frame's own part lives behind them, screen_rects.hip)
+void launch_screen_rects(const RayGenParams &g, const ObjRec *objects, const float *refT, int nRefs, uint2 *table, hipStream_t st);
 constexpr int QUAD_HEAD_WORDS = 128;   // the two count words, 256 bytes apart, in front of the entries of a context's table
 constexpr int PACKET_QUEUE_HEADS = 8, PACKET_HEAD_STRIDE = 64;   // every head on a 256-byte line of its own: atomics on one line serialise whatever the word
 constexpr int PACKET_SPLIT_WORDS = 320;                          // ... and behind the heads the lines of the split-walk counters (PacketArgs::splitCtl: 9 x 128 bytes, aligned)

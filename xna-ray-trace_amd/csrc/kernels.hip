@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "device_util.h"
 #include "pose.h"
+#include "screen_rects.h"
 #include "shade_math.h"
 
 #include <hip/hip_ext.h>
@@ -687,7 +688,19 @@ __global__ __launch_bounds__(APPEND_BLOCK) void k_raygen(RayGenParams g, SceneVi
         else if (wave < 2 && (wave == 0 || H.list)) reserve_cells(wave == 0 ? ldsLive : ldsHeavy, wave == 0 ? count : H.count);   // wave 0: the live list, wave 1: the long-ray list
         __syncthreads();
         // the block's entries, one coalesced store of wave 0 (Q.cap bounds the entries by construction, as liveCap the rays)
-        if (quadLen > 0 && quadAt < Q.cap) Q.table[quadAt] = make_uint2((unsigned)ldsLive[lane], (unsigned)quadLen);
+        if (quadLen > 0 && quadAt < Q.cap) {
+            Q.table[quadAt] = make_uint2((unsigned)ldsLive[lane], (unsigned)quadLen);
+            if (Q.rect) {   // ... and the screen rectangle of the cell's unit (screen_rects.h): the aligned pixel block of its first place, with the sample offsets
+                const int q0 = grp * span + (lane >> 4) * APPEND_BLOCK + (lane & 15) * 64;
+                int p0 = q0;
+                if constexpr (END) { if (keptWalk) p0 = lvl_walk_path(g.lvl, (unsigned)q0 >> g.lvl.shift, (unsigned)q0); }
+                const int sshift = g.samples == 16 ? 4 : (g.samples == 4 ? 2 : 0);
+                int x = 0, y = 0;
+                (void)path_pixel(g, (pathBase + p0) >> sshift, x, y);   // (a cell with a live ray has a tile; the block's first pixel is its smallest x and y: Z-order)
+                const ScrEntry e = screen_packet_rect(x, y, g.samples == 16 ? 2 : (g.samples == 4 ? 4 : 8), g.quadLevel >= 0 ? 4 : (g.samples == 16 ? 6 : 0));
+                Q.rect[quadAt] = make_uint2(e.x, e.y);
+            }
+        }
 #pragma unroll
         for (int r = 0; r < RG_ROUNDS; r++) {
             const int p = path_of(grp * span + r * APPEND_BLOCK + (int)threadIdx.x);

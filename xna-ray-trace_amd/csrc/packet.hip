@@ -32,6 +32,7 @@
 // share one walk of the mesh octree; a lane's answer for the body is merged into its scene-level best as OSM:370-378 does.
 #include "device_util.h"
 #include "kernels.h"
+#include "screen_rects.h"
 
 #include <hip/hip_ext.h>
 
@@ -41,7 +42,8 @@ constexpr int PK_LEVELS = 24;        // deeper octrees than this fall back to k_
 constexpr int PK_FRAME_WORDS = 4;    // blk, pending children (the first lane's order is found again from the lanes), lanes (2): one 16-byte LDS access
 // a wave's stack: PK_LEVELS frames, then per level one byte per lane -- which children of that level's block the lane's own box tests accepted
 constexpr int PK_SPLIT_AT = PK_LEVELS * (PK_FRAME_WORDS + 16);   // ... and behind them the wave's eight split-walk words (pk_walk; k_packet fills them per packet)
-// ... and 24 words nobody uses: a wave's stack stays 512 words (2 KB, a power-of-two stride), the LDS addressing the kernel was tuned with
+// ... then the four screen-box words of the one-body variants (the packet's rectangle, the frame's table: pk_walk; k_packet fills them per packet) and 20 words
+// nobody uses: a wave's stack stays 512 words (2 KB, a power-of-two stride), the LDS addressing the kernel was tuned with
 constexpr int PK_STACK_WORDS = PK_SPLIT_AT + 8 + 24;
 static_assert(PK_STACK_WORDS == 512, "a wave's stack is 2 KB");
 constexpr int PK_SLEVELS = 12;       // scene octree levels a packet can stack (deeper scene trees: k_intersect)
@@ -277,7 +279,7 @@ struct PkKernarg {
 // LEAF_RHO: the runs of a big leaf are tested under the leaf's margin (the one-body variants).  The two-level variant keeps the run's own test in its one-piece
 // form (xrt_core.h leaf_certainly_missed_fused) and so its code of before: there the lane's kept margin costs two more dwords of scratch per lane and crates have
 // few big leaves -- C3 / C4 measured slower with it (profiles/run_margin).
-template <bool SPLIT, bool LEAF_RHO>
+template <bool SPLIT, bool LEAF_RHO, bool SCR>
 __device__ __forceinline__ void pk_walk(const float *__restrict__ pblocks, const float *__restrict__ refT, const float *__restrict__ lrec,
                                         const SceneView &S, int cullMin, unsigned *stk, int lane, Lane &L,
                                         const RayCull &RC, bool fastL, int rootBlock, unsigned long long lanes0, bool nodeCull,
@@ -431,14 +433,35 @@ __device__ __forceinline__ void pk_walk(const float *__restrict__ pblocks, const
             PKC(3);
             const f4 *const nr = reinterpret_cast<const f4 *>(lrec + (size_t)node * LREC_WORDS);
             const f4 nlo = nr[0], nhi = nr[1];
+            int r0 = 0, r1 = 0;   // the leaf's references (with a table they are needed first, without one where they always were)
+            auto leaf_refs = [&]() {
+                const unsigned long long offLo = (unsigned long long)(unsigned)f2i(B.w[4]) | ((unsigned long long)(unsigned)f2i(B.w[5]) << 32);
+                const unsigned long long offHi = (unsigned long long)(unsigned)f2i(B.w[6]) | ((unsigned long long)(unsigned)f2i(B.w[7]) << 32);
+                r0 = d1 + child_ref_offset(offLo, offHi, c);
+                r1 = d1 + ((c == 7) ? d3 : child_ref_offset(offLo, offHi, c + 1));
+            };
+            // Screen boxes (screen_rects.h; the primary packets of a camera frame): lane i compares the entry of reference r0 + i with the packet's rectangle -- both
+            // wave-uniform facts, the rectangle from the packet's place -- and one ballot says which of the leaf's first 64 references any ray of the packet can
+            // be accepted by.  The others get no triangle step, a run without one no box test, a leaf without one is left here.  The entries are requested beside
+            // the node record: their latency runs under the facing test.  Every other launch: all bits set.
+            unsigned long long keepM = ~0ull;
+            if constexpr (SCR) {
+                leaf_refs();
+                const Frame4 sw = *reinterpret_cast<const Frame4 *>(sst + 8);   // the packet's rectangle (2 words), the frame's table or null (k_packet fills them per packet)
+                const unsigned long long tp = (unsigned long long)(unsigned)rfl((int)sw.c) | ((unsigned long long)(unsigned)rfl((int)sw.d) << 32);
+                {
+                    const bool mineE = lane < r1 - r0;
+                    uint2 e = make_uint2(0u, 0u);
+                    if (mineE) e = reinterpret_cast<const uint2 *>(tp)[r0 + lane];
+                    keepM = __ballot(mineE && screen_overlap(e.x, e.y, sw.a, sw.b));
+                }
+            }
             bool go = inC & !all_back_facing(nlo, nhi, L.r.d);
             if (keyed) go = go & !((L.mfound != 0) & (key > L.mKey));   // (wave-uniform branch: nobody has a candidate before `keyed`)
             if (!__any(go)) continue;
+            if constexpr (SCR) { if (keepM == 0ull && r1 - r0 <= 64) continue; }
             PKC(4);
-            const unsigned long long offLo = (unsigned long long)(unsigned)f2i(B.w[4]) | ((unsigned long long)(unsigned)f2i(B.w[5]) << 32);
-            const unsigned long long offHi = (unsigned long long)(unsigned)f2i(B.w[6]) | ((unsigned long long)(unsigned)f2i(B.w[7]) << 32);
-            const int r0 = d1 + child_ref_offset(offLo, offHi, c);
-            const int r1 = d1 + ((c == 7) ? d3 : child_ref_offset(offLo, offHi, c + 1));
+            if constexpr (!SCR) leaf_refs();
             // lanes whose ray cannot reach any triangle of the leaf (xrt_core.h leaf_certainly_missed = leaf_margin + grown_box_missed) stay out of it;
             // a leaf that has runs keeps each lane's margin for them, whether or not it is tested itself
             const bool big = r1 - r0 >= LEAF_RUN_MIN;
@@ -462,6 +485,7 @@ __device__ __forceinline__ void pk_walk(const float *__restrict__ pblocks, const
             // coherent packet comes near only a few of them.  Smaller leaves are one run.
             int nRuns = 1, rb = -1;
             if (big) { rb = f2i(lrec[(size_t)node * LREC_WORDS + 24]); if (rb >= 0) nRuns = (r1 - r0 + LEAF_RUN - 1) / LEAF_RUN; }
+            if constexpr (SCR) { if (rb < 0) nRuns = (r1 - r0 + 63) >> 6; }   // (with a table a leaf without runs is taken in pieces of 64 references, the width of the mask)
             // The leaf's margin bounds every triangle of the leaf (kappa, Tmax and Emax of a run are at most the leaf's), so a run's vertex box grown by the LEAF's
             // rho is a proven test of the run at a third of the cost.  Wave-uniform per leaf: a lane without a usable leaf margin (a ray in a
             // triangle's plane, axis-parallel, ..) can still be culled by a run's narrower normal box, and then all lanes take the run's own full test.
@@ -469,8 +493,16 @@ __device__ __forceinline__ void pk_walk(const float *__restrict__ pblocks, const
             for (int jr = 0; jr < nRuns; jr++) {
                 int ra = r0, rz = r1;
                 bool goR = go;
+                unsigned long long m = ~0ull;   // (the one-body variants: the references of this run that get a triangle step, bit j <-> reference ra + j)
+                if constexpr (SCR) {
+                    const int runLen = rb >= 0 ? LEAF_RUN : 64;
+                    ra = r0 + runLen * jr; rz = min(ra + runLen, r1);
+                    m = ra - r0 < 64 ? keepM >> (ra - r0) : ~0ull;   // (references past the leaf's 64th have no bit: they are tested)
+                    if (rz - ra < 64) m &= (1ull << (rz - ra)) - 1ull;
+                    if (m == 0ull) continue;
+                }
                 if (rb >= 0) {
-                    ra = r0 + LEAF_RUN * jr; rz = min(ra + LEAF_RUN, r1);
+                    if constexpr (!SCR) { ra = r0 + LEAF_RUN * jr; rz = min(ra + LEAF_RUN, r1); }
                     const f4 *tb = reinterpret_cast<const f4 *>(lrec + (size_t)rb + (size_t)jr * RUN_WORDS);
                     PKC(6);
                     if (cheap) goR = go && !grown_box_missed(L.r, tb[0], tb[1], rho);
@@ -480,8 +512,11 @@ __device__ __forceinline__ void pk_walk(const float *__restrict__ pblocks, const
                 }
                 PKC(7);
 #ifdef XRT_PK_COUNTERS
-                pkc[8] += (unsigned)(rz - ra);
-                pkc[14] += (unsigned)(rz - ra) * (unsigned)__popcll(__ballot(goR));
+                {
+                    const unsigned steps = SCR ? (unsigned)__popcll(m) : (unsigned)(rz - ra);
+                    pkc[8] += steps;
+                    pkc[14] += steps * (unsigned)__popcll(__ballot(goR));
+                }
 #endif
                 if (goR) {   // the lanes of this run, selected once for all its triangles
                     L.leafKey = key; L.leafNode = node;
@@ -497,6 +532,25 @@ __device__ __forceinline__ void pk_walk(const float *__restrict__ pblocks, const
                             }
                         }
                     };
+                    if constexpr (SCR) {   // the set bits of m in ascending order; the next one's record is requested before this one's arithmetic (none left: the same record again)
+                        int j0 = (int)__builtin_ctzll(m);
+                        m &= m - 1ull;
+                        TriWords qA = *reinterpret_cast<const TriWords *>(pt + j0 * TRI_REC_BYTES);
+                        for (;;) {
+                            const bool more1 = m != 0ull;
+                            const int j1 = more1 ? (int)__builtin_ctzll(m) : j0;
+                            m &= m - 1ull;
+                            const TriWords qB = *reinterpret_cast<const TriWords *>(pt + j1 * TRI_REC_BYTES);
+                            test(qA, ra + j0);
+                            if (!more1) break;
+                            const bool more0 = m != 0ull;
+                            j0 = more0 ? (int)__builtin_ctzll(m) : j1;
+                            m &= m - 1ull;
+                            qA = *reinterpret_cast<const TriWords *>(pt + j0 * TRI_REC_BYTES);
+                            test(qB, ra + j1);
+                            if (!more0) break;
+                        }
+                    } else {
                     TriWords qA = *reinterpret_cast<const TriWords *>(pt);
                     int r = ra;
                     for (;;) {
@@ -507,6 +561,7 @@ __device__ __forceinline__ void pk_walk(const float *__restrict__ pblocks, const
                         test(qB, r + 1);
                         r += 2; pt += 2 * TRI_REC_BYTES;
                         if (r >= rz) break;
+                    }
                     }
                 }
             }
@@ -575,8 +630,10 @@ template <int M> __device__ __forceinline__ unsigned *scene_frames() {
 // SP: the split-walk variant (pk_walk: PacketArgs::splitCtl != nullptr selects it at launch).  The variant without it is the kernel of round 3 / 4 instruction for
 // instruction: the one-body kernel sits at the edge of its register budget (80 vector registers for six waves per SIMD, ~80 spilled scalars), and code that merely
 // EXISTS beside the walk moved spills into its loops (measured: a frame of twice the length with the switch off).
+// The one-body variants without split walks hold TWO expansions of the walk -- with the table of screen boxes and without (pk_walk SCR) -- and are compiled for six
+// waves like the others: left to itself the allocator took 84 registers for the pair (five waves).  At 80 there is no scratch (tests/test_numerics_contract.py).
 template <int M, bool SP>
-__global__ __launch_bounds__(256, (M == MODE_SCENE) ? PK_SCENE_WAVES : (PK_SINGLE_WAVES >= 7 ? 7 : (SP ? 6 : 1))) __attribute__((amdgpu_num_sgpr(PK_SGPRS))) void k_packet(const float *__restrict__ pblocks, const float *__restrict__ refT,
+__global__ __launch_bounds__(256, (M == MODE_SCENE) ? PK_SCENE_WAVES : (PK_SINGLE_WAVES >= 7 ? 7 : 6)) __attribute__((amdgpu_num_sgpr(PK_SGPRS))) void k_packet(const float *__restrict__ pblocks, const float *__restrict__ refT,
                                                 const float *__restrict__ lrec, const MeshRec *__restrict__ meshes,
                                                 const f4 *__restrict__ snodes, const f4 *__restrict__ scull, const ObjRec *__restrict__ objects,
                                                 const int *__restrict__ objMesh, SceneView S, PacketArgs A) {
@@ -779,7 +836,27 @@ __global__ __launch_bounds__(256, (M == MODE_SCENE) ? PK_SCENE_WAVES : (PK_SINGL
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 }
             }
-            pk_walk<splitOn, true>(pblocks, refT, lrec, S, A.cullMin, stk, lane, L, RC, fastL, mr.rootBlock, lanes0, nodeCull, splitOn && item >= 0);
+            // Two expansions of the walk.  Which one a packet takes is a fact of the launch (PacketArgs::scrTable, read from the kernel arguments: scalar) and of
+            // the segment; a packet without a table -- every launch but #0 of a camera frame, the second segment -- pays one scalar load for the question and runs
+            // the walk of before.  A packet with one leaves its rectangle and the table's address in the wave's four screen-box words for the walk's leaves.
+            // (The split-walk variant, off by default, sits at its scratch budget: it takes no table.)
+            bool scr = false;
+            if constexpr (!splitOn) {
+                KA.fresh();
+                scr = !seg2 && KA.args()->scrTable != nullptr && KA.args()->pkTable != nullptr;
+                if (scr) {
+                    if (lane == 0) {
+                        const uint2 rc = KA.args()->pkRect[pk];
+                        const unsigned long long tp = (unsigned long long)KA.args()->scrTable;
+                        *reinterpret_cast<Frame4 *>(sst + 8) = Frame4{rc.x, rc.y, (unsigned)tp, (unsigned)(tp >> 32)};
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                }
+            }
+            if (scr) pk_walk<false, true, true>(pblocks, refT, lrec, S, A.cullMin, stk, lane, L, RC, fastL, mr.rootBlock, lanes0, nodeCull, false);
+            else pk_walk<splitOn, true, false>(pblocks, refT, lrec, S, A.cullMin, stk, lane, L, RC, fastL, mr.rootBlock, lanes0, nodeCull, splitOn && item >= 0);
             L.mesh = mesh;
             KA.fresh();
             bool mine = true;   // this wave writes the packet's results
@@ -947,7 +1024,7 @@ __global__ __launch_bounds__(256, (M == MODE_SCENE) ? PK_SCENE_WAVES : (PK_SINGL
                                 const bool meshAway = nodeCull && mesh_faces_away(mr, L.r.d);
                                 const unsigned long long lanes0 = __ballot(inRoot && !meshAway);
                                 if (lanes0 != 0ull)
-                                    pk_walk<false, false>(pblocks, refT, lrec, S, A.cullMin, stk, lane, L, RC, fastL, rootBlock, lanes0, nodeCull, false);
+                                    pk_walk<false, false, false>(pblocks, refT, lrec, S, A.cullMin, stk, lane, L, RC, fastL, rootBlock, lanes0, nodeCull, false);
                             }
                             if (L.mfound) {   // OSM:370-378
                                 L.mesh = m; C.obj = o;

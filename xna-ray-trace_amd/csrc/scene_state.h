@@ -234,6 +234,7 @@ struct xrt_scene {
         DevBuf<int> path0, path1, index0, heavyList, cnts;
         DevBuf<int> composeList;                // kernels.h EndArgs: [0 .. END_WORDS) the count words, [16 ..] the paths k_compose has to walk
         DevBuf<unsigned> quadTable;             // kernels.h QuadTable: the two count words at [0] and [64] (QUAD_HEAD_WORDS in all), then two words per entry
+        DevBuf<uint2> scrTable, pkRect;         // screen_rects.h: the frame's screen box per leaf reference (FramePlan::scrRefs), the screen rectangle per entry of quadTable
         int quadWord = 0;                       // ... the count word (0 / 1) the context's last chunk with a table counted into
         DevBuf<int> node0, node1, heapFlag;     // ray-tree frames: heap node of every ray; heapFlag[0]: a generation overflowed its buffers
         DevBuf<float> ref0, ref1, lvlAlpha;     // ... refraction index of the medium a ray travels in; alpha per level record

@@ -56,6 +56,7 @@ struct Settings {
     int packetGrabMax = 2;     // XRT_PK_GRAB (development): 8 -> 2 shortened the tail of a launch (C5 blocking 9.0 -> 7.8 ms); 1 loses to contention on the queue word
     int packetStaticDiv = 4;   // XRT_PK_STATIC (development): 1/2 .. 1/8 measured within 2 % of each other on C5
     bool packetQuads = true;   // XRT_PK_QUADS=0: a primary packet is 64 consecutive live rays, as before the packet table (kernels.h QuadTable; scheduling only: the A/B, bisecting)
+    bool packetScreen = true;  // XRT_PK_SCREEN=0: the primary packets of a one-body scene's camera frames test every triangle of a run, as before the table of screen boxes (screen_rects.h; work avoided only: the A/B, tests)
     bool levelMap = true;      // XRT_LEVEL_MAP=0: level records for every path of the frame (as before round 4's last build)
     int nodeCull = 1;          // XRT_NODE_CULL: SceneView::nodeCull (tools: a scheduling-free switch, results never change)
     bool noSingle = false;     // XRT_NO_SINGLE: a scene of one SceneObject with one Mesh is still traced as a two-level scene
@@ -147,6 +148,7 @@ inline Settings read_settings() {
     env_int("XRT_PK_GRAB", c.packetGrabMax, 1, 64);
     env_int("XRT_PK_STATIC", c.packetStaticDiv, 0, 64);
     env_flag("XRT_PK_QUADS", c.packetQuads);
+    env_flag("XRT_PK_SCREEN", c.packetScreen);
     env_flag("XRT_LEVEL_MAP", c.levelMap);
     env_int("XRT_NODE_CULL", c.nodeCull, 0, 2);
     c.noSingle = env_set("XRT_NO_SINGLE");

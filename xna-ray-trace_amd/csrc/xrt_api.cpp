@@ -27,6 +27,7 @@ using namespace xrt;
 #include "trace_plan.h"    // ... and how a list is split into chunks
 #include "surface.h"       // xrt_surface_hits: surface terms and next rays of a caller's hits (surface.hip)
 #include "compose.h"       // xrt_compose_hits: CastRay's return path on a caller's terms (compose.hip)
+#include "screen_rects.h"  // the screen boxes of a camera frame's primary packets (screen_rects.hip)
 
 namespace {
 
@@ -559,6 +560,17 @@ int plan_frame(const xrt_scene &s, int matVersion, const xrt_camera *cam, const 
         const long long walk = p.skipTiles ? ((long long)lvl_kept_tiles(g) << g.lvl.shift) : (long long)p.P;
         p.pkEntries = (size_t)((walk + 63) / 64);
     }
+    // The table of screen boxes (screen_rects.h): camera frames of a one-body scene whose launch #0 takes the packet table, in a viewport the fields hold.  One entry
+    // per leaf reference, written every frame in front of launch #0 (a real caller's camera moves) from the pose version the frame reads.  Where the host holds
+    // that pose, a camera or pose no entry can be proven for (make_screen_xf: an orthographic or singular matrix, rays that lose their direction far from the
+    // origin) takes no table: the frame then pays neither the two kernels nor the walk with a table whose every entry says "no cull".  After a pose update from
+    // device arrays the host cannot know, and the device's own evaluation decides entry by entry.  XRT_PK_SCREEN=0: never.
+    if (p.pkEntries && !batch && s.sceneMode == MODE_SINGLE && s.cfg.packetScreen && g.width <= SCR_MAX_EXTENT && g.height <= SCR_MAX_EXTENT &&
+        s.host->arrays.refN.size() < ((size_t)1 << 30)) {
+        bool ok = true;
+        if (!s.posesOnDevice && !s.host->arrays.objects.empty()) { ScreenXf X; make_screen_xf(g, s.host->arrays.objects[0].invWorld, X); ok = X.ok != 0; }
+        if (ok) p.scrRefs = s.host->arrays.refN.size();
+    }
     const bool laneClosest = (p.pkMask & 5) != 5;   // some closest-hit generation is traced ray by ray: the long-ray feedback has a reader
     p.wantFeedback = p.fast && !heap && !adaptive && s.deepMeshes && !s.cfg.noFeedback && laneClosest;   // (the paths of a deeper quadrant level are a list: no stable key)
     // "long ray first" (kernels.hip): the producer of generation k lists its long rays, launch #k takes them first
@@ -648,6 +660,7 @@ int ensure_frame_buffers(xrt_scene *s, xrt_scene::FrameCtx &F, const FramePlan &
             HIPCHECK(hipStreamSynchronize(s->stream));
         }
     }
+    if (P.scrRefs && ((rc = W.scrTable.ensure(P.scrRefs + SCREEN_XF_SLOTS)) || (rc = W.pkRect.ensure(P.pkEntries)))) return rc;
     if (P.useStamps) {
         if ((rc = W.stamps.ensure((size_t)MAX_STAMP_ROWS * STAMP_STRIDE))) return rc;
         if ((rc = F.stampHost.ensure((size_t)MAX_STAMP_ROWS * 2 * sizeof(unsigned long long), hipHostMallocMapped))) return rc;
@@ -693,6 +706,7 @@ struct FrameJob {
     int *overflowFlag;       // "a generation did not fit its buffers"
     bool startEvent;         // the frame's first raygen launch carries its start event (fast frames put nothing but kernels on the stream)
     unsigned pathEpoch = 0;  // path capture: the tag of the chunk attempt being enqueued
+    bool screenDone = false; // the frame's table of screen boxes is written (once per frame: every chunk has the same camera and pose)
 
     static constexpr int QW = 1 + 2 * PACKET_QUEUE_WORDS;   // queue words of a launch step (FramePlan::qStride)
 
@@ -751,6 +765,7 @@ int FrameJob::launch_packets(const Step &T, const IntersectArgs &I, bool shadow,
     const int k = T.k, word = shadow ? 1 : 0, R = P.R, nL = P.nL;
     int rc;
     PacketArgs PA = packet_args(s, I, I2, quads);
+    if (quads && quads->table && quads->rect) { PA.scrTable = W.scrTable.p; PA.pkRect = quads->rect; }   // (launch #0 of a camera frame with a table of screen boxes)
     PA.queue += PACKET_QUEUE_WORDS * word;   // (a step's queue words: the per-lane head, the packet heads of its closest-hit rays, those of its shadow rays)
     if (tileCostDev) {   // which tile pays for a packet: the path of its first ray (closest-hit rays: the path list; shadow rays: their hit's slot record)
         PA.tileCost = tileCostDev; PA.tileBase = (int)T.pathBase; PA.tileShift = 9 + (T.gp.samples == 16 ? 4 : (T.gp.samples == 4 ? 2 : 0));
@@ -834,6 +849,7 @@ int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int P
         W.quadWord ^= 1;
         quads.table = reinterpret_cast<uint2 *>(W.quadTable.p + QUAD_HEAD_WORDS); quads.cap = (int)P.pkEntries;
         quads.count = W.quadTable.p + 64 * W.quadWord; quads.clear = W.quadTable.p + 64 * (W.quadWord ^ 1);
+        if (P.scrRefs && !P.batch) quads.rect = W.pkRect.p;   // (screen_rects.h: every entry with the screen rectangle of its unit)
     }
     if (P.givenHits) {   // the caller's rays AND their closest hits: the live slots get ray, hit and hit word here, launch #0 below does not happen (hits.hip)
         Range r("xrt ingest hits");
@@ -850,6 +866,8 @@ int FrameJob::enqueue_chunk(const RayGenParams &gp, int *cnt, unsigned *q, int P
         startEvent = false;
     } else
     { Range r("xrt raygen"); launch_raygen(gb, S, rays[0], W.lvlB.p, W.index0.p, cnt, Pc, pathBase, heavy_for(0, hcnt), st, startEvent ? e0 : nullptr, (int)rayCap, &endArgs, &quads); startEvent = false; }
+    // the frame's screen boxes, behind the ray generation (which carries the frame's start event) and in front of launch #0
+    if (quads.rect && !screenDone) { Range r("xrt screen rects"); launch_screen_rects(gb, S.objects, S.refT, (int)P.scrRefs, W.scrTable.p, st); screenDone = true; }
     // (one buffer serves every generation: the closest-hit answers of launch #k are read by part A of k_shade #k alone -- part B works from the
     // slot records -- and launch #k+1 starts after it on the frame's stream)
     xrt_hit *hitsOf[2] = {W.hits.p, W.hits.p};
@@ -2294,7 +2312,7 @@ int trace_pixels_impl(xrt_scene *s, const xrt_camera *cam, const xrt_render_opts
             msIntersect += ms; msLongest = std::max(msLongest, (double)ms); launches++;
         }
         if (table && b.size() == 2) {   // (xrt_debug_packet_table: the table and the index list of a one-chunk call stay in the context until its next frame or list)
-            F0.plan.pkEntries = tableCap;
+            F0.plan.pkEntries = tableCap; F0.plan.scrRefs = 0;   // (a list takes no table of screen boxes: xrt_debug_screen_table reports none)
             s->quadCtx = 0; s->quadLive = (unsigned long long)hc[0];
         }
     }
@@ -3392,6 +3410,39 @@ int xrt_debug_packet_table(xrt_scene *scene, uint64_t counts[2], uint32_t *entri
         const size_t ne = std::min<size_t>(n, (size_t)entries_cap), np = std::min<size_t>((size_t)scene->quadLive, (size_t)paths_cap);
         if (ne) HIPCHECK(hipMemcpy(entries_out, W.quadTable.p + QUAD_HEAD_WORDS, ne * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (np) HIPCHECK(hipMemcpy(paths_out, W.index0.p, np * sizeof(int32_t), hipMemcpyDeviceToHost));
+        return XRT_OK;
+    });
+}
+
+int xrt_debug_screen_table(xrt_scene *scene, int32_t host_eval, uint64_t *count, uint32_t *entries_out, int64_t entries_cap) {
+    return guarded("xrt_debug_screen_table", [&]() -> int {
+        int rc = need_device(scene, "xrt_debug_screen_table");
+        if (rc != XRT_OK) return rc;
+        if (!count || entries_cap < 0 || (!entries_out && entries_cap > 0)) return fail(XRT_E_INVALID_ARG, "xrt_debug_screen_table: null argument or negative capacity");
+        BusyGuard guard(scene);
+        if (!guard.owned || scene->frames[0].pending || scene->frames[1].pending) return fail(XRT_E_BUSY, "Current render operation not finished.");
+        *count = 0;
+        if (scene->quadCtx < 0) return XRT_OK;
+        const xrt_scene::WorkBufs &W = scene->frames[scene->quadCtx].w;
+        const FramePlan &P = scene->frames[scene->quadCtx].plan;
+        if (!P.scrRefs || P.batch || !W.scrTable.p) return XRT_OK;
+        HIPCHECK(hipSetDevice(scene->device));
+        HIPCHECK(hipDeviceSynchronize());
+        *count = P.scrRefs;
+        const size_t ne = std::min<size_t>(P.scrRefs, (size_t)entries_cap);
+        if (host_eval) {   // the same functions in the host's build, on the host's copy of the records and of the body's pose
+            if (scene->posesOnDevice || scene->host->arrays.objects.empty()) return fail(XRT_E_UNSUPPORTED, "xrt_debug_screen_table: the host does not hold the body's pose");
+            ScreenXf X;
+            make_screen_xf(P.g, scene->host->arrays.objects[0].invWorld, X);
+            const float *refT = scene->host->arrays.refT.data();
+            for (size_t r = 0; r < ne; r++) {
+                const float *q = refT + r * TRI_REC_WORDS;
+                const ScrEntry e = screen_entry(X, q + 4, q + 7, q + 10);
+                entries_out[2 * r] = e.x; entries_out[2 * r + 1] = e.y;
+            }
+            return XRT_OK;
+        }
+        if (ne) HIPCHECK(hipMemcpy(entries_out, W.scrTable.p, ne * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
         return XRT_OK;
     });
 }
