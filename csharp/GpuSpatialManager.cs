@@ -151,7 +151,7 @@ namespace RayTraceProject.Spatial
         // Triangle.n1..n3 / uv1..uv3 / color (Triangle.cs:17-23) between frames: a host that wrote these fields of mesh.Triangles[first .. first + count)
         // -- scrolled UVs, painted colours, the highlight of the triangle a click hit (Game1.cs:296-325), a faded alpha -- calls this before the next
         // RenderAsync (tickets may be open; nothing is rebuilt).  There is no change detection on public fields: nothing is pushed unless the host asks.
-        // surfaceNormal and the vertices are not settable this way: a mesh whose geometry changed is added again and built.
+        // surfaceNormal and the vertices are not settable this way: a mesh whose geometry changed is pushed with PushMeshTriangles.
         public void PushTriangleShading(Mesh mesh, int first, int count)
         {
             if (this.scene == IntPtr.Zero || count <= 0) return;
@@ -168,6 +168,30 @@ namespace RayTraceProject.Spatial
             Xrt.Check(Xrt.xrt_scene_set_triangle_shading(this.scene, this.meshIds[mesh], null, first, count, n, uv, col));
         }
         public void PushTriangleShading(Mesh mesh) { PushTriangleShading(mesh, 0, mesh.Triangles.Length); }
+
+        // Mesh.Init() (Mesh.cs:27-32) on a mesh of the built scene: a host that assigned mesh.Triangles (or moved v1..v3 / surfaceNormal of its triangles) and
+        // mesh.MeshBoundingBox calls this where the reference calls mesh.Init().  The mesh keeps its id and its material, its MeshOctree alone is built, the
+        // body list and the scene octree stay (xrt_scene_set_mesh_triangles).  Not while RenderAsync tickets are open.  No change detection: nothing is pushed
+        // unless the host asks.
+        public void PushMeshTriangles(Mesh mesh)
+        {
+            if (this.scene == IntPtr.Zero) return;
+            Triangle[] t = mesh.Triangles;
+            int count = t.Length;
+            float[] v = new float[count * 9 + 1], n = new float[count * 9 + 1], uv = new float[count * 6 + 1], sn = new float[count * 3 + 1], col = new float[count * 4 + 1];
+            for (int i = 0; i < count; i++)
+            {
+                Put3(v, i * 9, t[i].v1); Put3(v, i * 9 + 3, t[i].v2); Put3(v, i * 9 + 6, t[i].v3);
+                Put3(n, i * 9, t[i].n1); Put3(n, i * 9 + 3, t[i].n2); Put3(n, i * 9 + 6, t[i].n3);
+                uv[i * 6] = t[i].uv1.X; uv[i * 6 + 1] = t[i].uv1.Y; uv[i * 6 + 2] = t[i].uv2.X; uv[i * 6 + 3] = t[i].uv2.Y;
+                uv[i * 6 + 4] = t[i].uv3.X; uv[i * 6 + 5] = t[i].uv3.Y;
+                Put3(sn, i * 3, t[i].surfaceNormal);
+                col[i * 4] = t[i].color.X; col[i * 4 + 1] = t[i].color.Y; col[i * 4 + 2] = t[i].color.Z; col[i * 4 + 3] = t[i].color.W;
+            }
+            BoundingBox b = mesh.MeshBoundingBox;
+            float[] bbox = { b.Min.X, b.Min.Y, b.Min.Z, b.Max.X, b.Max.Y, b.Max.Z };
+            Xrt.Check(Xrt.xrt_scene_set_mesh_triangles(this.scene, this.meshIds[mesh], v, n, uv, sn, col, count, bbox));
+        }
 
         static void Put3(float[] a, int o, Vector3 p) { a[o] = p.X; a[o + 1] = p.Y; a[o + 2] = p.Z; }
 

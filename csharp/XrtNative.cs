@@ -205,6 +205,10 @@ namespace RayTraceProject.Native
                                                                      int firstTri, int n, [In] float[] normals, [In] float[] uv, [In] float[] color);
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_triangle_shading_device(IntPtr scene, int meshId, IntPtr dTriIds,
                                                                      int firstTri, int n, IntPtr dNormals, IntPtr dUv, IntPtr dColor, IntPtr stream);
+        // Mesh.Triangles / Mesh.MeshBoundingBox set and Mesh.Init() run on a built scene (Mesh.cs:12-14, 27-32): the mesh takes nTri triangles (the arrays of
+        // xrt_scene_add_mesh) under its id and with its material; its MeshOctree alone is built (MeshOctree.cs:56-96); nTri = 0 empties the mesh
+        [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern int xrt_scene_set_mesh_triangles(IntPtr scene, int meshId, [In] float[] v,
+                                                                     [In] float[] n, [In] float[] uv, [In] float[] surfN, [In] float[] color, int nTri, [In] float[] bbox);
         // GetColorForQuadrant / the body of Render's inner loop (RayTracer.cs:215-311, 412-425) on a list of screen positions (centers: x0 y0 x1 y1 ..): the colour
         // of every entry in the caller's order, all three multisampling modes; an integer centre gets the frame's pixel bit for bit
         [DllImport(Lib, CallingConvention = CallingConvention.Cdecl)] public static extern unsafe int xrt_render_pixels(IntPtr scene, ref XrtCamera camera, XrtLight[] lights, int nLights,

@@ -818,7 +818,7 @@ int xrt_scene_set_bodies(xrt_scene *scene, int32_t n_bodies, const int32_t *mesh
  *     bit for bit: NaN payloads, infinities and -0.0 are stored as given.
  *   - never touched: Triangle.surfaceNormal and the vertices are NOT settable.  The culling test (RE:49) and every conservative
  *     rejection of this library (normal boxes, tight boxes, runs, pre-cull records, answers at emission) are built on them; a host that
- *     changes them adds the mesh again (xrt_scene_add_mesh) and builds.  Mesh octrees, runs, normal and tight boxes, poses, the scene
+ *     changes them gives the mesh its triangles again (xrt_scene_set_mesh_triangles below).  Mesh octrees, runs, normal and tight boxes, poses, the scene
  *     octree, materials, texels and tile tables are not touched either.
  *   - errors: mesh_id out of range, n < 0, first_tri < 0, a range or an id outside [0, ntri), tri_ids != NULL with first_tri != 0:
  *     XRT_E_INVALID_ARG.  A failing call applies nothing.  n == 0 does nothing and returns XRT_OK.  A triangle listed twice takes its
@@ -842,6 +842,48 @@ int xrt_scene_set_triangle_shading(xrt_scene *scene, int32_t mesh_id, const int3
                                    const float *color /* nullable, 4 n */);
 int xrt_scene_set_triangle_shading_device(xrt_scene *scene, int32_t mesh_id, const void *d_tri_ids /* nullable */, int32_t first_tri, int32_t n,
                                           const void *d_normals, const void *d_uv, const void *d_color /* each nullable */, void *stream);
+
+/* ---- replacing a mesh's triangles on a built scene: Mesh.Triangles / Mesh.MeshBoundingBox (MESH:12-14) and Mesh.Init() (MESH:27-32) ----
+ * Added within ABI 203: this export is additive; no existing struct, field or entry point changed.
+ * The reference's Mesh has public setters for Triangles and MeshBoundingBox, Triangle has public v1..v3 and surfaceNormal (TRI:17-23),
+ * and Mesh.Init() makes a fresh MeshOctree over whatever Triangles holds (MO:56-96): a host that edits or deforms a mesh and calls
+ * Init() traces the new geometry in its next query.  xrt_scene_set_mesh_triangles is that for mesh mesh_id of a built scene: the mesh
+ * takes new triangles under the same id, its octree alone is built, and the storage of the old triangles is released.
+ *   - arguments: v, n, uv, surf_n, color, ntri and bbox are exactly those of xrt_scene_add_mesh -- the layouts, the NULL defaults of n /
+ *     uv / color, values taken bit for bit, bbox = the new Mesh.MeshBoundingBox; surf_n is the caller's, the library does not derive it.
+ *     ntri may differ from the old count.  ntri == 0 is legal, as in xrt_scene_add_mesh: the mesh is then empty, every body that names it
+ *     is missed through it and its storage is released.  This is what the library offers as mesh removal; mesh ids never change.
+ *   - build: MeshOctree.Build (MO:56-96) runs for this mesh alone, with the mesh_threshold of the last xrt_scene_build.  No other mesh
+ *     octree is built.
+ *   - not touched: the mesh's material and texels (Mesh.MeshMaterial is another property), every other mesh, the body list, the bodies'
+ *     BoundingBox / WorldBoundingBox (the reference computes SceneObject.boundingBox once, in the constructor, SO:126-132), the scene
+ *     octree (Mesh.Init() does not call OctreeSpatialManager.Build: the bodies stay in the nodes of the last tree build, as after
+ *     xrt_scene_set_poses) and tile tables.
+ *   - refreshed, and only this: the pre-cull records of the bodies that name the mesh are built on Mesh.MeshBoundingBox; they are made
+ *     again from the new box and the body's current pose.
+ *   - equivalence: the scene equals the one obtained by starting from scratch with the new triangles in the place of the old ones and
+ *     replaying the same calls: the same meshes in id order, the same bodies, xrt_scene_build, then the pose, material and shading edits
+ *     made since.  Frames, hits and xrt_scene_get_tree output are equal.
+ *   - triangle values set through xrt_scene_set_triangle_shading_device on OTHER meshes survive (they are read back first); those of
+ *     the replaced mesh are replaced by what the call gives.  Poses set through xrt_scene_set_poses_device survive: the call supplies no
+ *     pose, so they are read back, not discarded.  The pose, material and shading versions start again from 0, as after
+ *     xrt_scene_set_bodies with a new mesh; the replicas of an n_gpus > 1 render are dropped and made again on the next such frame.
+ *   - ids: xrt_hit.tri and ignore_tri are positions in the new Triangles[].  Hits a host kept from before the call name old triangles;
+ *     the host forms of the *_hits calls range-check them as they always do.
+ *   - all or nothing: the argument checks of xrt_scene_add_mesh (same codes); a mesh id out of range: XRT_E_INVALID_ARG; an octree the
+ *     reference's recursion would not finish, or whose depth no longer fits the LDS stack ((scene depth + 1) + (mesh depth + 1) > 40
+ *     words): XRT_E_UNSUPPORTED.  Each is checked before anything is applied: the new octree is built aside and examined before it
+ *     takes the old one's place, so a failing call leaves the scene exactly as it was and still traceable.
+ *   - before the first xrt_scene_build (and for a mesh added since the last build) the call edits what the build will use.
+ *   - on a host-only scene (device -1) the host copy is edited and the call returns XRT_OK.  xrt_scene_save writes the new triangles
+ *     (the file format is unchanged).
+ *   - while a begin/end ticket is open or another thread renders on the scene: XRT_E_BUSY, as for xrt_scene_set_bodies; the frame in
+ *     flight is not disturbed.
+ * Not done: a device form with the vertices in HBM (the build is host code); an octree refit (the octree is built anew); an upload of
+ * only the changed part (the scene's arrays are sent again, as by xrt_scene_set_bodies with a new mesh); removing a mesh ID. */
+int xrt_scene_set_mesh_triangles(xrt_scene *scene, int32_t mesh_id, const float *v /* 9 ntri */, const float *n /* nullable */,
+                                 const float *uv /* nullable */, const float *surf_n /* 3 ntri */, const float *color /* nullable */,
+                                 int32_t ntri, const float bbox[6]);
 
 /* ---- seam 2 on caller-chosen pixels: GetColorForQuadrant (RT:215-311) and the body of Render's inner loop (RT:412-425), batched ---------
  * Added within ABI 203: these two exports are additive; no existing struct, field or entry point changed.

@@ -184,6 +184,7 @@ SYMBOLS = {
     "xrt_scene_set_triangle_shading": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_int32), C.c_int32, C.c_int32, _F, _F, _F]),
     "xrt_scene_set_triangle_shading_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                         C.c_void_p]),
+    "xrt_scene_set_mesh_triangles": (C.c_int, [C.c_void_p, C.c_int32, _F, _F, _F, _F, _F, C.c_int32, _F]),
     "xrt_render_pixels": (C.c_int, [C.c_void_p, _P(xrt_camera), _P(xrt_light), C.c_int32, _P(xrt_render_opts), _F, C.c_int64, _P(C.c_uint32), _F,
                                     _P(xrt_stats)]),
     "xrt_render_pixels_device": (C.c_int, [C.c_void_p, _P(xrt_camera), _P(xrt_light), C.c_int32, _P(xrt_render_opts), C.c_void_p, C.c_int64,

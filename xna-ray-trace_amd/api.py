@@ -220,17 +220,44 @@ def _get_tree(scene, mesh_id):
 
 
 class Mesh:
-    """Mesh.cs:9-40: Triangles[] (as arrays), MeshMaterial, MeshBoundingBox, Octree, Init(), RayIntersects()."""
+    """Mesh.cs:9-40: Triangles[] (as arrays), MeshMaterial, MeshBoundingBox, Octree, Init(), RayIntersects().  Triangles and
+    MeshBoundingBox have public setters (MESH:12-14); a host that assigns them calls Init(), as in the reference, and every built
+    OctreeSpatialManager that holds the mesh hands the new triangles to the library before its next query or frame."""
 
     def __init__(self, triangles, material, boundingBox=None, device=0):
         self.data = triangles            # fixtures.MeshData
-        self.Triangles = triangles
         self.MeshMaterial = material
         self.MeshBoundingBox = np.asarray(triangles.bbox if boundingBox is None else boundingBox, dtype=np.float32)
         self.Octree = None
         self.device = device
+        self._geom_serial = 0            # counts the Init() calls that followed an assignment: what a spatial manager compares
+        self._geom_assigned = False
+
+    @property
+    def Triangles(self):
+        return self.data
+
+    @Triangles.setter
+    def Triangles(self, triangles):   # MESH:12
+        self.data = triangles
+        self._geom_assigned = True
+
+    @property
+    def MeshBoundingBox(self):
+        return self._bbox
+
+    @MeshBoundingBox.setter
+    def MeshBoundingBox(self, box):   # MESH:14
+        self._bbox = np.asarray(box, dtype=np.float32)
+        self._geom_assigned = True
 
     def Init(self):   # MESH:27-32
+        """A fresh MeshOctree over whatever Triangles holds.  After an assignment to Triangles or MeshBoundingBox it also marks the mesh for
+        the spatial managers that hold it.  (The mirror cannot see writes INTO the arrays of a MeshData: assign Triangles again, or call
+        OctreeSpatialManager.SetMeshTriangles.)"""
+        if self._geom_assigned:
+            self._geom_serial += 1
+            self._geom_assigned = False
         self.Octree = MeshOctree(self)
         self.Octree.Build()
 
@@ -321,6 +348,7 @@ class OctreeSpatialManager(ISpatialManager):
         self._pushed = []        # per body: the pose serial the library has
         self._pushed_mats = []   # per mesh: (its Material, the material's serial) the library has
         self._pushed_tex = []    # per mesh: (Material, texel serial) of the texels the library has, or None
+        self._pushed_geom = []   # per mesh: the geometry serial (Mesh.Init calls) of the triangles the library has
         self.last_build_meshes = 0   # mesh octrees the last Build() built (xrt_scene_set_bodies' meshes_built_out; a full build: all)
 
     def _key(self):
@@ -330,12 +358,14 @@ class OctreeSpatialManager(ISpatialManager):
         if self._scene is not None and self._built_key == self._key():
             # same bodies and meshes: OctreeSpatialManager.Build alone over the current poses (xrt_scene_build_tree)
             self._push_poses()
+            self._push_meshes()
             self._push_materials()
             abi.check(abi.lib().xrt_scene_build_tree(self._scene.handle, self.itemTreshold))
             return
         if self._scene is not None and self._built_key is not None and self._built_key[0] == self.meshItemTreshold:
             # a scene of this manager's own Build, the mesh threshold unchanged: the list alone changes (xrt_scene_set_bodies).  Meshes the
             # library has keep their ids and their octrees; only those it has not seen are added (and built by the call).
+            self._push_meshes()
             self._push_materials()
             for body in self.Bodies:
                 for m in body.Meshes:
@@ -344,6 +374,7 @@ class OctreeSpatialManager(ISpatialManager):
                         self.meshes.append(m)
                         self._pushed_mats.append((m.MeshMaterial, m.MeshMaterial._serial))
                         self._pushed_tex.append((m.MeshMaterial, m.MeshMaterial._tex_serial) if m.MeshMaterial.UseTexture else None)
+                        self._pushed_geom.append(m._geom_serial)
             poses = [b._build_world() for b in self.Bodies]
             self.last_build_meshes = self.SetBodies([[self._mesh_ids[id(m)] for m in b.Meshes] for b in self.Bodies],
                                                     [p[0] for p in poses], [p[1] for p in poses], [b.BoundingBox for b in self.Bodies],
@@ -372,6 +403,7 @@ class OctreeSpatialManager(ISpatialManager):
         self._pushed = [b._pose_serial for b in self.Bodies]
         self._pushed_mats = [(m.MeshMaterial, m.MeshMaterial._serial) for m in self.meshes]
         self._pushed_tex = [(m.MeshMaterial, m.MeshMaterial._tex_serial) if m.MeshMaterial.UseTexture else None for m in self.meshes]
+        self._pushed_geom = [m._geom_serial for m in self.meshes]
 
     def SetBodies(self, body_meshes, world, inv, bbox, wbb, scene_threshold=0):
         """xrt_scene_set_bodies: the body list becomes len(body_meshes) bodies; body i has the mesh ids body_meshes[i] and world[i] (16
@@ -414,6 +446,33 @@ class OctreeSpatialManager(ISpatialManager):
         if w.size != 16 * n or iw.size != 16 * n or bb.size != 6 * n:
             raise ValueError("SetPoses: 16 + 16 + 6 floats per id")
         abi.check(abi.lib().xrt_scene_set_poses(self.handle, ids.ctypes.data_as(C.POINTER(C.c_int32)), n, _fp(w), _fp(iw), _fp(bb)))
+
+    def _push_meshes(self):
+        """The meshes whose Init() ran since the last push (Mesh.Triangles / MeshBoundingBox assigned, MESH:12-14, 27-32), each in one
+        xrt_scene_set_mesh_triangles (before every query, frame, Save and Build).  A mesh shared by several managers reaches each."""
+        if self._scene is None or self._built_key is None:
+            return
+        for i, mesh in enumerate(self.meshes):
+            if self._pushed_geom[i] != mesh._geom_serial:
+                self.SetMeshTriangles(i, mesh.data, mesh.MeshBoundingBox)
+
+    def SetMeshTriangles(self, mesh_or_id, triangles, boundingBox=None):
+        """xrt_scene_set_mesh_triangles: the mesh (a Mesh of this manager or a mesh id) takes the triangles of `triangles` (a MeshData) and
+        boundingBox (default: the triangles' own box) under its id and with its material.  Its octree alone is built; the body list, the
+        bodies' boxes and the scene octree stay.  The mirror's Mesh follows, so that a later from-scratch Build() and Save() agree."""
+        mid = mesh_or_id if isinstance(mesh_or_id, (int, np.integer)) else self.mesh_id(mesh_or_id)
+        d = triangles
+        bbox = np.ascontiguousarray(d.bbox if boundingBox is None else boundingBox, dtype=np.float32)
+        arr = lambda a, k: np.ascontiguousarray(a, dtype=np.float32) if d.ntri else np.zeros(k, dtype=np.float32)   # (an empty array has no address)
+        abi.check(abi.lib().xrt_scene_set_mesh_triangles(self.handle, int(mid), _fp(arr(d.v, 9)), _fp(arr(d.n, 9)), _fp(arr(d.uv, 6)),
+                                                         _fp(arr(d.surface_normal, 3)), _fp(arr(d.color, 4)), int(d.ntri), _fp(bbox)))
+        if 0 <= mid < len(self.meshes):   # (else a loaded scene: its geometry lives in the library alone)
+            mesh = self.meshes[mid]
+            if mesh.data is not d:   # a direct call: the other managers that hold the mesh see an Init()
+                mesh.data = d
+                mesh._geom_serial += 1
+            mesh._bbox = bbox
+            self._pushed_geom[mid] = mesh._geom_serial
 
     def _push_materials(self):
         """The materials changed since the last push -- a property set, or another Material assigned to Mesh.MeshMaterial -- in one
@@ -533,6 +592,7 @@ class OctreeSpatialManager(ISpatialManager):
 
     def Save(self, path):
         """xrt_scene_save: the built scene's meshes, materials, texels and bodies as one file (the reference's .xnb content)."""
+        self._push_meshes()
         self._push_materials()
         abi.check(abi.lib().xrt_scene_save(self.handle, str(path).encode()))
 
@@ -595,6 +655,7 @@ class OctreeSpatialManager(ISpatialManager):
         hits = np.zeros(rays.shape[0], dtype=HIT_DTYPE)
         st = abi.xrt_stats()
         self._push_poses()
+        self._push_meshes()
         self._push_materials()
         abi.check(abi.lib().xrt_scene_intersect(self.handle, rays.ctypes.data_as(C.POINTER(abi.xrt_ray)), None, rays.shape[0],
                                                 hits.ctypes.data_as(C.POINTER(abi.xrt_hit)), C.byref(st) if stats else None))
@@ -727,6 +788,8 @@ class RayTracer:
         sc = self.CurrentScene
         if hasattr(sc, "_push_poses"):
             sc._push_poses()
+        if hasattr(sc, "_push_meshes"):
+            sc._push_meshes()
         if hasattr(sc, "_push_materials"):
             sc._push_materials()
         return sc.handle

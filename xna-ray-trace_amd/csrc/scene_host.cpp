@@ -259,29 +259,63 @@ bool HostScene::build(int meshThreshold, int sceneThreshold, std::string &err) {
 // Meshes [raw.meshes, meshes.size()): Mesh.Init and their part of every per-mesh array, appended.  On failure `arrays` is of no use (builtMeshes -1).
 bool HostScene::mesh_part(std::string &err) {
     SceneArrays &A = arrays;
-    // what assemble() put behind the last mesh's part (padding, the dummies of empty arrays) comes off
-    A.blocks.resize(raw.blocks); A.refN.resize(raw.refN); A.refG.resize(3 * raw.refN); A.shade.resize(raw.shade); A.leafNB.resize(raw.leafNB); A.leafTB.resize(raw.leafTB);
-    A.runBase.resize(raw.runBase); A.runTB.resize(raw.runTB); A.childDfs.resize(raw.childDfs); A.pblocks.resize(raw.pblocks); A.meshes.resize(raw.meshes);
+    strip_padding();
     builtMeshes = -1;
     meshTrees.resize(meshes.size());
-    int triBase = raw.meshes ? A.totalTris : 0;
-    for (size_t mi = raw.meshes; mi < meshes.size(); mi++) {
-        const HostMesh &m = meshes[mi];
-        FlatTree &t = meshTrees[mi];
-        if (!build_mesh_tree(m, meshThreshold, t, err)) return false;   // Mesh.Init (MESH:27-32)
-        std::vector<int> lr = t.leafRefs;   // the references in STORAGE order (spatial_runs)
-        for (size_t bi = 0; bi < t.blocks.size() / 2; bi++) {   // what the kernels' tie rule relies on: every leaf's list is ascending in the triangle index (MO:225-233 hands lists down in order)
-            const f4 lo = t.blocks[2 * bi], hi = t.blocks[2 * bi + 1];
-            const int lref = f2i(lo.y), masks = f2i(lo.z), total = f2i(lo.w);
-            const int offw[4] = {f2i(hi.x), f2i(hi.y), f2i(hi.z), f2i(hi.w)};
-            auto off = [&](int q) { int w = offw[q >> 1]; return (q & 1) ? (int)((unsigned)w >> 16) : (w & 0xffff); };
-            for (int c = 0; c < 8; c++) {
-                if ((masks >> c) & 1) continue;
-                const int b0 = lref + off(c), b1 = lref + (c == 7 ? total : off(c + 1));
-                for (int r = b0 + 1; r < b1; r++) if (lr[(size_t)r] <= lr[(size_t)r - 1]) { err = "internal: a leaf's triangle list is not ascending"; return false; }
-            }
+    const size_t first = raw.meshes;
+    for (size_t mi = first; mi < meshes.size(); mi++) {
+        meshTreesBuilt++;
+        if (!build_mesh_tree(meshes[mi], meshThreshold, meshTrees[mi], err)) return false;   // Mesh.Init (MESH:27-32)
+    }
+    if (!append_parts(first, meshes.size(), first ? A.totalTris : 0, err)) return false;
+    builtMeshes = (int)meshes.size();
+    return true;
+}
+
+// What assemble() put behind the last mesh's part (padding, the dummies of empty arrays) comes off.
+void HostScene::strip_padding() {
+    SceneArrays &A = arrays;
+    A.blocks.resize(raw.blocks); A.refN.resize(raw.refN); A.refG.resize(3 * raw.refN); A.shade.resize(raw.shade); A.leafNB.resize(raw.leafNB); A.leafTB.resize(raw.leafTB);
+    A.runBase.resize(raw.runBase); A.runTB.resize(raw.runTB); A.childDfs.resize(raw.childDfs); A.pblocks.resize(raw.pblocks); A.meshes.resize(raw.meshes);
+}
+
+HostScene::RawSizes HostScene::sizes_now() const {
+    const SceneArrays &A = arrays;
+    RawSizes z;
+    z.blocks = A.blocks.size(); z.refN = A.refN.size(); z.shade = A.shade.size(); z.leafNB = A.leafNB.size(); z.leafTB = A.leafTB.size();
+    z.runBase = A.runBase.size(); z.runTB = A.runTB.size(); z.childDfs = A.childDfs.size(); z.pblocks = A.pblocks.size(); z.meshes = A.meshes.size();
+    return z;
+}
+
+// What the kernels' tie rule relies on: every leaf's list is ascending in the triangle index (MO:225-233 hands lists down in order).
+static bool leaf_lists_ascending(const FlatTree &t) {
+    const std::vector<int> &lr = t.leafRefs;
+    for (size_t bi = 0; bi < t.blocks.size() / 2; bi++) {
+        const f4 lo = t.blocks[2 * bi], hi = t.blocks[2 * bi + 1];
+        const int lref = f2i(lo.y), masks = f2i(lo.z), total = f2i(lo.w);
+        const int offw[4] = {f2i(hi.x), f2i(hi.y), f2i(hi.z), f2i(hi.w)};
+        auto off = [&](int q) { int w = offw[q >> 1]; return (q & 1) ? (int)((unsigned)w >> 16) : (w & 0xffff); };
+        for (int c = 0; c < 8; c++) {
+            if ((masks >> c) & 1) continue;
+            const int b0 = lref + off(c), b1 = lref + (c == 7 ? total : off(c + 1));
+            for (int r = b0 + 1; r < b1; r++) if (lr[(size_t)r] <= lr[(size_t)r - 1]) return false;
         }
-        if (t.rootIsLeaf) for (int r = 1; r < t.rootCount; r++) if (lr[(size_t)r] <= lr[(size_t)r - 1]) { err = "internal: a leaf's triangle list is not ascending"; return false; }
+    }
+    if (t.rootIsLeaf) for (int r = 1; r < t.rootCount; r++) if (lr[(size_t)r] <= lr[(size_t)r - 1]) return false;
+    return true;
+}
+
+// The parts of meshes [first, last), whose trees are in meshTrees, appended to the per-mesh arrays (which end without padding); the first of them
+// numbers its triangles from triBase.  partStart[mi] keeps where mesh mi's part begins, `raw` where the last one ends.
+bool HostScene::append_parts(size_t first, size_t last, int triBase, std::string &err) {
+    SceneArrays &A = arrays;
+    partStart.resize(meshes.size());
+    for (size_t mi = first; mi < last; mi++) {
+        const HostMesh &m = meshes[mi];
+        const FlatTree &t = meshTrees[mi];
+        if (!leaf_lists_ascending(t)) { err = "internal: a leaf's triangle list is not ascending"; return false; }
+        partStart[mi] = sizes_now();
+        std::vector<int> lr = t.leafRefs;   // the references in STORAGE order (spatial_runs)
         if (spatialRuns)
             for (size_t bi = 0; bi < t.blocks.size() / 2; bi++) {
                 const f4 lo = t.blocks[2 * bi], hi = t.blocks[2 * bi + 1];
@@ -463,9 +497,7 @@ bool HostScene::mesh_part(std::string &err) {
         triBase += m.ntri;
     }
     A.totalTris = triBase;
-    raw.blocks = A.blocks.size(); raw.refN = A.refN.size(); raw.shade = A.shade.size(); raw.leafNB = A.leafNB.size(); raw.leafTB = A.leafTB.size();
-    raw.runBase = A.runBase.size(); raw.runTB = A.runTB.size(); raw.childDfs = A.childDfs.size(); raw.pblocks = A.pblocks.size(); raw.meshes = A.meshes.size();
-    builtMeshes = (int)meshes.size();
+    raw = sizes_now();
     return true;
 }
 
@@ -600,15 +632,105 @@ bool HostScene::set_pose(int id, const float *world, const float *invWorld, cons
     HostObject &o = objects[(size_t)id];
     std::memcpy(o.world, world, 64); std::memcpy(o.invWorld, invWorld, 64); std::memcpy(o.worldBbox, worldBbox, 24);
     if (!built) return true;   // (the next build reads the pose)
+    ObjRec &r = arrays.objects[(size_t)id];
+    std::memcpy(r.invWorld, o.invWorld, 64); std::memcpy(r.world, o.world, 64);
+    refresh_cull(id);
+    return true;
+}
+
+// The pre-cull records of body id (its ObjRec's cull box, its records in scull) from its pose and the boxes of its meshes as they are now.
+void HostScene::refresh_cull(int id) {
     SceneArrays &A = arrays;
     ObjRec &r = A.objects[(size_t)id];
-    std::memcpy(r.invWorld, o.invWorld, 64); std::memcpy(r.world, o.world, 64);
-    object_cull_box(o, meshes, r, cullSafety);
+    object_cull_box(objects[(size_t)id], meshes, r, cullSafety);
     f4 rec[4];
     scull_record(r, id, rec);
     for (int k = A.scullPosStart[(size_t)id]; k < A.scullPosStart[(size_t)id + 1]; k++)
         for (int j = 0; j < 4; j++) A.scull[4 * (size_t)A.scullPos[(size_t)k] + j] = rec[j];
-    return true;
+}
+
+int HostScene::set_mesh_triangles(int mesh, const float *v, const float *n, const float *uv, const float *sn, const float *color, int ntri,
+                                  const float bbox[6], std::string &err) {
+    const std::string fn = "xrt_scene_set_mesh_triangles: ";
+    if (!v || !sn || !bbox || ntri < 0) { err = fn + "null argument"; return XRT_E_INVALID_ARG; }   // (the checks of add_mesh)
+    if (ntri >= (1 << 28)) { err = fn + "too many triangles"; return XRT_E_INVALID_ARG; }
+    if (mesh < 0 || mesh >= (int)meshes.size()) { err = fn + "mesh id " + std::to_string(mesh) + " out of range (" + std::to_string(meshes.size()) + " meshes)"; return XRT_E_INVALID_ARG; }
+    const size_t k = (size_t)mesh;
+    HostMesh nm;   // the new triangles under the mesh's material and texels (Mesh.MeshMaterial is another property)
+    nm.ntri = ntri;
+    nm.v.assign(v, v + (size_t)ntri * 9);
+    if (n) nm.n.assign(n, n + (size_t)ntri * 9); else nm.n.assign((size_t)ntri * 9, 0.0f);
+    if (uv) nm.uv.assign(uv, uv + (size_t)ntri * 6); else nm.uv.assign((size_t)ntri * 6, 0.0f);
+    nm.sn.assign(sn, sn + (size_t)ntri * 3);
+    if (color) nm.color.assign(color, color + (size_t)ntri * 4); else nm.color.assign((size_t)ntri * 4, 1.0f);
+    std::memcpy(nm.bbox, bbox, sizeof(nm.bbox));
+    auto take_material = [&]() {
+        HostMesh &om = meshes[k];
+        nm.reflectiveness = om.reflectiveness; nm.refractionIndex = om.refractionIndex;
+        nm.transparent = om.transparent; nm.interpolateNormals = om.interpolateNormals; nm.useTexture = om.useTexture;
+        nm.texW = om.texW; nm.texH = om.texH;
+        nm.texels.swap(om.texels); nm.texelsP.swap(om.texelsP);
+    };
+    if (mesh >= builtMeshes) {   // (no build yet, or the mesh waits for its build: the build reads the new triangles)
+        take_material();
+        meshes[k] = std::move(nm);
+        return XRT_OK;
+    }
+    // Mesh.Init (MESH:27-32) into a temporary; nothing of the scene is touched before every check has passed
+    FlatTree nt;
+    meshTreesBuilt++;
+    if (!build_mesh_tree(nm, meshThreshold, nt, err)) return XRT_E_UNSUPPORTED;
+    if (!leaf_lists_ascending(nt)) { err = "internal: a leaf's triangle list is not ascending"; return XRT_E_UNSUPPORTED; }
+    int depth = nt.maxDepth;   // the deepest mesh octree afterwards: the replaced one may have been it
+    for (size_t mi = 0; mi < (size_t)builtMeshes; mi++) if (mi != k && meshTrees[mi].maxDepth > depth) depth = meshTrees[mi].maxDepth;
+    if (built && intersect_stack_capacity((arrays.sceneDepth + 1) + (depth + 1)) < 0) {
+        err = fn + "octree too deep for the LDS stack (" + std::to_string((arrays.sceneDepth + 1) + (depth + 1)) + " levels)";
+        return XRT_E_UNSUPPORTED;
+    }
+    SceneArrays &A = arrays;
+    // the padding of assemble() comes off, then the parts of the meshes behind k, kept aside
+    strip_padding();
+    const RawSizes b = partStart[k], e = k + 1 < (size_t)builtMeshes ? partStart[k + 1] : raw;   // mesh k's old part
+    SceneArrays T;
+    auto cut = [](auto &from, auto &to, size_t at, size_t keep) { to.assign(from.begin() + (std::ptrdiff_t)at, from.end()); from.resize(keep); };
+    cut(A.blocks, T.blocks, e.blocks, b.blocks); cut(A.refN, T.refN, e.refN, b.refN); cut(A.refG, T.refG, 3 * e.refN, 3 * b.refN); cut(A.shade, T.shade, e.shade, b.shade);
+    cut(A.leafNB, T.leafNB, e.leafNB, b.leafNB); cut(A.leafTB, T.leafTB, e.leafTB, b.leafTB); cut(A.runBase, T.runBase, e.runBase, b.runBase);
+    cut(A.runTB, T.runTB, e.runTB, b.runTB); cut(A.childDfs, T.childDfs, e.childDfs, b.childDfs); cut(A.pblocks, T.pblocks, e.pblocks, b.pblocks);
+    cut(A.meshes, T.meshes, e.meshes, b.meshes);
+    const int triBase = A.meshes.empty() ? 0 : A.meshes.back().triBase + A.meshes.back().ntri, oldTris = meshes[k].ntri, total = A.totalTris;
+    take_material();
+    meshes[k] = std::move(nm);
+    meshTrees[k] = std::move(nt);
+    append_parts(k, k + 1, triBase, err);   // (cannot fail: the lists were checked above)
+    // ... and the others behind the new part, the words that count from an array's beginning moved by what the part grew: the block and
+    // reference bases of `blocks` and `pblocks` (words 0-1), the triangle base in refN.w, runBase, MeshRec's rootBlock / rootRef / triBase / dfsBase
+    const RawSizes s = sizes_now();
+    const int dBlock = (int)(s.blocks / 2) - (int)(e.blocks / 2), dRef = (int)s.refN - (int)e.refN, dTri = ntri - oldTris, dRun = (int)(s.runTB / 4) - (int)(e.runTB / 4);
+    for (size_t i = 0; i + 1 < T.blocks.size(); i += 2) { f4 &lo = T.blocks[i]; lo.x = i2f(f2i(lo.x) + dBlock); lo.y = i2f(f2i(lo.y) + dRef); }
+    for (size_t i = 0; i < T.pblocks.size(); i += PBLOCK_WORDS) { T.pblocks[i] = i2f(f2i(T.pblocks[i]) + dBlock); T.pblocks[i + 1] = i2f(f2i(T.pblocks[i + 1]) + dRef); }
+    for (f4 &q : T.refN) q.w = i2f(f2i(q.w) + dTri);
+    for (int &q : T.runBase) if (q >= 0) q += dRun;
+    for (MeshRec &mr : T.meshes) {
+        if (mr.rootBlock >= 0) mr.rootBlock += dBlock;
+        mr.rootRef += dRef; mr.triBase += dTri; mr.dfsBase += 8 * dBlock;
+    }
+    auto paste = [](auto &to, const auto &from) { to.insert(to.end(), from.begin(), from.end()); };
+    paste(A.blocks, T.blocks); paste(A.refN, T.refN); paste(A.refG, T.refG); paste(A.shade, T.shade); paste(A.leafNB, T.leafNB); paste(A.leafTB, T.leafTB);
+    paste(A.runBase, T.runBase); paste(A.runTB, T.runTB); paste(A.childDfs, T.childDfs); paste(A.pblocks, T.pblocks); paste(A.meshes, T.meshes);
+    for (size_t mi = k + 1; mi < (size_t)builtMeshes; mi++) {
+        RawSizes &p = partStart[mi];
+        p.blocks += s.blocks - e.blocks; p.refN += s.refN - e.refN; p.shade += s.shade - e.shade; p.leafNB += s.leafNB - e.leafNB; p.leafTB += s.leafTB - e.leafTB;
+        p.runBase += s.runBase - e.runBase; p.runTB += s.runTB - e.runTB; p.childDfs += s.childDfs - e.childDfs; p.pblocks += s.pblocks - e.pblocks; p.meshes += s.meshes - e.meshes;
+    }
+    raw = sizes_now();
+    A.totalTris = total + dTri;
+    A.meshDepth = depth;
+    assemble();
+    material_part();
+    if (built)   // the pre-cull records are built on Mesh.MeshBoundingBox: those of the bodies that name the mesh, from the bodies' current poses
+        for (size_t o = 0; o < objects.size(); o++)
+            if (std::find(objects[o].meshes.begin(), objects[o].meshes.end(), mesh) != objects[o].meshes.end()) refresh_cull((int)o);
+    return XRT_OK;
 }
 
 bool HostScene::set_materials(const int *ids, int n, const xrt_material *mats, MaterialEdit &edit, std::string &err) {

@@ -83,17 +83,33 @@ struct HostScene {
     // `arrays` is of no use, later calls return XRT_E_NOT_BUILT and only build() repairs it.
     int set_bodies(int n, const int *meshStart, const int *meshIds, const float *world, const float *invWorld, const float *bbox,
                    const float *worldBbox, int sceneThreshold, int &meshesBuilt, std::string &err);
+    // Mesh.Triangles (and Mesh.MeshBoundingBox) replaced and Mesh.Init() run (xrt.h xrt_scene_set_mesh_triangles): mesh `mesh` takes the ntri triangles
+    // given, arrays as for add_mesh, under its id and with its material.  Where `arrays` holds the mesh (it is among the built ones) its MeshOctree.Build
+    // runs with meshThreshold -- for this mesh alone -- into a temporary; the mesh's part of every per-mesh array is replaced by the new one, the parts of
+    // the meshes behind it move (their base-relative words take the difference), refT / lrec and the padding are made again, and, on a built scene, the
+    // pre-cull records of the bodies that name the mesh are made from the new box and the bodies' current poses.  The body list, the bodies' boxes and the
+    // scene octree are not touched.  `arrays` and meshTrees end byte for byte as build() leaves them for the new triangles.  Everything is checked before
+    // anything is applied: XRT_E_INVALID_ARG (arguments, mesh id) or XRT_E_UNSUPPORTED (the octree cannot be built, or (scene depth + 1) + (mesh depth + 1)
+    // no longer fits a compiled stack) leave the scene as it was.  A mesh that waits for its build (or a scene never built) only takes the new triangles.
+    int set_mesh_triangles(int mesh, const float *v, const float *n, const float *uv, const float *sn, const float *color, int ntri, const float bbox[6],
+                           std::string &err);
+    int meshTreesBuilt = 0;        // MeshOctree.Build runs (build_mesh_tree calls) of this scene so far, whatever came of them
     // Scene file (xrt_scene_save / xrt_scene_load): the meshes, materials, texels and bodies exactly as they were added --
     // what the reference keeps in .xnb files (Model.Tag, TMP:113-117) -- little-endian, no pointers.  The trees are rebuilt on load.
     bool save(const char *path, std::string &err) const;
     bool load(const char *path, std::string &err);
     SceneView host_view() const;
   private:
-    // build() in its four parts.  mesh_part appends what meshes [builtMeshes, meshes.size()) add to `arrays` (behind what the others left there,
-    // the padding of assemble() taken off first); body_part makes objects / objMesh and the scene octree from `objects`; material_part the material
+    // build() in its four parts.  mesh_part builds the octrees of meshes [builtMeshes, meshes.size()) and appends what they add to `arrays` (append_parts:
+    // behind what the others left there, the padding of assemble() taken off first -- strip_padding); body_part makes objects / objMesh and the scene octree from `objects`; material_part the material
     // table and the texel arena; assemble() the padding at the arrays' ends and the arrays derived from the whole (refT, lrec).
     struct RawSizes { size_t blocks = 0, refN = 0, shade = 0, leafNB = 0, leafTB = 0, runBase = 0, runTB = 0, childDfs = 0, pblocks = 0, meshes = 0; } raw;   // sizes without the padding
+    std::vector<RawSizes> partStart;   // per built mesh: where its part of the per-mesh arrays begins (it ends where the next one's begins, the last one's at `raw`)
+    RawSizes sizes_now() const;
+    void strip_padding();
     bool mesh_part(std::string &err);
+    bool append_parts(size_t first, size_t last, int triBase, std::string &err);
+    void refresh_cull(int id);
     bool body_part(int sceneThreshold, std::string &err);
     void material_part();
     void assemble();

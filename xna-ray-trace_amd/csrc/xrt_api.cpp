@@ -3122,6 +3122,44 @@ int xrt_scene_set_bodies(xrt_scene *scene, int32_t n_bodies, const int32_t *mesh
     });
 }
 
+int xrt_scene_set_mesh_triangles(xrt_scene *scene, int32_t mesh_id, const float *v, const float *n, const float *uv, const float *surf_n,
+                                 const float *color, int32_t ntri, const float bbox[6]) {
+    if (!scene) return fail(XRT_E_INVALID_ARG, "xrt_scene_set_mesh_triangles: null scene");
+    if (in_flight(scene)) return fail(XRT_E_BUSY, "xrt_scene_set_mesh_triangles: a frame is in flight");
+    std::lock_guard<std::mutex> lock(scene->apiMutex);
+    BusyGuard guard(scene);
+    if (!guard.owned) return fail(XRT_E_BUSY, "xrt_scene_set_mesh_triangles: a frame is in flight");
+    return guarded("xrt_scene_set_mesh_triangles", [&]() -> int {
+        // Where `arrays` holds the mesh its part is replaced there and the device copy made again; else the next build reads the new triangles.
+        const bool spliced = mesh_id >= 0 && mesh_id < scene->hs.builtMeshes;
+        // What was set on the device is the scene's: the triangle values (of the other meshes) are read back before `shade` is sent again, and
+        // the poses too -- the call supplies none, and the pre-cull records it refreshes are made from the bodies' current poses.
+        if (scene->device >= 0 && spliced) {
+            int rc;
+            if ((rc = pull_shading(scene))) return rc;
+            if (scene->resident && (rc = pull_poses(scene))) return rc;
+        }
+        std::string err;
+        const int hrc = scene->hs.set_mesh_triangles(mesh_id, v, n, uv, surf_n, color, ntri, bbox, err);
+        if (hrc != XRT_OK) return fail(hrc, "%s", err.c_str());   // (nothing was applied: the scene is as it was, its device copy included)
+        if (!spliced) return XRT_OK;
+        scene->resident = false;
+        scene->workers.clear();
+        scene->replicas.clear();   // (copies of the old triangles: made again on the next n_gpus > 1 frame)
+        // grid sizes learned from the old triangles (xrt_scene_set_bodies lists what else earlier frames leave behind: all of it is scheduling
+        // only, keyed by the frame or set again by scene_derive; no buffer is sized from any of it)
+        scene->genKey = -1; scene->genCompose = -1;
+        if (!scene->hs.built) return XRT_OK;   // (meshes wait for xrt_scene_set_bodies: it sends everything)
+        const SceneArrays &A = scene->hs.arrays;
+        scene->stackNeeded = (A.sceneDepth + 1) + (A.meshDepth + 1);   // (it fits: the host edit checked it before it applied anything)
+        if (scene->device < 0) return XRT_OK;
+        HIPCHECK(hipSetDevice(scene->device));
+        if (scene->poseStream) HIPCHECK(hipStreamSynchronize(scene->poseStream));
+        if (scene->shadeStream) HIPCHECK(hipStreamSynchronize(scene->shadeStream));   // (an update of triangle values from host arrays may still be on its way)
+        return scene_upload(scene);   // no frame is in flight: everything again (scene_derive, material_restart, shade_restart)
+    });
+}
+
 int xrt_scene_save(const xrt_scene *scene, const char *path) {
     if (!scene || !path) return fail(XRT_E_INVALID_ARG, "xrt_scene_save: null argument");
     return guarded("xrt_scene_save", [&]() -> int {
